@@ -24,6 +24,13 @@ Inputs are HBM-resident before the timed region.
              nq = 1024 queries against EVERY row of a 10M x 1024 corpus on the
              matrix cores (vrq_gemm_topk), top-k fused.
 
+A plain run sets up, runs --warmup untimed and --steps timed steps, and prints the headline line
+(value, ms_per_step, ...).  --full adds every further leg after the timed steps: per-stage HIP events
+and the rooflines built on them, recall, the real-data search, the CPU baselines and identity checks,
+the encoder roofline and the config-3 Phase-I leg.  --dump-outputs DIR writes what the last timed step
+returned (counts, rows, distances, scores) as DIR/<name>.npy; the inputs are seeded, so two builds
+given the same arguments can be compared array for array.
+
 rank 0 prints ONE JSON line (the driver contract).
 """
 from __future__ import annotations
@@ -92,6 +99,12 @@ def parse():
                     help="skip the config-3 Phase-I leg (roofline_phase1) of the default config-4 line")
     ap.add_argument("--scan", choices=["auto", "valu", "mfma"], default="auto",
                     help="Phase-I scan (auto = the library's choice for the shape)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every further leg: per-stage HIP events and rooflines, "
+                         "recall, real data, CPU baselines and identity checks, encoder and Phase-I legs "
+                         "(each can be dropped with its --no-* switch); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64)")
     ap.add_argument("--launch-probe", action="store_true", help=argparse.SUPPRESS)
     return ap.parse_args()
 
@@ -688,7 +701,7 @@ def timed_loop(P, a, world, dev):
     The timed steps carry no per-stage events: each timing event record costs ~4.8 us of GPU time on
     this stack (two consecutive records are that far apart), ~40 us per step at 8 records -- 7 % of a
     config-2 step.  The per-stage breakdown (stage_ms) comes from K further, instrumented steps run
-    after the timed region."""
+    after the timed region (stage_steps, --full only)."""
     for _ in range(a.warmup):
         P.step(False)
     torch.cuda.synchronize()
@@ -706,10 +719,40 @@ def timed_loop(P, a, world, dev):
         tt = torch.tensor([T], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         T = float(tt.item())
-    for _ in range(a.steps):  # per-stage HIP events (not timed)
+    return T
+
+
+def stage_steps(P, steps):
+    """K further steps with per-stage HIP events (not timed): what stage_ms() averages."""
+    for _ in range(steps):
         P.step(True)
     torch.cuda.synchronize()
-    return T
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: the arrays the last timed step returned, as DIR/<name>.npy in float64 (row ids
+    and counts are exact there).  ``arrays`` maps a name to (count i32[nq], values [nq, w]) device
+    tensors or to a plain tensor; slots past a query's count are unspecified in the library's output
+    and are written as -1 so that two runs compare equal."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in arrays.items():
+        if isinstance(v, tuple):
+            cnt, t = v
+            t = t.to(torch.float64)
+            unused = torch.arange(t.shape[1], device=t.device)[None, :] >= cnt[:, None]
+            t = torch.where(unused, torch.full_like(t, -1.0), t)
+        else:
+            t = v.to(torch.float64)
+        np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy())
+
+
+def search_outputs(final, phase1=False):
+    """Names for a three-phase step's (count, rows, dist, s2, s3)."""
+    cnt, rows, dist_, s2, s3 = final[:5]
+    out = {"count": cnt, "rows": (cnt, rows), "hamming": (cnt, dist_)}
+    if not phase1:
+        out.update(binary_score=(cnt, s2), cosine_score=(cnt, s3))
+    return out
 
 
 def run_c5(a, world, rank, dev):
@@ -722,6 +765,29 @@ def run_c5(a, world, rank, dev):
     log(f"[rank {rank}] c5 data ready in {time.perf_counter() - t_setup:.1f} s: shard rows {codes.shape[0]}")
     P = C5Pipeline(codes, x8, norms, row0, qf, a.k, world)
     T = timed_loop(P, a, world, dev)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {f"{nm}_{what}": v for mo, nm in ((2, "binary"), (3, "cosine"))
+                                      for what, v in (("count", P.final[mo][0]),
+                                                      ("rows", (P.final[mo][0], P.final[mo][1])),
+                                                      ("score", (P.final[mo][0], P.final[mo][2])))})
+    out = {
+        "metric": METRIC, "value": nq * a.steps / T, "unit": "queries/s", "n_gpus": world, "steps": a.steps,
+        "warmup": a.warmup, "ms_per_step": T / a.steps * 1e3, "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": None, "dtype": "i8 (int8-quantised f32 queries, proven error bound) + f64 exact rescoring",
+        "data": "synthetic (SURVEY.md 8(d) clustered d=1024 generator; int8/ubinary from the gfx950 encoder)",
+        "config": {"workload": f"{CONFIGS['c5']['name']}, {n} x 1024 corpus, nq={nq} queries per step, "
+                               f"fused top-{a.k}",
+                   "corpus_rows": n, "nq": nq, "k": a.k,
+                   "parallelism": f"row-shard x{world} + RCCL all_gather" if world > 1 else "1 GPU"},
+    }
+    if not a.full:
+        if rank == 0:
+            emit(out)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+    stage_steps(P, a.steps)
     rec = None
     if not a.no_recall:
         rec = recall_at_10(P.final[3][1], qf, n, rank, world, dev, min(a.recall_sample, nq))
@@ -757,17 +823,7 @@ def run_c5(a, world, rank, dev):
                 "kernel": "gemm_topk_kernel<BINARY> main pass", "algorithmic_bytes_per_launch": m * 128}
     roof_bin["frac"] = roof_bin["achieved"] / roof["peak"]
     roof_bin["clock"] = pmc_clock(tag, "gemm_topk_kernel_binary", I8_DENSE_PEAK_TOPS, roof_bin["achieved"])
-    out = {
-        "metric": METRIC, "value": nq * a.steps / T, "unit": "queries/s", "n_gpus": world, "steps": a.steps,
-        "warmup": a.warmup, "ms_per_step": T / a.steps * 1e3, "higher_is_better": True, "scaling": "strong",
-        "vs_baseline": None, "dtype": "i8 (int8-quantised f32 queries, proven error bound) + f64 exact rescoring",
-        "data": "synthetic (SURVEY.md 8(d) clustered d=1024 generator; int8/ubinary from the gfx950 encoder)",
-        "config": {"workload": f"{CONFIGS['c5']['name']}, {n} x 1024 corpus, nq={nq} queries per step, "
-                               f"fused top-{a.k}",
-                   "corpus_rows": n, "nq": nq, "k": a.k,
-                   "parallelism": f"row-shard x{world} + RCCL all_gather" if world > 1 else "1 GPU"},
-        "recall_at_10": rec, "phase_ms": st, "roofline": roof, "roofline_binary": roof_bin,
-    }
+    out.update({"recall_at_10": rec, "phase_ms": st, "roofline": roof, "roofline_binary": roof_bin})
     if multi is not None:
         out["multi_gpu"] = multi
     if world == 1 and not a.no_cpu_baseline:
@@ -953,7 +1009,7 @@ def main():
 PHASE1_NQS = (1, 8, 64)  # nq in {1, 8, 64} per pass
 
 
-def phase1_leg(dev, n, nqs, k, osb, steps, warmup, threads, cpu=True, scan="auto"):
+def phase1_leg(dev, n, nqs, k, osb, steps, warmup, threads, cpu=True, scan="auto", stages=True, on_timed=None):
     """BASELINE config 3, the north star's numeric target: Phase-I-only Hamming top-K (K = k * osb)
     over n uniform random 1024-bit codes (queries = corpus rows with 64-256 flipped
     bits), at each batch size of `nqs` (the first nq queries of one query set).  Per batch size:
@@ -961,7 +1017,9 @@ def phase1_leg(dev, n, nqs, k, osb, steps, warmup, threads, cpu=True, scan="auto
     stream; the dominant kernel (K1r, hamming_mfma_rows_kernel) is priced against HBM with its
     algorithmic bytes n * 128 + nq * 128.  With `cpu`, the C restatement of FAISS hammings_knn_hc
     (oracle/hamming_knn.c, checker) runs the largest query set over the same corpus on the host:
-    (dist, row) of the whole top-K and the top-10 ids must be identical at every nq."""
+    (dist, row) of the whole top-K and the top-10 ids must be identical at every nq.
+    ``on_timed(P)`` is called after each batch size's timed passes; without ``stages`` the per-stage
+    passes and every figure derived from them are left out."""
     codes = synth.random_codes(n, device=dev)
     qall, _ = synth.flip_queries(codes, max(nqs))
     x8 = torch.empty((1, 1024), dtype=torch.int8, device=dev)
@@ -979,9 +1037,14 @@ def phase1_leg(dev, n, nqs, k, osb, steps, warmup, threads, cpu=True, scan="auto
             P.step(False)
         torch.cuda.synchronize()
         T = time.perf_counter() - t0
-        for _ in range(steps):  # per-stage HIP events, after the timed region (see timed_loop)
-            P.step(True)
-        torch.cuda.synchronize()
+        outs[nq] = (P.dist.cpu().numpy(), P.rows.cpu().numpy())
+        if on_timed is not None:
+            on_timed(P)
+        if not stages:  # a plain --config c3 run: the timed passes only
+            points[str(nq)] = {"nq": nq, "qps": nq * steps / T, "ms_per_step": T / steps * 1e3}
+            del P
+            continue
+        stage_steps(P, steps)  # per-stage HIP events, after the timed region (see timed_loop)
         st = P.stage_ms()
         mb = n * 128 + nq * 128
         kern = K1R_MAIN if P.kind == N.VRQ_SCAN_KIND_MFMA and nq <= 128 else \
@@ -999,7 +1062,6 @@ def phase1_leg(dev, n, nqs, k, osb, steps, warmup, threads, cpu=True, scan="auto
         pt["traffic"] = pmc_traffic(tag, "hamming_mfma_rows_kernel")
         pt["clock"] = pmc_clock(tag, "hamming_mfma_rows_kernel", MFMA_FP4_PEAK_TOPS, pt["mfma"]["achieved"])
         points[str(nq)] = pt
-        outs[nq] = (P.dist.cpu().numpy(), P.rows.cpu().numpy())
         del P
     out = {"workload": f"BASELINE config 3: Phase-I-only Hamming top-{min(k * osb, n)} (k={k}), {n} x 1024 "
                        "uniform random codes, queries = corpus rows with 64-256 flipped bits",
@@ -1048,20 +1110,25 @@ def run_c3(a, world, rank, dev):
     nq = a.nq or CONFIGS["c3"]["nq"]
     N.load()
     t0 = time.perf_counter()
+    def dump(P):
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, search_outputs(P.final, phase1=True))
     leg = phase1_leg(dev, n, (nq,), a.k, a.binary_oversample, a.steps, a.warmup, cpu_threads(a),
-                     cpu=not a.no_cpu_baseline, scan=a.scan)
+                     cpu=a.full and not a.no_cpu_baseline, scan=a.scan, stages=a.full, on_timed=dump)
     pt = leg["points"][str(nq)]
     log(f"[rank 0] c3 leg in {time.perf_counter() - t0:.1f} s")
-    roof = {k: pt[k] for k in ("achieved", "frac", "kernel", "kernel_ms", "algorithmic_bytes_per_launch", "timing",
-                               "mfma", "rocprof", "traffic")}
-    roof.update(bound="hbm", peak=HBM_PEAK_GBS, unit="GB/s", rows=n)
     out = {"metric": METRIC, "value": pt["qps"], "unit": "queries/s", "n_gpus": 1, "steps": a.steps,
            "warmup": a.warmup, "ms_per_step": pt["ms_per_step"], "higher_is_better": True, "scaling": "strong",
            "vs_baseline": None, "dtype": "u8", "data": "synthetic (uniform random 1024-bit codes, bit-flipped-row queries)",
            "config": {"workload": f"{CONFIGS['c3']['name']}, {n} x 1024 corpus, nq={nq} queries per step",
                       "corpus_rows": n, "nq": nq, "k": a.k, "binary_oversample": a.binary_oversample,
-                      "parallelism": "1 GPU"},
-           "phase_ms": pt["phase_ms"], "roofline": roof, "peak_note": leg["peak_note"]}
+                      "parallelism": "1 GPU"}}
+    if not a.full:
+        return emit(out)
+    roof = {k: pt[k] for k in ("achieved", "frac", "kernel", "kernel_ms", "algorithmic_bytes_per_launch", "timing",
+                               "mfma", "rocprof", "traffic")}
+    roof.update(bound="hbm", peak=HBM_PEAK_GBS, unit="GB/s", rows=n)
+    out.update({"phase_ms": pt["phase_ms"], "roofline": roof, "peak_note": leg["peak_note"]})
     if "cpu_baseline" in leg:
         out["cpu_baseline"] = leg["cpu_baseline"]
         out["cpu_gpu_identity"] = leg["cpu_gpu_identity"][str(nq)]
@@ -1191,6 +1258,28 @@ def run_3phase(a, world, rank, dev):
     P = Pipeline(codes, x8, norms, row0, n, qf, qb, a.k, a.binary_oversample, a.int8_oversample, world, False,
                  a.scan)
     T = timed_loop(P, a, world, dev)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, search_outputs(P.final))
+    m = codes.shape[0]
+    out = {
+        "metric": METRIC, "value": nq * a.steps / T, "unit": "queries/s", "n_gpus": world, "steps": a.steps,
+        "warmup": a.warmup, "ms_per_step": T / a.steps * 1e3, "higher_is_better": True,
+        "scaling": "strong", "vs_baseline": None, "dtype": "u8+f64",
+        "data": "synthetic (SURVEY.md 8(d) clustered d=1024 generator; int8/ubinary from the gfx950 encoder)",
+        "config": {"workload": f"{cfg['name']}, {n} x 1024 corpus, nq={nq} queries per step",
+                   "corpus_rows": n, "rows_per_gpu": m, "nq": nq, "k": a.k, "binary_oversample": a.binary_oversample,
+                   "int8_oversample": a.int8_oversample, "parallelism": f"row-shard x{world} + RCCL all_gather"
+                   if world > 1 else "1 GPU"},
+        "scan_kind": "mfma" if P.kind == N.VRQ_SCAN_KIND_MFMA else "valu",
+    }
+    if not a.full:
+        if rank == 0:
+            emit(out)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+    stage_steps(P, a.steps)
     st = P.stage_ms()
 
     top_rows = P.final[1]
@@ -1218,7 +1307,6 @@ def run_3phase(a, world, rank, dev):
             dist.destroy_process_group()
         return
 
-    m = codes.shape[0]
     K = P.K
     tag = f"{a.config}_n{n}_nq{nq}_g{world}"
     # whole Phase-I scan against HBM: algorithmic bytes = corpus codes + queries + K keys/query
@@ -1259,19 +1347,8 @@ def run_3phase(a, world, rank, dev):
         valu_ops = nq * m * 64  # 32 v_xor + 32 v_bcnt lane-ops per (query, 1024-bit row)
         roof_valu = {"bound": "valu", "achieved": valu_ops / (st["scan"] * 1e-3) / 1e12, "peak": VALU_PEAK_TOPS,
                      "unit": "T lane-ops/s", "frac": valu_ops / (st["scan"] * 1e-3) / 1e12 / VALU_PEAK_TOPS}
-    out = {
-        "metric": METRIC, "value": nq * a.steps / T, "unit": "queries/s", "n_gpus": world, "steps": a.steps,
-        "warmup": a.warmup, "ms_per_step": T / a.steps * 1e3, "higher_is_better": True,
-        "scaling": "strong", "vs_baseline": None, "dtype": "u8+f64",
-        "data": "synthetic (SURVEY.md 8(d) clustered d=1024 generator; int8/ubinary from the gfx950 encoder)",
-        "config": {"workload": f"{cfg['name']}, {n} x 1024 corpus, nq={nq} queries per step",
-                   "corpus_rows": n, "rows_per_gpu": m, "nq": nq, "k": a.k, "binary_oversample": a.binary_oversample,
-                   "int8_oversample": a.int8_oversample, "parallelism": f"row-shard x{world} + RCCL all_gather"
-                   if world > 1 else "1 GPU"},
-        "recall_at_10": rec,
-        "phase_ms": st, "scan_kind": "mfma" if P.kind == N.VRQ_SCAN_KIND_MFMA else "valu",
-        "roofline": roof, "roofline_scan_hbm": roof_scan_hbm, "roofline_valu": roof_valu,
-    }
+    out.update({"recall_at_10": rec, "phase_ms": st, "roofline": roof, "roofline_scan_hbm": roof_scan_hbm,
+                "roofline_valu": roof_valu})
     if multi:
         out["multi_gpu"] = multi
     if not a.no_recall:

@@ -15,7 +15,7 @@ for run in ${RUNS:-c3:8}; do
   CFG=${run%%:*}; NQ=${run#*:}
   OUT=gpurun_out/${TAG:-prof}/${CFG}_nq${NQ}
   mkdir -p $OUT
-  B="--config $CFG --nq $NQ --no-cpu-baseline --no-recall --no-encode --no-phase1 ${BARGS:-}"
+  B="--full --config $CFG --nq $NQ --no-cpu-baseline --no-recall --no-encode --no-phase1 ${BARGS:-}"
   timeout -k 10 ${PT:-400} rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 bench.py --steps $S --warmup $W $B > $OUT/bench_trace.json 2> $OUT/bench_trace.err || { echo TRACE_FAIL $run; tail -20 $OUT/bench_trace.err; exit 1; }
   python3 tools/trace_dispatches.py $OUT/trace $OUT/dispatch.json --warmup $W --command "python3 bench.py --steps $S --warmup $W $B" > $OUT/dispatch.txt
   if [ "${PMC:-1}" = "1" ]; then
