@@ -88,7 +88,9 @@ const char* vrq_strerror(int code);
  * queries    u8[nq, code_bytes]
  * out_dist   i32[nq, k]  ascending (dist, row) -- FAISS order; missing = INT32_MAX
  * out_rows   i64[nq, k]  row_offset + row; missing = -1
- * Supported: code_bytes in {64, 128, 256}, 1 <= k <= 1024, n < 2^40.
+ * Supported: code_bytes in {32, 48, 64, 96, 128, 192, 256} (d = 256, 384, 512, 768, 1024, 1536,
+ * 2048), 1 <= k <= 1024, n <= 2^32.  The matrix-core scan serves 128-byte codes only; the other
+ * sizes always take the wavefront popcount scan.
  * ------------------------------------------------------------------------- */
 size_t vrq_hamming_topk_workspace_size(int64_t n, int32_t code_bytes, int32_t nq, int32_t k);
 int vrq_hamming_topk(const uint8_t* codes, int64_t n, int32_t code_bytes, int64_t row_offset,
@@ -132,6 +134,32 @@ int vrq_search3_finish(const uint8_t* codes, const int8_t* x8, const double* nor
                        const float* qf, int32_t nq, int32_t k, int32_t K, int32_t K3, int32_t flags,
                        int32_t* out_count, int64_t* out_rows, int32_t* out_dist, double* out_binary,
                        double* out_cosine, const void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * The same search at the other embedding dims (additive to ABI version 1; the functions above keep
+ * their "dim must be 1024" contract).
+ * vrq_dim_supported: 1 for dim in {256, 384, 512, 768, 1024, 1536, 2048}, else 0 (host-only; the
+ *   source of truth for the functions below, which return VRQ_EUNSUPPORTED for every other dim).
+ * vrq_search3_dim / vrq_search3_dim_workspace_size: the arguments and semantics of vrq_search3 /
+ *   vrq_search3_workspace_size.  At dim == 1024 they forward to them (identical results and
+ *   workspace size, every flag).  At the other dims: flags 0 and VRQ_SEARCH_PHASE1_ONLY;
+ *   VRQ_SEARCH_SCAN_VALU is accepted (the wavefront scan is the only one there);
+ *   VRQ_SEARCH_SCAN_MFMA, VRQ_SCAN_STAGE_* and VRQ_SEARCH_SHARD return VRQ_EUNSUPPORTED.
+ * vrq_rescore_binary_dim / vrq_rescore_int8_cosine_dim: the arguments of vrq_rescore_binary /
+ *   vrq_rescore_int8_cosine; at 1024 they forward to them (bit-identical).
+ * ------------------------------------------------------------------------- */
+int vrq_dim_supported(int32_t dim);
+size_t vrq_search3_dim_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K);
+int vrq_search3_dim(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
+                    int64_t n, int32_t dim, int64_t row_offset, const float* qf, const uint8_t* qb, int32_t nq,
+                    int32_t k, int32_t K, int32_t K3, int32_t flags, int32_t* out_count, int64_t* out_rows,
+                    int32_t* out_dist, double* out_binary, double* out_cosine, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int vrq_rescore_binary_dim(const float* qf, int32_t nq, int32_t dim, const uint8_t* codes, int64_t n,
+                           const int64_t* cand_rows, int32_t ncand, double* out, void* stream);
+int vrq_rescore_int8_cosine_dim(const float* qf, int32_t nq, int32_t dim, const int8_t* x8,
+                                const double* norms, int64_t n, const int64_t* cand_rows,
+                                int32_t ncand, double* out, void* stream);
 
 /* Which Phase-I scan vrq_search3 / vrq_search3_scan / vrq_hamming_topk would run for this
  * shape and flags: VRQ_SCAN_KIND_VALU (wavefront popcount) or VRQ_SCAN_KIND_MFMA (matrix

@@ -1,0 +1,118 @@
+#!/usr/bin/env python
+"""Search at embedding dims other than 1024: HIP-event timing of vrq_search3_dim per (dim, nq), full
+three-phase (k = 10, K = 100, K3 = 30) and VRQ_SEARCH_PHASE1_ONLY, next to the yardstick -- the 1024-bit
+wavefront scan (vrq_search3, VRQ_SEARCH_SCAN_VALU | VRQ_SEARCH_PHASE1_ONLY) over a corpus of the same
+byte count, run twice per point so that a difference can be judged against the yardstick's own spread.
+
+One JSON line per point: ms, QPS and, for nq <= 8, the Phase-I corpus bytes per second as a share of the
+8 TB/s HBM peak.  Random codes and int8 rows (the timing does not depend on their values); queries are
+corpus rows with d/16 .. d/4 flipped bits.
+
+    python tools/dim_bench.py --out profiles/dim_bench.jsonl
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from vectorragquantization_amd import _native as N  # noqa: E402
+from vectorragquantization_amd import synth  # noqa: E402
+from vectorragquantization_amd.quant import int8_row_norms  # noqa: E402
+
+HBM_PEAK = 8e12
+K_OUT, K1, K3 = 10, 100, 30
+
+
+def timed(call, warmup, reps):
+    for _ in range(warmup):
+        call()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        call()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def search_call(lib, fn, name, codes, x8, norms, qf, qb, dim, flags, dev):
+    n, nq = codes.shape[0], qb.shape[0]
+    kout = K1 if flags & N.VRQ_SEARCH_PHASE1_ONLY else K_OUT
+    size = lib.vrq_search3_workspace_size if dim == 1024 else lib.vrq_search3_dim_workspace_size
+    ws = torch.empty((size(n, dim, nq, K1),), dtype=torch.uint8, device=dev)
+    cnt = torch.empty((nq,), dtype=torch.int32, device=dev)
+    rows = torch.empty((nq, kout), dtype=torch.int64, device=dev)
+    dist = torch.empty((nq, kout), dtype=torch.int32, device=dev)
+    s2 = torch.empty((nq, kout), dtype=torch.float64, device=dev)
+    s3 = torch.empty((nq, kout), dtype=torch.float64, device=dev)
+    st = N.stream_handle(dev)
+    keep = (ws, cnt, rows, dist, s2, s3)
+
+    def call():
+        N.check(fn(N.ptr(codes), N.ptr(x8), N.ptr(norms), 0, n, dim, 0, N.ptr(qf), N.ptr(qb), nq, K_OUT, K1, K3, flags,
+                   N.ptr(cnt), N.ptr(rows), N.ptr(dist), N.ptr(s2), N.ptr(s3), N.ptr(ws), ws.numel(), st), name)
+    return call, keep
+
+
+def point(d, n, nq, mode, ms, cb):
+    rec = {"dim": d, "n": n, "nq": nq, "mode": mode, "ms": round(ms, 4), "qps": round(nq / (ms * 1e-3), 1)}
+    if nq <= 8 and mode != "full":
+        bps = n * cb / (ms * 1e-3)
+        rec["phase1_TBps"] = round(bps / 1e12, 3)
+        rec["hbm_frac"] = round(bps / HBM_PEAK, 3)
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--dims", default="256,384,512,768,1536,2048")
+    ap.add_argument("--n", type=int, default=10_000_000)
+    ap.add_argument("--nq", default="1,8,64,1024")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    a = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    lib = N.load()
+    out = open(a.out, "a") if a.out else None
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if out:
+            out.write(line + "\n")
+            out.flush()
+
+    P1 = N.VRQ_SEARCH_PHASE1_ONLY
+    for d in (int(x) for x in a.dims.split(",")):
+        cb, n = d // 8, a.n
+        codes = synth.random_codes(n, cb, device=dev)
+        x8 = torch.randint(-127, 127, (n, d), dtype=torch.int8, device=dev)
+        norms = int8_row_norms(x8)
+        ny = n * cb // 128                                   # the yardstick corpus: same bytes, 128-byte codes
+        ycodes = synth.random_codes(ny, 128, device=dev, seed=synth.SEED + 7)
+        for nq in (int(x) for x in a.nq.split(",")):
+            qb, _ = synth.flip_queries(codes, nq, flips=(d // 16, d // 4))
+            qf = torch.randn((nq, d), device=dev) / d ** 0.5
+            yqb, _ = synth.flip_queries(ycodes, nq)
+            for mode, flags in (("phase1", P1), ("full", 0)):
+                call, keep = search_call(lib, lib.vrq_search3_dim, "vrq_search3_dim", codes, x8, norms, qf, qb, d,
+                                         flags, dev)
+                emit(point(d, n, nq, mode, timed(call, a.warmup, a.reps), cb))
+                del call, keep
+            for rep in (0, 1):
+                call, keep = search_call(lib, lib.vrq_search3, "vrq_search3", ycodes, None, None, None, yqb, 1024,
+                                         P1 | N.VRQ_SEARCH_SCAN_VALU, dev)
+                rec = point(1024, ny, nq, "yardstick_valu_phase1", timed(call, a.warmup, a.reps), 128)
+                rec.update({"for_dim": d, "repeat": rep})
+                emit(rec)
+                del call, keep
+        del codes, x8, norms, ycodes
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()

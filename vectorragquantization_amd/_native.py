@@ -60,6 +60,12 @@ SIGNATURES = {
     "vrq_search3_scan": (C.c_int, [_P, _I64, _I32, _P, _I32, _I32, _I32, _P, _SZ, _P]),
     "vrq_search3_finish": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I64, _P, _I32, _I32, _I32, _I32, _I32,
                                      _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "vrq_dim_supported": (C.c_int, [_I32]),
+    "vrq_search3_dim_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
+    "vrq_search3_dim": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32,
+                                  _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "vrq_rescore_binary_dim": (C.c_int, [_P, _I32, _I32, _P, _I64, _P, _I32, _P, _P]),
+    "vrq_rescore_int8_cosine_dim": (C.c_int, [_P, _I32, _I32, _P, _P, _I64, _P, _I32, _P, _P]),
     "vrq_scan_kind": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _P]),
     "vrq_scan_plan": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _P]),
     "vrq_scan_sample_plan": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _P]),

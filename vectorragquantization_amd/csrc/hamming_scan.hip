@@ -30,73 +30,9 @@
 //    query groups, so re-reads of a chunk hit that XCD's L2.
 #include "vrq_internal.h"
 #include "vrq_scan.h"
+#include "wave_scan.h"
 
 namespace vrq {
-
-constexpr int LOCAL_BITS = 20;
-constexpr uint32_t LOCAL_MASK = (1u << LOCAL_BITS) - 1;
-
-// Wave-level bitonic sort (ascending) of the CAP u32 keys at buf[0..CAP);
-// entries at index >= cnt are treated as +inf.  Result written back to buf.
-template <int CAP>
-__device__ __forceinline__ void wave_sort_keys(uint32_t* buf, int cnt) {
-  constexpr int E = CAP / WAVE;
-  int l = lane_id();
-  // opaque lane id: keeps the network's lane masks from being hoisted into the scan
-  // loop, where they would hold ~100 SGPRs live and push the resident query words out
-  asm volatile("" : "+v"(l));
-  uint32_t v[E];
-#pragma unroll
-  for (int e = 0; e < E; ++e) {
-    const int i = e * WAVE + l;
-    v[e] = (i < cnt) ? buf[i] : 0xffffffffu;
-  }
-#pragma unroll
-  for (int size = 2; size <= CAP; size <<= 1) {
-#pragma unroll
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      if (stride >= WAVE) {
-        const int es = stride / WAVE;
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-          if ((e & es) == 0) {
-            const int i = e * WAVE + l;
-            const bool up = (i & size) == 0;
-            const uint32_t a = v[e], b = v[e + es];
-            const uint32_t mn = a < b ? a : b, mx = a < b ? b : a;
-            v[e] = up ? mn : mx;
-            v[e + es] = up ? mx : mn;
-          }
-        }
-      } else {
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-          const int i = e * WAVE + l;
-          const uint32_t p = shfl_xor_u32(v[e], stride);
-          const bool up = (i & size) == 0;
-          const bool lower = (l & stride) == 0;
-          const uint32_t mn = v[e] < p ? v[e] : p, mx = v[e] < p ? p : v[e];
-          v[e] = (lower == up) ? mn : mx;
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < E; ++e) buf[e * WAVE + l] = v[e];
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-typedef uint32_t v16u __attribute__((ext_vector_type(16)));
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t lds_addr(const void* p) {
-  return (uint32_t)(uintptr_t)((__attribute__((address_space(3))) const void*)p);
-}
 
 // 128 query bytes -> 32 SGPRs (two s_load_dwordx16 from the scalar cache) and the
 // wait, in ONE asm statement: the SGPRs are valid at ASMEND, so hipcc can neither
@@ -108,23 +44,6 @@ __device__ __forceinline__ void load_q(v16u& a, v16u& b, const uint8_t* p) {
                : "s"(p)
                : "memory");
 }
-
-// d += popcount(q ^ r): v_xor_b32 (SGPR q) + v_bcnt_u32_b32 (bcnt accumulates).  The
-// empty asm pins the accumulation order so LLVM does not re-associate the chain
-// into bcnt(x,0) + v_add3 trees (+15 % VALU).
-__device__ __forceinline__ void xor_bcnt(uint32_t& d, uint32_t q, uint32_t r) {
-  d = __popc(q ^ r) + d;
-  asm("" : "+v"(d));
-}
-
-template <class T>
-__device__ __forceinline__ T* uniform_ptr(T* p) {  // provably wave-uniform (SGPR) pointer
-  const uint64_t u = (uint64_t)(uintptr_t)p;
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
-  return (T*)(uintptr_t)(((uint64_t)hi << 32) | lo);
-}
-
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_barrier" ::: "memory"); }
 
 // One workgroup = WPG waves scanning one CHUNK of rows for WPG*QG queries; every wave
 // owns QG queries (resident in SGPRs for the whole chunk) and the per-query top-K
@@ -346,19 +265,22 @@ static int cap_for(int K) {
 
 int scan_plan(int64_t n, int cb, int nq, int K, ScanPlan* p) {
   if (K < 1 || nq < 1 || n < 1) return VRQ_EINVAL;
-  if (cb != 128 || K > 1024) return VRQ_EUNSUPPORTED;
+  if ((cb != 128 && !dim_code_bytes_supported(cb)) || K > 1024) return VRQ_EUNSUPPORTED;
   p->cap = cap_for(K);
-  p->qg = nq >= 2 ? 2 : 1;
+  p->qg = cb != 128 ? dim_scan_queries_per_wave(cb) : nq >= 2 ? 2 : 1;
   const int waves_needed = (nq + p->qg - 1) / p->qg;
   int wpg = 1;
-  while (wpg < 8 && wpg < waves_needed) wpg <<= 1;
+  while (cb == 128 && wpg < 8 && wpg < waves_needed) wpg <<= 1;  // (K1d: one wave per workgroup)
   p->wpg = wpg;
   const int per_group = p->qg * wpg;
   p->nqg = (nq + per_group - 1) / per_group;
   int64_t want = kTargetWaves / ((int64_t)p->nqg * wpg);
   if (want < 1) want = 1;
   int64_t cr = (n + want - 1) / want;
-  if (cr < kMinChunkRows) cr = kMinChunkRows;
+  // (narrower codes: the same minimum of bytes per chunk, so a small batch over n rows of cb bytes merges
+  // as many lists per query as over n * cb / 128 rows of 128 bytes)
+  const int64_t min_rows = cb < 128 ? kMinChunkRows * 128 / cb : kMinChunkRows;
+  if (cr < min_rows) cr = min_rows;
   cr = (cr + 63) & ~int64_t(63);
   // the merge (select_rescore.hip) takes at most 4096 lists per query
   if ((n + cr - 1) / cr > 4096) cr = ((n + 4095) / 4096 + 63) & ~int64_t(63);
@@ -400,7 +322,7 @@ static int launch_c(const ScanPlan& p, const uint8_t* codes, int64_t n, const ui
 
 int scan_launch(const ScanPlan& p, const uint8_t* codes, int64_t n, int cb, const uint8_t* q, int nq, int K,
                 uint64_t* lists, hipStream_t s) {
-  if (cb != 128) return VRQ_EUNSUPPORTED;
+  if (cb != 128) return dim_scan_launch(p, codes, n, cb, q, nq, K, lists, s);
   switch (p.cap) {
     case 256: return launch_c<256>(p, codes, n, q, nq, K, lists, s);
     case 512: return launch_c<512>(p, codes, n, q, nq, K, lists, s);

@@ -32,10 +32,11 @@ constexpr uint64_t ROW_MASK = (1ull << KEY_ROW_BITS) - 1;
 // Per-query LDS state, sized for at most KM candidates (binary_k) and ML lists.  The general
 // instance (KMAX, MAX_LISTS) takes ~89 KiB, one workgroup per CU; the common shape (K <= 128,
 // <= 64 lists) runs the small instance (~11 KiB) so 8 workgroups share a CU.
-template <int KM, int ML>
-struct SelShared {
-  static constexpr int kKM = KM, kML = ML;
-  uint32_t hist[NBINS];
+// (NB = histogram bins of the selection: every distance the code size allows, + padding)
+template <int KM, int ML, int NB>
+struct SelState {
+  static constexpr int kKM = KM, kML = ML, kBins = NB;
+  uint32_t hist[NB];
   int32_t ltcnt[ML];
   int32_t eqend[ML];
   uint64_t sel[KM];         // Phase-I keys (dist << 40 | row), FAISS order after select
@@ -49,9 +50,17 @@ struct SelShared {
   int32_t scan[SEL_THREADS / WAVE + 1];
   int32_t misc[8];
 };
+template <int KM, int ML>
+struct SelShared : SelState<KM, ML, NBINS> {};
 constexpr int KSMALL = 128, LSMALL = 64;
 typedef SelShared<KMAX, MAX_LISTS> SelBig;
 typedef SelShared<KSMALL, LSMALL> SelSmall;
+// the instances of the other embedding dims (vrq_search3_dim): dist in [0, 2048]
+constexpr int NBINS_DIM = 2049 + 3;
+template <int KM, int ML>
+struct SelSharedDim : SelState<KM, ML, NBINS_DIM> {};
+typedef SelSharedDim<KMAX, MAX_LISTS> SelDimBig;
+typedef SelSharedDim<KSMALL, LSMALL> SelDimSmall;
 
 // Block-wide exclusive scan of one int per thread; returns exclusive prefix, total in *tot.
 __device__ inline int block_excl_scan(int v, int* tot, int32_t* scratch) {
@@ -81,6 +90,7 @@ __device__ inline int block_excl_scan(int v, int* tot, int32_t* scratch) {
 // ascending by key (= FAISS (dist, row) order) with sh.pay = list*K + pos.  Returns Kp.
 template <class KeyAt, class SH>
 __device__ int select_topk(const KeyAt& L, int nl, int K, SH& sh) {
+  constexpr int NBINS = SH::kBins;  // (keys with dist >= NBINS would be dropped: the instance covers its dims)
   const int tid = threadIdx.x;
   const int total = nl * K;
   for (int i = tid; i < NBINS; i += SEL_THREADS) sh.hist[i] = 0;
@@ -500,6 +510,144 @@ __global__ __launch_bounds__(SEL_THREADS, SH::kKM <= KSMALL ? 4 : 1) void select
   finish_query(Kp, false, a, qi, sh);
 }
 
+// ---------------------------------------------------------------------------
+// The other embedding dims (vrq_search3_dim: dim a multiple of 128 up to 2048, a runtime argument).
+// The same definitions as exact_scores.h with the loops over dim / 4 nibbles and dim / 128 lane pairs.
+// ---------------------------------------------------------------------------
+// Phase III of one row, one wave: lane l takes dims 2l, 2l+1 of every 128-dim block (coalesced 128-byte
+// int8 and 512-byte query reads); exact products, exact f64 sum, one rounding to f32, f64 division.
+__device__ __forceinline__ double phase3_cos_dim(const float* __restrict__ q, const int8_t* __restrict__ xrow,
+                                                 double nrm, int dim) {
+  double s = 0.0;
+  for (int d = 2 * lane_id(); d < dim; d += 2 * WAVE) {
+    const char2 x = *reinterpret_cast<const char2*>(xrow + d);
+    const float2 qq = *reinterpret_cast<const float2*>(q + d);
+    s += (double)qq.x * (double)x.x;
+    s += (double)qq.y * (double)x.y;
+  }
+  s = wave_sum_f64(s);
+  const float f = (float)s;
+  return nrm == 0.0 ? -__builtin_inf() : (double)f / nrm;
+}
+// Phase II of one row, one wave (the stand-alone rescoring): the same lane -> dims map
+__device__ __forceinline__ double phase2_dot_dim(const float* __restrict__ q, const uint8_t* __restrict__ code_row,
+                                                 int dim) {
+  double s = 0.0;
+  for (int d = 2 * lane_id(); d < dim; d += 2 * WAVE) {
+    const uint32_t byte = code_row[d >> 3];  // packbits is MSB-first: dim d at bit 7 - d % 8
+    const float2 qq = *reinterpret_cast<const float2*>(q + d);
+    s += ((byte >> (7 - (d & 7))) & 1) ? (double)qq.x : -(double)qq.x;
+    s += ((byte >> (6 - (d & 7))) & 1) ? (double)qq.y : -(double)qq.y;
+  }
+  return wave_sum_f64(s);
+}
+
+// Phase II of the Kp candidates by nibble tables, as phase2_nibble_tables, over cb = dim / 8 code bytes in
+// passes of up to 64 bytes (cb is a multiple of 16; the last pass of a 48-, 96- or 192-byte code is shorter).
+template <class SH>
+__device__ void phase2_nibble_tables_dim(const float* __restrict__ q, const uint8_t* __restrict__ codes,
+                                         const int64_t* __restrict__ remap, int Kp, int cb, SH& sh, double* qtab) {
+  constexpr int NW = SEL_THREADS / WAVE;
+  const int tid = threadIdx.x, w = tid / WAVE, l = lane_id();
+  for (int jb = 0; jb < Kp; jb += SEL_THREADS) {
+    const int j = jb + NW * l + w;
+    const bool live = j < Kp;
+    int64_t row = (int64_t)(sh.sel[live ? j : 0] & ROW_MASK);
+    if (remap) row = remap[row];
+    double acc = 0.0;
+    for (int b0 = 0; b0 < cb; b0 += QT_NIB / 2) {
+      const int nb = cb - b0 < QT_NIB / 2 ? cb - b0 : QT_NIB / 2;  // code bytes of this pass
+      uint4 cw[4];
+      const uint4* src = reinterpret_cast<const uint4*>(codes + row * cb + b0);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) cw[i] = 16 * i < nb ? src[i] : make_uint4(0, 0, 0, 0);
+      __syncthreads();  // (the previous pass's lookups are done)
+      for (int e = tid; e < nb * 2 * 16; e += SEL_THREADS) {
+        const int p = e >> 4, v = e & 15, d0 = 4 * (2 * b0 + p);
+        double t = 0.0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          const double x = (double)q[d0 + b];
+          t += ((v >> (3 - b)) & 1) ? x : -x;
+        }
+        qtab[e] = t;
+      }
+      __syncthreads();
+      if (live) {
+        const uint32_t wd[16] = {cw[0].x, cw[0].y, cw[0].z, cw[0].w, cw[1].x, cw[1].y, cw[1].z, cw[1].w,
+                                 cw[2].x, cw[2].y, cw[2].z, cw[2].w, cw[3].x, cw[3].y, cw[3].z, cw[3].w};
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+          if (4 * k < nb) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {  // byte 4k + c of the pass (little-endian in the dword)
+              const uint32_t byte = (wd[k] >> (8 * c)) & 0xffu;
+              const int pb = 2 * (4 * k + c);
+              acc += qtab[pb * 16 + (byte >> 4)];
+              acc += qtab[(pb + 1) * 16 + (byte & 15)];
+            }
+          }
+        }
+      }
+    }
+    if (live) sh.s2[j] = acc;
+  }
+  __syncthreads();
+}
+
+// the K1d lists of one query: [nchunks][K], no suffix list
+struct ChunkKeys {
+  const uint64_t* lists;
+  __device__ uint64_t operator[](int i) const { return lists[i]; }
+};
+
+// K2 for the other dims: merge of the K1d lists (histogram over every distance up to 2048) + Phase II +
+// Phase III + the stable sorts.  mode: 0 = full 3-phase; 1 = Phase I only.
+template <class SH>
+__global__ __launch_bounds__(SEL_THREADS, SH::kKM <= KSMALL ? 4 : 1) void select_rescore_dim_kernel(
+    const uint64_t* __restrict__ lists, int nlp, int K, int dim, const uint8_t* __restrict__ codes,
+    const int8_t* __restrict__ x8, const double* __restrict__ norms, const float* __restrict__ qf, int mode,
+    FinishArgs fa) {
+  __shared__ SH sh;
+  const int qi = blockIdx.x;
+  const int tid = threadIdx.x, w = tid / WAVE, l = lane_id();
+  const ChunkKeys Lq{lists + (int64_t)qi * nlp * K};
+  const int Kp = select_topk(Lq, nlp, K, sh);
+  if (mode == 1) {
+    for (int i = tid; i < fa.kout; i += SEL_THREADS) {
+      const int64_t o = (int64_t)qi * fa.kout + i;
+      if (i < Kp) {
+        fa.out_rows[o] = (int64_t)(sh.sel[i] & ROW_MASK) + fa.row_offset;
+        fa.out_dist[o] = (int32_t)(sh.sel[i] >> KEY_ROW_BITS);
+      } else {
+        fa.out_rows[o] = -1;
+        fa.out_dist[o] = DIST_NONE;
+      }
+    }
+    if (tid == 0 && fa.out_count) fa.out_count[qi] = Kp;
+    return;
+  }
+  const float* q = qf + (int64_t)qi * dim;
+  __shared__ double qtab[QT_NIB * 16];
+  phase2_nibble_tables_dim(q, codes, fa.remap, Kp, dim / 8, sh, qtab);
+  // Phase III of the K3 survivors of the Phase-II sort, one wave per row; finish_query then finds its
+  // scores in sh.s3 (by Phase-I rank) and repeats the cheap Phase-II sort
+  stable_desc_order(sh.s2, Kp, sh);
+  const int K3p = fa.K3 < Kp ? fa.K3 : Kp;
+  for (int i = tid; i < K3p; i += SEL_THREADS) sh.ord2[i] = sh.sidx[i];
+  __syncthreads();
+  for (int j = w; j < K3p; j += SEL_THREADS / WAVE) {
+    int64_t row = (int64_t)(sh.sel[sh.ord2[j]] & ROW_MASK);
+    if (fa.remap) row = fa.remap[row];
+    const double c = phase3_cos_dim(q, x8 + row * dim, norms[row], dim);
+    if (l == 0) sh.s3[sh.ord2[j]] = c;
+  }
+  __syncthreads();
+  FinishArgs a = fa;
+  a.q = q;
+  finish_query(Kp, true, a, qi, sh);
+}
+
 // Shard merge: the lists are the shards' (dist, global row) candidates (VRQ_SEARCH_SHARD
 // outputs stacked [S][nq][K]); the payload carried to the finish step is s2/s3.
 struct ShardKeys {
@@ -559,6 +707,40 @@ __global__ __launch_bounds__(256) void rescore_kernel(int which, const float* __
   load_q(qv, qf + (int64_t)qi * DIM);
   const double v = which == 0 ? phase2_dot(qv, codes + row * (DIM / 8)) : phase3_cos(qv, x8 + row * DIM, norms[row]);
   if (lane_id() == 0) out[gw] = v;
+}
+
+// The same for the other dims (vrq_rescore_*_dim).
+__global__ __launch_bounds__(256) void rescore_dim_kernel(int which, const float* __restrict__ qf, int nq, int dim,
+                                                          const uint8_t* __restrict__ codes,
+                                                          const int8_t* __restrict__ x8,
+                                                          const double* __restrict__ norms, int64_t n,
+                                                          const int64_t* __restrict__ cand, int ncand,
+                                                          double* __restrict__ out) {
+  const int64_t gw = ((int64_t)blockIdx.x * 256 + threadIdx.x) / WAVE;
+  if (gw >= (int64_t)nq * ncand) return;
+  const int qi = (int)(gw / ncand);
+  const int64_t row = cand[gw];
+  if (row < 0 || row >= n) {
+    if (lane_id() == 0) out[gw] = __builtin_nan("");
+    return;
+  }
+  const float* q = qf + (int64_t)qi * dim;
+  const double v = which == 0 ? phase2_dot_dim(q, codes + row * (dim / 8), dim)
+                              : phase3_cos_dim(q, x8 + row * dim, norms[row], dim);
+  if (lane_id() == 0) out[gw] = v;
+}
+
+static int launch_select_dim(hipStream_t s, int nq, const uint64_t* lists, int nl, int K, int dim,
+                             const uint8_t* codes, const int8_t* x8, const double* norms, const float* qf, int mode,
+                             const FinishArgs& fa) {
+  if (K <= KSMALL && nl <= LSMALL)
+    hipLaunchKernelGGL(select_rescore_dim_kernel<SelDimSmall>, dim3(nq), dim3(SEL_THREADS), 0, s, lists, nl, K, dim,
+                       codes, x8, norms, qf, mode, fa);
+  else
+    hipLaunchKernelGGL(select_rescore_dim_kernel<SelDimBig>, dim3(nq), dim3(SEL_THREADS), 0, s, lists, nl, K, dim,
+                       codes, x8, norms, qf, mode, fa);
+  VRQ_LAUNCH_CHECK();
+  return VRQ_OK;
 }
 
 // launch the small-LDS instance when the shape fits it
@@ -646,6 +828,8 @@ int vrq_hamming_topk(const uint8_t* codes, int64_t n, int32_t code_bytes, int64_
   if (p.nchunks > MAX_LISTS) return VRQ_EUNSUPPORTED;
   rc = scan_launch(p, codes, n, code_bytes, queries, nq, k, lists, s);
   if (rc != VRQ_OK) return rc;
+  if (code_bytes != DIM / 8)  // (the merge instance whose histogram covers distances up to 2048)
+    return launch_select_dim(s, nq, lists, p.nchunks, k, code_bytes * 8, nullptr, nullptr, nullptr, nullptr, 1, fa);
   return launch_select(s, nq, lists, p.nchunks, nullptr, k, nullptr, nullptr, nullptr, nullptr, 1, fa);
 }
 
@@ -844,6 +1028,92 @@ int vrq_rescore_int8_cosine(const float* qf, int32_t nq, int32_t dim, const int8
   VRQ_CHECK_ARG(qf && x8 && norms && cand_rows && out);
   hipLaunchKernelGGL(rescore_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, 1, qf,
                      nq, nullptr, x8, norms, n, cand_rows, ncand, out);
+  VRQ_LAUNCH_CHECK();
+  return VRQ_OK;
+}
+
+// ---- the other embedding dims: additive entry points, dim == 1024 forwards to the ABI-1 functions ----
+int vrq_dim_supported(int32_t dim) {
+  return dim == DIM || (dim > 0 && dim % 8 == 0 && dim_code_bytes_supported(dim / 8)) ? 1 : 0;
+}
+
+size_t vrq_search3_dim_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K) {
+  if (dim == DIM) return vrq_search3_workspace_size(n, dim, nq, K);
+  if (n < 1 || nq < 1 || K < 1 || !vrq_dim_supported(dim)) return 0;
+  ScanPlan p;
+  if (scan_plan(n, dim / 8, nq, K, &p) != VRQ_OK) return 0;
+  return p.list_bytes;
+}
+
+int vrq_search3_dim(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
+                    int64_t n, int32_t dim, int64_t row_offset, const float* qf, const uint8_t* qb, int32_t nq,
+                    int32_t k, int32_t K, int32_t K3, int32_t flags, int32_t* out_count, int64_t* out_rows,
+                    int32_t* out_dist, double* out_binary, double* out_cosine, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+  if (dim == DIM)
+    return vrq_search3(codes, x8, norms, rescore_row, n, dim, row_offset, qf, qb, nq, k, K, K3, flags, out_count,
+                       out_rows, out_dist, out_binary, out_cosine, workspace, workspace_bytes, stream);
+  VRQ_CHECK_ARG(n >= 0 && nq >= 0 && k >= 0 && K >= 0 && K3 >= 0);
+  VRQ_CHECK_ARG(out_count && out_rows && out_dist);
+  if (!vrq_dim_supported(dim) || K > KMAX) return VRQ_EUNSUPPORTED;
+  // the matrix-core scans and the sharded mode are 1024-only; VRQ_SEARCH_SCAN_VALU names the only scan there is
+  if (flags & ~(VRQ_SEARCH_PHASE1_ONLY | VRQ_SEARCH_SCAN_VALU)) return VRQ_EUNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  const int mode = (flags & VRQ_SEARCH_PHASE1_ONLY) ? 1 : 0;
+  const int kout = mode == 0 ? k : K;
+  if (nq == 0) return VRQ_OK;
+  if (mode != 1) VRQ_CHECK_ARG(out_binary && out_cosine);
+  if (n == 0 || K == 0 || (mode == 0 && k == 0))
+    return fill_empty(nq, kout, out_count, out_rows, out_dist, out_binary, out_cosine, s);
+  VRQ_CHECK_ARG(codes && qb && workspace);
+  if (mode != 1) VRQ_CHECK_ARG(qf && x8 && norms);
+  ScanPlan p;
+  int rc = scan_plan(n, dim / 8, nq, K, &p);
+  if (rc != VRQ_OK) return rc;
+  if (workspace_bytes < p.list_bytes) return VRQ_EWORKSPACE;
+  if (p.nchunks > MAX_LISTS) return VRQ_EUNSUPPORTED;
+  rc = scan_launch(p, codes, n, dim / 8, qb, nq, K, (uint64_t*)workspace, s);
+  if (rc != VRQ_OK) return rc;
+  FinishArgs fa{};
+  fa.x8 = x8;
+  fa.norms = norms;
+  fa.remap = rescore_row;
+  fa.row_offset = row_offset;
+  fa.k = k;
+  fa.K3 = K3;
+  fa.out_count = out_count;
+  fa.out_rows = out_rows;
+  fa.out_dist = out_dist;
+  fa.out_s2 = out_binary;
+  fa.out_s3 = out_cosine;
+  fa.kout = kout;
+  return launch_select_dim(s, nq, (const uint64_t*)workspace, p.nchunks, K, dim, codes, x8, norms, qf, mode, fa);
+}
+
+int vrq_rescore_binary_dim(const float* qf, int32_t nq, int32_t dim, const uint8_t* codes, int64_t n,
+                           const int64_t* cand_rows, int32_t ncand, double* out, void* stream) {
+  if (dim == DIM) return vrq_rescore_binary(qf, nq, dim, codes, n, cand_rows, ncand, out, stream);
+  VRQ_CHECK_ARG(nq >= 0 && ncand >= 0 && n >= 0);
+  if (!vrq_dim_supported(dim)) return VRQ_EUNSUPPORTED;
+  const int64_t waves = (int64_t)nq * ncand;
+  if (waves == 0) return VRQ_OK;
+  VRQ_CHECK_ARG(qf && codes && cand_rows && out);
+  hipLaunchKernelGGL(rescore_dim_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, 0, qf,
+                     nq, dim, codes, nullptr, nullptr, n, cand_rows, ncand, out);
+  VRQ_LAUNCH_CHECK();
+  return VRQ_OK;
+}
+
+int vrq_rescore_int8_cosine_dim(const float* qf, int32_t nq, int32_t dim, const int8_t* x8, const double* norms,
+                                int64_t n, const int64_t* cand_rows, int32_t ncand, double* out, void* stream) {
+  if (dim == DIM) return vrq_rescore_int8_cosine(qf, nq, dim, x8, norms, n, cand_rows, ncand, out, stream);
+  VRQ_CHECK_ARG(nq >= 0 && ncand >= 0 && n >= 0);
+  if (!vrq_dim_supported(dim)) return VRQ_EUNSUPPORTED;
+  const int64_t waves = (int64_t)nq * ncand;
+  if (waves == 0) return VRQ_OK;
+  VRQ_CHECK_ARG(qf && x8 && norms && cand_rows && out);
+  hipLaunchKernelGGL(rescore_dim_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, 1, qf,
+                     nq, dim, nullptr, x8, norms, n, cand_rows, ncand, out);
   VRQ_LAUNCH_CHECK();
   return VRQ_OK;
 }

@@ -30,6 +30,13 @@ int scan_plan(int64_t n, int cb, int nq, int K, ScanPlan* p);
 int scan_launch(const ScanPlan& p, const uint8_t* codes, int64_t n, int cb, const uint8_t* q, int nq, int K,
                 uint64_t* lists, hipStream_t s);
 
+// ---- K1d: the wavefront scan for the other code sizes (search_dim.hip); scan_plan / scan_launch
+// dispatch to it for cb != 128 (one wave per workgroup: wpg = 1, qg fixed per code size) ----
+bool dim_code_bytes_supported(int cb);   // 32, 48, 64, 96, 192, 256
+int dim_scan_queries_per_wave(int cb);
+int dim_scan_launch(const ScanPlan& p, const uint8_t* codes, int64_t n, int cb, const uint8_t* q, int nq, int K,
+                    uint64_t* lists, hipStream_t s);
+
 // ---- K1m: matrix-core scan for large query batches (hamming_mfma.hip) ----
 constexpr int kMfmaMaxK = 128;           // K bound of the path
 // the minimum dense sample (VRQ_MIN_SAMPLE: A/B builds).  Round 6: 65 536 rows; with the round-6 suffix and
