@@ -325,6 +325,37 @@ int vrq_flat_ip_topk(const float* xf, const int8_t* x8, const double* inv_scale,
                      int32_t* out_count, int64_t* out_rows, double* out_scores, void* workspace,
                      size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Exhaustive top-k and the exact float inner product at every supported embedding dim (additive to
+ * ABI version 1; the functions above keep their "dim = 1024" contract).  The arguments, outputs and
+ * result order of vrq_gemm_topk / vrq_flat_ip_topk / vrq_gemm_topk_workspace_size.
+ * At dim == 1024 without VRQ_GEMM_SCAN_EXACT they forward to those functions (identical results,
+ * workspace size and flags).  At the other dims of vrq_dim_supported, and at 1024 with
+ * VRQ_GEMM_SCAN_EXACT, they run K5d, an exact scan that scores every (query, row) pair once in f64:
+ * no matrix-core pass, no sampled threshold and no fallback, so no query is ever left unserved.
+ * There: flags 0, VRQ_GEMM_SCAN_EXACT and VRQ_GEMM_NO_FALLBACK (a no-op); VRQ_GEMM_STAGE_* returns
+ * VRQ_EUNSUPPORTED; vrq_flat_ip_topk_dim ignores x8, inv_scale and bounds (may be NULL; there is no
+ * prepare step off 1024); mode VRQ_GEMM_FLOAT_IP passed to vrq_gemm_topk_dim returns VRQ_EINVAL.
+ * Workspace: vrq_gemm_topk_dim_workspace_size; at 1024 that is the forwarded path's size, and a
+ * caller that sets VRQ_GEMM_SCAN_EXACT there sizes the workspace as the maximum of it and the bytes
+ * vrq_gemm_topk_dim_plan reports.  Supported: 1 <= k <= 1024, 1 <= n < 2^32, finite inputs.
+ * vrq_gemm_topk_dim_plan (host-only; tests and tools): K5d's plan, info i64[6] = rows per tile, rows
+ * per chunk, chunks, queries per workgroup, list capacity per (query, chunk), workspace bytes;
+ * VRQ_EUNSUPPORTED for shapes K5d does not serve.
+ * ------------------------------------------------------------------------- */
+#define VRQ_GEMM_SCAN_EXACT 256 /* _dim entry points only: run the exact exhaustive scan (K5d) at
+                                   dim == 1024 too, instead of forwarding */
+size_t vrq_gemm_topk_dim_workspace_size(int32_t mode, int64_t n, int32_t dim, int32_t nq, int32_t k);
+int vrq_gemm_topk_dim_plan(int32_t mode, int64_t n, int32_t dim, int32_t nq, int32_t k, int64_t* info);
+int vrq_gemm_topk_dim(int32_t mode, const uint8_t* codes, const int8_t* x8, const double* norms, int64_t n,
+                      int32_t dim, int64_t row_offset, const float* qf, int32_t nq, int32_t k, int32_t flags,
+                      int32_t* out_count, int64_t* out_rows, double* out_scores, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int vrq_flat_ip_topk_dim(const float* xf, const int8_t* x8, const double* inv_scale, const double* bounds, int64_t n,
+                         int32_t dim, int64_t row_offset, const float* qf, int32_t nq, int32_t k, int32_t flags,
+                         int32_t* out_count, int64_t* out_rows, double* out_scores, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

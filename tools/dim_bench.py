@@ -9,6 +9,15 @@ One JSON line per point: ms, QPS and, for nq <= 8, the Phase-I corpus bytes per 
 corpus rows with d/16 .. d/4 flipped bits.
 
     python tools/dim_bench.py --out profiles/dim_bench.jsonl
+
+--exhaustive times K5d instead, the exact exhaustive top-k behind vrq_gemm_topk_dim / vrq_flat_ip_topk_dim
+(VRQ_GEMM_SCAN_EXACT, so 1024 runs it too): per mode and dim, nq = 1, 8, 64, 1024 at k = 10 over a corpus
+of a fixed byte count per mode (binary codes 256 MiB, int8 rows 1 GiB, float rows 2 GiB: with the int8
+shadow of the 1024 matrix path the largest allocation stays under 3 GiB).  Each line carries ms, QPS, row
+bytes per second as a share of the 8 TB/s HBM peak and the workspace bytes; at 1024 the forwarded matrix
+path is timed on the same buffers in the same run.
+
+    python tools/dim_bench.py --exhaustive --out profiles/exhaustive_dim_bench.jsonl
 """
 import argparse
 import json
@@ -66,6 +75,59 @@ def point(d, n, nq, mode, ms, cb):
     return rec
 
 
+EX_BYTES = {"binary": 1 << 28, "int8_cosine": 1 << 30, "float_ip": 1 << 31}
+EX_MODE = {"binary": N.VRQ_GEMM_BINARY, "int8_cosine": N.VRQ_GEMM_INT8_COSINE, "float_ip": N.VRQ_GEMM_FLOAT_IP}
+
+
+def exhaustive_leg(a, lib, dev, emit):
+    from vectorragquantization_amd.flat import flat_ip_prepare
+    st = N.stream_handle(dev)
+    for mode in a.modes.split(","):
+        m = EX_MODE[mode]
+        for d in (int(x) for x in a.dims.split(",")):
+            rb = d // 8 if mode == "binary" else d if mode == "int8_cosine" else 4 * d
+            n = EX_BYTES[mode] // rb
+            codes = x8 = norms = xf = inv = bounds = None
+            if mode == "binary":
+                codes = synth.random_codes(n, rb, device=dev)
+            elif mode == "int8_cosine":
+                x8 = torch.randint(-127, 127, (n, d), dtype=torch.int8, device=dev)
+                norms = int8_row_norms(x8)
+            else:
+                xf = torch.randn((n, d), device=dev) / d ** 0.5
+                if d == 1024:
+                    bounds = torch.zeros((2,), dtype=torch.float64, device=dev)
+                    x8, inv = flat_ip_prepare(xf, bounds)
+            for nq in (int(x) for x in a.nq.split(",")):
+                qf = torch.randn((nq, d), device=dev) / d ** 0.5
+                cnt = torch.empty((nq,), dtype=torch.int32, device=dev)
+                rows = torch.empty((nq, K_OUT), dtype=torch.int64, device=dev)
+                sc = torch.empty((nq, K_OUT), dtype=torch.float64, device=dev)
+                legs = [("k5d", N.VRQ_GEMM_SCAN_EXACT)] + ([("matrix", 0)] if d == 1024 else [])
+                for leg, flags in legs:
+                    need = N.gemm_topk_dim_workspace(lib, m, n, d, nq, K_OUT, flags)
+                    ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+
+                    def call():
+                        if mode == "float_ip":
+                            rc = lib.vrq_flat_ip_topk_dim(N.ptr(xf), N.ptr(x8), N.ptr(inv), N.ptr(bounds), n, d, 0,
+                                                          N.ptr(qf), nq, K_OUT, flags, N.ptr(cnt), N.ptr(rows),
+                                                          N.ptr(sc), N.ptr(ws), need, st)
+                        else:
+                            rc = lib.vrq_gemm_topk_dim(m, N.ptr(codes), N.ptr(x8), N.ptr(norms), n, d, 0, N.ptr(qf), nq,
+                                                       K_OUT, flags, N.ptr(cnt), N.ptr(rows), N.ptr(sc), N.ptr(ws),
+                                                       need, st)
+                        N.check(rc, "exhaustive top-k")
+                    ms = timed(call, a.warmup, a.reps)
+                    bps = n * rb / (ms * 1e-3)
+                    emit({"kernel": leg, "mode": mode, "dim": d, "n": n, "row_bytes": rb, "nq": nq, "k": K_OUT,
+                          "ms": round(ms, 4), "qps": round(nq / (ms * 1e-3), 1), "row_TBps": round(bps / 1e12, 4),
+                          "hbm_frac": round(bps / HBM_PEAK, 4), "workspace_bytes": int(need)})
+                    del ws
+            del codes, x8, norms, xf, inv, bounds
+            torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dims", default="256,384,512,768,1536,2048")
@@ -74,7 +136,12 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    ap.add_argument("--exhaustive", action="store_true",
+                    help="time K5d (exact exhaustive top-k) per mode and dim, 1024 included, instead of the search")
+    ap.add_argument("--modes", default="binary,int8_cosine,float_ip", help="--exhaustive: modes to time")
     a = ap.parse_args()
+    if a.exhaustive and a.dims == ap.get_default("dims"):
+        a.dims = "256,384,512,768,1024,1536,2048"
     dev = torch.device("cuda", 0)
     lib = N.load()
     out = open(a.out, "a") if a.out else None
@@ -86,6 +153,9 @@ def main():
             out.write(line + "\n")
             out.flush()
 
+    if a.exhaustive:
+        exhaustive_leg(a, lib, dev, emit)
+        return
     P1 = N.VRQ_SEARCH_PHASE1_ONLY
     for d in (int(x) for x in a.dims.split(",")):
         cb, n = d // 8, a.n

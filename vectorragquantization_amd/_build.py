@@ -20,7 +20,7 @@ LIB = os.path.join(PKG, "libvrq.so")
 PROBE_LIB = os.path.join(PKG, "libvrq_probe.so")
 OBJDIR = os.path.join(PKG, "_obj")
 SOURCES = ["hamming_scan.hip", "hamming_mfma.hip", "select_rescore.hip", "encode.hip", "gemm_topk.hip", "dequant.hip",
-           "search_dim.hip"]
+           "search_dim.hip", "exhaustive_dim.hip"]
 ARCH = os.environ.get("VRQ_OFFLOAD_ARCH", "gfx950")
 CFLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"--offload-arch={ARCH}",
           "-Wall", "-Wno-unused-function", "-Wno-unused-variable"]

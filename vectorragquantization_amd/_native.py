@@ -33,6 +33,7 @@ VRQ_GEMM_STAGE_SAMPLE = 16
 VRQ_GEMM_STAGE_MAIN = 32
 VRQ_GEMM_STAGE_FINISH = 64
 VRQ_GEMM_NO_FALLBACK = 128
+VRQ_GEMM_SCAN_EXACT = 256  # _dim entry points: the exact exhaustive scan (K5d) at dim 1024 too
 VRQ_RESCORE_F32 = 16  # vrq_rescore_dequant: compare_float32 rows
 VRQ_SCAN_KIND_VALU = 0
 VRQ_SCAN_KIND_MFMA = 1
@@ -82,6 +83,12 @@ SIGNATURES = {
     "vrq_gemm_topk_layout": (C.c_int, [_I32, _I64, _I32, _I32, _I32, _P]),
     "vrq_gemm_topk": (C.c_int, [_I32, _P, _P, _P, _I64, _I32, _I64, _P, _I32, _I32, _I32, _P, _P, _P, _P, _SZ,
                                 _P]),
+    "vrq_gemm_topk_dim_workspace_size": (_SZ, [_I32, _I64, _I32, _I32, _I32]),
+    "vrq_gemm_topk_dim_plan": (C.c_int, [_I32, _I64, _I32, _I32, _I32, _P]),
+    "vrq_gemm_topk_dim": (C.c_int, [_I32, _P, _P, _P, _I64, _I32, _I64, _P, _I32, _I32, _I32, _P, _P, _P, _P, _SZ,
+                                    _P]),
+    "vrq_flat_ip_topk_dim": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I64, _P, _I32, _I32, _I32, _P, _P, _P, _P, _SZ,
+                                       _P]),
     "vrq_flat_ip_prepare": (C.c_int, [_P, _I64, _I32, _P, _P, _P, _P]),
     "vrq_flat_ip_topk": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I64, _P, _I32, _I32, _I32, _P, _P, _P, _P, _SZ,
                                    _P]),
@@ -155,6 +162,18 @@ def load_probe():
         if _probe is None:
             _probe = _open(_build.PROBE_LIB, _build.PROBE_LIB, probe=True)
         return _probe
+
+
+def gemm_topk_dim_workspace(lib, mode: int, n: int, dim: int, nq: int, k: int, flags: int = 0) -> int:
+    """Workspace bytes of a vrq_gemm_topk_dim / vrq_flat_ip_topk_dim call (0: unsupported shape).  At
+    dim 1024 with VRQ_GEMM_SCAN_EXACT: the maximum of the forwarded path's size and the exact scan's."""
+    need = lib.vrq_gemm_topk_dim_workspace_size(mode, n, dim, nq, k)
+    if dim == 1024 and flags & VRQ_GEMM_SCAN_EXACT:
+        info = (C.c_int64 * 6)()
+        if lib.vrq_gemm_topk_dim_plan(mode, n, dim, nq, k, info) != VRQ_OK:
+            return 0
+        need = max(need, int(info[5]))
+    return need
 
 
 def check(rc: int, what: str) -> None:

@@ -67,7 +67,9 @@ def gemm_topk(mode: str, qf: torch.Tensor, k: int, codes: torch.Tensor | None = 
     batch over EVERY row on the matrix cores (``vrq_gemm_topk``, BASELINE config 5): the scores of
     ``CohereEnhancedVectorDB.py:283-293`` / ``:302-318`` ordered like the reference's stable
     ``sorted(..., reverse=True)`` over rows in index order.  Returns (count i32[nq], rows i64[nq, k],
-    scores f64[nq, k]) device tensors.  ``flags``: VRQ_GEMM_STAGE_* / VRQ_GEMM_NO_FALLBACK; ``lib``:
+    scores f64[nq, k]) device tensors.  At the other supported dims (256 ... 2048), or with
+    VRQ_GEMM_SCAN_EXACT in ``flags``, the call goes through ``vrq_gemm_topk_dim`` to the exact
+    exhaustive scan (K5d); same return contract.  ``flags``: VRQ_GEMM_STAGE_* / VRQ_GEMM_NO_FALLBACK; ``lib``:
     another build of the library (the probe build, for sweeps), default libvrq.so."""
     m = {"binary": N.VRQ_GEMM_BINARY, "int8_cosine": N.VRQ_GEMM_INT8_COSINE}[mode]
     src = codes if m == N.VRQ_GEMM_BINARY else x8
@@ -77,6 +79,19 @@ def gemm_topk(mode: str, qf: torch.Tensor, k: int, codes: torch.Tensor | None = 
     rows = torch.full((nq, k), -2, dtype=torch.int64, device=dev)
     scores = torch.empty((nq, k), dtype=torch.float64, device=dev)
     lib = lib or N.load()
+    dim = qf.shape[1]
+    if dim != 1024 or flags & N.VRQ_GEMM_SCAN_EXACT:
+        # the exact exhaustive scan (K5d) behind vrq_gemm_topk_dim: every supported dim, no matrix pass
+        need = N.gemm_topk_dim_workspace(lib, m, n, dim, nq, k, flags)
+        if need == 0:
+            raise N.VrqNativeError(f"vrq_gemm_topk_dim: unsupported shape n={n} dim={dim} nq={nq} k={k} "
+                                   "(dims: vrq_dim_supported)")
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+        N.check(lib.vrq_gemm_topk_dim(m, N.ptr(codes), N.ptr(x8), N.ptr(norms), n, dim, row_offset, N.ptr(qf), nq,
+                                      k, flags, N.ptr(cnt), N.ptr(rows), N.ptr(scores), N.ptr(workspace),
+                                      workspace.numel(), N.stream_handle(dev)), "vrq_gemm_topk_dim")
+        return cnt, rows, scores
     need = lib.vrq_gemm_topk_workspace_size(m, n, qf.shape[1], nq, k)
     if need == 0:
         raise N.VrqNativeError(f"vrq_gemm_topk: unsupported shape n={n} dim={qf.shape[1]} nq={nq} k={k}")

@@ -11,7 +11,9 @@ bypass HTTP: ``add_vectors`` / ``search_vectors``.
 Device layout (rows = FAISS internal order): the float32 rows xf[n, 1024] (the exact scores read
 them), the matrix pass's per-row-scaled int8 copy x8[n, 1024] and 1/scale f64[n], and the corpus
 error bounds f64[2] -- all from ``vrq_flat_ip_prepare`` at add time.  A search is one
-``vrq_flat_ip_topk`` call for the whole query batch.
+``vrq_flat_ip_topk`` call for the whole query batch.  At the other supported dims (256, 384, 512,
+768, 1536, 2048) the index keeps only xf and the ids, and a search is one ``vrq_flat_ip_topk_dim``
+call: the exact exhaustive scan (K5d), no prepare step.
 """
 from __future__ import annotations
 
@@ -47,13 +49,28 @@ def flat_ip_topk(xf: torch.Tensor, x8: torch.Tensor, inv_scale: torch.Tensor, bo
                  workspace: torch.Tensor | None = None):
     """Exact IndexFlatIP top-k of a query batch (``vrq_flat_ip_topk``).  Returns device tensors
     (count i32[nq], rows i64[nq, k] (+ row_offset, -1 padded), scores f64[nq, k] holding float32
-    values), ordered (score desc, row asc)."""
+    values), ordered (score desc, row asc).  Off dim 1024 (or with VRQ_GEMM_SCAN_EXACT) the exact
+    exhaustive scan behind ``vrq_flat_ip_topk_dim`` serves the call from ``xf`` alone."""
     dev = qf.device
     nq, n = qf.shape[0], xf.shape[0]
     cnt = torch.full((nq,), -2, dtype=torch.int32, device=dev)  # -2: never written
     rows = torch.full((nq, k), -2, dtype=torch.int64, device=dev)
     scores = torch.empty((nq, k), dtype=torch.float64, device=dev)
     lib = N.load()
+    dim = qf.shape[1]
+    if dim != 1024 or flags & N.VRQ_GEMM_SCAN_EXACT:
+        # the exact exhaustive scan (K5d): reads xf only; x8 / inv_scale / bounds may be None
+        need = N.gemm_topk_dim_workspace(lib, N.VRQ_GEMM_FLOAT_IP, n, dim, nq, k, flags)
+        if need == 0:
+            raise N.VrqNativeError(f"vrq_flat_ip_topk_dim: unsupported shape n={n} dim={dim} nq={nq} k={k} "
+                                   "(dims: vrq_dim_supported)")
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+        N.check(lib.vrq_flat_ip_topk_dim(N.ptr(xf), N.ptr(x8), N.ptr(inv_scale), N.ptr(bounds), n, dim, row_offset,
+                                         N.ptr(qf), nq, k, flags, N.ptr(cnt), N.ptr(rows), N.ptr(scores),
+                                         N.ptr(workspace), workspace.numel(), N.stream_handle(dev)),
+                "vrq_flat_ip_topk_dim")
+        return cnt, rows, scores
     need = lib.vrq_gemm_topk_workspace_size(N.VRQ_GEMM_FLOAT_IP, n, qf.shape[1], nq, k)
     if need == 0:
         raise N.VrqNativeError(f"vrq_flat_ip_topk: unsupported shape n={n} dim={qf.shape[1]} nq={nq} k={k}")
@@ -106,13 +123,21 @@ class FloatIndexIDMap:
     ``search``, ``reconstruct``, ``remove_ids``, ``ntotal`` and the ``index.faiss`` format."""
 
     def __init__(self, d: int = 1024, device=None):
+        if not N.load().vrq_dim_supported(int(d)):
+            raise ValueError(f"FloatIndexIDMap: d = {d} is not an embedding dim vrq_dim_supported accepts "
+                             "(256, 384, 512, 768, 1024, 1536, 2048)")
         self.d = d
         self.device = _device(device)
         self._xf = _GrowBuffer((d,), torch.float32, self.device)
-        self._x8 = _GrowBuffer((d,), torch.int8, self.device)
-        self._inv = _GrowBuffer((), torch.float64, self.device)
         self._ids = _GrowBuffer((), torch.int64, self.device)
-        self.bounds = torch.zeros((2,), dtype=torch.float64, device=self.device)
+        # the matrix pass's operands exist at 1024 only; the other dims search xf with the exact scan
+        self._matrix = d == 1024
+        if self._matrix:
+            self._x8 = _GrowBuffer((d,), torch.int8, self.device)
+            self._inv = _GrowBuffer((), torch.float64, self.device)
+            self.bounds = torch.zeros((2,), dtype=torch.float64, device=self.device)
+        else:
+            self._x8 = self._inv = self.bounds = None
         self._ws = None
 
     @property
@@ -132,22 +157,24 @@ class FloatIndexIDMap:
         xf = as_device_tensor(x, torch.float32, self.device).reshape(ids_t.shape[0], self.d)
         if ids_t.shape[0] == 0:
             return
-        with torch.cuda.device(self.device):
-            x8, inv = flat_ip_prepare(xf, self.bounds)
+        if self._matrix:
+            with torch.cuda.device(self.device):
+                x8, inv = flat_ip_prepare(xf, self.bounds)
+            self._x8.append(x8)
+            self._inv.append(inv)
         self._xf.append(xf)
-        self._x8.append(x8)
-        self._inv.append(inv)
         self._ids.append(ids_t)
 
     def search_rows(self, qf, k: int, flags: int = 0):
         """Device (count, rows, scores) of the exact top-k (internal rows); ``flags`` as
         ``vrq_flat_ip_topk`` (e.g. VRQ_GEMM_NO_FALLBACK)."""
         qf = as_device_tensor(qf, torch.float32, self.device).reshape(-1, self.d)
-        lib = N.load()
-        need = lib.vrq_gemm_topk_workspace_size(N.VRQ_GEMM_FLOAT_IP, self.ntotal, self.d, qf.shape[0], k)
+        need = N.gemm_topk_dim_workspace(N.load(), N.VRQ_GEMM_FLOAT_IP, self.ntotal, self.d, qf.shape[0], k, flags)
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty((max(need, 8),), dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
+            if not self._matrix:
+                return flat_ip_topk(self._xf.view(), None, None, None, qf, k, flags=flags, workspace=self._ws)
             return flat_ip_topk(self._xf.view(), self._x8.view(), self._inv.view(), self.bounds, qf, k,
                                 flags=flags, workspace=self._ws)
 
@@ -182,7 +209,8 @@ class FloatIndexIDMap:
         removed = int(self.ntotal - int(keep.sum()))
         if removed:
             for b in (self._xf, self._x8, self._inv, self._ids):
-                b.keep(keep)
+                if b is not None:
+                    b.keep(keep)
         return removed  # the bounds stay valid upper bounds over the survivors
 
     def to_bytes(self) -> bytes:
@@ -218,6 +246,9 @@ class CohereVectorDBFloat:
         self.folder = folder
         self.model = model
         self.embedding_dim = embedding_dim
+        if not N.load().vrq_dim_supported(int(embedding_dim)):  # before anything is written to the folder
+            raise ValueError(f"CohereVectorDBFloat: embedding_dim = {embedding_dim} is not an embedding dim "
+                             "vrq_dim_supported accepts (256, 384, 512, 768, 1024, 1536, 2048)")
         self._setup_config(folder, model, embedding_dim)
         path = os.path.join(folder, "index.faiss")
         if os.path.exists(path):                                            # :55-64
