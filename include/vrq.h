@@ -89,8 +89,8 @@ const char* vrq_strerror(int code);
  * out_dist   i32[nq, k]  ascending (dist, row) -- FAISS order; missing = INT32_MAX
  * out_rows   i64[nq, k]  row_offset + row; missing = -1
  * Supported: code_bytes in {32, 48, 64, 96, 128, 192, 256} (d = 256, 384, 512, 768, 1024, 1536,
- * 2048), 1 <= k <= 1024, n <= 2^32.  The matrix-core scan serves 128-byte codes only; the other
- * sizes always take the wavefront popcount scan.
+ * 2048), 1 <= k <= 1024, n <= 2^32.  Every code size has a matrix-core scan (k <= 128, n >= 65536); it is
+ * chosen by shape, see vrq_scan_kind.
  * ------------------------------------------------------------------------- */
 size_t vrq_hamming_topk_workspace_size(int64_t n, int32_t code_bytes, int32_t nq, int32_t k);
 int vrq_hamming_topk(const uint8_t* codes, int64_t n, int32_t code_bytes, int64_t row_offset,
@@ -142,9 +142,16 @@ int vrq_search3_finish(const uint8_t* codes, const int8_t* x8, const double* nor
  *   source of truth for the functions below, which return VRQ_EUNSUPPORTED for every other dim).
  * vrq_search3_dim / vrq_search3_dim_workspace_size: the arguments and semantics of vrq_search3 /
  *   vrq_search3_workspace_size.  At dim == 1024 they forward to them (identical results and
- *   workspace size, every flag).  At the other dims: flags 0 and VRQ_SEARCH_PHASE1_ONLY;
- *   VRQ_SEARCH_SCAN_VALU is accepted (the wavefront scan is the only one there);
- *   VRQ_SEARCH_SCAN_MFMA, VRQ_SCAN_STAGE_* and VRQ_SEARCH_SHARD return VRQ_EUNSUPPORTED.
+ *   workspace size, every flag).  At the other dims: flags 0 and VRQ_SEARCH_PHASE1_ONLY; the Phase-I
+ *   scan is chosen by shape (vrq_scan_kind tells which) and VRQ_SEARCH_SCAN_VALU forces the wavefront
+ *   scan (identical results); VRQ_SEARCH_SCAN_MFMA, VRQ_SCAN_STAGE_* and VRQ_SEARCH_SHARD return
+ *   VRQ_EUNSUPPORTED here: forcing and staging the matrix-core scan go through the pair below.
+ * vrq_search3_dim_scan / vrq_search3_dim_finish: the two launches vrq_search3_dim is made of, with the
+ *   arguments of vrq_search3_scan / vrq_search3_finish (the same flags to both).  At dim == 1024 they
+ *   forward.  At the other dims they accept VRQ_SEARCH_PHASE1_ONLY, VRQ_SEARCH_SCAN_VALU,
+ *   VRQ_SEARCH_SCAN_MFMA (the row-split matrix-core scan K1rd, for K <= 128 and n >= 65536) and
+ *   VRQ_SCAN_STAGE_*; VRQ_SEARCH_SHARD returns VRQ_EUNSUPPORTED.  The workspace size of
+ *   vrq_search3_dim_workspace_size covers either scan.
  * vrq_rescore_binary_dim / vrq_rescore_int8_cosine_dim: the arguments of vrq_rescore_binary /
  *   vrq_rescore_int8_cosine; at 1024 they forward to them (bit-identical).
  * ------------------------------------------------------------------------- */
@@ -155,14 +162,21 @@ int vrq_search3_dim(const uint8_t* codes, const int8_t* x8, const double* norms,
                     int32_t k, int32_t K, int32_t K3, int32_t flags, int32_t* out_count, int64_t* out_rows,
                     int32_t* out_dist, double* out_binary, double* out_cosine, void* workspace,
                     size_t workspace_bytes, void* stream);
+int vrq_search3_dim_scan(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq,
+                         int32_t K, int32_t flags, void* workspace, size_t workspace_bytes, void* stream);
+int vrq_search3_dim_finish(const uint8_t* codes, const int8_t* x8, const double* norms,
+                           const int64_t* rescore_row, int64_t n, int32_t dim, int64_t row_offset,
+                           const float* qf, int32_t nq, int32_t k, int32_t K, int32_t K3, int32_t flags,
+                           int32_t* out_count, int64_t* out_rows, int32_t* out_dist, double* out_binary,
+                           double* out_cosine, const void* workspace, size_t workspace_bytes, void* stream);
 int vrq_rescore_binary_dim(const float* qf, int32_t nq, int32_t dim, const uint8_t* codes, int64_t n,
                            const int64_t* cand_rows, int32_t ncand, double* out, void* stream);
 int vrq_rescore_int8_cosine_dim(const float* qf, int32_t nq, int32_t dim, const int8_t* x8,
                                 const double* norms, int64_t n, const int64_t* cand_rows,
                                 int32_t ncand, double* out, void* stream);
 
-/* Which Phase-I scan vrq_search3 / vrq_search3_scan / vrq_hamming_topk would run for this
- * shape and flags: VRQ_SCAN_KIND_VALU (wavefront popcount) or VRQ_SCAN_KIND_MFMA (matrix
+/* Which Phase-I scan vrq_search3 / vrq_search3_scan / vrq_hamming_topk (and the _dim entry points,
+ * for every dim of vrq_dim_supported) would run for this shape and flags: VRQ_SCAN_KIND_VALU (wavefront popcount) or VRQ_SCAN_KIND_MFMA (matrix
  * core; *prefix_rows, if non-NULL, receives the rows scanned outside the thresholded
  * matrix-core pass: 0, or n for the wavefront scan), or a
  * negative VRQ_E* code for an unsupported shape.  Host-only, no device work. */
@@ -175,14 +189,18 @@ int vrq_scan_kind(int64_t n, int32_t dim, int32_t nq, int32_t K, int32_t flags, 
  * the candidate lists (u64 keys (v + 1025) << 40 | row, v = dist - tau), of the list lengths (i32
  * [nq][chunks]) and of tau_s / tau_p / rerun (i32 [nq] each, 256-B aligned), sample rows, sampled
  * order j, offset of the sorted K-lists, workspace bytes.  VRQ_EUNSUPPORTED when the shape takes the
- * wavefront scan. */
+ * wavefront scan.  At the other dims of vrq_dim_supported the fields keep their meaning: info[0] = 3, the
+ * row-split kernel of the other code sizes (K1rd), info[1] its M-blocks per wave (the grid holds
+ * ceil(nq / (32 info[1])) query blocks per chunk group); the key bias is dim + 1 (keys
+ * (v + dim + 1) << 40 | row) where it is 1025 at 1024. */
 int vrq_scan_plan(int64_t n, int32_t dim, int32_t nq, int32_t K, int32_t flags, int64_t* info);
 /* Host-only introspection of the matrix-core scan's dense sample pass (tests and tools): info i64[6]
  * = the row-split kernel runs it (1) or K1m's MB = 2 instance (0), sample chunks, rows per sample
  * chunk, rows between consecutive sample chunks, rows between consecutive 64-row sample tiles, and
  * the u16 lane-minimum columns per query at workspace offset 0 (32 per sample chunk: column
  * chunk * 32 + r = min over the chunk's tiles and both 32-row halves of tile row r of
- * dist - popcount(query), + 1024).  VRQ_EUNSUPPORTED when the shape takes the wavefront scan. */
+ * dist - popcount(query), + 1024; + dim at the other dims, where info[0] is 1).  VRQ_EUNSUPPORTED when
+ * the shape takes the wavefront scan. */
 int vrq_scan_sample_plan(int64_t n, int32_t dim, int32_t nq, int32_t K, int32_t flags, int64_t* info);
 
 /* ---------------------------------------------------------------------------

@@ -18,6 +18,15 @@ bytes per second as a share of the 8 TB/s HBM peak and the workspace bytes; at 1
 path is timed on the same buffers in the same run.
 
     python tools/dim_bench.py --exhaustive --out profiles/exhaustive_dim_bench.jsonl
+
+--ab times the two Phase-I scans of the other dims against each other on the same buffers in the same run
+(vrq_search3_dim_scan + vrq_search3_dim_finish): the wavefront scan K1d forced by VRQ_SEARCH_SCAN_VALU --
+the yardstick, timed twice per point, before and after the other leg -- and the matrix-core scan K1rd
+forced by VRQ_SEARCH_SCAN_MFMA, Phase I only and full, plus "auto" (no forcing flag: the default choice).
+Each matrix line carries the corpus re-read factor ceil(nq / (32 MB)) and the Phase-I rate
+2 dim nq n / time in POPS and as a share of the 10.07 POPS FP4 dense peak.
+
+    python tools/dim_bench.py --ab --nq 1,8,64,128,1024 --out profiles/dim_mfma_bench.jsonl
 """
 import argparse
 import json
@@ -73,6 +82,67 @@ def point(d, n, nq, mode, ms, cb):
         rec["phase1_TBps"] = round(bps / 1e12, 3)
         rec["hbm_frac"] = round(bps / HBM_PEAK, 3)
     return rec
+
+
+FP4_PEAK = 10.07e15
+
+
+def pair_call(lib, codes, x8, norms, qf, qb, dim, flags, dev):
+    """One search as the stage-able pair (the forcing flags go to both launches)."""
+    n, nq = codes.shape[0], qb.shape[0]
+    kout = K1 if flags & N.VRQ_SEARCH_PHASE1_ONLY else K_OUT
+    ws = torch.empty((lib.vrq_search3_dim_workspace_size(n, dim, nq, K1),), dtype=torch.uint8, device=dev)
+    cnt = torch.empty((nq,), dtype=torch.int32, device=dev)
+    rows = torch.empty((nq, kout), dtype=torch.int64, device=dev)
+    dist = torch.empty((nq, kout), dtype=torch.int32, device=dev)
+    s2 = torch.empty((nq, kout), dtype=torch.float64, device=dev)
+    s3 = torch.empty((nq, kout), dtype=torch.float64, device=dev)
+    st = N.stream_handle(dev)
+    keep = (ws, cnt, rows, dist, s2, s3)
+
+    def call():
+        N.check(lib.vrq_search3_dim_scan(N.ptr(codes), n, dim, N.ptr(qb), nq, K1, flags, N.ptr(ws), ws.numel(), st),
+                "vrq_search3_dim_scan")
+        N.check(lib.vrq_search3_dim_finish(N.ptr(codes), N.ptr(x8), N.ptr(norms), 0, n, dim, 0, N.ptr(qf), nq, K_OUT,
+                                           K1, K3, flags, N.ptr(cnt), N.ptr(rows), N.ptr(dist), N.ptr(s2), N.ptr(s3),
+                                           N.ptr(ws), ws.numel(), st), "vrq_search3_dim_finish")
+    return call, keep
+
+
+def ab_leg(a, lib, dev, emit):
+    import numpy as np
+    P1 = N.VRQ_SEARCH_PHASE1_ONLY
+    for d in (int(x) for x in a.dims.split(",")):
+        cb, n = d // 8, a.n
+        codes = synth.random_codes(n, cb, device=dev)
+        x8 = torch.randint(-127, 127, (n, d), dtype=torch.int8, device=dev)
+        norms = int8_row_norms(x8)
+        for nq in (int(x) for x in a.nq.split(",")):
+            qb, _ = synth.flip_queries(codes, nq, flips=(d // 16, d // 4))
+            qf = torch.randn((nq, d), device=dev) / d ** 0.5
+            info = np.zeros(12, np.int64)
+            N.check(lib.vrq_scan_plan(n, d, nq, K1, N.VRQ_SEARCH_SCAN_MFMA, info.ctypes.data), "vrq_scan_plan")
+            mb = int(info[1])
+            auto = "mfma" if lib.vrq_scan_kind(n, d, nq, K1, 0, None) == N.VRQ_SCAN_KIND_MFMA else "valu"
+            for mode, mflags in (("phase1", P1), ("full", 0)):
+                legs = (("valu", N.VRQ_SEARCH_SCAN_VALU, 0), ("mfma", N.VRQ_SEARCH_SCAN_MFMA, 0),
+                        ("valu", N.VRQ_SEARCH_SCAN_VALU, 1), ("auto", 0, 0))
+                for scan, sflags, rep in legs:
+                    call, keep = pair_call(lib, codes, x8, norms, qf, qb, d, mflags | sflags, dev)
+                    ms = timed(call, a.warmup, a.reps)
+                    rec = {"dim": d, "n": n, "nq": nq, "mode": mode, "scan": scan, "repeat": rep, "ms": round(ms, 4),
+                           "qps": round(nq / (ms * 1e-3), 1)}
+                    if scan == "auto":
+                        rec["auto_is"] = auto
+                    if scan == "mfma":
+                        rec.update({"mb": mb, "reread": -(-nq // (32 * mb)), "workspace_bytes": int(info[11])})
+                        if mode == "phase1":
+                            pops = 2.0 * d * nq * n / (ms * 1e-3)
+                            rec.update({"phase1_pops": round(pops / 1e15, 4), "fp4_peak_frac": round(pops / FP4_PEAK, 4)})
+                    emit(rec)
+                    del call, keep
+        del codes, x8, norms
+        torch.cuda.empty_cache()
 
 
 EX_BYTES = {"binary": 1 << 28, "int8_cosine": 1 << 30, "float_ip": 1 << 31}
@@ -138,6 +208,8 @@ def main():
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     ap.add_argument("--exhaustive", action="store_true",
                     help="time K5d (exact exhaustive top-k) per mode and dim, 1024 included, instead of the search")
+    ap.add_argument("--ab", action="store_true",
+                    help="time the forced wavefront scan (twice) and the forced matrix-core scan on the same buffers")
     ap.add_argument("--modes", default="binary,int8_cosine,float_ip", help="--exhaustive: modes to time")
     a = ap.parse_args()
     if a.exhaustive and a.dims == ap.get_default("dims"):
@@ -155,6 +227,9 @@ def main():
 
     if a.exhaustive:
         exhaustive_leg(a, lib, dev, emit)
+        return
+    if a.ab:
+        ab_leg(a, lib, dev, emit)
         return
     P1 = N.VRQ_SEARCH_PHASE1_ONLY
     for d in (int(x) for x in a.dims.split(",")):

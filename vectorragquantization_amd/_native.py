@@ -37,6 +37,7 @@ VRQ_GEMM_SCAN_EXACT = 256  # _dim entry points: the exact exhaustive scan (K5d) 
 VRQ_RESCORE_F32 = 16  # vrq_rescore_dequant: compare_float32 rows
 VRQ_SCAN_KIND_VALU = 0
 VRQ_SCAN_KIND_MFMA = 1
+VRQ_SCAN_PLAN_K1RD = 3  # info[0] of vrq_scan_plan at the dims other than 1024
 
 ENC_MODES = {
     "int8g": 0,   # VectorDBInt8Global
@@ -65,6 +66,9 @@ SIGNATURES = {
     "vrq_search3_dim_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
     "vrq_search3_dim": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32,
                                   _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "vrq_search3_dim_scan": (C.c_int, [_P, _I64, _I32, _P, _I32, _I32, _I32, _P, _SZ, _P]),
+    "vrq_search3_dim_finish": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I64, _P, _I32, _I32, _I32, _I32, _I32,
+                                         _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "vrq_rescore_binary_dim": (C.c_int, [_P, _I32, _I32, _P, _I64, _P, _I32, _P, _P]),
     "vrq_rescore_int8_cosine_dim": (C.c_int, [_P, _I32, _I32, _P, _P, _I64, _P, _I32, _P, _P]),
     "vrq_scan_kind": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _P]),

@@ -781,6 +781,9 @@ size_t vrq_hamming_topk_workspace_size(int64_t n, int32_t code_bytes, int32_t nq
   MfmaPlan mp;
   if (code_bytes == 128 && mfma_use(n, nq, k, 0) && mfma_plan(n, nq, k, &mp) == VRQ_OK)
     return mp.bytes > p.list_bytes ? mp.bytes : p.list_bytes;
+  // the other code sizes: wherever the matrix-core scan (K1rd) can be chosen
+  if (code_bytes != 128 && k <= kMfmaMaxK && n >= kMfmaMinRows && mfma_dim_plan(n, code_bytes, nq, k, &mp) == VRQ_OK)
+    return mp.bytes > p.list_bytes ? mp.bytes : p.list_bytes;
   return p.list_bytes;
 }
 
@@ -820,6 +823,17 @@ int vrq_hamming_topk(const uint8_t* codes, int64_t n, int32_t code_bytes, int64_
     if (rc != VRQ_OK) return rc;
     return launch_select(s, nq, lists, 0, (const uint64_t*)((uint8_t*)workspace + mp.off_suffix), k, nullptr,
                          nullptr, nullptr, nullptr, 1, fa);
+  }
+  if (code_bytes != 128 && mfma_dim_use(n, code_bytes, nq, k, 0)) {
+    MfmaPlan mp;
+    int rc = mfma_dim_plan(n, code_bytes, nq, k, &mp);
+    if (rc != VRQ_OK) return rc;
+    if (workspace_bytes < mp.bytes) return VRQ_EWORKSPACE;
+    rc = mfma_dim_scan_launch(mp, codes, n, code_bytes, queries, nq, k, (uint8_t*)workspace, s, 0);
+    if (rc != VRQ_OK) return rc;
+    // (the sorted K-list per query is one list of the merge)
+    return launch_select_dim(s, nq, (const uint64_t*)((uint8_t*)workspace + mp.off_suffix), 1, k, code_bytes * 8,
+                             nullptr, nullptr, nullptr, nullptr, 1, fa);
   }
   ScanPlan p;
   int rc = scan_plan(n, code_bytes, nq, k, &p);
@@ -922,10 +936,10 @@ int vrq_search3(const uint8_t* codes, const int8_t* x8, const double* norms, con
 
 int vrq_scan_kind(int64_t n, int32_t dim, int32_t nq, int32_t K, int32_t flags, int64_t* prefix_rows) {
   if (n < 1 || nq < 1 || K < 1) return VRQ_EINVAL;
-  if (dim != DIM || K > KMAX) return VRQ_EUNSUPPORTED;
-  if (mfma_use(n, nq, K, flags)) {
+  if (!vrq_dim_supported(dim) || K > KMAX) return VRQ_EUNSUPPORTED;
+  if (dim != DIM ? mfma_dim_use(n, dim / 8, nq, K, flags) : mfma_use(n, nq, K, flags)) {
     MfmaPlan mp;
-    const int rc = mfma_plan(n, nq, K, &mp);
+    const int rc = dim != DIM ? mfma_dim_plan(n, dim / 8, nq, K, &mp) : mfma_plan(n, nq, K, &mp);
     if (rc != VRQ_OK) return rc;
     if (prefix_rows) *prefix_rows = 0;  // every row goes through the matrix-core pass
     return VRQ_SCAN_KIND_MFMA;
@@ -939,12 +953,12 @@ int vrq_scan_kind(int64_t n, int32_t dim, int32_t nq, int32_t K, int32_t flags, 
 
 int vrq_scan_plan(int64_t n, int32_t dim, int32_t nq, int32_t K, int32_t flags, int64_t* info) {
   if (!info || n < 1 || nq < 1 || K < 1) return VRQ_EINVAL;
-  if (dim != DIM || K > KMAX) return VRQ_EUNSUPPORTED;
-  if (!mfma_use(n, nq, K, flags)) return VRQ_EUNSUPPORTED;
+  if (!vrq_dim_supported(dim) || K > KMAX) return VRQ_EUNSUPPORTED;
+  if (!(dim != DIM ? mfma_dim_use(n, dim / 8, nq, K, flags) : mfma_use(n, nq, K, flags))) return VRQ_EUNSUPPORTED;
   MfmaPlan p;
-  const int rc = mfma_plan(n, nq, K, &p);
+  const int rc = dim != DIM ? mfma_dim_plan(n, dim / 8, nq, K, &p) : mfma_plan(n, nq, K, &p);
   if (rc != VRQ_OK) return rc;
-  info[0] = p.rows ? 1 : p.swap ? 2 : 0;
+  info[0] = dim != DIM ? kMfmaKindRowsDim : p.rows ? 1 : p.swap ? 2 : 0;
   info[1] = p.mb;
   info[2] = p.chunk_rows;
   info[3] = p.nchunks;
@@ -961,10 +975,10 @@ int vrq_scan_plan(int64_t n, int32_t dim, int32_t nq, int32_t K, int32_t flags, 
 
 int vrq_scan_sample_plan(int64_t n, int32_t dim, int32_t nq, int32_t K, int32_t flags, int64_t* info) {
   if (!info || n < 1 || nq < 1 || K < 1) return VRQ_EINVAL;
-  if (dim != DIM || K > KMAX) return VRQ_EUNSUPPORTED;
-  if (!mfma_use(n, nq, K, flags)) return VRQ_EUNSUPPORTED;
+  if (!vrq_dim_supported(dim) || K > KMAX) return VRQ_EUNSUPPORTED;
+  if (!(dim != DIM ? mfma_dim_use(n, dim / 8, nq, K, flags) : mfma_use(n, nq, K, flags))) return VRQ_EUNSUPPORTED;
   MfmaPlan p;
-  const int rc = mfma_plan(n, nq, K, &p);
+  const int rc = dim != DIM ? mfma_dim_plan(n, dim / 8, nq, K, &p) : mfma_plan(n, nq, K, &p);
   if (rc != VRQ_OK) return rc;
   info[0] = p.rows_sample;
   info[1] = p.sample_chunks;
@@ -1042,22 +1056,48 @@ size_t vrq_search3_dim_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_
   if (n < 1 || nq < 1 || K < 1 || !vrq_dim_supported(dim)) return 0;
   ScanPlan p;
   if (scan_plan(n, dim / 8, nq, K, &p) != VRQ_OK) return 0;
+  MfmaPlan mp;  // wherever the matrix-core scan (K1rd) can be chosen: the larger of the two
+  if (K <= kMfmaMaxK && n >= kMfmaMinRows && mfma_dim_plan(n, dim / 8, nq, K, &mp) == VRQ_OK)
+    return mp.bytes > p.list_bytes ? mp.bytes : p.list_bytes;
   return p.list_bytes;
 }
 
-int vrq_search3_dim(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
-                    int64_t n, int32_t dim, int64_t row_offset, const float* qf, const uint8_t* qb, int32_t nq,
-                    int32_t k, int32_t K, int32_t K3, int32_t flags, int32_t* out_count, int64_t* out_rows,
-                    int32_t* out_dist, double* out_binary, double* out_cosine, void* workspace,
-                    size_t workspace_bytes, void* stream) {
+int vrq_search3_dim_scan(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq, int32_t K,
+                         int32_t flags, void* workspace, size_t workspace_bytes, void* stream) {
+  if (dim == DIM) return vrq_search3_scan(codes, n, dim, qb, nq, K, flags, workspace, workspace_bytes, stream);
+  VRQ_CHECK_ARG(n >= 0 && nq >= 0 && K >= 0);
+  if (!vrq_dim_supported(dim) || K > KMAX) return VRQ_EUNSUPPORTED;
+  if (flags & VRQ_SEARCH_SHARD) return VRQ_EUNSUPPORTED;  // the sharded mode is 1024-only
+  if (nq == 0 || n == 0 || K == 0) return VRQ_OK;
+  VRQ_CHECK_ARG(codes && qb && workspace);
+  const int cb = dim / 8;
+  if (mfma_dim_use(n, cb, nq, K, flags)) {
+    MfmaPlan mp;
+    const int rc = mfma_dim_plan(n, cb, nq, K, &mp);
+    if (rc != VRQ_OK) return rc;
+    if (workspace_bytes < mp.bytes) return VRQ_EWORKSPACE;
+    return mfma_dim_scan_launch(mp, codes, n, cb, qb, nq, K, (uint8_t*)workspace, (hipStream_t)stream, flags);
+  }
+  ScanPlan p;
+  const int rc = scan_plan(n, cb, nq, K, &p);
+  if (rc != VRQ_OK) return rc;
+  if (workspace_bytes < p.list_bytes) return VRQ_EWORKSPACE;
+  if (p.nchunks > MAX_LISTS) return VRQ_EUNSUPPORTED;
+  return scan_launch(p, codes, n, cb, qb, nq, K, (uint64_t*)workspace, (hipStream_t)stream);
+}
+
+int vrq_search3_dim_finish(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
+                           int64_t n, int32_t dim, int64_t row_offset, const float* qf, int32_t nq, int32_t k,
+                           int32_t K, int32_t K3, int32_t flags, int32_t* out_count, int64_t* out_rows,
+                           int32_t* out_dist, double* out_binary, double* out_cosine, const void* workspace,
+                           size_t workspace_bytes, void* stream) {
   if (dim == DIM)
-    return vrq_search3(codes, x8, norms, rescore_row, n, dim, row_offset, qf, qb, nq, k, K, K3, flags, out_count,
-                       out_rows, out_dist, out_binary, out_cosine, workspace, workspace_bytes, stream);
+    return vrq_search3_finish(codes, x8, norms, rescore_row, n, dim, row_offset, qf, nq, k, K, K3, flags, out_count,
+                              out_rows, out_dist, out_binary, out_cosine, workspace, workspace_bytes, stream);
   VRQ_CHECK_ARG(n >= 0 && nq >= 0 && k >= 0 && K >= 0 && K3 >= 0);
   VRQ_CHECK_ARG(out_count && out_rows && out_dist);
   if (!vrq_dim_supported(dim) || K > KMAX) return VRQ_EUNSUPPORTED;
-  // the matrix-core scans and the sharded mode are 1024-only; VRQ_SEARCH_SCAN_VALU names the only scan there is
-  if (flags & ~(VRQ_SEARCH_PHASE1_ONLY | VRQ_SEARCH_SCAN_VALU)) return VRQ_EUNSUPPORTED;
+  if (flags & VRQ_SEARCH_SHARD) return VRQ_EUNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   const int mode = (flags & VRQ_SEARCH_PHASE1_ONLY) ? 1 : 0;
   const int kout = mode == 0 ? k : K;
@@ -1065,15 +1105,27 @@ int vrq_search3_dim(const uint8_t* codes, const int8_t* x8, const double* norms,
   if (mode != 1) VRQ_CHECK_ARG(out_binary && out_cosine);
   if (n == 0 || K == 0 || (mode == 0 && k == 0))
     return fill_empty(nq, kout, out_count, out_rows, out_dist, out_binary, out_cosine, s);
-  VRQ_CHECK_ARG(codes && qb && workspace);
+  VRQ_CHECK_ARG(codes && workspace);
   if (mode != 1) VRQ_CHECK_ARG(qf && x8 && norms);
-  ScanPlan p;
-  int rc = scan_plan(n, dim / 8, nq, K, &p);
-  if (rc != VRQ_OK) return rc;
-  if (workspace_bytes < p.list_bytes) return VRQ_EWORKSPACE;
-  if (p.nchunks > MAX_LISTS) return VRQ_EUNSUPPORTED;
-  rc = scan_launch(p, codes, n, dim / 8, qb, nq, K, (uint64_t*)workspace, s);
-  if (rc != VRQ_OK) return rc;
+  const int cb = dim / 8;
+  const uint64_t* lists = (const uint64_t*)workspace;
+  int nl;
+  if (mfma_dim_use(n, cb, nq, K, flags)) {
+    MfmaPlan mp;
+    const int rc = mfma_dim_plan(n, cb, nq, K, &mp);
+    if (rc != VRQ_OK) return rc;
+    if (workspace_bytes < mp.bytes) return VRQ_EWORKSPACE;
+    // the matrix-core scan leaves one sorted K-list per query: the single list of the merge
+    lists = (const uint64_t*)((const uint8_t*)workspace + mp.off_suffix);
+    nl = 1;
+  } else {
+    ScanPlan p;
+    const int rc = scan_plan(n, cb, nq, K, &p);
+    if (rc != VRQ_OK) return rc;
+    if (workspace_bytes < p.list_bytes) return VRQ_EWORKSPACE;
+    if (p.nchunks > MAX_LISTS) return VRQ_EUNSUPPORTED;
+    nl = p.nchunks;
+  }
   FinishArgs fa{};
   fa.x8 = x8;
   fa.norms = norms;
@@ -1087,7 +1139,35 @@ int vrq_search3_dim(const uint8_t* codes, const int8_t* x8, const double* norms,
   fa.out_s2 = out_binary;
   fa.out_s3 = out_cosine;
   fa.kout = kout;
-  return launch_select_dim(s, nq, (const uint64_t*)workspace, p.nchunks, K, dim, codes, x8, norms, qf, mode, fa);
+  return launch_select_dim(s, nq, lists, nl, K, dim, codes, x8, norms, qf, mode, fa);
+}
+
+int vrq_search3_dim(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
+                    int64_t n, int32_t dim, int64_t row_offset, const float* qf, const uint8_t* qb, int32_t nq,
+                    int32_t k, int32_t K, int32_t K3, int32_t flags, int32_t* out_count, int64_t* out_rows,
+                    int32_t* out_dist, double* out_binary, double* out_cosine, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+  if (dim == DIM)
+    return vrq_search3(codes, x8, norms, rescore_row, n, dim, row_offset, qf, qb, nq, k, K, K3, flags, out_count,
+                       out_rows, out_dist, out_binary, out_cosine, workspace, workspace_bytes, stream);
+  VRQ_CHECK_ARG(n >= 0 && nq >= 0 && k >= 0 && K >= 0 && K3 >= 0);
+  VRQ_CHECK_ARG(out_count && out_rows && out_dist);
+  if (!vrq_dim_supported(dim) || K > KMAX) return VRQ_EUNSUPPORTED;
+  // forcing the matrix-core scan and staging it go through vrq_search3_dim_scan / _finish; the sharded
+  // mode is 1024-only.  VRQ_SEARCH_SCAN_VALU forces the wavefront scan; otherwise the scan is chosen
+  // by shape (mfma_dim_use).
+  if (flags & ~(VRQ_SEARCH_PHASE1_ONLY | VRQ_SEARCH_SCAN_VALU)) return VRQ_EUNSUPPORTED;
+  const int mode = (flags & VRQ_SEARCH_PHASE1_ONLY) ? 1 : 0;
+  const bool empty = n == 0 || K == 0 || (mode == 0 && k == 0);
+  if (nq > 0 && mode != 1) VRQ_CHECK_ARG(out_binary && out_cosine);
+  if (!empty && nq > 0) {
+    VRQ_CHECK_ARG(codes && qb && workspace);
+    if (mode != 1) VRQ_CHECK_ARG(qf && x8 && norms);
+    const int rc = vrq_search3_dim_scan(codes, n, dim, qb, nq, K, flags, workspace, workspace_bytes, stream);
+    if (rc != VRQ_OK) return rc;
+  }
+  return vrq_search3_dim_finish(codes, x8, norms, rescore_row, n, dim, row_offset, qf, nq, k, K, K3, flags, out_count,
+                                out_rows, out_dist, out_binary, out_cosine, workspace, workspace_bytes, stream);
 }
 
 int vrq_rescore_binary_dim(const float* qf, int32_t nq, int32_t dim, const uint8_t* codes, int64_t n,

@@ -81,4 +81,21 @@ bool mfma_use(int64_t n, int nq, int K, int flags);
 int mfma_scan_launch(const MfmaPlan& p, const uint8_t* codes, int64_t n, const uint8_t* q, int nq, int K,
                      uint8_t* ws, hipStream_t s, int flags);
 
+// helpers of the plan and the recheck that the scan of the other code sizes shares
+int mfma_sample_order(double lam, int K);
+int mfma_sample_check_launch(const int32_t* ccnt, int nchunks, int K, int nq, int32_t* rerun, int32_t* qbflag, int qpb,
+                             hipStream_t s);
+
+// ---- K1rd: the row-split matrix-core scan for the other code sizes (hamming_mfma_dim.hip): cb = 32, 48,
+// 64, 96, 192, 256.  Same four stages, same workspace layout and the same constants as the 1024-bit scan;
+// an MfmaPlan with rows = rows_sample = 1, mb M-blocks per wave and nqb = ceil(nq / (32 mb)) query blocks
+// (the dense sample pass runs min(mb, 2) M-blocks per wave in nqb_s blocks).  Keys carry
+// (dist - tau + dim + 1) << 40 | row, the u16 lane minima dist - pc(q) + dim. ----
+constexpr int kMfmaKindRowsDim = 3;      // info[0] of vrq_scan_plan
+int mfma_dim_min_queries(int cb);        // the measured default threshold (INT32_MAX: forced only)
+int mfma_dim_plan(int64_t n, int cb, int nq, int K, MfmaPlan* p);
+bool mfma_dim_use(int64_t n, int cb, int nq, int K, int flags);
+int mfma_dim_scan_launch(const MfmaPlan& p, const uint8_t* codes, int64_t n, int cb, const uint8_t* q, int nq, int K,
+                         uint8_t* ws, hipStream_t s, int flags);
+
 }  // namespace vrq
