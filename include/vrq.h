@@ -71,10 +71,18 @@ extern "C" {
 #define VRQ_ENC_INT4_LOCAL 4   /* VectorDBInt4._quantize_to_int4 (+min/max) + _to_binary */
 #define VRQ_ENC_BIN_INT16 5    /* VectorDBInt16._to_binary on int16 input */
 #define VRQ_ENC_COHERE 6       /* synthetic Cohere provider: int8 (global limit) + ubinary = packbits(x > 0) */
+#define VRQ_ENC_SIGNED_BINARY 7 /* CohereVectorDBBinary._to_signed_binary + _pack_signed_binary
+                                   (CohereVectorDBBinary.py:133-150): codes = packbits(x >= mean(x)) -- the
+                                   only mode that keeps the elements equal to the float32 mean (a constant
+                                   row encodes to all ones); codes only: q, minmax and limit are unused */
 /* vrq_rescore_dequant only: the compare_float32 branch of the VectorDB* searches
  * (VectorDBInt8Global.py:239-240, VectorDBInt8.py:231-232, VectorDBInt4.py:262-263,
  * VectorDBInt16Global.py:240-241, VectorDBInt4Global.py:257-258): q = f32[n, dim] float rows */
 #define VRQ_RESCORE_F32 16
+/* vrq_rescore_dequant / vrq_search2 only: CohereVectorDBBinary._unpack_signed_binary
+ * (CohereVectorDBBinary.py:152-159, rescoring at :231-232): q = u8[n, dim/8] packed sign codes, row
+ * element i = +1.0f if bit i (MSB-first) is set, else -1.0f; minmax and limit ignored; dim % 128 == 0 */
+#define VRQ_RESCORE_SIGNED_BINARY 17
 
 int vrq_abi_version(void);
 const char* vrq_strerror(int code);
@@ -238,8 +246,10 @@ int vrq_rescore_int8_cosine(const float* qf, int32_t nq, int32_t dim, const int8
  *   VectorDBInt4Global.py:129-164,190-196   VectorDBInt8.py:114-126,140-146
  *   VectorDBInt4.py:116-154,186-192          VectorDBInt16.py:148-157
  * x       f32[n, dim] (i16[n, dim] for VRQ_ENC_BIN_INT16)
- * codes   u8[n, dim/8]           packbits(x > mean(x)) MSB-first (or x > 0 for COHERE)
- * q       i8[n, dim] | i16[n, dim] | i8[n, (dim+1)/2] (int4 nibbles) | unused
+ * codes   u8[n, dim/8]           packbits(x > mean(x)) MSB-first (x > 0 for COHERE, x >= mean(x) for
+ *                                SIGNED_BINARY)
+ * q       i8[n, dim] | i16[n, dim] | i8[n, (dim+1)/2] (int4 nibbles) | unused (BIN_INT16 and
+ *         SIGNED_BINARY: may be NULL)
  * minmax  f64[n, 2] (local modes only; may be NULL otherwise)
  * limit   global clip limit (Global modes / COHERE), as passed by the caller
  * dim must be a multiple of 8 and <= 8192.
@@ -261,13 +271,45 @@ int vrq_encode(int32_t mode, const void* x, int64_t n, int32_t dim, double limit
  * ones.  vrq_dequantize writes f32[n, dim]; vrq_rescore_dequant writes, per (query, candidate), the
  * reference score float(np.dot(query_float, dequantised row)) (VectorDBInt8Global.py:232-238 and the
  * same loop in the other classes) as the correctly rounded float32 dot (NaN for negative rows).
- * vrq_rescore_dequant also takes mode VRQ_RESCORE_F32 (q = the f32 float rows, compare_float32).
+ * vrq_rescore_dequant also takes mode VRQ_RESCORE_F32 (q = the f32 float rows, compare_float32) and
+ * VRQ_RESCORE_SIGNED_BINARY (q = the packed sign codes; dim a multiple of 128, else VRQ_EUNSUPPORTED).
  * ------------------------------------------------------------------------- */
 int vrq_dequantize(int32_t mode, const void* q, const double* minmax, int64_t n, int32_t dim, double limit,
                    float* out, void* stream);
 int vrq_rescore_dequant(int32_t mode, const float* qf, int32_t nq, int32_t dim, const void* q,
                         const double* minmax, double limit, int64_t n, const int64_t* cand_rows,
                         int32_t ncand, double* out, void* stream);
+/* ---------------------------------------------------------------------------
+ * Fused two-phase search -- CohereVectorDBBinary.search (CohereVectorDBBinary.py:215-239) and the
+ * identical loops of the VectorDBInt* classes (e.g. VectorDBInt8Global.py:224-252) for a batch of nq
+ * queries, in two launches (scan + finish) instead of vrq_hamming_topk, a gather, vrq_rescore_dequant,
+ * a sort and three more gathers:
+ *   Phase I   top-K by Hamming over `codes` in FAISS (dist, row) order (K = min(k*binary_oversample,
+ *             ntotal)): exactly the scan vrq_search3_dim_scan runs for the shape and flags
+ *   Phase II  every candidate row r gets the vrq_rescore_dequant score of `mode` (any mode it accepts;
+ *             q / minmax / limit as there) taken from row rescore_row[r] (r itself if NULL: see
+ *             vrq_search3).  For VRQ_RESCORE_SIGNED_BINARY the caller normally passes q = codes.
+ *   then      a stable sort by score descending over the Phase-I order (-0.0 ties +0.0), first k
+ * outputs [nq, k]: out_rows i64 = row_offset + r (missing -1), out_dist i32 (missing INT32_MAX),
+ *   out_score f64 (missing NaN); out_count i32[nq] = min(k, K, n).  Inputs must be finite.
+ * Supported: every dim of vrq_dim_supported, 1 <= K <= 1024; n, K, k or nq = 0 behave as in
+ * vrq_search3_dim_finish.  flags: 0, VRQ_SEARCH_SCAN_VALU, VRQ_SEARCH_SCAN_MFMA (as vrq_search3_dim_scan;
+ * identical results); any other bit returns VRQ_EUNSUPPORTED.
+ * vrq_search2 = vrq_search3_dim_scan + vrq_search2_finish with the same flags and workspace (size:
+ * vrq_search2_workspace_size = vrq_search3_dim_workspace_size); the finish reads the lists the scan left
+ * and needs no other scratch.
+ * ------------------------------------------------------------------------- */
+size_t vrq_search2_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K);
+int vrq_search2(int32_t mode, const uint8_t* codes, const void* q, const double* minmax, double limit,
+                const int64_t* rescore_row, int64_t n, int32_t dim, int64_t row_offset, const float* qf,
+                const uint8_t* qb, int32_t nq, int32_t k, int32_t K, int32_t flags, int32_t* out_count,
+                int64_t* out_rows, int32_t* out_dist, double* out_score, void* workspace,
+                size_t workspace_bytes, void* stream);
+int vrq_search2_finish(int32_t mode, const uint8_t* codes, const void* q, const double* minmax, double limit,
+                       const int64_t* rescore_row, int64_t n, int32_t dim, int64_t row_offset, const float* qf,
+                       int32_t nq, int32_t k, int32_t K, int32_t flags, int32_t* out_count, int64_t* out_rows,
+                       int32_t* out_dist, double* out_score, const void* workspace, size_t workspace_bytes,
+                       void* stream);
 /* np.linalg.norm(int8 row) in float64 (CohereEnhancedVectorDB.py:308), computed once at add time */
 int vrq_int8_row_norms(const int8_t* x8, int64_t n, int32_t dim, double* out, void* stream);
 /* ---------------------------------------------------------------------------

@@ -9,7 +9,7 @@ from ._native import VrqNativeError, load as load_native  # noqa: F401
 
 __all__ = ["VrqNativeError", "load_native", "CohereEnhancedVectorDB", "BinaryIndexIDMap2", "encode",
            "ShardedSearch", "CohereVectorDBFloat", "VectorDBInt8Global", "VectorDBInt16Global", "VectorDBInt4Global",
-           "VectorDBInt8", "VectorDBInt4", "VectorDBInt16", "CohereVectorDBInt8"]
+           "VectorDBInt8", "VectorDBInt4", "VectorDBInt16", "CohereVectorDBInt8", "CohereVectorDBBinary"]
 
 _VECTORDB = ("VectorDBInt8Global", "VectorDBInt16Global", "VectorDBInt4Global", "VectorDBInt8", "VectorDBInt4",
              "VectorDBInt16", "CohereVectorDBInt8")
@@ -28,6 +28,9 @@ def __getattr__(name):  # lazy: importing the package must not require a GPU
     if name in _VECTORDB:
         from . import vectordb
         return getattr(vectordb, name)
+    if name == "CohereVectorDBBinary":
+        from .binary import CohereVectorDBBinary
+        return CohereVectorDBBinary
     if name == "CohereVectorDBFloat":
         from .flat import CohereVectorDBFloat
         return CohereVectorDBFloat

@@ -35,6 +35,8 @@ VRQ_GEMM_STAGE_FINISH = 64
 VRQ_GEMM_NO_FALLBACK = 128
 VRQ_GEMM_SCAN_EXACT = 256  # _dim entry points: the exact exhaustive scan (K5d) at dim 1024 too
 VRQ_RESCORE_F32 = 16  # vrq_rescore_dequant: compare_float32 rows
+VRQ_RESCORE_SIGNED_BINARY = 17  # vrq_rescore_dequant / vrq_search2: packed sign codes as +-1 rows
+VRQ_ENC_SIGNED_BINARY = 7
 VRQ_SCAN_KIND_VALU = 0
 VRQ_SCAN_KIND_MFMA = 1
 VRQ_SCAN_PLAN_K1RD = 3  # info[0] of vrq_scan_plan at the dims other than 1024
@@ -47,6 +49,7 @@ ENC_MODES = {
     "int4": 4,    # VectorDBInt4
     "bin16": 5,   # VectorDBInt16._to_binary
     "cohere": 6,  # synthetic Cohere provider (int8 global + sign bits)
+    "sbin": 7,    # CohereVectorDBBinary (packbits(x >= mean), codes only)
 }
 
 # name -> (restype, argtypes); mirrors include/vrq.h
@@ -81,6 +84,11 @@ SIGNATURES = {
     "vrq_int8_row_norms": (C.c_int, [_P, _I64, _I32, _P, _P]),
     "vrq_dequantize": (C.c_int, [_I32, _P, _P, _I64, _I32, _D, _P, _P]),
     "vrq_rescore_dequant": (C.c_int, [_I32, _P, _I32, _I32, _P, _P, _D, _I64, _P, _I32, _P, _P]),
+    "vrq_search2_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
+    "vrq_search2": (C.c_int, [_I32, _P, _P, _P, _D, _P, _I64, _I32, _I64, _P, _P, _I32, _I32, _I32, _I32,
+                              _P, _P, _P, _P, _P, _SZ, _P]),
+    "vrq_search2_finish": (C.c_int, [_I32, _P, _P, _P, _D, _P, _I64, _I32, _I64, _P, _I32, _I32, _I32, _I32,
+                                     _P, _P, _P, _P, _P, _SZ, _P]),
     "vrq_gemm_topk_workspace_size": (_SZ, [_I32, _I64, _I32, _I32, _I32]),
     "vrq_gemm_topk_pieces": (C.c_int, []),
     "vrq_gemm_topk_plan": (C.c_int, [_I32, _I64, _I32, _I32, _I32, _P]),

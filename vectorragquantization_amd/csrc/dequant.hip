@@ -15,61 +15,15 @@
 //   f64 sum of the exact f32 x f32 products rounded once to f32 (NumPy's sdot is within a few ulp).
 //   VRQ_RESCORE_F32 (rescoring only): the compare_float32 branch (VectorDBInt8Global.py:239-240 and
 //   the same branch in the other classes) -- q is the f32 float_embeddings rows, used as they are.
+//   VRQ_RESCORE_SIGNED_BINARY (rescoring only): CohereVectorDBBinary._unpack_signed_binary (:152-159) --
+//   q is the packed sign codes, element i = +1 if bit i (MSB first) is set, else -1.
+// The per-(query, row) score is dequant_dot (dequant_dot.h), shared with the fused two-phase finish.
+#include "dequant_dot.h"
 #include "vrq_internal.h"
 
 namespace vrq {
 
 constexpr int DQ_MAX_DIM = 8192;
-
-struct DeqRow {
-  int mode;
-  double limit;
-  float sf;   // float32 scale (INT8/INT16 global, INT8 local)
-  double sd;  // float64 scale (INT4 modes)
-  bool zero;  // local modes with min == max
-};
-
-__device__ __forceinline__ DeqRow deq_row(int mode, double limit, const double* minmax, int64_t r) {
-  DeqRow d{mode, limit, 0.f, 0.0, false};
-  switch (mode) {
-    case VRQ_RESCORE_F32: break;
-    case VRQ_ENC_INT8_GLOBAL: d.sf = (float)(limit / 127.0); break;
-    case VRQ_ENC_INT16_GLOBAL: d.sf = (float)(limit / 32767.0); break;
-    case VRQ_ENC_INT4_GLOBAL: d.sd = limit / 7.0; break;
-    case VRQ_ENC_INT8_LOCAL: {
-      const float mn = (float)minmax[2 * r], mx = (float)minmax[2 * r + 1];
-      d.zero = mn == mx;
-      d.sf = __fdiv_rn(fmaxf(fabsf(mn), fabsf(mx)), 127.0f);  // np.float32 / int -> float32
-      break;
-    }
-    default: {  // VRQ_ENC_INT4_LOCAL
-      const double mn = minmax[2 * r], mx = minmax[2 * r + 1];
-      d.zero = mn == mx;
-      d.sd = fmax(fabs(mn), fabs(mx)) / 7.0;
-      break;
-    }
-  }
-  return d;
-}
-
-// element i of row r (q = the mode's code array)
-__device__ __forceinline__ float deq_elem(const DeqRow& d, const void* q, int64_t r, int dim, int i) {
-  if (d.zero) return 0.f;
-  switch (d.mode) {
-    case VRQ_RESCORE_F32:
-      return reinterpret_cast<const float*>(q)[r * dim + i];
-    case VRQ_ENC_INT8_GLOBAL:
-    case VRQ_ENC_INT8_LOCAL:
-      return __fmul_rn((float)reinterpret_cast<const int8_t*>(q)[r * dim + i], d.sf);
-    case VRQ_ENC_INT16_GLOBAL:
-      return __fmul_rn((float)reinterpret_cast<const int16_t*>(q)[r * dim + i], d.sf);
-    default: {
-      const uint8_t b = reinterpret_cast<const uint8_t*>(q)[r * ((dim + 1) / 2) + (i >> 1)];
-      const int nib = (i & 1) ? (b & 15) : (b >> 4);
-      return (float)__dmul_rn((double)(nib - 8), d.sd);
-    }
-  }
-}
 
 __global__ __launch_bounds__(256) void dequant_kernel(int mode, const void* __restrict__ q,
                                                       const double* __restrict__ minmax, int64_t n, int dim,
@@ -95,11 +49,8 @@ __global__ __launch_bounds__(256) void rescore_dequant_kernel(int mode, const fl
     if (l == 0) out[wv] = __builtin_nan("");
     return;
   }
-  const DeqRow d = deq_row(mode, limit, minmax, r);
-  double s = 0.0;
-  for (int i = l; i < dim; i += WAVE) s += (double)qf[(int64_t)qi * dim + i] * (double)deq_elem(d, q, r, dim, i);
-  s = wave_sum_f64(s);  // exact products, f64 accumulation, one rounding to f32 below
-  if (l == 0) out[wv] = (double)(float)s;
+  const double v = dequant_dot(mode, qf + (int64_t)qi * dim, dim, q, minmax, limit, r);
+  if (l == 0) out[wv] = v;
 }
 
 }  // namespace vrq
@@ -134,9 +85,11 @@ int vrq_dequantize(int32_t mode, const void* q, const double* minmax, int64_t n,
 int vrq_rescore_dequant(int32_t mode, const float* qf, int32_t nq, int32_t dim, const void* q, const double* minmax,
                         double limit, int64_t n, const int64_t* cand_rows, int32_t ncand, double* out,
                         void* stream) {
-  VRQ_CHECK_ARG((mode >= VRQ_ENC_INT8_GLOBAL && mode <= VRQ_ENC_INT4_LOCAL) || mode == VRQ_RESCORE_F32);
+  VRQ_CHECK_ARG((mode >= VRQ_ENC_INT8_GLOBAL && mode <= VRQ_ENC_INT4_LOCAL) || mode == VRQ_RESCORE_F32 ||
+                mode == VRQ_RESCORE_SIGNED_BINARY);
   VRQ_CHECK_ARG(nq >= 0 && ncand >= 0 && n >= 0 && dim > 0);
   if (dim > DQ_MAX_DIM) return VRQ_EUNSUPPORTED;
+  if (mode == VRQ_RESCORE_SIGNED_BINARY && dim % 128 != 0) return VRQ_EUNSUPPORTED;  // 16-byte code pieces
   if (nq == 0 || ncand == 0) return VRQ_OK;
   VRQ_CHECK_ARG(qf && q && cand_rows && out);
   if (mode == VRQ_ENC_INT8_LOCAL || mode == VRQ_ENC_INT4_LOCAL) VRQ_CHECK_ARG(minmax);

@@ -15,6 +15,8 @@
 //    correctly rounded float32 quotient.  np.round = rintf (half to even);
 //    .astype(int8) from float truncates (VectorDBInt8.py:126).
 //  * VectorDBInt4Global ignores its limit (reference bug, reproduced).
+//  * VRQ_ENC_SIGNED_BINARY (CohereVectorDBBinary._to_signed_binary, :133-141): the same float32 mean,
+//    thresholded with >= -- elements equal to the mean are set, a constant row is all ones.  Codes only.
 #include "vrq_internal.h"
 
 namespace vrq {
@@ -243,11 +245,15 @@ __global__ __launch_bounds__(EPB * 64) void encode_kernel(const void* __restrict
       uint32_t byte = 0;
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
-        const bool bit = (MODE == VRQ_ENC_COHERE) ? (e[k] > 0.f) : (e[k] > mean);
+        const bool bit = (MODE == VRQ_ENC_COHERE)          ? (e[k] > 0.f)
+                         : (MODE == VRQ_ENC_SIGNED_BINARY) ? (e[k] >= mean)
+                                                           : (e[k] > mean);
         byte |= (bit ? 1u : 0u) << (7 - k);
       }
       crow[gi] = (uint8_t)byte;
-      if constexpr (MODE == VRQ_ENC_INT8_GLOBAL || MODE == VRQ_ENC_COHERE) {
+      if constexpr (MODE == VRQ_ENC_SIGNED_BINARY) {
+        // codes only
+      } else if constexpr (MODE == VRQ_ENC_INT8_GLOBAL || MODE == VRQ_ENC_COHERE) {
         uint32_t w[2] = {0, 0};
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
@@ -415,12 +421,15 @@ __global__ __launch_bounds__(ENC_WPB * 64) void encode1024_kernel(const float* _
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int idx = 4 * k + q;  // element 16l + idx -> byte idx / 8, bit 7 - idx % 8
-          const bool bit = (MODE == VRQ_ENC_COHERE) ? (cv[q] > 0.f) : (cv[q] > mean);
+          const bool bit = (MODE == VRQ_ENC_COHERE)          ? (cv[q] > 0.f)
+                           : (MODE == VRQ_ENC_SIGNED_BINARY) ? (cv[q] >= mean)
+                                                             : (cv[q] > mean);
           bits |= (bit ? 1u : 0u) << ((idx < 8) ? 7 - idx : 23 - idx);
         }
       }
       *reinterpret_cast<uint16_t*>(codes + v * 128 + 2 * l) = (uint16_t)bits;
     }
+    if constexpr (MODE == VRQ_ENC_SIGNED_BINARY) return;  // codes only
     float scale = gscale;
     bool flat = false;
     if constexpr (MODE == VRQ_ENC_INT4_GLOBAL || MODE == VRQ_ENC_INT8_LOCAL || MODE == VRQ_ENC_INT4_LOCAL) {
@@ -545,12 +554,12 @@ int vrq_encode(int32_t mode, const void* x, int64_t n, int32_t dim, double limit
                double* minmax, void* stream) {
   VRQ_CHECK_ARG(n >= 0 && dim > 0 && (dim % 8) == 0);
   if (dim > MAX_DIM || (dim % 4) != 0) return VRQ_EUNSUPPORTED;
-  VRQ_CHECK_ARG(mode >= VRQ_ENC_INT8_GLOBAL && mode <= VRQ_ENC_COHERE);
+  VRQ_CHECK_ARG(mode >= VRQ_ENC_INT8_GLOBAL && mode <= VRQ_ENC_SIGNED_BINARY);
   const bool global_mode = mode == VRQ_ENC_INT8_GLOBAL || mode == VRQ_ENC_INT16_GLOBAL || mode == VRQ_ENC_COHERE;
   if (global_mode) VRQ_CHECK_ARG(limit > 0.0);
   if (n == 0) return VRQ_OK;
   VRQ_CHECK_ARG(x && codes);
-  if (mode != VRQ_ENC_BIN_INT16) VRQ_CHECK_ARG(q);
+  if (mode != VRQ_ENC_BIN_INT16 && mode != VRQ_ENC_SIGNED_BINARY) VRQ_CHECK_ARG(q);
   if (mode == VRQ_ENC_INT8_LOCAL || mode == VRQ_ENC_INT4_LOCAL) VRQ_CHECK_ARG(minmax);
   PwPlan P{};
   pw_build(0, dim, &P);
@@ -579,7 +588,7 @@ int vrq_encode(int32_t mode, const void* x, int64_t n, int32_t dim, double limit
     const dim3 grid((unsigned)g), block(ENC_WPB * 64);
     const float* xf = (const float*)x + v0 * 1024;
     uint8_t* cv = codes + v0 * 128;
-    void* qv = (uint8_t*)q + v0 * qrow;
+    void* qv = q ? (void*)((uint8_t*)q + v0 * qrow) : nullptr;
     double* mv = minmax ? minmax + 2 * v0 : nullptr;
     switch (mode) {
       case VRQ_ENC_INT8_GLOBAL:
@@ -596,6 +605,9 @@ int vrq_encode(int32_t mode, const void* x, int64_t n, int32_t dim, double limit
         break;
       case VRQ_ENC_INT4_LOCAL:
         hipLaunchKernelGGL(encode1024_kernel<VRQ_ENC_INT4_LOCAL>, grid, block, 0, s, xf, nv, limit, cv, qv, mv);
+        break;
+      case VRQ_ENC_SIGNED_BINARY:
+        hipLaunchKernelGGL(encode1024_kernel<VRQ_ENC_SIGNED_BINARY>, grid, block, 0, s, xf, nv, limit, cv, qv, mv);
         break;
       default:
         hipLaunchKernelGGL(encode1024_kernel<VRQ_ENC_COHERE>, grid, block, 0, s, xf, nv, limit, cv, qv, mv);
@@ -631,6 +643,9 @@ int vrq_encode(int32_t mode, const void* x, int64_t n, int32_t dim, double limit
         break;
       case VRQ_ENC_BIN_INT16:
         hipLaunchKernelGGL(encode_kernel<VRQ_ENC_BIN_INT16>, grid, block, lds, s, xv, nv, dim, limit, cv, qv, mv, P, epb);
+        break;
+      case VRQ_ENC_SIGNED_BINARY:
+        hipLaunchKernelGGL(encode_kernel<VRQ_ENC_SIGNED_BINARY>, grid, block, lds, s, xv, nv, dim, limit, cv, qv, mv, P, epb);
         break;
       default:
         hipLaunchKernelGGL(encode_kernel<VRQ_ENC_COHERE>, grid, block, lds, s, xv, nv, dim, limit, cv, qv, mv, P, epb);

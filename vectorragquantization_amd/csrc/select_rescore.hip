@@ -17,6 +17,7 @@
 // BLAS summation order, <= a few ulp away: the 1e-5 tolerance of the north
 // star).  The norm is sqrt of an exact integer sum (correctly rounded, equal
 // to np.linalg.norm) and the division is IEEE double, as in the reference.
+#include "dequant_dot.h"
 #include "exact_scores.h"
 #include "vrq_internal.h"
 #include "vrq_scan.h"
@@ -61,6 +62,24 @@ template <int KM, int ML>
 struct SelSharedDim : SelState<KM, ML, NBINS_DIM> {};
 typedef SelSharedDim<KMAX, MAX_LISTS> SelDimBig;
 typedef SelSharedDim<KSMALL, LSMALL> SelDimSmall;
+// Per-query LDS state of the two-phase finish (vrq_search2): what select_topk and stable_desc_order use,
+// one score array, every distance up to 2048 (all dims of vrq_dim_supported, 1024 included).
+template <int KM, int ML>
+struct Sel2State {
+  static constexpr int kKM = KM, kML = ML, kBins = NBINS_DIM;
+  uint32_t hist[NBINS_DIM];
+  int32_t ltcnt[ML];
+  int32_t eqend[ML];
+  uint64_t sel[KM];
+  int32_t pay[KM];
+  uint64_t skey[KM];
+  int32_t sidx[KM];
+  double s2[KM];
+  int32_t scan[SEL_THREADS / WAVE + 1];
+  int32_t misc[8];
+};
+typedef Sel2State<KMAX, MAX_LISTS> Sel2Big;
+typedef Sel2State<KSMALL, LSMALL> Sel2Small;
 
 // Block-wide exclusive scan of one int per thread; returns exclusive prefix, total in *tot.
 __device__ inline int block_excl_scan(int v, int* tot, int32_t* scratch) {
@@ -648,6 +667,60 @@ __global__ __launch_bounds__(SEL_THREADS, SH::kKM <= KSMALL ? 4 : 1) void select
   finish_query(Kp, true, a, qi, sh);
 }
 
+// K2b, the finish of the fused two-phase search (vrq_search2; CohereVectorDBBinary.py:215-239 and the same
+// loop of the VectorDBInt* classes, e.g. VectorDBInt8Global.py:224-252): exact merge of the lists the scan
+// left (the K1 / K1d chunk lists, or the single sorted list of a matrix-core scan), one wave per candidate
+// for the rescoring score of `mode` (dequant_dot, bit-identical to vrq_rescore_dequant), the stable sort by
+// score descending over the Phase-I order, the first k.  No global scratch.
+struct Finish2Args {
+  int mode;
+  const void* q;
+  const double* minmax;
+  double limit;
+  const int64_t* remap;  // rescore row of each Phase-I row, or null
+  int64_t row_offset;
+  int k;
+  int32_t* out_count;
+  int64_t* out_rows;
+  int32_t* out_dist;
+  double* out_score;
+};
+
+template <class SH>
+__global__ __launch_bounds__(SEL_THREADS, SH::kKM <= KSMALL ? 4 : 1) void select_rescore2_kernel(
+    const uint64_t* __restrict__ lists, int nl, int K, int dim, const float* __restrict__ qf, Finish2Args fa) {
+  __shared__ SH sh;
+  const int qi = blockIdx.x;
+  const int tid = threadIdx.x, w = tid / WAVE, l = lane_id();
+  const ChunkKeys Lq{lists + (int64_t)qi * nl * K};
+  const int Kp = select_topk(Lq, nl, K, sh);
+  const float* q = qf + (int64_t)qi * dim;
+  for (int j = w; j < Kp; j += SEL_THREADS / WAVE) {  // (j, hence the row, is wave-uniform)
+    int64_t row = (int64_t)(sh.sel[j] & ROW_MASK);
+    if (fa.remap) row = fa.remap[row];
+    const double sc = dequant_dot(fa.mode, q, dim, fa.q, fa.minmax, fa.limit, row);
+    if (l == 0) sh.s2[j] = sc;
+  }
+  __syncthreads();
+  stable_desc_order(sh.s2, Kp, sh);  // sh.sidx[0..Kp) = Phase-I ranks by score desc, ties in Phase-I order
+  const int m = fa.k < Kp ? fa.k : Kp;
+  for (int i = tid; i < fa.k; i += SEL_THREADS) {
+    const int64_t o = (int64_t)qi * fa.k + i;
+    if (i < m) {
+      const int r = sh.sidx[i];
+      const uint64_t key = sh.sel[r];
+      fa.out_rows[o] = (int64_t)(key & ROW_MASK) + fa.row_offset;
+      fa.out_dist[o] = (int32_t)(key >> KEY_ROW_BITS);
+      fa.out_score[o] = sh.s2[r];
+    } else {
+      fa.out_rows[o] = -1;
+      fa.out_dist[o] = DIST_NONE;
+      fa.out_score[o] = __builtin_nan("");
+    }
+  }
+  if (tid == 0) fa.out_count[qi] = m;
+}
+
 // Shard merge: the lists are the shards' (dist, global row) candidates (VRQ_SEARCH_SHARD
 // outputs stacked [S][nq][K]); the payload carried to the finish step is s2/s3.
 struct ShardKeys {
@@ -1196,6 +1269,81 @@ int vrq_rescore_int8_cosine_dim(const float* qf, int32_t nq, int32_t dim, const 
                      nq, dim, nullptr, x8, norms, n, cand_rows, ncand, out);
   VRQ_LAUNCH_CHECK();
   return VRQ_OK;
+}
+
+// ---- the fused two-phase search (every dim of vrq_dim_supported) ----
+size_t vrq_search2_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K) {
+  return vrq_search3_dim_workspace_size(n, dim, nq, K);
+}
+
+static bool search2_mode_ok(int mode) {
+  return (mode >= VRQ_ENC_INT8_GLOBAL && mode <= VRQ_ENC_INT4_LOCAL) || mode == VRQ_RESCORE_F32 ||
+         mode == VRQ_RESCORE_SIGNED_BINARY;
+}
+
+int vrq_search2_finish(int32_t mode, const uint8_t* codes, const void* q, const double* minmax, double limit,
+                       const int64_t* rescore_row, int64_t n, int32_t dim, int64_t row_offset, const float* qf,
+                       int32_t nq, int32_t k, int32_t K, int32_t flags, int32_t* out_count, int64_t* out_rows,
+                       int32_t* out_dist, double* out_score, const void* workspace, size_t workspace_bytes,
+                       void* stream) {
+  VRQ_CHECK_ARG(search2_mode_ok(mode));
+  VRQ_CHECK_ARG(n >= 0 && nq >= 0 && k >= 0 && K >= 0);
+  VRQ_CHECK_ARG(out_count && out_rows && out_dist && out_score);
+  if (!vrq_dim_supported(dim) || K > KMAX) return VRQ_EUNSUPPORTED;
+  if (flags & ~(VRQ_SEARCH_SCAN_VALU | VRQ_SEARCH_SCAN_MFMA)) return VRQ_EUNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  if (nq == 0) return VRQ_OK;
+  if (n == 0 || K == 0 || k == 0) return fill_empty(nq, k, out_count, out_rows, out_dist, out_score, nullptr, s);
+  VRQ_CHECK_ARG(codes && workspace && qf && q);
+  if (mode == VRQ_ENC_INT8_LOCAL || mode == VRQ_ENC_INT4_LOCAL) VRQ_CHECK_ARG(minmax);
+  // the lists the scan left, located as vrq_search3_finish / vrq_search3_dim_finish do at that dim
+  const int cb = dim / 8;
+  const uint64_t* lists = (const uint64_t*)workspace;
+  int nl;
+  if (dim != DIM ? mfma_dim_use(n, cb, nq, K, flags) : mfma_use(n, nq, K, flags)) {
+    MfmaPlan mp;
+    const int rc = dim != DIM ? mfma_dim_plan(n, cb, nq, K, &mp) : mfma_plan(n, nq, K, &mp);
+    if (rc != VRQ_OK) return rc;
+    if (workspace_bytes < mp.bytes) return VRQ_EWORKSPACE;
+    // the matrix-core scan leaves one sorted K-list per query: the single list of the merge
+    lists = (const uint64_t*)((const uint8_t*)workspace + mp.off_suffix);
+    nl = 1;
+  } else {
+    ScanPlan p;
+    const int rc = scan_plan(n, cb, nq, K, &p);
+    if (rc != VRQ_OK) return rc;
+    if (workspace_bytes < p.list_bytes) return VRQ_EWORKSPACE;
+    if (p.nchunks > MAX_LISTS) return VRQ_EUNSUPPORTED;
+    nl = p.nchunks;
+  }
+  const Finish2Args fa{mode, q, minmax, limit, rescore_row, row_offset, k, out_count, out_rows, out_dist, out_score};
+  if (K <= KSMALL && nl <= LSMALL)
+    hipLaunchKernelGGL(select_rescore2_kernel<Sel2Small>, dim3(nq), dim3(SEL_THREADS), 0, s, lists, nl, K, dim, qf,
+                       fa);
+  else
+    hipLaunchKernelGGL(select_rescore2_kernel<Sel2Big>, dim3(nq), dim3(SEL_THREADS), 0, s, lists, nl, K, dim, qf, fa);
+  VRQ_LAUNCH_CHECK();
+  return VRQ_OK;
+}
+
+int vrq_search2(int32_t mode, const uint8_t* codes, const void* q, const double* minmax, double limit,
+                const int64_t* rescore_row, int64_t n, int32_t dim, int64_t row_offset, const float* qf,
+                const uint8_t* qb, int32_t nq, int32_t k, int32_t K, int32_t flags, int32_t* out_count,
+                int64_t* out_rows, int32_t* out_dist, double* out_score, void* workspace, size_t workspace_bytes,
+                void* stream) {
+  VRQ_CHECK_ARG(search2_mode_ok(mode));
+  VRQ_CHECK_ARG(n >= 0 && nq >= 0 && k >= 0 && K >= 0);
+  VRQ_CHECK_ARG(out_count && out_rows && out_dist && out_score);
+  if (!vrq_dim_supported(dim) || K > KMAX) return VRQ_EUNSUPPORTED;
+  if (flags & ~(VRQ_SEARCH_SCAN_VALU | VRQ_SEARCH_SCAN_MFMA)) return VRQ_EUNSUPPORTED;
+  if (nq > 0 && n > 0 && K > 0 && k > 0) {
+    VRQ_CHECK_ARG(codes && qb && workspace && qf && q);
+    if (mode == VRQ_ENC_INT8_LOCAL || mode == VRQ_ENC_INT4_LOCAL) VRQ_CHECK_ARG(minmax);
+    const int rc = vrq_search3_dim_scan(codes, n, dim, qb, nq, K, flags, workspace, workspace_bytes, stream);
+    if (rc != VRQ_OK) return rc;
+  }
+  return vrq_search2_finish(mode, codes, q, minmax, limit, rescore_row, n, dim, row_offset, qf, nq, k, K, flags,
+                            out_count, out_rows, out_dist, out_score, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

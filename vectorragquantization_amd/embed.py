@@ -15,6 +15,9 @@ GPU for the whole batch (``vrq_encode``).
 ``CohereRerankHTTPProvider`` the ``/v2/rerank`` call of ``search_rerank_cohere``
 (``CohereVectorDBInt8.py:237-339``), both used by ``vectordb.CohereVectorDBInt8``.
 
+``AzureEmbeddingsHTTPProvider`` is ``CohereVectorDBBinary._generate_embeddings`` (one ``{"input": [text]}``
+request per text), used by ``binary.CohereVectorDBBinary``.
+
 ``CohereHTTPProvider`` reproduces ``CohereEnhancedVectorDB._get_embeddings``
 (``CohereEnhancedVectorDB.py:136-169``): one JSON POST to ``/v2/embed`` with
 ``model``, ``texts``, ``input_type``, ``truncate: NONE``, ``embedding_types``;
@@ -157,6 +160,50 @@ class OllamaHTTPProvider:
                 else:
                     logger.warning(f"No embedding generated for text: {text}")
                     continue
+                if e.ndim > 1:
+                    e = e[0]
+                if e.shape[0] != self.dim:
+                    logger.error(f"Unexpected embedding dimension: {e.shape[0]}. Expected: {self.dim}. "
+                                 f"Skipping '{text}'.")
+                    continue
+                out[text] = e
+            except Exception as ex:  # the reference logs and skips the text
+                logger.error(f"Failed to generate embedding for text: '{text}'. Error: {ex}")
+        return out
+
+
+class AzureEmbeddingsHTTPProvider:
+    """``CohereVectorDBBinary._generate_embeddings`` (``CohereVectorDBBinary.py:99-131``): the reference
+    calls ``EmbeddingsClient(endpoint, AzureKeyCredential(key)).embed({"input": [text]})`` once per text
+    and takes ``response.data[0].embedding``.  This client posts the same ``{"input": [text]}`` body to
+    the endpoint's ``/embeddings`` route with the key as a Bearer token and reads ``data[0].embedding``;
+    endpoint and key come from ``COHERE_EMBED_ENDPOINT`` / ``COHERE_EMBED_KEY`` when not given, and a
+    missing one raises like the reference's constructor (``:52-61``).  Texts whose request fails, or
+    whose vector is missing or of the wrong dimension, are skipped with a log line."""
+
+    def __init__(self, endpoint: str | None = None, api_key: str | None = None, embedding_dim: int = 1024):
+        endpoint = endpoint or os.environ.get("COHERE_EMBED_ENDPOINT")
+        if not endpoint:
+            raise Exception("COHERE_EMBED_ENDPOINT is not set in the environment.")
+        api_key = api_key or os.environ.get("COHERE_EMBED_KEY")
+        if not api_key:
+            raise Exception("COHERE_EMBED_KEY is not set in the environment.")
+        self.endpoint, self.api_key, self.dim = endpoint, api_key, embedding_dim
+
+    def embed_floats(self, texts) -> dict:
+        import requests
+        url = self.endpoint if self.endpoint.endswith("/embeddings") else self.endpoint.rstrip("/") + "/embeddings"
+        headers = {"Authorization": f"Bearer {self.api_key}", "Content-Type": "application/json"}
+        out = {}
+        for text in texts:
+            try:
+                r = requests.post(url, headers=headers, json={"input": [text]})
+                r.raise_for_status()
+                data = r.json().get("data")
+                if not data:
+                    logger.warning(f"No embedding returned for text: {text}")
+                    continue
+                e = np.array(data[0]["embedding"], dtype=np.float32)
                 if e.ndim > 1:
                     e = e[0]
                 if e.shape[0] != self.dim:

@@ -17,6 +17,7 @@ VectorDBInt8           ``_quantize_to_int8`` (``:114-126``)          ``int8``
 VectorDBInt4           ``_quantize_to_int4`` (``:116-154``)          ``int4``
 VectorDBInt16          ``_to_binary`` on int16 (``:148-157``)        ``bin16``
 all of them            ``_to_binary`` (e.g. ``VectorDBInt8Global.py:154-160``)
+CohereVectorDBBinary   ``_to_signed_binary`` + ``_pack_signed_binary``  ``sbin`` (codes only)
 =====================  ==========================================  ==================
 """
 from __future__ import annotations
@@ -32,7 +33,8 @@ def encode(mode: str, X, limit: float = 0.3, device=None) -> dict:
     """Batch encode on device.  X: f32[n, d] (i16[n, d] for ``bin16``).
 
     Returns ``{"codes": u8[n, d/8], "q": int8[n,d] | int16[n,d] | int8[n,d/2] | None,
-    "minmax": f64[n,2] | None}`` as device tensors.
+    "minmax": f64[n,2] | None}`` as device tensors.  ``sbin`` (``CohereVectorDBBinary``,
+    ``packbits(x >= mean(x))``) and ``bin16`` give codes only; ``limit`` is ignored by them.
     """
     if mode not in N.ENC_MODES:
         raise ValueError(f"unknown encode mode {mode!r}")
@@ -127,6 +129,48 @@ def vectordb_search(mode: str, codes: torch.Tensor, q: torch.Tensor, qf: torch.T
     key = torch.where(rows >= 0, score + 0.0, torch.full_like(score, float("-inf")))
     o = torch.sort(-key, dim=1, stable=True).indices[:, :k]
     return torch.gather(rows, 1, o), torch.gather(dist, 1, o), torch.gather(score, 1, o)
+
+
+_SEARCH2_MODES = {**_DEQ_MODES, "f32": N.VRQ_RESCORE_F32, "sbin": N.VRQ_RESCORE_SIGNED_BINARY}
+
+
+def search2(mode: str, codes: torch.Tensor, q: torch.Tensor, qf: torch.Tensor, qb: torch.Tensor, k: int = 10,
+            binary_oversample: int = 10, minmax: torch.Tensor = None, limit: float = 0.0,
+            rescore_row: torch.Tensor = None, flags: int = 0):
+    """The two-phase search of ``vectordb_search`` as ONE fused call (``vrq_search2``: the Phase-I scan and
+    a finish kernel that merges, rescores, sorts and cuts; ``CohereVectorDBBinary.py:215-239`` and the same
+    loop of the ``VectorDBInt*`` classes).  ``mode`` is a ``vectordb_search`` rescoring mode (``int8g`` ...
+    ``int4``, ``f32``) or ``sbin``: ``q`` = packed sign codes (normally ``codes`` itself) scored as +-1
+    rows.  ``flags``: 0, ``VRQ_SEARCH_SCAN_VALU`` or ``VRQ_SEARCH_SCAN_MFMA``.  Same return contract as
+    ``vectordb_search``: (rows i64[nq, kk], hamming i32[nq, kk], score f64[nq, kk]) on the device,
+    kk = min(k, K); rows past the corpus are -1 (score NaN)."""
+    if mode not in _SEARCH2_MODES:
+        raise ValueError(f"unknown search2 mode {mode!r}")
+    dev = codes.device
+    n, cb = codes.shape
+    nq, d = qf.shape
+    K = min(k * binary_oversample, n)
+    kk = min(k, K)
+    rows = torch.empty((nq, kk), dtype=torch.int64, device=dev)
+    dist = torch.empty((nq, kk), dtype=torch.int32, device=dev)
+    score = torch.empty((nq, kk), dtype=torch.float64, device=dev)
+    if nq == 0 or kk == 0:
+        return rows, dist, score
+    if d != cb * 8 or qb.shape != (nq, cb):
+        raise N.VrqNativeError(f"search2: {cb}-byte codes but queries of dim {d} / codes {tuple(qb.shape)}")
+    if q is None or q.shape[0] != n or (minmax is not None and minmax.shape[0] != n) or \
+            (rescore_row is not None and rescore_row.shape[0] != n):
+        # the ABI indexes q / minmax / rescore_row by candidate row and cannot see their lengths
+        raise N.VrqNativeError(f"search2: {n} code rows but {None if q is None else q.shape[0]} stored rows")
+    lib = N.load()
+    count = torch.empty((nq,), dtype=torch.int32, device=dev)
+    ws = torch.empty((max(8, lib.vrq_search2_workspace_size(n, d, nq, K)),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        N.check(lib.vrq_search2(_SEARCH2_MODES[mode], N.ptr(codes), N.ptr(q), N.ptr(minmax), float(limit),
+                                N.ptr(rescore_row), n, d, 0, N.ptr(qf), N.ptr(qb), nq, kk, K, flags, N.ptr(count),
+                                N.ptr(rows), N.ptr(dist), N.ptr(score), N.ptr(ws), ws.numel(),
+                                N.stream_handle(dev)), f"vrq_search2({mode})")
+    return rows, dist, score
 
 
 def int8_row_norms(x8: torch.Tensor) -> torch.Tensor:
