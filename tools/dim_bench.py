@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Search at embedding dims other than 1024: HIP-event timing of vrq_search3_dim per (dim, nq), full
 three-phase (k = 10, K = 100, K3 = 30) and VRQ_SEARCH_PHASE1_ONLY, next to the yardstick -- the 1024-bit
-wavefront scan (vrq_search3, VRQ_SEARCH_SCAN_VALU | VRQ_SEARCH_PHASE1_ONLY) over a corpus of the same
+wavefront scan (vrq_search3_dim at 1024, VRQ_SEARCH_SCAN_VALU | VRQ_SEARCH_PHASE1_ONLY) over a corpus of the same
 byte count, run twice per point so that a difference can be judged against the yardstick's own spread.
 
 One JSON line per point: ms, QPS and, for nq <= 8, the Phase-I corpus bytes per second as a share of the
@@ -56,11 +56,10 @@ def timed(call, warmup, reps):
     return e0.elapsed_time(e1) / reps
 
 
-def search_call(lib, fn, name, codes, x8, norms, qf, qb, dim, flags, dev):
+def search_call(lib, codes, x8, norms, qf, qb, dim, flags, dev):
     n, nq = codes.shape[0], qb.shape[0]
     kout = K1 if flags & N.VRQ_SEARCH_PHASE1_ONLY else K_OUT
-    size = lib.vrq_search3_workspace_size if dim == 1024 else lib.vrq_search3_dim_workspace_size
-    ws = torch.empty((size(n, dim, nq, K1),), dtype=torch.uint8, device=dev)
+    ws = torch.empty((lib.vrq_search3_dim_workspace_size(n, dim, nq, K1),), dtype=torch.uint8, device=dev)
     cnt = torch.empty((nq,), dtype=torch.int32, device=dev)
     rows = torch.empty((nq, kout), dtype=torch.int64, device=dev)
     dist = torch.empty((nq, kout), dtype=torch.int32, device=dev)
@@ -70,8 +69,9 @@ def search_call(lib, fn, name, codes, x8, norms, qf, qb, dim, flags, dev):
     keep = (ws, cnt, rows, dist, s2, s3)
 
     def call():
-        N.check(fn(N.ptr(codes), N.ptr(x8), N.ptr(norms), 0, n, dim, 0, N.ptr(qf), N.ptr(qb), nq, K_OUT, K1, K3, flags,
-                   N.ptr(cnt), N.ptr(rows), N.ptr(dist), N.ptr(s2), N.ptr(s3), N.ptr(ws), ws.numel(), st), name)
+        N.check(lib.vrq_search3_dim(N.ptr(codes), N.ptr(x8), N.ptr(norms), 0, n, dim, 0, N.ptr(qf), N.ptr(qb), nq,
+                                    K_OUT, K1, K3, flags, N.ptr(cnt), N.ptr(rows), N.ptr(dist), N.ptr(s2), N.ptr(s3),
+                                    N.ptr(ws), ws.numel(), st), "vrq_search3_dim")
     return call, keep
 
 
@@ -244,13 +244,11 @@ def main():
             qf = torch.randn((nq, d), device=dev) / d ** 0.5
             yqb, _ = synth.flip_queries(ycodes, nq)
             for mode, flags in (("phase1", P1), ("full", 0)):
-                call, keep = search_call(lib, lib.vrq_search3_dim, "vrq_search3_dim", codes, x8, norms, qf, qb, d,
-                                         flags, dev)
+                call, keep = search_call(lib, codes, x8, norms, qf, qb, d, flags, dev)
                 emit(point(d, n, nq, mode, timed(call, a.warmup, a.reps), cb))
                 del call, keep
             for rep in (0, 1):
-                call, keep = search_call(lib, lib.vrq_search3, "vrq_search3", ycodes, None, None, None, yqb, 1024,
-                                         P1 | N.VRQ_SEARCH_SCAN_VALU, dev)
+                call, keep = search_call(lib, ycodes, None, None, None, yqb, 1024, P1 | N.VRQ_SEARCH_SCAN_VALU, dev)
                 rec = point(1024, ny, nq, "yardstick_valu_phase1", timed(call, a.warmup, a.reps), 128)
                 rec.update({"for_dim": d, "repeat": rep})
                 emit(rec)

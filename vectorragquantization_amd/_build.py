@@ -20,7 +20,10 @@ LIB = os.path.join(PKG, "libvrq.so")
 PROBE_LIB = os.path.join(PKG, "libvrq_probe.so")
 OBJDIR = os.path.join(PKG, "_obj")
 SOURCES = ["hamming_scan.hip", "hamming_mfma.hip", "select_rescore.hip", "encode.hip", "gemm_topk.hip", "dequant.hip",
-           "search_dim.hip", "exhaustive_dim.hip", "hamming_mfma_dim.hip"]
+           "search_dim.hip", "exhaustive_dim.hip", "hamming_mfma_dim.hip", "scan_route.hip"]
+# sources without device code: their objects carry no gfx950 bundle, so they are kept apart (_obj/host/) from
+# the objects whose disassembly the tests read
+HOST_ONLY = {"scan_route.hip"}
 ARCH = os.environ.get("VRQ_OFFLOAD_ARCH", "gfx950")
 CFLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"--offload-arch={ARCH}",
           "-Wall", "-Wno-unused-function", "-Wno-unused-variable"]
@@ -84,12 +87,12 @@ class _BuildLock:
 def _build_one(lib: str, probe: bool, verbose: bool, force_all: bool = False) -> None:
     hipcc = _hipcc()
     odir = os.path.join(OBJDIR, "probe") if probe else OBJDIR
-    os.makedirs(odir, exist_ok=True)
+    os.makedirs(os.path.join(odir, "host"), exist_ok=True)
 
     headers = [d for d in _deps() if d.endswith(".h")]
 
     def compile_one(src):
-        obj = os.path.join(odir, os.path.splitext(src)[0] + ".o")
+        obj = os.path.join(odir, "host" if src in HOST_ONLY else "", os.path.splitext(src)[0] + ".o")
         cmd = [hipcc, *CFLAGS, *(["-DVRQ_TUNING_ENV"] if probe else []), *EXTRA.get(src, []), "-c",
                os.path.join(CSRC, src), "-o", obj]
         # incremental: an object newer than its source and every header, built by the same command

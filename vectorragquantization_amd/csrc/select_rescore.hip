@@ -25,8 +25,6 @@
 namespace vrq {
 
 constexpr int SEL_THREADS = 256;
-constexpr int KMAX = 1024;          // max K (binary_k) handled per query
-constexpr int MAX_LISTS = 4096;     // max chunk lists merged per query
 constexpr int NBINS = 1025 + 3;     // dist in [0, 1024] for 1024-bit codes
 constexpr uint64_t ROW_MASK = (1ull << KEY_ROW_BITS) - 1;
 
@@ -375,15 +373,37 @@ __device__ void finish_query(int Kp, bool have_s3, const FinishArgs& a, int qi, 
   if (tid == 0) a.out_count[qi] = m;
 }
 
-// Per-query lists of the scan: nlp chunk lists [nq][nlp][K], optionally followed by one
-// more list per query from a separate [nq][K] array (the matrix-core scan's suffix list,
-// whose rows all follow the prefix lists' rows).
-struct ScanKeys {
+// The lists a scan left for one query, [nl][K]: the chunk lists of the wavefront scans (K1 / K1d), or the
+// single sorted list of a matrix-core scan.
+struct ChunkKeys {
   const uint64_t* lists;
-  const uint64_t* suffix;
-  int nlpK;
-  __device__ uint64_t operator[](int i) const { return i < nlpK ? lists[i] : suffix[i - nlpK]; }
+  __device__ uint64_t operator[](int i) const { return lists[i]; }
 };
+
+// Outputs in Phase-I order (VRQ_SEARCH_PHASE1_ONLY, and VRQ_SEARCH_SHARD with the two scores): the Kp
+// selected candidates sh.sel[0..Kp), padded to a.kout.
+template <class SH>
+__device__ void write_phase1_order(int Kp, bool with_scores, const FinishArgs& a, int qi, const SH& sh) {
+  for (int i = threadIdx.x; i < a.kout; i += SEL_THREADS) {
+    const int64_t o = (int64_t)qi * a.kout + i;
+    if (i < Kp) {
+      a.out_rows[o] = (int64_t)(sh.sel[i] & ROW_MASK) + a.row_offset;
+      a.out_dist[o] = (int32_t)(sh.sel[i] >> KEY_ROW_BITS);
+      if (with_scores) {
+        a.out_s2[o] = sh.s2[i];
+        a.out_s3[o] = sh.s3[i];
+      }
+    } else {
+      a.out_rows[o] = -1;
+      a.out_dist[o] = DIST_NONE;
+      if (with_scores) {
+        a.out_s2[o] = __builtin_nan("");
+        a.out_s3[o] = __builtin_nan("");
+      }
+    }
+  }
+  if (threadIdx.x == 0 && a.out_count) a.out_count[qi] = Kp;
+}
 
 // Phase II (:283-293) of the Kp candidates sh.sel[0..Kp) -> sh.s2, one candidate per lane.  The score is
 // a sum of 256 nibble terms: for nibble p of the packed code (dims 4p..4p+3, MSB first) and its value v,
@@ -445,18 +465,17 @@ __device__ void phase2_nibble_tables(const float* __restrict__ q, const uint8_t*
 template <class SH>
 // (the small instance at 4 waves per SIMD: every query of a 1024-query batch resident at once)
 __global__ __launch_bounds__(SEL_THREADS, SH::kKM <= KSMALL ? 4 : 1) void select_rescore_kernel(
-    const uint64_t* __restrict__ lists, int nlp, const uint64_t* __restrict__ suffix, int K,
-    const uint8_t* __restrict__ codes, const int8_t* __restrict__ x8, const double* __restrict__ norms,
-    const float* __restrict__ qf, int mode, FinishArgs fa) {
+    const uint64_t* __restrict__ lists, int nl, bool sorted, int K, const uint8_t* __restrict__ codes,
+    const int8_t* __restrict__ x8, const double* __restrict__ norms, const float* __restrict__ qf, int mode,
+    FinishArgs fa) {
   __shared__ SH sh;
   const int qi = blockIdx.x;
   const int tid = threadIdx.x, w = tid / WAVE, l = lane_id();
-  const ScanKeys Lq{lists + (int64_t)qi * nlp * K, suffix ? suffix + (int64_t)qi * K : nullptr, nlp * K};
+  const uint64_t* sq = lists + (int64_t)qi * nl * K;
   int Kp;
-  if (nlp == 0 && suffix) {
+  if (sorted) {
     // the matrix-core scan's suffix stage left one list, already the exact top-K in FAISS (dist, row)
     // order with KEY_NONE padding after its valid prefix: taken as is
-    const uint64_t* sq = suffix + (int64_t)qi * K;
     if (tid == 0) sh.misc[0] = 0;
     __syncthreads();
     int valid = 0;
@@ -470,25 +489,12 @@ __global__ __launch_bounds__(SEL_THREADS, SH::kKM <= KSMALL ? 4 : 1) void select
     __syncthreads();
     Kp = sh.misc[0];
   } else {
-    Kp = select_topk(Lq, nlp + (suffix ? 1 : 0), K, sh);
+    Kp = select_topk(ChunkKeys{sq}, nl, K, sh);
   }
   if (mode == 1) {
-    for (int i = tid; i < fa.kout; i += SEL_THREADS) {
-      const int64_t o = (int64_t)qi * fa.kout + i;
-      if (i < Kp) {
-        fa.out_rows[o] = (int64_t)(sh.sel[i] & ROW_MASK) + fa.row_offset;
-        fa.out_dist[o] = (int32_t)(sh.sel[i] >> KEY_ROW_BITS);
-      } else {
-        fa.out_rows[o] = -1;
-        fa.out_dist[o] = DIST_NONE;
-      }
-    }
-    if (tid == 0 && fa.out_count) fa.out_count[qi] = Kp;
+    write_phase1_order(Kp, false, fa, qi, sh);
     return;
   }
-#ifdef VRQ_FIN_BISECT  // timing-only probe builds (wrong results): 1 = stop after the selection
-  if (VRQ_FIN_BISECT == 1) return;
-#endif
   // Phase II for all Kp candidates (float64, :283-293)
   const float* q = qf + (int64_t)qi * DIM;
   __shared__ double qtab[QT_NIB * 16];
@@ -503,27 +509,10 @@ __global__ __launch_bounds__(SEL_THREADS, SH::kKM <= KSMALL ? 4 : 1) void select
       if (l == 0) sh.s3[j] = c;
     }
     __syncthreads();
-    for (int i = tid; i < fa.kout; i += SEL_THREADS) {
-      const int64_t o = (int64_t)qi * fa.kout + i;
-      if (i < Kp) {
-        fa.out_rows[o] = (int64_t)(sh.sel[i] & ROW_MASK) + fa.row_offset;
-        fa.out_dist[o] = (int32_t)(sh.sel[i] >> KEY_ROW_BITS);
-        fa.out_s2[o] = sh.s2[i];
-        fa.out_s3[o] = sh.s3[i];
-      } else {
-        fa.out_rows[o] = -1;
-        fa.out_dist[o] = DIST_NONE;
-        fa.out_s2[o] = __builtin_nan("");
-        fa.out_s3[o] = __builtin_nan("");
-      }
-    }
-    if (tid == 0) fa.out_count[qi] = Kp;
+    write_phase1_order(Kp, true, fa, qi, sh);
     return;
   }
   __syncthreads();
-#ifdef VRQ_FIN_BISECT  // 2 = stop after Phase II
-  if (VRQ_FIN_BISECT == 2) return;
-#endif
   FinishArgs a = fa;
   a.q = q;
   finish_query(Kp, false, a, qi, sh);
@@ -614,12 +603,6 @@ __device__ void phase2_nibble_tables_dim(const float* __restrict__ q, const uint
   __syncthreads();
 }
 
-// the K1d lists of one query: [nchunks][K], no suffix list
-struct ChunkKeys {
-  const uint64_t* lists;
-  __device__ uint64_t operator[](int i) const { return lists[i]; }
-};
-
 // K2 for the other dims: merge of the K1d lists (histogram over every distance up to 2048) + Phase II +
 // Phase III + the stable sorts.  mode: 0 = full 3-phase; 1 = Phase I only.
 template <class SH>
@@ -633,17 +616,7 @@ __global__ __launch_bounds__(SEL_THREADS, SH::kKM <= KSMALL ? 4 : 1) void select
   const ChunkKeys Lq{lists + (int64_t)qi * nlp * K};
   const int Kp = select_topk(Lq, nlp, K, sh);
   if (mode == 1) {
-    for (int i = tid; i < fa.kout; i += SEL_THREADS) {
-      const int64_t o = (int64_t)qi * fa.kout + i;
-      if (i < Kp) {
-        fa.out_rows[o] = (int64_t)(sh.sel[i] & ROW_MASK) + fa.row_offset;
-        fa.out_dist[o] = (int32_t)(sh.sel[i] >> KEY_ROW_BITS);
-      } else {
-        fa.out_rows[o] = -1;
-        fa.out_dist[o] = DIST_NONE;
-      }
-    }
-    if (tid == 0 && fa.out_count) fa.out_count[qi] = Kp;
+    write_phase1_order(Kp, false, fa, qi, sh);
     return;
   }
   const float* q = qf + (int64_t)qi * dim;
@@ -761,8 +734,31 @@ __global__ __launch_bounds__(SEL_THREADS) void merge_shards_kernel(int S, int K,
   finish_query(Kp, true, a, qi, sh);
 }
 
+// The two scores of one row for one query, one wave: at 1024 dims from the lane-resident query slice
+// (exact_scores.h), at the other dims from the query in memory (the loops above).
+struct Scorer1024 {
+  float qv[DPL];
+  __device__ Scorer1024(const float* __restrict__ qf, int qi, int) { load_q(qv, qf + (int64_t)qi * DIM); }
+  __device__ double binary(const uint8_t* codes, int64_t row) const { return phase2_dot(qv, codes + row * (DIM / 8)); }
+  __device__ double cosine(const int8_t* x8, int64_t row, double nrm) const {
+    return phase3_cos(qv, x8 + row * DIM, nrm);
+  }
+};
+struct ScorerDim {
+  const float* q;
+  int dim;
+  __device__ ScorerDim(const float* __restrict__ qf, int qi, int d) : q(qf + (int64_t)qi * d), dim(d) {}
+  __device__ double binary(const uint8_t* codes, int64_t row) const {
+    return phase2_dot_dim(q, codes + row * (dim / 8), dim);
+  }
+  __device__ double cosine(const int8_t* x8, int64_t row, double nrm) const {
+    return phase3_cos_dim(q, x8 + row * dim, nrm, dim);
+  }
+};
+
 // Stand-alone candidate rescoring: one wave per (query, candidate).
-__global__ __launch_bounds__(256) void rescore_kernel(int which, const float* __restrict__ qf, int nq,
+template <class Scorer>
+__global__ __launch_bounds__(256) void rescore_kernel(int which, const float* __restrict__ qf, int nq, int dim,
                                                       const uint8_t* __restrict__ codes,
                                                       const int8_t* __restrict__ x8,
                                                       const double* __restrict__ norms, int64_t n,
@@ -776,57 +772,45 @@ __global__ __launch_bounds__(256) void rescore_kernel(int which, const float* __
     if (lane_id() == 0) out[gw] = __builtin_nan("");
     return;
   }
-  float qv[DPL];
-  load_q(qv, qf + (int64_t)qi * DIM);
-  const double v = which == 0 ? phase2_dot(qv, codes + row * (DIM / 8)) : phase3_cos(qv, x8 + row * DIM, norms[row]);
+  const Scorer sc(qf, qi, dim);
+  const double v = which == 0 ? sc.binary(codes, row) : sc.cosine(x8, row, norms[row]);
   if (lane_id() == 0) out[gw] = v;
 }
 
-// The same for the other dims (vrq_rescore_*_dim).
-__global__ __launch_bounds__(256) void rescore_dim_kernel(int which, const float* __restrict__ qf, int nq, int dim,
-                                                          const uint8_t* __restrict__ codes,
-                                                          const int8_t* __restrict__ x8,
-                                                          const double* __restrict__ norms, int64_t n,
-                                                          const int64_t* __restrict__ cand, int ncand,
-                                                          double* __restrict__ out) {
-  const int64_t gw = ((int64_t)blockIdx.x * 256 + threadIdx.x) / WAVE;
-  if (gw >= (int64_t)nq * ncand) return;
-  const int qi = (int)(gw / ncand);
-  const int64_t row = cand[gw];
-  if (row < 0 || row >= n) {
-    if (lane_id() == 0) out[gw] = __builtin_nan("");
-    return;
-  }
-  const float* q = qf + (int64_t)qi * dim;
-  const double v = which == 0 ? phase2_dot_dim(q, codes + row * (dim / 8), dim)
-                              : phase3_cos_dim(q, x8 + row * dim, norms[row], dim);
-  if (lane_id() == 0) out[gw] = v;
-}
-
-static int launch_select_dim(hipStream_t s, int nq, const uint64_t* lists, int nl, int K, int dim,
-                             const uint8_t* codes, const int8_t* x8, const double* norms, const float* qf, int mode,
-                             const FinishArgs& fa) {
-  if (K <= KSMALL && nl <= LSMALL)
-    hipLaunchKernelGGL(select_rescore_dim_kernel<SelDimSmall>, dim3(nq), dim3(SEL_THREADS), 0, s, lists, nl, K, dim,
-                       codes, x8, norms, qf, mode, fa);
+static int launch_rescore(int which, const float* qf, int nq, int dim, const uint8_t* codes, const int8_t* x8,
+                          const double* norms, int64_t n, const int64_t* cand, int ncand, double* out,
+                          hipStream_t s) {
+  const dim3 grid((unsigned)(((int64_t)nq * ncand + 3) / 4));
+  if (dim == DIM)
+    hipLaunchKernelGGL(rescore_kernel<Scorer1024>, grid, dim3(256), 0, s, which, qf, nq, dim, codes, x8, norms, n,
+                       cand, ncand, out);
   else
-    hipLaunchKernelGGL(select_rescore_dim_kernel<SelDimBig>, dim3(nq), dim3(SEL_THREADS), 0, s, lists, nl, K, dim,
-                       codes, x8, norms, qf, mode, fa);
+    hipLaunchKernelGGL(rescore_kernel<ScorerDim>, grid, dim3(256), 0, s, which, qf, nq, dim, codes, x8, norms, n,
+                       cand, ncand, out);
   VRQ_LAUNCH_CHECK();
   return VRQ_OK;
 }
 
-// launch the small-LDS instance when the shape fits it
-static int launch_select(hipStream_t s, int nq, const uint64_t* lists, int nlp, const uint64_t* suffix, int K,
+// K2 on the lists a route's scan left in `ws`: the 1024 kernel at dim 1024, the runtime-dim kernel
+// otherwise; of either, the small-LDS instance when the shape fits it.
+static int launch_select(hipStream_t s, int nq, const void* ws, const Phase1Route& r, int K, int dim,
                          const uint8_t* codes, const int8_t* x8, const double* norms, const float* qf, int mode,
                          const FinishArgs& fa) {
-  const int nl = nlp + (suffix ? 1 : 0);
-  if (K <= KSMALL && nl <= LSMALL)
-    hipLaunchKernelGGL(select_rescore_kernel<SelSmall>, dim3(nq), dim3(SEL_THREADS), 0, s, lists, nlp, suffix, K,
-                       codes, x8, norms, qf, mode, fa);
+  const uint64_t* lists = (const uint64_t*)((const uint8_t*)ws + r.off_lists);
+  const bool small = K <= KSMALL && r.nl <= LSMALL;
+  const dim3 grid(nq), block(SEL_THREADS);
+  if (dim == DIM && small)
+    hipLaunchKernelGGL(select_rescore_kernel<SelSmall>, grid, block, 0, s, lists, r.nl, r.sorted, K, codes, x8, norms,
+                       qf, mode, fa);
+  else if (dim == DIM)
+    hipLaunchKernelGGL(select_rescore_kernel<SelBig>, grid, block, 0, s, lists, r.nl, r.sorted, K, codes, x8, norms,
+                       qf, mode, fa);
+  else if (small)  // (a matrix-core scan's sorted list is the single list of the merge)
+    hipLaunchKernelGGL(select_rescore_dim_kernel<SelDimSmall>, grid, block, 0, s, lists, r.nl, K, dim, codes, x8,
+                       norms, qf, mode, fa);
   else
-    hipLaunchKernelGGL(select_rescore_kernel<SelBig>, dim3(nq), dim3(SEL_THREADS), 0, s, lists, nlp, suffix, K,
-                       codes, x8, norms, qf, mode, fa);
+    hipLaunchKernelGGL(select_rescore_dim_kernel<SelDimBig>, grid, block, 0, s, lists, r.nl, K, dim, codes, x8, norms,
+                       qf, mode, fa);
   VRQ_LAUNCH_CHECK();
   return VRQ_OK;
 }
@@ -837,27 +821,48 @@ using namespace vrq;
 
 extern "C" {
 
-size_t vrq_search3_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K) {
-  if (n < 1 || nq < 1 || K < 1 || dim != DIM) return 0;
-  ScanPlan p;
-  if (scan_plan(n, dim / 8, nq, K, &p) != VRQ_OK) return 0;
-  MfmaPlan mp;
-  if (K <= kMfmaMaxK && n >= kMfmaMinRows && mfma_plan(n, nq, K, &mp) == VRQ_OK)
-    return mp.bytes > p.list_bytes ? mp.bytes : p.list_bytes;
-  return p.list_bytes;
+// ---- Phase I: every entry point below takes its scan from the route (vrq_scan.h) ----
+size_t vrq_hamming_topk_workspace_size(int64_t n, int32_t code_bytes, int32_t nq, int32_t k) {
+  return phase1_workspace_bytes(n, code_bytes, nq, k);
 }
 
-size_t vrq_hamming_topk_workspace_size(int64_t n, int32_t code_bytes, int32_t nq, int32_t k) {
-  if (n < 1 || nq < 1 || k < 1) return 0;
-  ScanPlan p;
-  if (scan_plan(n, code_bytes, nq, k, &p) != VRQ_OK) return 0;
-  MfmaPlan mp;
-  if (code_bytes == 128 && mfma_use(n, nq, k, 0) && mfma_plan(n, nq, k, &mp) == VRQ_OK)
-    return mp.bytes > p.list_bytes ? mp.bytes : p.list_bytes;
-  // the other code sizes: wherever the matrix-core scan (K1rd) can be chosen
-  if (code_bytes != 128 && k <= kMfmaMaxK && n >= kMfmaMinRows && mfma_dim_plan(n, code_bytes, nq, k, &mp) == VRQ_OK)
-    return mp.bytes > p.list_bytes ? mp.bytes : p.list_bytes;
-  return p.list_bytes;
+size_t vrq_search3_dim_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K) {
+  return vrq_dim_supported(dim) ? phase1_workspace_bytes(n, dim / 8, nq, K) : 0;
+}
+
+size_t vrq_search3_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K) {
+  return dim == DIM ? vrq_search3_dim_workspace_size(n, dim, nq, K) : 0;
+}
+
+size_t vrq_search2_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K) {
+  return vrq_search3_dim_workspace_size(n, dim, nq, K);
+}
+
+// the route of a call (n, nq, K >= 1) and the workspace check every entry point makes before it launches
+static int route_checked(int64_t n, int cb, int nq, int K, int flags, size_t workspace_bytes, Phase1Route* r) {
+  const int rc = phase1_route(n, cb, nq, K, flags, r);
+  if (rc != VRQ_OK) return rc;
+  return workspace_bytes < r->bytes ? VRQ_EWORKSPACE : VRQ_OK;
+}
+
+static FinishArgs finish_args(const int8_t* x8, const double* norms, const int64_t* remap, int64_t row_offset, int k,
+                              int K3, int32_t* out_count, int64_t* out_rows, int32_t* out_dist, double* out_s2,
+                              double* out_s3, int32_t* out_src, int kout) {
+  FinishArgs fa{};
+  fa.x8 = x8;
+  fa.norms = norms;
+  fa.remap = remap;
+  fa.row_offset = row_offset;
+  fa.k = k;
+  fa.K3 = K3;
+  fa.out_count = out_count;
+  fa.out_rows = out_rows;
+  fa.out_dist = out_dist;
+  fa.out_s2 = out_s2;
+  fa.out_s3 = out_s3;
+  fa.out_src = out_src;
+  fa.kout = kout;
+  return fa;
 }
 
 static int fill_empty(int32_t nq, int32_t kout, int32_t* out_count, int64_t* out_rows, int32_t* out_dist,
@@ -881,65 +886,89 @@ int vrq_hamming_topk(const uint8_t* codes, int64_t n, int32_t code_bytes, int64_
   if (nq == 0) return VRQ_OK;
   if (n == 0 || k == 0) return fill_empty(nq, k, nullptr, out_rows, out_dist, nullptr, nullptr, s);
   VRQ_CHECK_ARG(codes && queries && workspace);
-  FinishArgs fa{};
-  fa.row_offset = row_offset;
-  fa.out_rows = out_rows;
-  fa.out_dist = out_dist;
-  fa.kout = k;
-  uint64_t* lists = (uint64_t*)workspace;
-  if (code_bytes == 128 && mfma_use(n, nq, k, 0)) {
-    MfmaPlan mp;
-    int rc = mfma_plan(n, nq, k, &mp);
-    if (rc != VRQ_OK) return rc;
-    if (workspace_bytes < mp.bytes) return VRQ_EWORKSPACE;
-    rc = mfma_scan_launch(mp, codes, n, queries, nq, k, (uint8_t*)workspace, s, 0);
-    if (rc != VRQ_OK) return rc;
-    return launch_select(s, nq, lists, 0, (const uint64_t*)((uint8_t*)workspace + mp.off_suffix), k, nullptr,
-                         nullptr, nullptr, nullptr, 1, fa);
-  }
-  if (code_bytes != 128 && mfma_dim_use(n, code_bytes, nq, k, 0)) {
-    MfmaPlan mp;
-    int rc = mfma_dim_plan(n, code_bytes, nq, k, &mp);
-    if (rc != VRQ_OK) return rc;
-    if (workspace_bytes < mp.bytes) return VRQ_EWORKSPACE;
-    rc = mfma_dim_scan_launch(mp, codes, n, code_bytes, queries, nq, k, (uint8_t*)workspace, s, 0);
-    if (rc != VRQ_OK) return rc;
-    // (the sorted K-list per query is one list of the merge)
-    return launch_select_dim(s, nq, (const uint64_t*)((uint8_t*)workspace + mp.off_suffix), 1, k, code_bytes * 8,
-                             nullptr, nullptr, nullptr, nullptr, 1, fa);
-  }
-  ScanPlan p;
-  int rc = scan_plan(n, code_bytes, nq, k, &p);
+  Phase1Route r;
+  int rc = route_checked(n, code_bytes, nq, k, 0, workspace_bytes, &r);
   if (rc != VRQ_OK) return rc;
-  if (workspace_bytes < p.list_bytes) return VRQ_EWORKSPACE;
-  if (p.nchunks > MAX_LISTS) return VRQ_EUNSUPPORTED;
-  rc = scan_launch(p, codes, n, code_bytes, queries, nq, k, lists, s);
+  rc = phase1_launch(r, codes, n, code_bytes, queries, nq, k, workspace, s, 0);
   if (rc != VRQ_OK) return rc;
-  if (code_bytes != DIM / 8)  // (the merge instance whose histogram covers distances up to 2048)
-    return launch_select_dim(s, nq, lists, p.nchunks, k, code_bytes * 8, nullptr, nullptr, nullptr, nullptr, 1, fa);
-  return launch_select(s, nq, lists, p.nchunks, nullptr, k, nullptr, nullptr, nullptr, nullptr, 1, fa);
+  const FinishArgs fa = finish_args(nullptr, nullptr, nullptr, row_offset, 0, 0, nullptr, out_rows, out_dist, nullptr,
+                                    nullptr, nullptr, k);
+  return launch_select(s, nq, workspace, r, k, code_bytes * 8, nullptr, nullptr, nullptr, nullptr, 1, fa);
 }
 
+// The staged three-phase search at every dim of vrq_dim_supported.  The sharded mode is 1024-only.
+int vrq_search3_dim_scan(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq, int32_t K,
+                         int32_t flags, void* workspace, size_t workspace_bytes, void* stream) {
+  VRQ_CHECK_ARG(n >= 0 && nq >= 0 && K >= 0);
+  if (!vrq_dim_supported(dim) || K > KMAX) return VRQ_EUNSUPPORTED;
+  if (dim != DIM && (flags & VRQ_SEARCH_SHARD)) return VRQ_EUNSUPPORTED;
+  if (nq == 0 || n == 0 || K == 0) return VRQ_OK;
+  VRQ_CHECK_ARG(codes && qb && workspace);
+  Phase1Route r;
+  const int rc = route_checked(n, dim / 8, nq, K, flags, workspace_bytes, &r);
+  if (rc != VRQ_OK) return rc;
+  return phase1_launch(r, codes, n, dim / 8, qb, nq, K, workspace, (hipStream_t)stream, flags);
+}
+
+int vrq_search3_dim_finish(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
+                           int64_t n, int32_t dim, int64_t row_offset, const float* qf, int32_t nq, int32_t k,
+                           int32_t K, int32_t K3, int32_t flags, int32_t* out_count, int64_t* out_rows,
+                           int32_t* out_dist, double* out_binary, double* out_cosine, const void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  VRQ_CHECK_ARG(n >= 0 && nq >= 0 && k >= 0 && K >= 0 && K3 >= 0);
+  VRQ_CHECK_ARG(out_count && out_rows && out_dist);
+  if (!vrq_dim_supported(dim) || K > KMAX) return VRQ_EUNSUPPORTED;
+  if (dim != DIM && (flags & VRQ_SEARCH_SHARD)) return VRQ_EUNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  const int mode = (flags & VRQ_SEARCH_PHASE1_ONLY) ? 1 : (flags & VRQ_SEARCH_SHARD) ? 2 : 0;
+  const int kout = mode == 0 ? k : K;
+  if (nq == 0) return VRQ_OK;
+  if (mode != 1) VRQ_CHECK_ARG(out_binary && out_cosine);
+  if (n == 0 || K == 0 || (mode == 0 && k == 0))
+    return fill_empty(nq, kout, out_count, out_rows, out_dist, out_binary, out_cosine, s);
+  VRQ_CHECK_ARG(codes && workspace);
+  if (mode != 1) VRQ_CHECK_ARG(qf && x8 && norms);
+  Phase1Route r;
+  const int rc = route_checked(n, dim / 8, nq, K, flags, workspace_bytes, &r);
+  if (rc != VRQ_OK) return rc;
+  const FinishArgs fa = finish_args(x8, norms, rescore_row, row_offset, k, K3, out_count, out_rows, out_dist,
+                                    out_binary, out_cosine, nullptr, kout);
+  return launch_select(s, nq, workspace, r, K, dim, codes, x8, norms, qf, mode, fa);
+}
+
+int vrq_search3_dim(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
+                    int64_t n, int32_t dim, int64_t row_offset, const float* qf, const uint8_t* qb, int32_t nq,
+                    int32_t k, int32_t K, int32_t K3, int32_t flags, int32_t* out_count, int64_t* out_rows,
+                    int32_t* out_dist, double* out_binary, double* out_cosine, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+  VRQ_CHECK_ARG(n >= 0 && nq >= 0 && k >= 0 && K >= 0 && K3 >= 0);
+  const int mode = (flags & VRQ_SEARCH_PHASE1_ONLY) ? 1 : (flags & VRQ_SEARCH_SHARD) ? 2 : 0;
+  const bool run = nq > 0 && n > 0 && K > 0 && (mode != 0 || k > 0);
+  if (dim != DIM) {
+    // The whole call checks every argument before it launches the scan (at 1024, the ABI-1 behaviour stays:
+    // the finish checks its own after the scan), and takes no flag but these two: forcing the matrix-core
+    // scan and staging it go through vrq_search3_dim_scan / _finish.
+    VRQ_CHECK_ARG(out_count && out_rows && out_dist);
+    if (!vrq_dim_supported(dim) || K > KMAX) return VRQ_EUNSUPPORTED;
+    if (flags & ~(VRQ_SEARCH_PHASE1_ONLY | VRQ_SEARCH_SCAN_VALU)) return VRQ_EUNSUPPORTED;
+    if (nq > 0 && mode != 1) VRQ_CHECK_ARG(out_binary && out_cosine);
+    if (run) VRQ_CHECK_ARG(codes && qb && workspace);
+    if (run && mode != 1) VRQ_CHECK_ARG(qf && x8 && norms);
+  }
+  if (run) {
+    const int rc = vrq_search3_dim_scan(codes, n, dim, qb, nq, K, flags, workspace, workspace_bytes, stream);
+    if (rc != VRQ_OK) return rc;
+  }
+  return vrq_search3_dim_finish(codes, x8, norms, rescore_row, n, dim, row_offset, qf, nq, k, K, K3, flags, out_count,
+                                out_rows, out_dist, out_binary, out_cosine, workspace, workspace_bytes, stream);
+}
+
+// ABI 1: the same three at dim 1024 only
 int vrq_search3_scan(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq, int32_t K,
                      int32_t flags, void* workspace, size_t workspace_bytes, void* stream) {
   VRQ_CHECK_ARG(n >= 0 && nq >= 0 && K >= 0);
   if (dim != DIM) return VRQ_EUNSUPPORTED;
-  if (K > KMAX) return VRQ_EUNSUPPORTED;
-  if (nq == 0 || n == 0 || K == 0) return VRQ_OK;
-  VRQ_CHECK_ARG(codes && qb && workspace);
-  if (mfma_use(n, nq, K, flags)) {
-    MfmaPlan mp;
-    const int rc = mfma_plan(n, nq, K, &mp);
-    if (rc != VRQ_OK) return rc;
-    if (workspace_bytes < mp.bytes) return VRQ_EWORKSPACE;
-    return mfma_scan_launch(mp, codes, n, qb, nq, K, (uint8_t*)workspace, (hipStream_t)stream, flags);
-  }
-  ScanPlan p;
-  int rc = scan_plan(n, dim / 8, nq, K, &p);
-  if (rc != VRQ_OK) return rc;
-  if (workspace_bytes < p.list_bytes) return VRQ_EWORKSPACE;
-  if (p.nchunks > MAX_LISTS) return VRQ_EUNSUPPORTED;
-  return scan_launch(p, codes, n, dim / 8, qb, nq, K, (uint64_t*)workspace, (hipStream_t)stream);
+  return vrq_search3_dim_scan(codes, n, dim, qb, nq, K, flags, workspace, workspace_bytes, stream);
 }
 
 int vrq_search3_finish(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
@@ -950,46 +979,8 @@ int vrq_search3_finish(const uint8_t* codes, const int8_t* x8, const double* nor
   VRQ_CHECK_ARG(n >= 0 && nq >= 0 && k >= 0 && K >= 0 && K3 >= 0);
   VRQ_CHECK_ARG(out_count && out_rows && out_dist);
   if (dim != DIM) return VRQ_EUNSUPPORTED;
-  if (K > KMAX) return VRQ_EUNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  const int mode = (flags & VRQ_SEARCH_PHASE1_ONLY) ? 1 : (flags & VRQ_SEARCH_SHARD) ? 2 : 0;
-  const int kout = mode == 0 ? k : K;
-  if (nq == 0) return VRQ_OK;
-  if (mode != 1) VRQ_CHECK_ARG(out_binary && out_cosine);
-  if (n == 0 || K == 0 || (mode == 0 && k == 0))
-    return fill_empty(nq, kout, out_count, out_rows, out_dist, out_binary, out_cosine, s);
-  VRQ_CHECK_ARG(codes && workspace);
-  if (mode != 1) VRQ_CHECK_ARG(qf && x8 && norms);
-  int nlp;
-  const uint64_t* suffix = nullptr;
-  if (mfma_use(n, nq, K, flags)) {
-    MfmaPlan mp;
-    const int rc = mfma_plan(n, nq, K, &mp);
-    if (rc != VRQ_OK) return rc;
-    if (workspace_bytes < mp.bytes) return VRQ_EWORKSPACE;
-    nlp = 0;  // the matrix-core scan leaves one sorted list per query
-    suffix = (const uint64_t*)((const uint8_t*)workspace + mp.off_suffix);
-  } else {
-    ScanPlan p;
-    const int rc = scan_plan(n, dim / 8, nq, K, &p);
-    if (rc != VRQ_OK) return rc;
-    if (workspace_bytes < p.list_bytes) return VRQ_EWORKSPACE;
-    nlp = p.nchunks;
-  }
-  FinishArgs fa{};
-  fa.x8 = x8;
-  fa.norms = norms;
-  fa.remap = rescore_row;
-  fa.row_offset = row_offset;
-  fa.k = k;
-  fa.K3 = K3;
-  fa.out_count = out_count;
-  fa.out_rows = out_rows;
-  fa.out_dist = out_dist;
-  fa.out_s2 = out_binary;
-  fa.out_s3 = out_cosine;
-  fa.kout = kout;
-  return launch_select(s, nq, (const uint64_t*)workspace, nlp, suffix, K, codes, x8, norms, qf, mode, fa);
+  return vrq_search3_dim_finish(codes, x8, norms, rescore_row, n, dim, row_offset, qf, nq, k, K, K3, flags, out_count,
+                                out_rows, out_dist, out_binary, out_cosine, workspace, workspace_bytes, stream);
 }
 
 int vrq_search3(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
@@ -997,40 +988,36 @@ int vrq_search3(const uint8_t* codes, const int8_t* x8, const double* norms, con
                 int32_t K, int32_t K3, int32_t flags, int32_t* out_count, int64_t* out_rows, int32_t* out_dist,
                 double* out_binary, double* out_cosine, void* workspace, size_t workspace_bytes, void* stream) {
   VRQ_CHECK_ARG(n >= 0 && nq >= 0 && k >= 0 && K >= 0 && K3 >= 0);
-  const int mode = (flags & VRQ_SEARCH_PHASE1_ONLY) ? 1 : (flags & VRQ_SEARCH_SHARD) ? 2 : 0;
-  const bool empty = n == 0 || K == 0 || (mode == 0 && k == 0);
-  if (!empty && nq > 0) {
-    const int rc = vrq_search3_scan(codes, n, dim, qb, nq, K, flags, workspace, workspace_bytes, stream);
-    if (rc != VRQ_OK) return rc;
-  }
-  return vrq_search3_finish(codes, x8, norms, rescore_row, n, dim, row_offset, qf, nq, k, K, K3, flags, out_count,
-                            out_rows, out_dist, out_binary, out_cosine, workspace, workspace_bytes, stream);
+  if (dim != DIM) return VRQ_EUNSUPPORTED;
+  return vrq_search3_dim(codes, x8, norms, rescore_row, n, dim, row_offset, qf, qb, nq, k, K, K3, flags, out_count,
+                         out_rows, out_dist, out_binary, out_cosine, workspace, workspace_bytes, stream);
 }
 
+// ---- introspection: the answers are read out of the route ----
 int vrq_scan_kind(int64_t n, int32_t dim, int32_t nq, int32_t K, int32_t flags, int64_t* prefix_rows) {
   if (n < 1 || nq < 1 || K < 1) return VRQ_EINVAL;
   if (!vrq_dim_supported(dim) || K > KMAX) return VRQ_EUNSUPPORTED;
-  if (dim != DIM ? mfma_dim_use(n, dim / 8, nq, K, flags) : mfma_use(n, nq, K, flags)) {
-    MfmaPlan mp;
-    const int rc = dim != DIM ? mfma_dim_plan(n, dim / 8, nq, K, &mp) : mfma_plan(n, nq, K, &mp);
-    if (rc != VRQ_OK) return rc;
-    if (prefix_rows) *prefix_rows = 0;  // every row goes through the matrix-core pass
-    return VRQ_SCAN_KIND_MFMA;
-  }
-  ScanPlan p;
-  const int rc = scan_plan(n, dim / 8, nq, K, &p);
+  Phase1Route r;
+  const int rc = phase1_route(n, dim / 8, nq, K, flags, &r);
   if (rc != VRQ_OK) return rc;
-  if (prefix_rows) *prefix_rows = n;
-  return VRQ_SCAN_KIND_VALU;
+  if (prefix_rows) *prefix_rows = r.mfma ? 0 : n;  // (every row goes through the matrix-core pass)
+  return r.mfma ? VRQ_SCAN_KIND_MFMA : VRQ_SCAN_KIND_VALU;
+}
+
+// the matrix-core plan of a shape; VRQ_EUNSUPPORTED where the wavefront scan runs
+static int mfma_route(int64_t n, int32_t dim, int32_t nq, int32_t K, int32_t flags, const int64_t* info,
+                      Phase1Route* r) {
+  if (!info || n < 1 || nq < 1 || K < 1) return VRQ_EINVAL;
+  if (!vrq_dim_supported(dim) || K > KMAX) return VRQ_EUNSUPPORTED;
+  const int rc = phase1_route(n, dim / 8, nq, K, flags, r);
+  return rc != VRQ_OK ? rc : r->mfma ? VRQ_OK : VRQ_EUNSUPPORTED;
 }
 
 int vrq_scan_plan(int64_t n, int32_t dim, int32_t nq, int32_t K, int32_t flags, int64_t* info) {
-  if (!info || n < 1 || nq < 1 || K < 1) return VRQ_EINVAL;
-  if (!vrq_dim_supported(dim) || K > KMAX) return VRQ_EUNSUPPORTED;
-  if (!(dim != DIM ? mfma_dim_use(n, dim / 8, nq, K, flags) : mfma_use(n, nq, K, flags))) return VRQ_EUNSUPPORTED;
-  MfmaPlan p;
-  const int rc = dim != DIM ? mfma_dim_plan(n, dim / 8, nq, K, &p) : mfma_plan(n, nq, K, &p);
+  Phase1Route r;
+  const int rc = mfma_route(n, dim, nq, K, flags, info, &r);
   if (rc != VRQ_OK) return rc;
+  const MfmaPlan& p = r.mp;
   info[0] = dim != DIM ? kMfmaKindRowsDim : p.rows ? 1 : p.swap ? 2 : 0;
   info[1] = p.mb;
   info[2] = p.chunk_rows;
@@ -1047,12 +1034,10 @@ int vrq_scan_plan(int64_t n, int32_t dim, int32_t nq, int32_t K, int32_t flags, 
 }
 
 int vrq_scan_sample_plan(int64_t n, int32_t dim, int32_t nq, int32_t K, int32_t flags, int64_t* info) {
-  if (!info || n < 1 || nq < 1 || K < 1) return VRQ_EINVAL;
-  if (!vrq_dim_supported(dim) || K > KMAX) return VRQ_EUNSUPPORTED;
-  if (!(dim != DIM ? mfma_dim_use(n, dim / 8, nq, K, flags) : mfma_use(n, nq, K, flags))) return VRQ_EUNSUPPORTED;
-  MfmaPlan p;
-  const int rc = dim != DIM ? mfma_dim_plan(n, dim / 8, nq, K, &p) : mfma_plan(n, nq, K, &p);
+  Phase1Route r;
+  const int rc = mfma_route(n, dim, nq, K, flags, info, &r);
   if (rc != VRQ_OK) return rc;
+  const MfmaPlan& p = r.mp;
   info[0] = p.rows_sample;
   info[1] = p.sample_chunks;
   info[2] = p.sample_chunk_rows;
@@ -1073,16 +1058,8 @@ int vrq_merge_shards(int32_t nshards, int32_t nq, int32_t K, const int32_t* coun
   if (nq == 0) return VRQ_OK;
   if (K == 0 || k == 0) return fill_empty(nq, k, out_count, out_rows, out_dist, out_binary, out_cosine, s);
   VRQ_CHECK_ARG(counts && rows && dist && s2 && s3);
-  FinishArgs fa{};
-  fa.k = k;
-  fa.K3 = K3;
-  fa.out_count = out_count;
-  fa.out_rows = out_rows;
-  fa.out_dist = out_dist;
-  fa.out_s2 = out_binary;
-  fa.out_s3 = out_cosine;
-  fa.out_src = out_src;
-  fa.kout = k;
+  const FinishArgs fa = finish_args(nullptr, nullptr, nullptr, 0, k, K3, out_count, out_rows, out_dist, out_binary,
+                                    out_cosine, out_src, k);
   if (K <= KSMALL && nshards <= LSMALL)
     hipLaunchKernelGGL(merge_shards_kernel<SelSmall>, dim3(nq), dim3(SEL_THREADS), 0, s, nshards, K, counts, rows,
                        dist, s2, s3, nq, fa);
@@ -1093,189 +1070,44 @@ int vrq_merge_shards(int32_t nshards, int32_t nq, int32_t K, const int32_t* coun
   return VRQ_OK;
 }
 
+// ---- stand-alone rescoring: every dim of vrq_dim_supported; the ABI-1 names take 1024 only ----
+int vrq_rescore_binary_dim(const float* qf, int32_t nq, int32_t dim, const uint8_t* codes, int64_t n,
+                           const int64_t* cand_rows, int32_t ncand, double* out, void* stream) {
+  VRQ_CHECK_ARG(nq >= 0 && ncand >= 0 && n >= 0);
+  if (!vrq_dim_supported(dim)) return VRQ_EUNSUPPORTED;
+  if ((int64_t)nq * ncand == 0) return VRQ_OK;
+  VRQ_CHECK_ARG(qf && codes && cand_rows && out);
+  return launch_rescore(0, qf, nq, dim, codes, nullptr, nullptr, n, cand_rows, ncand, out, (hipStream_t)stream);
+}
+
+int vrq_rescore_int8_cosine_dim(const float* qf, int32_t nq, int32_t dim, const int8_t* x8, const double* norms,
+                                int64_t n, const int64_t* cand_rows, int32_t ncand, double* out, void* stream) {
+  VRQ_CHECK_ARG(nq >= 0 && ncand >= 0 && n >= 0);
+  if (!vrq_dim_supported(dim)) return VRQ_EUNSUPPORTED;
+  if ((int64_t)nq * ncand == 0) return VRQ_OK;
+  VRQ_CHECK_ARG(qf && x8 && norms && cand_rows && out);
+  return launch_rescore(1, qf, nq, dim, nullptr, x8, norms, n, cand_rows, ncand, out, (hipStream_t)stream);
+}
+
 int vrq_rescore_binary(const float* qf, int32_t nq, int32_t dim, const uint8_t* codes, int64_t n,
                        const int64_t* cand_rows, int32_t ncand, double* out, void* stream) {
   VRQ_CHECK_ARG(nq >= 0 && ncand >= 0 && n >= 0);
   if (dim != DIM) return VRQ_EUNSUPPORTED;
-  const int64_t waves = (int64_t)nq * ncand;
-  if (waves == 0) return VRQ_OK;
-  VRQ_CHECK_ARG(qf && codes && cand_rows && out);
-  hipLaunchKernelGGL(rescore_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, 0, qf,
-                     nq, codes, nullptr, nullptr, n, cand_rows, ncand, out);
-  VRQ_LAUNCH_CHECK();
-  return VRQ_OK;
+  return vrq_rescore_binary_dim(qf, nq, dim, codes, n, cand_rows, ncand, out, stream);
 }
 
 int vrq_rescore_int8_cosine(const float* qf, int32_t nq, int32_t dim, const int8_t* x8, const double* norms,
                             int64_t n, const int64_t* cand_rows, int32_t ncand, double* out, void* stream) {
   VRQ_CHECK_ARG(nq >= 0 && ncand >= 0 && n >= 0);
   if (dim != DIM) return VRQ_EUNSUPPORTED;
-  const int64_t waves = (int64_t)nq * ncand;
-  if (waves == 0) return VRQ_OK;
-  VRQ_CHECK_ARG(qf && x8 && norms && cand_rows && out);
-  hipLaunchKernelGGL(rescore_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, 1, qf,
-                     nq, nullptr, x8, norms, n, cand_rows, ncand, out);
-  VRQ_LAUNCH_CHECK();
-  return VRQ_OK;
+  return vrq_rescore_int8_cosine_dim(qf, nq, dim, x8, norms, n, cand_rows, ncand, out, stream);
 }
 
-// ---- the other embedding dims: additive entry points, dim == 1024 forwards to the ABI-1 functions ----
 int vrq_dim_supported(int32_t dim) {
   return dim == DIM || (dim > 0 && dim % 8 == 0 && dim_code_bytes_supported(dim / 8)) ? 1 : 0;
 }
 
-size_t vrq_search3_dim_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K) {
-  if (dim == DIM) return vrq_search3_workspace_size(n, dim, nq, K);
-  if (n < 1 || nq < 1 || K < 1 || !vrq_dim_supported(dim)) return 0;
-  ScanPlan p;
-  if (scan_plan(n, dim / 8, nq, K, &p) != VRQ_OK) return 0;
-  MfmaPlan mp;  // wherever the matrix-core scan (K1rd) can be chosen: the larger of the two
-  if (K <= kMfmaMaxK && n >= kMfmaMinRows && mfma_dim_plan(n, dim / 8, nq, K, &mp) == VRQ_OK)
-    return mp.bytes > p.list_bytes ? mp.bytes : p.list_bytes;
-  return p.list_bytes;
-}
-
-int vrq_search3_dim_scan(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq, int32_t K,
-                         int32_t flags, void* workspace, size_t workspace_bytes, void* stream) {
-  if (dim == DIM) return vrq_search3_scan(codes, n, dim, qb, nq, K, flags, workspace, workspace_bytes, stream);
-  VRQ_CHECK_ARG(n >= 0 && nq >= 0 && K >= 0);
-  if (!vrq_dim_supported(dim) || K > KMAX) return VRQ_EUNSUPPORTED;
-  if (flags & VRQ_SEARCH_SHARD) return VRQ_EUNSUPPORTED;  // the sharded mode is 1024-only
-  if (nq == 0 || n == 0 || K == 0) return VRQ_OK;
-  VRQ_CHECK_ARG(codes && qb && workspace);
-  const int cb = dim / 8;
-  if (mfma_dim_use(n, cb, nq, K, flags)) {
-    MfmaPlan mp;
-    const int rc = mfma_dim_plan(n, cb, nq, K, &mp);
-    if (rc != VRQ_OK) return rc;
-    if (workspace_bytes < mp.bytes) return VRQ_EWORKSPACE;
-    return mfma_dim_scan_launch(mp, codes, n, cb, qb, nq, K, (uint8_t*)workspace, (hipStream_t)stream, flags);
-  }
-  ScanPlan p;
-  const int rc = scan_plan(n, cb, nq, K, &p);
-  if (rc != VRQ_OK) return rc;
-  if (workspace_bytes < p.list_bytes) return VRQ_EWORKSPACE;
-  if (p.nchunks > MAX_LISTS) return VRQ_EUNSUPPORTED;
-  return scan_launch(p, codes, n, cb, qb, nq, K, (uint64_t*)workspace, (hipStream_t)stream);
-}
-
-int vrq_search3_dim_finish(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
-                           int64_t n, int32_t dim, int64_t row_offset, const float* qf, int32_t nq, int32_t k,
-                           int32_t K, int32_t K3, int32_t flags, int32_t* out_count, int64_t* out_rows,
-                           int32_t* out_dist, double* out_binary, double* out_cosine, const void* workspace,
-                           size_t workspace_bytes, void* stream) {
-  if (dim == DIM)
-    return vrq_search3_finish(codes, x8, norms, rescore_row, n, dim, row_offset, qf, nq, k, K, K3, flags, out_count,
-                              out_rows, out_dist, out_binary, out_cosine, workspace, workspace_bytes, stream);
-  VRQ_CHECK_ARG(n >= 0 && nq >= 0 && k >= 0 && K >= 0 && K3 >= 0);
-  VRQ_CHECK_ARG(out_count && out_rows && out_dist);
-  if (!vrq_dim_supported(dim) || K > KMAX) return VRQ_EUNSUPPORTED;
-  if (flags & VRQ_SEARCH_SHARD) return VRQ_EUNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  const int mode = (flags & VRQ_SEARCH_PHASE1_ONLY) ? 1 : 0;
-  const int kout = mode == 0 ? k : K;
-  if (nq == 0) return VRQ_OK;
-  if (mode != 1) VRQ_CHECK_ARG(out_binary && out_cosine);
-  if (n == 0 || K == 0 || (mode == 0 && k == 0))
-    return fill_empty(nq, kout, out_count, out_rows, out_dist, out_binary, out_cosine, s);
-  VRQ_CHECK_ARG(codes && workspace);
-  if (mode != 1) VRQ_CHECK_ARG(qf && x8 && norms);
-  const int cb = dim / 8;
-  const uint64_t* lists = (const uint64_t*)workspace;
-  int nl;
-  if (mfma_dim_use(n, cb, nq, K, flags)) {
-    MfmaPlan mp;
-    const int rc = mfma_dim_plan(n, cb, nq, K, &mp);
-    if (rc != VRQ_OK) return rc;
-    if (workspace_bytes < mp.bytes) return VRQ_EWORKSPACE;
-    // the matrix-core scan leaves one sorted K-list per query: the single list of the merge
-    lists = (const uint64_t*)((const uint8_t*)workspace + mp.off_suffix);
-    nl = 1;
-  } else {
-    ScanPlan p;
-    const int rc = scan_plan(n, cb, nq, K, &p);
-    if (rc != VRQ_OK) return rc;
-    if (workspace_bytes < p.list_bytes) return VRQ_EWORKSPACE;
-    if (p.nchunks > MAX_LISTS) return VRQ_EUNSUPPORTED;
-    nl = p.nchunks;
-  }
-  FinishArgs fa{};
-  fa.x8 = x8;
-  fa.norms = norms;
-  fa.remap = rescore_row;
-  fa.row_offset = row_offset;
-  fa.k = k;
-  fa.K3 = K3;
-  fa.out_count = out_count;
-  fa.out_rows = out_rows;
-  fa.out_dist = out_dist;
-  fa.out_s2 = out_binary;
-  fa.out_s3 = out_cosine;
-  fa.kout = kout;
-  return launch_select_dim(s, nq, lists, nl, K, dim, codes, x8, norms, qf, mode, fa);
-}
-
-int vrq_search3_dim(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
-                    int64_t n, int32_t dim, int64_t row_offset, const float* qf, const uint8_t* qb, int32_t nq,
-                    int32_t k, int32_t K, int32_t K3, int32_t flags, int32_t* out_count, int64_t* out_rows,
-                    int32_t* out_dist, double* out_binary, double* out_cosine, void* workspace,
-                    size_t workspace_bytes, void* stream) {
-  if (dim == DIM)
-    return vrq_search3(codes, x8, norms, rescore_row, n, dim, row_offset, qf, qb, nq, k, K, K3, flags, out_count,
-                       out_rows, out_dist, out_binary, out_cosine, workspace, workspace_bytes, stream);
-  VRQ_CHECK_ARG(n >= 0 && nq >= 0 && k >= 0 && K >= 0 && K3 >= 0);
-  VRQ_CHECK_ARG(out_count && out_rows && out_dist);
-  if (!vrq_dim_supported(dim) || K > KMAX) return VRQ_EUNSUPPORTED;
-  // forcing the matrix-core scan and staging it go through vrq_search3_dim_scan / _finish; the sharded
-  // mode is 1024-only.  VRQ_SEARCH_SCAN_VALU forces the wavefront scan; otherwise the scan is chosen
-  // by shape (mfma_dim_use).
-  if (flags & ~(VRQ_SEARCH_PHASE1_ONLY | VRQ_SEARCH_SCAN_VALU)) return VRQ_EUNSUPPORTED;
-  const int mode = (flags & VRQ_SEARCH_PHASE1_ONLY) ? 1 : 0;
-  const bool empty = n == 0 || K == 0 || (mode == 0 && k == 0);
-  if (nq > 0 && mode != 1) VRQ_CHECK_ARG(out_binary && out_cosine);
-  if (!empty && nq > 0) {
-    VRQ_CHECK_ARG(codes && qb && workspace);
-    if (mode != 1) VRQ_CHECK_ARG(qf && x8 && norms);
-    const int rc = vrq_search3_dim_scan(codes, n, dim, qb, nq, K, flags, workspace, workspace_bytes, stream);
-    if (rc != VRQ_OK) return rc;
-  }
-  return vrq_search3_dim_finish(codes, x8, norms, rescore_row, n, dim, row_offset, qf, nq, k, K, K3, flags, out_count,
-                                out_rows, out_dist, out_binary, out_cosine, workspace, workspace_bytes, stream);
-}
-
-int vrq_rescore_binary_dim(const float* qf, int32_t nq, int32_t dim, const uint8_t* codes, int64_t n,
-                           const int64_t* cand_rows, int32_t ncand, double* out, void* stream) {
-  if (dim == DIM) return vrq_rescore_binary(qf, nq, dim, codes, n, cand_rows, ncand, out, stream);
-  VRQ_CHECK_ARG(nq >= 0 && ncand >= 0 && n >= 0);
-  if (!vrq_dim_supported(dim)) return VRQ_EUNSUPPORTED;
-  const int64_t waves = (int64_t)nq * ncand;
-  if (waves == 0) return VRQ_OK;
-  VRQ_CHECK_ARG(qf && codes && cand_rows && out);
-  hipLaunchKernelGGL(rescore_dim_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, 0, qf,
-                     nq, dim, codes, nullptr, nullptr, n, cand_rows, ncand, out);
-  VRQ_LAUNCH_CHECK();
-  return VRQ_OK;
-}
-
-int vrq_rescore_int8_cosine_dim(const float* qf, int32_t nq, int32_t dim, const int8_t* x8, const double* norms,
-                                int64_t n, const int64_t* cand_rows, int32_t ncand, double* out, void* stream) {
-  if (dim == DIM) return vrq_rescore_int8_cosine(qf, nq, dim, x8, norms, n, cand_rows, ncand, out, stream);
-  VRQ_CHECK_ARG(nq >= 0 && ncand >= 0 && n >= 0);
-  if (!vrq_dim_supported(dim)) return VRQ_EUNSUPPORTED;
-  const int64_t waves = (int64_t)nq * ncand;
-  if (waves == 0) return VRQ_OK;
-  VRQ_CHECK_ARG(qf && x8 && norms && cand_rows && out);
-  hipLaunchKernelGGL(rescore_dim_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, 1, qf,
-                     nq, dim, nullptr, x8, norms, n, cand_rows, ncand, out);
-  VRQ_LAUNCH_CHECK();
-  return VRQ_OK;
-}
-
 // ---- the fused two-phase search (every dim of vrq_dim_supported) ----
-size_t vrq_search2_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K) {
-  return vrq_search3_dim_workspace_size(n, dim, nq, K);
-}
-
 static bool search2_mode_ok(int mode) {
   return (mode >= VRQ_ENC_INT8_GLOBAL && mode <= VRQ_ENC_INT4_LOCAL) || mode == VRQ_RESCORE_F32 ||
          mode == VRQ_RESCORE_SIGNED_BINARY;
@@ -1296,32 +1128,18 @@ int vrq_search2_finish(int32_t mode, const uint8_t* codes, const void* q, const 
   if (n == 0 || K == 0 || k == 0) return fill_empty(nq, k, out_count, out_rows, out_dist, out_score, nullptr, s);
   VRQ_CHECK_ARG(codes && workspace && qf && q);
   if (mode == VRQ_ENC_INT8_LOCAL || mode == VRQ_ENC_INT4_LOCAL) VRQ_CHECK_ARG(minmax);
-  // the lists the scan left, located as vrq_search3_finish / vrq_search3_dim_finish do at that dim
-  const int cb = dim / 8;
-  const uint64_t* lists = (const uint64_t*)workspace;
-  int nl;
-  if (dim != DIM ? mfma_dim_use(n, cb, nq, K, flags) : mfma_use(n, nq, K, flags)) {
-    MfmaPlan mp;
-    const int rc = dim != DIM ? mfma_dim_plan(n, cb, nq, K, &mp) : mfma_plan(n, nq, K, &mp);
-    if (rc != VRQ_OK) return rc;
-    if (workspace_bytes < mp.bytes) return VRQ_EWORKSPACE;
-    // the matrix-core scan leaves one sorted K-list per query: the single list of the merge
-    lists = (const uint64_t*)((const uint8_t*)workspace + mp.off_suffix);
-    nl = 1;
-  } else {
-    ScanPlan p;
-    const int rc = scan_plan(n, cb, nq, K, &p);
-    if (rc != VRQ_OK) return rc;
-    if (workspace_bytes < p.list_bytes) return VRQ_EWORKSPACE;
-    if (p.nchunks > MAX_LISTS) return VRQ_EUNSUPPORTED;
-    nl = p.nchunks;
-  }
+  Phase1Route r;
+  const int rc = route_checked(n, dim / 8, nq, K, flags, workspace_bytes, &r);
+  if (rc != VRQ_OK) return rc;
+  // (a matrix-core scan's sorted list is the single list of the merge)
+  const uint64_t* lists = (const uint64_t*)((const uint8_t*)workspace + r.off_lists);
   const Finish2Args fa{mode, q, minmax, limit, rescore_row, row_offset, k, out_count, out_rows, out_dist, out_score};
-  if (K <= KSMALL && nl <= LSMALL)
-    hipLaunchKernelGGL(select_rescore2_kernel<Sel2Small>, dim3(nq), dim3(SEL_THREADS), 0, s, lists, nl, K, dim, qf,
+  if (K <= KSMALL && r.nl <= LSMALL)
+    hipLaunchKernelGGL(select_rescore2_kernel<Sel2Small>, dim3(nq), dim3(SEL_THREADS), 0, s, lists, r.nl, K, dim, qf,
                        fa);
   else
-    hipLaunchKernelGGL(select_rescore2_kernel<Sel2Big>, dim3(nq), dim3(SEL_THREADS), 0, s, lists, nl, K, dim, qf, fa);
+    hipLaunchKernelGGL(select_rescore2_kernel<Sel2Big>, dim3(nq), dim3(SEL_THREADS), 0, s, lists, r.nl, K, dim, qf,
+                       fa);
   VRQ_LAUNCH_CHECK();
   return VRQ_OK;
 }

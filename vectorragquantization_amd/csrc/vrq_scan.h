@@ -98,4 +98,28 @@ bool mfma_dim_use(int64_t n, int cb, int nq, int K, int flags);
 int mfma_dim_scan_launch(const MfmaPlan& p, const uint8_t* codes, int64_t n, int cb, const uint8_t* q, int nq, int K,
                          uint8_t* ws, hipStream_t s, int flags);
 
+// ---- the Phase-I route (scan_route.hip): which of the scans above runs for a call shape, its plan, the
+// workspace it needs and where it leaves its lists.  Every search entry point takes its scan from here;
+// nothing else calls mfma_use / mfma_dim_use or the three planners. ----
+constexpr int KMAX = 1024;          // max K (binary_k) handled per query
+constexpr int MAX_LISTS = 4096;     // max chunk lists merged per query (select_rescore.hip)
+
+struct Phase1Route {
+  bool mfma;         // a matrix-core scan (K1m / K1s / K1r at 128 code bytes, K1rd otherwise)
+  ScanPlan sp;       // valid when !mfma
+  MfmaPlan mp;       // valid when mfma
+  size_t bytes;      // workspace this route needs
+  size_t off_lists;  // where the finish finds the lists [nq][nl][K] in the workspace (0, or mp.off_suffix)
+  int nl;            // lists per query (sp.nchunks, or 1)
+  bool sorted;       // the single list is already the exact top-K in (dist, row) order, KEY_NONE padded
+};
+// VRQ_EINVAL for an empty shape, VRQ_EUNSUPPORTED where no scan serves it (code size, K, more than
+// MAX_LISTS chunk lists).  flags: VRQ_SEARCH_SCAN_VALU / VRQ_SEARCH_SCAN_MFMA force a scan, the rest is ignored.
+int phase1_route(int64_t n, int cb, int nq, int K, int flags, Phase1Route* r);
+// runs the route's scan (flags: the VRQ_SCAN_STAGE_* bits of a matrix-core scan)
+int phase1_launch(const Phase1Route& r, const uint8_t* codes, int64_t n, int cb, const uint8_t* q, int nq, int K,
+                  void* ws, hipStream_t s, int flags);
+// the largest `bytes` of the routes any flags can select (a pure function of the shape); 0: no route
+size_t phase1_workspace_bytes(int64_t n, int cb, int nq, int K);
+
 }  // namespace vrq

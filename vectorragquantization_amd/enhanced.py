@@ -128,17 +128,14 @@ def search3(codes: torch.Tensor, x8: torch.Tensor, norms: torch.Tensor, qf: torc
     if rescore_row is not None and rescore_row.shape[0] != n:
         raise N.VrqNativeError(f"vrq_search3: rescore_row has {rescore_row.shape[0]} entries for {n} rows")
     lib = N.load()
-    # 1024 keeps the ABI-1 entry points; the other dims go through the additive *_dim ones
-    name, fn, size_fn = ("vrq_search3", lib.vrq_search3, lib.vrq_search3_workspace_size) if dim == 1024 else \
-        ("vrq_search3_dim", lib.vrq_search3_dim, lib.vrq_search3_dim_workspace_size)
-    need = size_fn(n, dim, nq, K) if n and nq and K else 0
+    need = lib.vrq_search3_dim_workspace_size(n, dim, nq, K) if n and nq and K else 0
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev)
-    rc = fn(N.ptr(codes) if n else 0, N.ptr(x8) if n else 0, N.ptr(norms) if n else 0,
-            N.ptr(rescore_row), n, dim, row_offset, N.ptr(qf), N.ptr(qb), nq, k, K, K3, flags,
-            N.ptr(cnt), N.ptr(rows), N.ptr(dist), N.ptr(s2), N.ptr(s3), N.ptr(workspace),
-            workspace.numel(), N.stream_handle(dev))
-    N.check(rc, name)
+    rc = lib.vrq_search3_dim(N.ptr(codes) if n else 0, N.ptr(x8) if n else 0, N.ptr(norms) if n else 0,
+                             N.ptr(rescore_row), n, dim, row_offset, N.ptr(qf), N.ptr(qb), nq, k, K, K3, flags,
+                             N.ptr(cnt), N.ptr(rows), N.ptr(dist), N.ptr(s2), N.ptr(s3), N.ptr(workspace),
+                             workspace.numel(), N.stream_handle(dev))
+    N.check(rc, "vrq_search3_dim")
     return cnt, rows, dist, s2, s3
 
 
@@ -341,8 +338,7 @@ class CohereEnhancedVectorDB:
         if self._ws is None or self._ws.device != self.device:
             self._ws = torch.empty((8,), dtype=torch.uint8, device=self.device)
         lib = N.load()
-        size_fn = lib.vrq_search3_workspace_size if self.embedding_dim == 1024 else lib.vrq_search3_dim_workspace_size
-        need = size_fn(n, self.embedding_dim, qf.shape[0], K) if n and K else 0
+        need = lib.vrq_search3_dim_workspace_size(n, self.embedding_dim, qf.shape[0], K) if n and K else 0
         if self._ws.numel() < need:
             self._ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
