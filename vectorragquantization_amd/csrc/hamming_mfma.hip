@@ -23,8 +23,9 @@
 //    dist < tau(q), tau(q) = the exact K-th smallest distance of the query over a PREFIX of
 //    the corpus (computed by the exact scan).  FAISS admits a row only if dist < heap_top,
 //    rows in increasing index: a suffix row with dist >= tau(q) ranks after >= K prefix rows,
-//    so the strict test loses nothing.  A max3 tree + one compare per (M-block, lane) rejects
-//    hit-free blocks; hits are ballot-compacted into a per-wave LDS stage of packed 32-bit
+//    so the strict test loses nothing.  A max3 tree over all of a lane's accumulators (one row,
+//    each register carrying its own query's seed) + one compare per n-block rejects hit-free
+//    n-blocks; hits are ballot-compacted into a per-wave LDS stage of packed 32-bit
 //    entries and, once per tile, appended to per-(query, chunk) lists in HBM at positions
 //    taken from per-query LDS counters.  suffix_topk_kernel merges the lists into one sorted
 //    K-list per query, exactly in every case (overflow -> exact rescan).
@@ -49,6 +50,9 @@ constexpr int GPW = (PKT / 1024) / MWAVES;  // LDS-DMA instructions per wave per
 constexpr int BAHEAD = 3;                   // B fragments read this many groups ahead
 constexpr int NRING = BAHEAD < 4 ? 4 : 8;   // B fragment ring (power of two > BAHEAD)
 constexpr int STG = 512;                    // per-wave staged hit entries (u32)
+#ifndef VRQ_K1M_NSR  // A/B builds: M-blocks per wave whose accumulator seeds stay in registers (capped at MB)
+#define VRQ_K1M_NSR 4
+#endif
 #ifndef VRQ_K1M_DMA_AHEAD  // A/B builds: K1m refills a packed slot one iteration earlier (two tiles of DMA lead)
 #define VRQ_K1M_DMA_AHEAD 0
 #endif
@@ -58,6 +62,9 @@ template <int MB>
 struct MfmaShape {
   static constexpr int QPW = 32 * MB;                 // queries per wave
   static constexpr int QPB = MWAVES * QPW;            // queries per workgroup
+  // M-blocks whose seeds stay in registers as the C operand of every n-block's first MFMA; the others
+  // re-read theirs from LDS into the accumulators after each epilogue
+  static constexpr int NSR = VRQ_K1M_NSR < MB ? VRQ_K1M_NSR : MB;
   static constexpr int SMEM =
       NPK * PKT + NUB * UBT + NUB * RT * 4 + MWAVES * QPW * 8 + MWAVES * (STG + 1) * 4 + MWAVES * MB * 128;
   static_assert(SMEM <= 160 * 1024, "LDS budget");
@@ -89,9 +96,12 @@ constexpr int ENT_V_SHIFT = 14, ENT_Q_SHIFT = 7, ENT_V_BIAS = 1025;
 // MFMAs on the fragment of group gi.  Around them, spread so no group's vector work much exceeds
 // its MFMA shadow: the packed reads of unpack unit u (gi = 8u+1) and its unpack + LDS writes
 // (gi = 8u+6), the row-popcount reads (gi = 12) and writes (gi = 28); for the previous n-block the
-// hit test of M-block m (j = 2+m), one branch to the (rare) hit extraction (j = 3+MB) and the
-// accumulator re-seeds (j = 4+MB, two M-blocks per group); the asynchronous hit flush
-// (gi = 20+MB and 24+MB).
+// max3 tree of M-block m folded into the lane's running maximum (j = 2+m), one compare + ballot after
+// the last of them, one branch to the (rare) hit extraction (j = 3+MB), which works out the M-blocks
+// that hold the candidates itself, and the accumulator re-seeds of the M-blocks m >= NSR (j = 4+MB+m,
+// one M-block per group, four ds_read_b128); the asynchronous hit flush (gi = 20+MB and 24+MB).  The
+// M-blocks m < NSR take their seeds from registers as the C operand of the n-block's first MFMA and
+// have no re-seed group.
 enum { MFMA_MAIN = 0, MFMA_SAMPLE = 1, MFMA_RERUN = 2 };
 
 // The per-group LDS wait of the schedule above.  Group gi consumes the B fragment read at the top of
@@ -99,20 +109,20 @@ enum { MFMA_MAIN = 0, MFMA_SAMPLE = 1, MFMA_RERUN = 2 };
 // operations issued after that read: the B reads of the groups since, and every other LDS operation
 // of those groups on the no-hit path (a hit adds stage writes, which only makes the counted wait
 // stricter).  Per group g: pre(g) = reads issued after its B read and before its wait (packed unit,
-// row popcounts), post(g) = operations issued in its slots (unpack writes, the popcount write, four
-// accumulator-seed reads, the two hit-flush steps).  Groups gi < BAHEAD read tiles the previous
+// row popcounts), post(g) = operations issued in its slots (unpack writes, the popcount write, the four
+// accumulator-seed reads of an M-block m >= nsr, the two hit-flush steps).  Groups gi < BAHEAD read tiles the previous
 // iteration's lgkmcnt(0) retired: their wait counts this iteration's operations so far.  Capped at 15
 // (the counter's range; a smaller count only waits longer).
 constexpr int k1m_pre(int g) { return ((g & 7) == 1 ? 1 : 0) + (g == 12 ? 2 : 0); }
-constexpr int k1m_post(int g, int mb, bool dense) {
+constexpr int k1m_post(int g, int mb, int nsr, bool dense) {
   const int j = g & 15;
-  return ((g & 7) == 6 ? 2 : 0) + (g == 28 ? 1 : 0) + (!dense && j >= 4 + mb && j < 4 + 2 * mb ? 4 : 0) +
+  return ((g & 7) == 6 ? 2 : 0) + (g == 28 ? 1 : 0) + (!dense && j >= 4 + mb + nsr && j < 4 + 2 * mb ? 4 : 0) +
          (!dense && g == 20 + mb ? 1 : 0) + (!dense && g == 24 + mb ? 1 : 0);
 }
-constexpr int k1m_wait(int gi, int mb, bool dense) {
+constexpr int k1m_wait(int gi, int mb, int nsr, bool dense) {
   const int g0 = gi - BAHEAD;
   int n = 1 + k1m_pre(gi);  // this group's B read and pre-wait reads
-  for (int g = g0 < 0 ? 0 : g0; g < gi; ++g) n += (g == g0 ? 0 : 1) + k1m_pre(g) + k1m_post(g, mb, dense);
+  for (int g = g0 < 0 ? 0 : g0; g < gi; ++g) n += (g == g0 ? 0 : 1) + k1m_pre(g) + k1m_post(g, mb, nsr, dense);
   return n < 15 ? n : 15;
 }
 
@@ -167,6 +177,7 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
     const int32_t* __restrict__ qbflag, uint16_t* __restrict__ dv, int64_t dv_stride) {
   constexpr bool DENSE = MODE == MFMA_SAMPLE;
   constexpr int QPW = MfmaShape<MB>::QPW, QPB = MfmaShape<MB>::QPB;
+  constexpr int NSR = DENSE ? 0 : MfmaShape<MB>::NSR;
   __shared__ __attribute__((aligned(16))) uint8_t smem[MfmaShape<MB>::SMEM];
   uint8_t* pk = smem;                                       // NPK packed tiles
   uint8_t* ub = smem + NPK * PKT;                           // NUB unpacked tiles
@@ -202,16 +213,22 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
   // LDS-DMA of packed tile t: this wave's GPW pieces of 64 x 16 B (lane -> (row, piece) through the
   // swizzle).  Whole tiles take a uniform base + a fixed per-lane offset; the last partial tile
   // clamps each row to the chunk's last row.
-  uint32_t doff[GPW];
-#pragma unroll
-  for (int i = 0; i < GPW; ++i) {
-    const int p = (w * GPW + i) * 64 + l;
+  // Only piece 0's offset is kept across the tile loop.  Piece i is 8 i rows further down, which adds
+  // 1024 i bytes and XORs bit 2 of the swizzled piece index (bit 6 of the offset) for odd i; the offsets are
+  // re-derived from an opaque copy at every issue, so no 64-bit form of them is held in registers.
+  static_assert(GPW == 2, "piece offsets derived for two pieces per wave");
+  uint32_t doff0;
+  {
+    const int p = w * GPW * 64 + l;
     const int r = p >> 3, c = (p & 7) ^ ((r >> 1) & 7);
-    doff[i] = (uint32_t)(r * 128 + c * 16);
+    doff0 = (uint32_t)(r * 128 + c * 16);
   }
   auto issue = [&](int t) __attribute__((always_inline)) {
     uint8_t* buf = pk + (t % NPK) * PKT;
     const int64_t tr0 = row0 + (int64_t)t * tile_stride;
+    uint32_t d0 = doff0;
+    asm volatile("" : "+v"(d0));
+    const uint32_t doff[GPW] = {d0, (d0 + 1024u) ^ 64u};
     if (tr0 + RT <= row1) {
       const uint8_t* base = codes + tr0 * 128;
 #pragma unroll
@@ -287,9 +304,10 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
     for (int s = 0; s < KS; ++s) asm volatile("" : "+a"(A[m][s]));
   // accumulator seed tau'/2 per register (register g of lane half h holds query
   // (g&3) + 8(g>>2) + 4h of the M-block): after the K loop acc = <q,r> + tau'/2, and the row is
-  // a candidate iff pc(r) - 2<q,r> < tau'  <=>  acc > pc(r)/2.  The seeds of M-block m stay in LDS
-  // (sd: [m][h][g] floats, 64 B per lane half: broadcast reads) and are loaded into the
-  // accumulators of an n-block right after that block's epilogue.
+  // a candidate iff pc(r) - 2<q,r> < tau'  <=>  acc > pc(r)/2.  The seeds go through LDS once
+  // (sd: [m][h][g] floats, 64 B per lane half: broadcast reads).  Those of M-blocks m < NSR then stay
+  // in registers (seedr) and are the C operand of every n-block's first MFMA; those of the M-blocks
+  // m >= NSR are re-read into the accumulators of an n-block right after that block's epilogue.
   float* sd = reinterpret_cast<float*>(pcr + NUB * RT + 2 * MWAVES * QPW + MWAVES * (STG + 1)) + w * MB * 32;
 #pragma unroll
   for (int m = 0; m < MB; ++m)
@@ -372,12 +390,14 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
     }
   };
   auto flush_from = [&](int i_begin, int64_t base_row) __attribute__((always_inline)) {
+    int lf = l;  // (opaque copy of the lane id: nothing derived from it on this rare path is hoisted)
+    asm volatile("" : "+v"(lf));
     if (nst > STG) {  // staging overflowed in this tile: every list of the wave -> exact rescan
-      for (int i = l; i < QPW; i += 64) lds_add32(lc0 + (uint32_t)(i * 4), capc + 1);
+      for (int i = lf; i < QPW; i += 64) lds_add32(lc0 + (uint32_t)(i * 4), capc + 1);
       nst = STG;
     }
     for (int i0 = i_begin; i0 < nst; i0 += 64) {
-      const int i = i0 + l;
+      const int i = i0 + lf;
       int e = 0, pos = 0;
       if (i < nst) lds_read32(e, stg0 + (uint32_t)(i * 4));
       asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(e)::"memory");
@@ -397,13 +417,13 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
     for (int g = 0; g < 16; ++g) {
       const uint64_t mask = __ballot(a[g] > hp);
       if (mask) {
-        if ((mask >> l) & 1) {
+        // lane-dependent values of this rare path are derived from an opaque copy of the lane
+        // id, so loop-invariant code motion cannot hoist them into registers held by the loop
+        int lo = l;
+        asm volatile("" : "+v"(lo));
+        if ((mask >> lo) & 1) {
           const int below = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
                                                       __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
-          // lane-dependent values of this rare path are derived from an opaque copy of the lane
-          // id, so loop-invariant code motion cannot hoist them into registers held by the loop
-          int lo = l;
-          asm volatile("" : "+v"(lo));
           const int ql = 32 * m + (g & 3) + 8 * (g >> 2) + 4 * (lo >> 5);
           // acc = <q,r> + tau'/2 with tau' = tau(q) - pc(q), so pc(r) - 2 acc = dist - tau(q) in
           // [-1025, -1] for a hit (exact integers): no per-query value to fetch on this path
@@ -420,9 +440,17 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
   // largest register (the others are <= hp), found by a max3 tree, its query row by the mask's
   // lowest bit -- at its rank among the hit lanes.  Otherwise the 16-ballot walk above.
   auto block_hits_fast = [&](const v16f& a, int m, int pc, float hp, int rel7) __attribute__((always_inline)) {
-    uint32_t m16 = 0;
+    // built in three pieces of at most 7 bits, so every per-bit mask is an inline constant (1 .. 64)
+    // and no mask constant sits in a register across the MFMA loop
+    uint32_t m16 = 0, mmid = 0, mhi = 0;
 #pragma unroll
-    for (int g = 0; g < 16; ++g) m16 |= (a[g] > hp ? 1u : 0u) << g;
+    for (int g = 0; g < 7; ++g) m16 |= (a[g] > hp ? 1u : 0u) << g;
+#pragma unroll
+    for (int g = 7; g < 14; ++g) mmid |= (a[g] > hp ? 1u : 0u) << (g - 7);
+#pragma unroll
+    for (int g = 14; g < 16; ++g) mhi |= (a[g] > hp ? 1u : 0u) << (g - 14);
+    asm volatile("" : "+v"(mmid), "+v"(mhi));
+    m16 |= (mmid << 7) | (mhi << 14);
 #ifdef VRQ_K1M_PROBE_NOSLOW  // timing-only probe builds (wrong lists when a lane holds two hits)
     if (false) {
 #else
@@ -463,13 +491,27 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
   v4i ring[NRING];
   const uint32_t bl0 = ub0 + (uint32_t)(l * 16);  // + tile slot + group * 1024: this lane's B fragment
   int pcvP = 0;  // previous tile's n-block 1 row popcount
-  uint64_t hitm[MB];  // per M-block: lanes of the previous n-block with a candidate (wave-uniform)
-#pragma unroll
-  for (int m = 0; m < MB; ++m) hitm[m] = 0;
+  int lmax = 0;         // this lane's running maximum over the previous n-block's accumulators (float bits)
+  uint64_t anyhit = 0;  // lanes of the previous n-block that hold a candidate (wave-uniform)
   int hpb = 0;   // the previous n-block's per-lane threshold pc(r)/2, as float bits
   v16f acc[2][MB];  // [n-block][m]
+  v16f seedr[NSR > 0 ? NSR : 1];  // register-resident seeds of M-blocks m < NSR, loaded once
+  static_for<0, NSR>([&](auto M) {
+    constexpr int m = decltype(M)::value;
+    v4i p0, p1, p2, p3;
+    lds_read128(p0, sd0 + (uint32_t)(m * 128));
+    lds_read128(p1, sd0 + (uint32_t)(m * 128 + 16));
+    lds_read128(p2, sd0 + (uint32_t)(m * 128 + 32));
+    lds_read128(p3, sd0 + (uint32_t)(m * 128 + 48));
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(p0), "+v"(p1), "+v"(p2), "+v"(p3)::"memory");
+    const v16i x = __builtin_shufflevector(__builtin_shufflevector(p0, p1, 0, 1, 2, 3, 4, 5, 6, 7),
+                                           __builtin_shufflevector(p2, p3, 0, 1, 2, 3, 4, 5, 6, 7), 0, 1, 2, 3, 4,
+                                           5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
+    seedr[m] = __builtin_bit_cast(v16f, x);
+    acc[0][m] = acc[1][m] = seedr[m];  // (tile 0 tests acc[1] against a threshold nothing exceeds)
+  });
   if constexpr (!DENSE)
-    static_for<0, MB>([&](auto M) {
+    static_for<NSR, MB>([&](auto M) {
       constexpr int m = decltype(M)::value;
       load_seed(acc[0][m], m);
       load_seed(acc[1][m], m);
@@ -505,8 +547,9 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
     const uint32_t ubw = ub0 + (uint32_t)(((t + 2) % NUB) * UBT);
     const uint32_t pks = pk0 + (uint32_t)(((t + 2) % NPK) * PKT);
     int pcv[2];
-    lds_read32(pcv[0], pcr0 + (uint32_t)(((t % NUB) * RT + ri) * 4));
-    lds_read32(pcv[1], pcr0 + (uint32_t)(((t % NUB) * RT + 32 + ri) * 4));
+    const uint32_t pcra = pcr0 + (uint32_t)(((t % NUB) * RT + ri) * 4);
+    lds_read32_imm<0>(pcv[0], pcra);
+    lds_read32_imm<32 * 4>(pcv[1], pcra);
     v2i pv;
     v4i pa, pb;
     VRQ_SCHED_FENCE();
@@ -518,31 +561,34 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
       else
         lds_read128_imm<(gi + BAHEAD - NG) * 1024>(ring[(gi + BAHEAD) & (NRING - 1)], bln);
       // packed reads of the unpack units (used 5 groups later) and of the row popcounts
-      if constexpr ((gi & 7) == 1) lds_read64(pv, pks + usrc[gi >> 3]);
+      // (unit u's source is unit 0's with u XORed into the swizzled piece index, the second popcount piece
+      // the first with its lowest index bit flipped: one kept address each)
+      if constexpr ((gi & 7) == 1) lds_read64(pv, xor_add<16 * (gi >> 3)>(usrc[0], pks));
       if constexpr (gi == 12) {
-        lds_read128(pa, pks + psrc0);
-        lds_read128(pb, pks + psrc1);
+        lds_read128(pa, xor_add<0>(psrc0, pks));
+        lds_read128(pb, xor_add<16>(psrc0, pks));
       }
       // every LDS operation issued up to the B read of group gi - BAHEAD has completed (k1m_wait): the
       // fragment of this group, the packed unit read 5 groups ago, the popcounts, the seeds
       asm volatile("s_waitcnt lgkmcnt(%7)"
                    : "+v"(ring[gi & (NRING - 1)]), "+v"(pv), "+v"(pcv[0]), "+v"(pcv[1]), "+v"(pa), "+v"(pb), "+v"(fe)
-                   : "n"(k1m_wait(gi, MB, DENSE))
+                   : "n"(k1m_wait(gi, MB, NSR, DENSE))
                    : "memory");
       // The group's non-MFMA work is cut into four slots that sit between its MFMAs (slot k after
       // MFMA k; at MB = 2 slots 2k and 2k+1 after MFMA k): an in-order wave issues them while the
       // matrix core runs, at most ~3 vector instructions per slot, instead of one burst after the
       // last MFMA of the group.  Per group kind:
-      //   hit test of M-block m (j = 2+m): max3 pairs in slots 0-2, the last max3 + compare in 3
+      //   hit test, M-block m's share (j = 2+m): max3 pairs in slots 0-2, in slot 3 the last max3 into
+      //     the lane's running maximum and, after M-block MB-1, the n-block's one compare + ballot
       //   the n-block threshold pc(r)/2 (j = 1), the (rare) hit-extraction branch (j = 3+MB, slot 3)
       //   unpack of unit u (gi = 8u+6): 3 + 2 ops per dword, the two LDS writes in slots 1 and 3
       //   row popcounts (gi = 28): 4 + 4 bcnt, the lane-quad sums, the LDS write
-      //   accumulator re-seeds (j = 4+MB .. 3+2MB... one M-block per group, one read per slot)
+      //   accumulator re-seeds of the M-blocks m >= NSR (j = 4+MB+m: one M-block per group, one read per slot)
       //   asynchronous hit flush (gi = 20+MB and 24+MB, slot 3)
       constexpr bool TEST = !DENSE && j >= 2 && j < 2 + MB;
       constexpr int tm = TEST ? j - 2 : 0;
       constexpr bool UNPACK = (gi & 7) == 6;
-      constexpr bool SEED = !DENSE && j >= 4 + MB && j < 4 + 2 * MB;
+      constexpr bool SEED = !DENSE && j >= 4 + MB + NSR && j < 4 + 2 * MB;  // (M-blocks m >= NSR only)
       constexpr int sm = SEED ? j - 4 - MB : 0;
       int e0 = 0, e1 = 0, e2 = 0, e3 = 0, e4 = 0, f0 = 0;
       uint32_t u0 = 0, u1 = 0, u2 = 0;
@@ -564,7 +610,11 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
             f0 = max(max(e0, e1), e2);
             asm volatile("" ::"v"(e4), "v"(f0));
           } else {
-            hitm[tm] = __ballot(max(max(e3, e4), max(bb[15], f0)) > hpb);
+            // every accumulator of the lane belongs to one row and carries its own query's seed: the
+            // lane's maximum over all MB x 16 registers decides the whole n-block with one compare
+            const int mx = max(max(e3, e4), f0);
+            lmax = tm == 0 ? max(bb[15], mx) : max(max(lmax, bb[15]), mx);
+            if constexpr (tm == MB - 1) anyhit = __ballot(lmax > hpb);
           }
         }
         if constexpr (!DENSE && j == 1 && k == 0) {
@@ -589,7 +639,7 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
             r.y = (int)u1;
             r.z = (int)u2;
             r.w = (int)((wv >> 1) & 0x44444444u);
-            lds_write128(ubw + udst[gi >> 3] + (uint32_t)(half * 1024), r);
+            lds_write128_imm<(gi >> 3) * 2048 + half * 1024>(ubw + udst[0], r);  // udst[u] = udst[0] + 2048 u
           }
         }
         if constexpr (gi == 28) {  // row popcounts of tile t+2
@@ -638,11 +688,9 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
             lds_add_rtn32(fpos, lc0 + (uint32_t)(((fe >> ENT_Q_SHIFT) & 127) * 4), l < nfl ? 1 : 0);
           // hit extraction of the previous n-block's flagged M-blocks, once per n-block (rare)
           if constexpr (!DENSE && j == 3 + MB) {
-            // (hitm[m] is assigned by every n-block's test of M-block m before this point)
-            uint64_t any = hitm[0];
-#pragma unroll
-            for (int m = 1; m < MB; ++m) any |= hitm[m];
-            if (any) {
+            // (anyhit is assigned by every n-block's test of M-block MB-1 before this point; which M-blocks
+            // hold the candidates is worked out here, off the no-hit path)
+            if (anyhit) {
               const int pcr_ = nbk == 0 ? pcvP : pcv[0];
               const int lr = (nbk == 0 ? (t - 1) * RT + 32 : t * RT) + ri;
               const int pc = row_pc(pcr_, lr);
@@ -650,7 +698,8 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
               static_for<0, MB>([&](auto M) {
                 constexpr int mm = decltype(M)::value;
 #ifndef VRQ_K1M_PROBE_NOHITS  // timing-only probe builds: no hit extraction at all
-                if (hitm[mm]) block_hits_fast(acc[nbk ^ 1][mm], mm, pc, hp, (nbk == 0 ? 32 : 64) + ri);
+                if (any_above(acc[nbk ^ 1][mm], hp))
+                  block_hits_fast(acc[nbk ^ 1][mm], mm, pc, hp, (nbk == 0 ? 32 : 64) + ri);
 #endif
               });
             }
@@ -659,9 +708,13 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
       };
       static_for<0, MB>([&](auto M) {
         constexpr int m = decltype(M)::value;
-        if constexpr (s == 0 && !DENSE)  // the seeds loaded after the block's last epilogue have landed
-          asm volatile("" : "+v"(acc[nbk][m]));
-        acc[nbk][m] = mfma_fp4(A[m][s], ring[gi & (NRING - 1)], (s == 0 && DENSE) ? v16f{} : acc[nbk][m]);
+        if constexpr (s == 0 && m < NSR) {  // register-resident seeds: the C operand
+          acc[nbk][m] = mfma_fp4(A[m][s], ring[gi & (NRING - 1)], seedr[m < NSR ? m : 0]);
+        } else {
+          if constexpr (s == 0 && !DENSE)  // the seeds loaded after the block's last epilogue have landed
+            asm volatile("" : "+v"(acc[nbk][m]));
+          acc[nbk][m] = mfma_fp4(A[m][s], ring[gi & (NRING - 1)], (s == 0 && DENSE) ? v16f{} : acc[nbk][m]);
+        }
         // pin the accumulator here: the MFMA intrinsics are pure, and without a use at this
         // point IR-level sinking moves them past the scheduling fences
         asm volatile("" : "+v"(acc[nbk][m]));
@@ -735,11 +788,14 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
 #endif
   if constexpr (DENSE)
     dmin.out(dv, dv_stride, (int64_t)chunk * 32 + ri, qbase, h, nq);
-  else
-    for (int i = l; i < QPW; i += 64) {
+  else {
+    int lz = l;  // (opaque copy: the loop's lane-derived values are formed here, after the tile loop)
+    asm volatile("" : "+v"(lz));
+    for (int i = lz; i < QPW; i += 64) {
       const int q = qbase + i;
       if (q < nq && (!rerun || rerun[q])) ccnt[(int64_t)q * nchunks + chunk] = lcnt[i];
     }
+  }
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -66,6 +66,22 @@ __device__ __forceinline__ void lds_read32_inplace(int& d, uint32_t a) {
 __device__ __forceinline__ void lds_write128(uint32_t a, const v4i& v) {
   asm volatile("ds_write_b128 %0, %1" ::"v"(a), "v"(v) : "memory");
 }
+template <int OFF>
+__device__ __forceinline__ void lds_read32_imm(int& d, uint32_t a) {
+  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(d) : "v"(a), "n"(OFF) : "memory");
+}
+template <int OFF>
+__device__ __forceinline__ void lds_write128_imm(uint32_t a, const v4i& v) {
+  asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(a), "v"(v), "n"(OFF) : "memory");
+}
+// (a ^ X) + s in one VALU instruction, for per-lane LDS addresses that differ from a kept one by an XOR
+// swizzle term: volatile, so the sum is formed where it is used and no copy of it is held across a loop
+template <int X>
+__device__ __forceinline__ uint32_t xor_add(uint32_t a, uint32_t s) {
+  uint32_t d;
+  asm volatile("v_xad_u32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "n"(X), "s"(s));
+  return d;
+}
 __device__ __forceinline__ void lds_write32(uint32_t a, int v) {
   asm volatile("ds_write_b32 %0, %1" ::"v"(a), "v"(v) : "memory");
 }
