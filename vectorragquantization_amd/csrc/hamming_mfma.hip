@@ -29,17 +29,19 @@
 //    entries and, once per tile, appended to per-(query, chunk) lists in HBM at positions
 //    taken from per-query LDS counters.  suffix_topk_kernel merges the lists into one sorted
 //    K-list per query, exactly in every case (overflow -> exact rescan).
+// This file holds the matrix kernels (K1m, K1s, K1r), their planner and launcher.  The stages around the
+// matrix passes -- thresholds from the dense sample, the recheck, the suffix merge -- are mfma_threshold.hip's,
+// shared with the other code sizes; mfma_hits.h holds the constants, DenseMin and K1r's hit stage.
 #include <stdlib.h>
 
 #include "mfma_common.h"
 #include "mfma_fp4.h"
+#include "mfma_hits.h"
 #include "vrq_internal.h"
 #include "vrq_scan.h"
 
 namespace vrq {
 
-constexpr int MWAVES = 4;                   // waves per workgroup (one per SIMD)
-constexpr int RT = 64;                      // rows per tile (2 n-blocks of 32)
 constexpr int KS = 16;                      // k-steps of 64 bits (1024-bit codes)
 constexpr int NG = 2 * KS;                  // k-step groups per tile (n-block, k-step)
 constexpr int PKT = RT * 128;               // packed tile bytes (8 KiB)
@@ -49,7 +51,6 @@ constexpr int UBT = NG * 1024;              // unpacked tile bytes (32 KiB)
 constexpr int GPW = (PKT / 1024) / MWAVES;  // LDS-DMA instructions per wave per tile (2)
 constexpr int BAHEAD = 3;                   // B fragments read this many groups ahead
 constexpr int NRING = BAHEAD < 4 ? 4 : 8;   // B fragment ring (power of two > BAHEAD)
-constexpr int STG = 512;                    // per-wave staged hit entries (u32)
 #ifndef VRQ_K1M_NSR  // A/B builds: M-blocks per wave whose accumulator seeds stay in registers (capped at MB)
 #define VRQ_K1M_NSR 4
 #endif
@@ -76,20 +77,17 @@ constexpr int kRowsMaxQueries = 128;        // batches of <= 128 queries take th
 // Packed tile image: 16-byte piece c of tile row r lives at slot r*8 + (c ^ ((r>>1)&7)).
 __device__ __forceinline__ int pk_slot(int r, int c) { return r * 8 + (c ^ ((r >> 1) & 7)); }
 
-// Staged hit entry (u32): (v + 1025) << 14 | query-in-wave << 7 | row - (t-1)*64, where
-// v = dist - tau(q) in [-1025, -1] (tau = the threshold the pass ran with; the suffix kernel adds it
-// back) and the row is relative to the previous tile's first row (the epilogue of a tile's second
-// n-block runs in the next tile's iteration).  List keys carry the same field: (v + 1025) << 40 | row.
-constexpr int ENT_V_SHIFT = 14, ENT_Q_SHIFT = 7, ENT_V_BIAS = 1025;
+// Staged hit entries (layout: mfma_hits.h) carry v + 1025 at 1024 bits; K1m's row field is
+// row - (t-1)*64, relative to the previous tile's first row (the epilogue of a tile's second n-block runs
+// in the next tile's iteration).
+constexpr int ENT_V_BIAS = 1025;
 
 // DENSE = the sample pass: no thresholds; every (query, row) pair's v = dist - pc(q) folds into
 // the lane's running minima (dense_out below), written once per chunk.  Chunk c
 // starts at row row_begin + c * chunk_stride and its tile t at + t * tile_stride: the sample pass
 // spreads 64-row tiles evenly over the whole corpus (tile_stride >= 64, chunk_rows = its tiles x 64
 // dv columns); the thresholded pass uses chunk_stride = chunk_rows and tile_stride = 64.
-// MODE: MFMA_MAIN (thresholded pass), MFMA_SAMPLE (dense sample pass, DENSE below) or MFMA_RERUN
-// (the exact re-run of failed query blocks: same code as MAIN, a separate symbol so profiles and
-// traces tell the two launches apart).
+// MODE: MFMA_MAIN, MFMA_SAMPLE (DENSE below) or MFMA_RERUN (mfma_hits.h).
 //
 // Schedule of the 32 k-step groups of a tile (group gi = (n-block gi>>4, k-step j = gi&15)): every
 // group reads the B fragment of group gi+BAHEAD (one ds_read_b128, immediate offset) and runs MB
@@ -102,7 +100,6 @@ constexpr int ENT_V_SHIFT = 14, ENT_Q_SHIFT = 7, ENT_V_BIAS = 1025;
 // one M-block per group, four ds_read_b128); the asynchronous hit flush (gi = 20+MB and 24+MB).  The
 // M-blocks m < NSR take their seeds from registers as the C operand of the n-block's first MFMA and
 // have no re-seed group.
-enum { MFMA_MAIN = 0, MFMA_SAMPLE = 1, MFMA_RERUN = 2 };
 
 // The per-group LDS wait of the schedule above.  Group gi consumes the B fragment read at the top of
 // group gi - BAHEAD; DS operations complete in order, so the wait may leave in flight exactly the DS
@@ -126,48 +123,6 @@ constexpr int k1m_wait(int gi, int mb, int nsr, bool dense) {
   return n < 15 ? n : 15;
 }
 
-// The dense sample pass keeps, per lane and accumulator register, the minimum of v = dist - pc(q)
-// over the sample rows of its chunk that the lane holds (lane row ri of every n-block): 32 values
-// per (query, chunk), each the distance of a DISTINCT sample row, written once per chunk as u16
-// (v + 1024; 0xFFFF: the lane saw no row) to dv[q][col], col = chunk * 32 + ri (DenseMin).  The order
-// statistics sample_select_kernel takes over these minima are >= those over every sample distance:
-// tau_p (K-th + 1) still has K distinct rows below it, and tau_s only admits more rows (the recheck
-// proves it per query either way).
-// The minima are kept in float: v = pc(r) - 2 acc is one v_fma_f32 and the fold one v_min_f32 per
-// register (exact: integers far below 2^24), a row past the chunk end contributes +inf.
-template <bool ON, int MB>
-struct DenseMin {  // the sample pass's lane minima (ON); empty in the thresholded passes
-  float v[MB][16];
-  __device__ __forceinline__ DenseMin() {
-#pragma unroll
-    for (int m = 0; m < MB; ++m)
-#pragma unroll
-      for (int g = 0; g < 16; ++g) v[m][g] = __builtin_inff();
-  }
-  // v = pc(r) - 2 <q, r> of the 16 registers of M-block m (a row past the chunk end: no value)
-  __device__ __forceinline__ void fold(const v16f& a, int m, int pc, bool ok) {
-    const float pcf = ok ? (float)pc : __builtin_inff();
-#pragma unroll
-    for (int g = 0; g < 16; ++g) v[m][g] = fminf(v[m][g], fmaf(-2.0f, a[g], pcf));
-  }
-  // -> dv[q][col] as u16 (v + 1024; 0xFFFF: no row), col = chunk * 32 + lane row
-  __device__ __forceinline__ void out(uint16_t* __restrict__ dv, int64_t dv_stride, int64_t col, int qbase, int h,
-                                      int nq) const {
-#pragma unroll
-    for (int m = 0; m < MB; ++m)
-#pragma unroll
-      for (int g = 0; g < 16; ++g) {
-        const int q = qbase + 32 * m + (g & 3) + 8 * (g >> 2) + 4 * h;
-        if (q < nq)
-          dv[(int64_t)q * dv_stride + col] = v[m][g] == __builtin_inff() ? (uint16_t)0xFFFF : (uint16_t)((int)v[m][g] + 1024);
-      }
-  }
-};
-template <int MB>
-struct DenseMin<false, MB> {
-  __device__ __forceinline__ void fold(const v16f&, int, int, bool) {}
-  __device__ __forceinline__ void out(uint16_t*, int64_t, int64_t, int, int, int) const {}
-};
 template <int MODE, int MB>
 __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
     const uint8_t* __restrict__ codes, int64_t n, int64_t row_begin, const uint8_t* __restrict__ queries, int nq,
@@ -482,7 +437,7 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
   };
   // DENSE: the 16 values v = dist - pc(q) of block (m, n-block) (row lr of the chunk) fold into this
   // lane's running minima; only those leave the kernel (dense_out)
-  DenseMin<DENSE, MB> dmin;
+  DenseMin<DENSE, MB, 1024> dmin;
   auto block_dense = [&](const v16f& a, int m, int pc, int lr) __attribute__((always_inline)) {
     dmin.fold(a, m, pc, lr < nrows);
   };
@@ -1449,49 +1404,11 @@ __global__ __launch_bounds__(MWAVES * 64, RowsShape<MB>::OCC) void hamming_mfma_
 
   const int64_t qstride = (int64_t)nchunks * capc;
   uint64_t* const cbase = cand + (int64_t)chunk * capc;  // + q * qstride + pos
-  int nst = 0;
-  auto flush_all = [&](int64_t base_row) __attribute__((always_inline)) {  // staged hits -> lists (sync)
-    if (nst > STG) {
-      for (int i = l; i < QPW; i += 64) lds_add32(lc0 + (uint32_t)(i * 4), capc + 1);
-      nst = STG;
-    }
-    for (int i0 = 0; i0 < nst; i0 += 64) {
-      const int i = i0 + l;
-      int e = 0, pos = 0;
-      if (i < nst) lds_read32(e, stg0 + (uint32_t)(i * 4));
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(e)::"memory");
-      const int ql = (e >> ENT_Q_SHIFT) & 127;
-      if (i < nst) lds_add_rtn32(pos, lc0 + (uint32_t)(ql * 4), 1);
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pos)::"memory");
-      if (i < nst && pos < capc)
-        cbase[(int64_t)ql * qstride + pos] =
-            ((uint64_t)(uint32_t)(e >> ENT_V_SHIFT) << KEY_ROW_BITS) | (uint64_t)(base_row + (e & 127));
-    }
-    nst = 0;
-  };
-  auto block_hits = [&](const v16f& a, int m, int pc, float hp) __attribute__((always_inline)) {
-#pragma unroll
-    for (int g = 0; g < 16; ++g) {
-      const uint64_t mask = __ballot(a[g] > hp);
-      if (mask) {
-        if ((mask >> l) & 1) {
-          const int below = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
-                                                      __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
-          int lo = l;
-          asm volatile("" : "+v"(lo));
-          const int ql = 32 * m + (g & 3) + 8 * (g >> 2) + 4 * (lo >> 5);
-          const int v = pc - (int)(2.0f * a[g]);  // dist - tau(q), as in K1m
-          const int pos = nst + below < STG ? nst + below : STG;
-          lds_write32(stg0 + (uint32_t)(pos * 4), ((v + ENT_V_BIAS) << ENT_V_SHIFT) | (ql << ENT_Q_SHIFT) | (lo & 31));
-        }
-        nst += __popcll(mask);
-      }
-    }
-  };
+  HitStage<ENT_V_BIAS, QPW> hs{stg0, lc0, cbase, qstride, capc, l};
 
   // DENSE: the 16 values v = dist - pc(q) of M-block m of an n-block (local row lr of the chunk) fold
   // into this lane's running minima (as K1m's)
-  DenseMin<DENSE, MB> dmin;
+  DenseMin<DENSE, MB, 1024> dmin;
   // ---- main loop over n-blocks; k-step s runs the MB MFMAs of n-block blk on the unpacked dword
   // s of rb[par], while the previous n-block's epilogue, this block's row popcount and the next
   // block's packed reads (into rb[par ^ 1]) fill the MFMA gaps ----
@@ -1551,9 +1468,9 @@ __global__ __launch_bounds__(MWAVES * 64, RowsShape<MB>::OCC) void hamming_mfma_
           const float hp = 0.5f * (float)pc;
           static_for<0, MB>([&](auto M) {
             constexpr int mm = decltype(M)::value;
-            if (hitm[mm]) block_hits(acc[par ^ 1][mm], mm, pc, hp);
+            if (hitm[mm]) hs.block_hits(acc[par ^ 1][mm], mm, pc, hp);
           });
-          if (nst) flush_all(row0 + (int64_t)(blk - 1) * 32);
+          if (hs.nst) hs.flush_all(row0 + (int64_t)(blk - 1) * 32);
         }
       }
       if constexpr (!DENSE && !SEEDREG && s >= MB + 2 && s < 2 * MB + 2)
@@ -1595,9 +1512,9 @@ __global__ __launch_bounds__(MWAVES * 64, RowsShape<MB>::OCC) void hamming_mfma_
       const float hp = 0.5f * (float)pc;
       static_for<0, MB>([&](auto M) {
         constexpr int mm = decltype(M)::value;
-        if (any_above(acc[par][mm], hp)) block_hits(acc[par][mm], mm, pc, hp);
+        if (any_above(acc[par][mm], hp)) hs.block_hits(acc[par][mm], mm, pc, hp);
       });
-      if (nst) flush_all(row0 + (int64_t)(nblk - 1) * 32);
+      if (hs.nst) hs.flush_all(row0 + (int64_t)(nblk - 1) * 32);
     }
   }
   wait_lgkm0();
@@ -1752,46 +1669,8 @@ __global__ __launch_bounds__(MWAVES * 64, LeanShape<MB>::OCC) void hamming_mfma_
 
   const int64_t qstride = (int64_t)nchunks * capc;
   uint64_t* const cbase = cand + (int64_t)chunk * capc;
-  int nst = 0;
-  auto flush_all = [&](int64_t base_row) __attribute__((always_inline)) {
-    if (nst > STG) {
-      for (int i = l; i < QPW; i += 64) lds_add32(lc0 + (uint32_t)(i * 4), capc + 1);
-      nst = STG;
-    }
-    for (int i0 = 0; i0 < nst; i0 += 64) {
-      const int i = i0 + l;
-      int e = 0, pos = 0;
-      if (i < nst) lds_read32(e, stg0 + (uint32_t)(i * 4));
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(e)::"memory");
-      const int ql = (e >> ENT_Q_SHIFT) & 127;
-      if (i < nst) lds_add_rtn32(pos, lc0 + (uint32_t)(ql * 4), 1);
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pos)::"memory");
-      if (i < nst && pos < capc)
-        cbase[(int64_t)ql * qstride + pos] =
-            ((uint64_t)(uint32_t)(e >> ENT_V_SHIFT) << KEY_ROW_BITS) | (uint64_t)(base_row + (e & 127));
-    }
-    nst = 0;
-  };
-  auto block_hits = [&](const v16f& a, int m, int pc, float hp) __attribute__((always_inline)) {
-#pragma unroll
-    for (int g = 0; g < 16; ++g) {
-      const uint64_t mask = __ballot(a[g] > hp);
-      if (mask) {
-        if ((mask >> l) & 1) {
-          const int below = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
-                                                      __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
-          int lo = l;
-          asm volatile("" : "+v"(lo));
-          const int ql = 32 * m + (g & 3) + 8 * (g >> 2) + 4 * (lo >> 5);
-          const int v = pc - (int)(2.0f * a[g]);
-          const int pos = nst + below < STG ? nst + below : STG;
-          lds_write32(stg0 + (uint32_t)(pos * 4), ((v + ENT_V_BIAS) << ENT_V_SHIFT) | (ql << ENT_Q_SHIFT) | (lo & 31));
-        }
-        nst += __popcll(mask);
-      }
-    }
-  };
-  DenseMin<DENSE, MB> dmin;
+  HitStage<ENT_V_BIAS, QPW> hs{stg0, lc0, cbase, qstride, capc, l};
+  DenseMin<DENSE, MB, 1024> dmin;
   v16f acc[MB];
   for (int blk = 0; blk < nblk; ++blk) {
     // entering the second n-block of tile t: the next n-block's quads (read from k-step 3 on) come from
@@ -1852,9 +1731,9 @@ __global__ __launch_bounds__(MWAVES * 64, LeanShape<MB>::OCC) void hamming_mfma_
       if (any) {  // rare
         static_for<0, MB>([&](auto M) {
           constexpr int m = decltype(M)::value;
-          if (hitm[m]) block_hits(acc[m], m, pc, hp);
+          if (hitm[m]) hs.block_hits(acc[m], m, pc, hp);
         });
-        if (nst) flush_all(row0 + (int64_t)blk * 32);
+        if (hs.nst) hs.flush_all(row0 + (int64_t)blk * 32);
       }
     }
     // the next n-block's rows landed (every destination named)
@@ -1869,413 +1748,6 @@ __global__ __launch_bounds__(MWAVES * 64, LeanShape<MB>::OCC) void hamming_mfma_
   else
     for (int i = l; i < QPW; i += 64)
       if (i < nq && (!rerun || rerun[i])) ccnt[(int64_t)i * nchunks + chunk] = lcnt[i];
-}
-
-// Thresholds from the dense sample (S rows spread over the corpus, every distance exact):
-//   tau_p(q) = d_(K) + 1, accept dist <= the K-th smallest sample distance: the sample rows alone
-//              put >= K corpus rows under it, so the candidates always hold the exact top-K
-//              (the guaranteed threshold of the re-run);
-//   tau_s(q) = d_(j) + 1 for the plan's j < K: with iid rows the corpus holds ~j*n/S rows under
-//              it, >= K with probability 1 - 1e-6 (plan); sample_check_kernel proves it per query.
-// One workgroup per query: histogram of the S u16 values v + 1024 (v = dist - pc(q)).
-__global__ __launch_bounds__(256) void sample_select_kernel(const uint16_t* __restrict__ dv, int64_t S,
-                                                            const uint8_t* __restrict__ queries, int K, int j,
-                                                            int32_t* __restrict__ tau_s, int32_t* __restrict__ tau_p,
-                                                            int32_t* __restrict__ rerun, int32_t* __restrict__ qbflag,
-                                                            int nqb) {
-  constexpr int NB = 2049;
-  __shared__ uint32_t hist[NB + 3];
-  __shared__ int pcq;
-  const int qi = blockIdx.x, tid = threadIdx.x;
-  if (qi == 0 && qbflag)
-    for (int i = tid; i < nqb; i += 256) qbflag[i] = 0;
-  for (int i = tid; i < NB; i += 256) hist[i] = 0;
-  if (tid == 0) pcq = 0;
-  __syncthreads();
-  if (tid < 32) atomicAdd(&pcq, __popc(reinterpret_cast<const uint32_t*>(queries + (int64_t)qi * 128)[tid]));
-  const uint16_t* d = dv + (int64_t)qi * S;
-  const int64_t S8 = S & ~int64_t(7);
-  // 16-B loads of 8 values, 8 loads in flight per thread (one workgroup per query: with few queries
-  // the pass is latency-bound on a handful of CUs)
-  constexpr int U = 8;
-  auto add8 = [&](const uint4& w) {
-    const uint32_t x[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const uint32_t lo = x[k] & 0xffff, hi = x[k] >> 16;
-      if (lo < NB) atomicAdd(&hist[lo], 1u);
-      if (hi < NB) atomicAdd(&hist[hi], 1u);
-    }
-  };
-  int64_t i = (int64_t)tid * 8;
-  for (; i + (U - 1) * 256 * 8 < S8; i += U * 256 * 8) {
-    uint4 w[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) w[u] = *reinterpret_cast<const uint4*>(d + i + u * 256 * 8);
-#pragma unroll
-    for (int u = 0; u < U; ++u) add8(w[u]);
-  }
-  for (; i < S8; i += 256 * 8) add8(*reinterpret_cast<const uint4*>(d + i));
-  for (int64_t i = S8 + tid; i < S; i += 256)
-    if (d[i] < NB) atomicAdd(&hist[d[i]], 1u);
-  __syncthreads();
-  if (tid < 64) {  // one wave: prefix sums over NB bins, 33 per lane
-    constexpr int BPL = (NB + 63) / 64;
-    int loc = 0;
-    for (int i = 0; i < BPL; ++i) {
-      const int b = tid * BPL + i;
-      if (b < NB) loc += (int)hist[b];
-    }
-    int inc = loc;
-    for (int o = 1; o < 64; o <<= 1) {
-      const int y = __shfl_up(inc, o, 64);
-      if (tid >= o) inc += y;
-    }
-    // k-th smallest: bin b holds it iff cum < k <= cum + hist[b]
-    int cum = inc - loc, rk = NB, rj = NB;
-    for (int i = 0; i < BPL; ++i) {
-      const int b = tid * BPL + i;
-      if (b < NB) {
-        const int hh = (int)hist[b];
-        if (cum < K && cum + hh >= K) rk = b;
-        if (cum < j && cum + hh >= j) rj = b;
-        cum += hh;
-      }
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-      rk = min(rk, __shfl_xor(rk, o, 64));
-      rj = min(rj, __shfl_xor(rj, o, 64));
-    }
-    if (tid == 0) {
-      // fewer than K valid sample values (not for a planned sample): accept every row
-      const int dk = rk < NB ? rk - 1024 + pcq : 1024;
-      const int dj = rj < NB ? rj - 1024 + pcq : 1024;
-      tau_p[qi] = dk + 1;
-      tau_s[qi] = (j < K ? dj : dk) + 1;
-      rerun[qi] = 0;  // (the suffix reads tau_p for re-run queries; until a recheck, none)
-    }
-  }
-}
-
-// Proof of the sampled threshold per query: C = candidates with dist < tau_s over the whole corpus
-// (the list lengths; an overflowed list counts > capc, and its exact rescan needs no threshold).
-// C >= K means the K-th smallest key of the corpus has dist < tau_s, so the candidates hold the
-// exact top-K.  Otherwise the query is flagged for the re-run with tau_p.  One wave per query.
-__global__ __launch_bounds__(256) void sample_check_kernel(const int32_t* __restrict__ ccnt, int nchunks, int K,
-                                                           int nq, int32_t* __restrict__ rerun,
-                                                           int32_t* __restrict__ qbflag, int qpb) {
-  const int q = blockIdx.x * 4 + (threadIdx.x >> 6), l = lane_id();
-  if (q >= nq) return;
-  int64_t c = 0;
-  for (int i = l; i < nchunks; i += 64) c += ccnt[(int64_t)q * nchunks + i];
-  c = wave_sum_i64(c);
-  const bool fail = c < K;
-  if (l == 0) {
-    rerun[q] = fail ? 1 : 0;
-    if (fail) atomicOr(&qbflag[q / qpb], 1);
-  }
-}
-
-// Suffix candidates -> one sorted list of K keys per query (KEY_NONE padded).
-// The matrix-core kernel left, per (query, chunk), a list of keys (v + 1025) << 40 | row
-// (v = dist - tau(q)) and its length.  Exact in every case:
-//   all lists complete, total <= SUF_CAP  -> sort them all;
-//   all lists complete, total  > SUF_CAP  -> histogram of v, threshold T = K-th smallest v, sort
-//                                            the keys with v <= T (if they fit);
-//   some list overflowed (or neither fits) -> exact rescan of the query's suffix rows.
-constexpr int SUF_THREADS = 256;
-constexpr int SUF_CAP = 4096;
-constexpr int SUF_COFF = 2049 + 3;  // chunk offsets of the parallel list gather live in the histogram's space
-struct SufShared {
-  uint32_t hist[2049 + 3];
-  uint64_t buf[SUF_CAP];
-  uint32_t qw[32];
-  int32_t misc[8];
-  int32_t scan[SUF_THREADS / WAVE];
-};
-
-__device__ __forceinline__ int row_dist(const uint8_t* __restrict__ codes, int64_t r, const uint32_t* qw) {
-  const uint4* p = reinterpret_cast<const uint4*>(codes + r * 128);
-  int d = 0;
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const uint4 v = p[c];
-    d += __popc(v.x ^ qw[4 * c]) + __popc(v.y ^ qw[4 * c + 1]) + __popc(v.z ^ qw[4 * c + 2]) +
-         __popc(v.w ^ qw[4 * c + 3]);
-  }
-  return d;
-}
-
-// block-wide exclusive scan (SUF_THREADS threads), total in *tot
-__device__ inline int suf_excl_scan(int v, int* tot, int32_t* scratch) {
-  const int l = lane_id(), w = threadIdx.x / WAVE;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < WAVE; o <<= 1) {
-    const int y = __shfl_up(x, o, WAVE);
-    if (l >= o) x += y;
-  }
-  __syncthreads();
-  if (l == WAVE - 1) scratch[w] = x;
-  __syncthreads();
-  int base = 0, all = 0;
-  for (int i = 0; i < SUF_THREADS / WAVE; ++i) {
-    const int s = scratch[i];
-    if (i < w) base += s;
-    all += s;
-  }
-  __syncthreads();
-  *tot = all;
-  return base + x - v;
-}
-
-// Exact top-K of the query's suffix rows [row_begin, n) by brute force (one workgroup): distance
-// histogram -> threshold T, then the dist < T rows (any order, sorted by the caller) and the
-// first R rows with dist == T in row order.  Leaves m keys (real dist) in sh.buf; returns m.
-__device__ int suffix_rescan(const uint8_t* __restrict__ codes, int64_t n, int64_t row_begin, int K, SufShared& sh) {
-  const int tid = threadIdx.x;
-  for (int i = tid; i < 1025; i += SUF_THREADS) sh.hist[i] = 0;
-  __syncthreads();
-  uint32_t qw[32];
-  for (int i = 0; i < 32; ++i) qw[i] = sh.qw[i];
-  for (int64_t r = row_begin + tid; r < n; r += SUF_THREADS) atomicAdd(&sh.hist[row_dist(codes, r, qw)], 1u);
-  __syncthreads();
-  if (tid == 0) {
-    int cum = 0, T = 1025, clt = 0;
-    for (int d = 0; d < 1025; ++d) {
-      if (cum + (int)sh.hist[d] >= K) {
-        T = d;
-        clt = cum;
-        break;
-      }
-      cum += (int)sh.hist[d];
-    }
-    if (T == 1025) clt = cum;
-    sh.misc[0] = T;
-    sh.misc[1] = clt;
-    sh.misc[2] = 0;  // dist < T appended
-    sh.misc[3] = 0;  // dist == T taken
-  }
-  __syncthreads();
-  const int T = sh.misc[0], clt = sh.misc[1];
-  const int R = K - clt;
-  for (int64_t base = row_begin; base < n; base += SUF_THREADS) {
-    const int64_t r = base + tid;
-    const int d = r < n ? row_dist(codes, r, qw) : 0x7fffffff;
-    if (d < T) {
-      const int pos = atomicAdd(&sh.misc[2], 1);
-      sh.buf[pos] = ((uint64_t)(uint32_t)d << KEY_ROW_BITS) | (uint64_t)r;
-    }
-    const int eq = (d == T) ? 1 : 0;
-    if (__syncthreads_or(eq)) {
-      int tot;
-      const int pre = suf_excl_scan(eq, &tot, sh.scan);  // rank among this block's eq rows, row order
-      const int rank = sh.misc[3] + pre;
-      if (eq && rank < R) sh.buf[clt + rank] = ((uint64_t)(uint32_t)d << KEY_ROW_BITS) | (uint64_t)r;
-      __syncthreads();
-      if (tid == 0) sh.misc[3] += tot;
-      __syncthreads();
-    }
-  }
-  __syncthreads();
-  const int taken = sh.misc[3] < R ? sh.misc[3] : R;
-  return clt + (taken > 0 ? taken : 0);
-}
-
-__global__ __launch_bounds__(SUF_THREADS) void suffix_topk_kernel(const uint8_t* __restrict__ codes, int64_t n,
-                                                                   int64_t row_begin,
-                                                                   const uint8_t* __restrict__ queries,
-                                                                   const uint64_t* __restrict__ cand,
-                                                                   const int32_t* __restrict__ ccnt, int nchunks,
-                                                                   int capc, int K, const int32_t* __restrict__ tau_main,
-                                                                   const int32_t* __restrict__ tau_p,
-                                                                   const int32_t* __restrict__ rerun,
-                                                                   uint64_t* __restrict__ out) {
-  __shared__ SufShared sh;
-  const int qi = blockIdx.x, tid = threadIdx.x;
-  if (tid < 32) sh.qw[tid] = reinterpret_cast<const uint32_t*>(queries + (int64_t)qi * 128)[tid];
-  if (tid < 8) sh.misc[tid] = 0;
-  __syncthreads();
-  if (tid < 32) atomicAdd(&sh.misc[4], __popc(sh.qw[tid]));  // pc(q)
-  const int32_t* cq = ccnt + (int64_t)qi * nchunks;
-  const uint64_t* Cq = cand + (int64_t)qi * nchunks * capc;
-  // per-chunk counts -> offsets (CPT chunks per thread)
-  const int CPT = (nchunks + SUF_THREADS - 1) / SUF_THREADS;
-  int mine = 0, over = 0;
-  for (int j = 0; j < CPT; ++j) {
-    const int c = tid * CPT + j;
-    if (c < nchunks) {
-      const int v = cq[c];
-      over |= v > capc;
-      mine += v < capc ? v : capc;
-    }
-  }
-  int total;
-  int off = suf_excl_scan(mine, &total, sh.scan);
-  const bool overflow = __syncthreads_or(over) != 0;
-  // the threshold the query's lists were recorded with: the main pass's, or tau_p after a re-run;
-  // dist = v-field + tau(q) - ENT_V_BIAS
-  const int tauq = (rerun && rerun[qi]) ? tau_p[qi] : tau_main[qi];
-  const int64_t dfix = (int64_t)tauq - ENT_V_BIAS;
-  int m = -1;
-  bool real_dist = false;
-  if (!overflow && total <= SUF_CAP && nchunks < SUF_COFF) {
-    // every list entry gathered by its own thread (entry e of chunk c = the largest c with coff[c] <= e):
-    // independent loads, all in flight at once (a per-thread loop over its chunks' entries waited for
-    // each load before its LDS store)
-    int32_t* coff = reinterpret_cast<int32_t*>(sh.hist);
-    for (int j = 0; j < CPT; ++j) {
-      const int c = tid * CPT + j;
-      if (c < nchunks) {
-        const int v = cq[c];
-        coff[c] = off;
-        off += v < capc ? v : capc;
-      }
-    }
-    if (tid == 0) coff[nchunks] = total;
-    __syncthreads();
-    for (int e = tid; e < total; e += SUF_THREADS) {
-      int lo = 0, hi = nchunks;  // coff[lo] <= e < coff[hi]
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (coff[mid] <= e) lo = mid; else hi = mid;
-      }
-      sh.buf[e] = Cq[(int64_t)lo * capc + (e - coff[lo])];
-    }
-    m = total;
-  } else if (!overflow && total <= SUF_CAP) {
-    for (int j = 0; j < CPT; ++j) {
-      const int c = tid * CPT + j;
-      if (c < nchunks) {
-        const int v = cq[c];
-        for (int i = 0; i < v; ++i) sh.buf[off + i] = Cq[(int64_t)c * capc + i];
-        off += v;
-      }
-    }
-    m = total;
-  } else if (!overflow) {
-    // histogram over the v-field of every candidate, threshold T with >= K keys at v <= T
-    for (int i = tid; i < 2049; i += SUF_THREADS) sh.hist[i] = 0;
-    __syncthreads();
-    for (int c = 0; c < nchunks; ++c) {
-      const int v = cq[c];
-      for (int i = tid; i < v; i += SUF_THREADS)
-        atomicAdd(&sh.hist[(uint32_t)(Cq[(int64_t)c * capc + i] >> KEY_ROW_BITS)], 1u);
-    }
-    __syncthreads();
-    if (tid == 0) {
-      int cum = 0, T = 2048;
-      for (int d = 0; d < 2049; ++d) {
-        cum += (int)sh.hist[d];
-        if (cum >= K) {
-          T = d;
-          break;
-        }
-      }
-      sh.misc[5] = T;
-      sh.misc[6] = cum;  // keys with v <= T
-      sh.misc[7] = 0;
-    }
-    __syncthreads();
-    if (sh.misc[6] <= SUF_CAP) {
-      const uint32_t T = (uint32_t)sh.misc[5];
-      for (int c = 0; c < nchunks; ++c) {
-        const int v = cq[c];
-        for (int i = tid; i < v; i += SUF_THREADS) {
-          const uint64_t key = Cq[(int64_t)c * capc + i];
-          if ((uint32_t)(key >> KEY_ROW_BITS) <= T) sh.buf[atomicAdd(&sh.misc[7], 1)] = key;
-        }
-      }
-      __syncthreads();
-      m = sh.misc[7];
-    }
-  }
-  __syncthreads();
-  if (m < 0) {  // overflowed list, or too many candidates: exact rescan (real distances)
-    m = suffix_rescan(codes, n, row_begin, K, sh);
-    real_dist = true;
-  }
-  __syncthreads();
-  if (!real_dist && m > SUF_THREADS) {
-    // only the keys with v <= T (T: the K-th smallest v-field) can be among the first K: histogram, then
-    // keep those in place, so the sort below usually runs on ~K keys instead of every candidate
-    for (int i = tid; i < 2049; i += SUF_THREADS) sh.hist[i] = 0;
-    __syncthreads();
-    for (int i = tid; i < m; i += SUF_THREADS) atomicAdd(&sh.hist[(uint32_t)(sh.buf[i] >> KEY_ROW_BITS)], 1u);
-    __syncthreads();
-    {  // T = the smallest v with cum(v) >= K: BPT bins per thread, one block scan
-      constexpr int BPT = (2049 + SUF_THREADS - 1) / SUF_THREADS;
-      int loc = 0;
-      for (int b = 0; b < BPT; ++b) {
-        const int d = tid * BPT + b;
-        if (d < 2049) loc += (int)sh.hist[d];
-      }
-      int tot;
-      int cum = suf_excl_scan(loc, &tot, sh.scan);
-      for (int b = 0; b < BPT; ++b) {
-        const int d = tid * BPT + b;
-        if (d >= 2049) break;
-        const int h = (int)sh.hist[d];
-        if (cum < K && cum + h >= K) sh.misc[5] = d;
-        cum += h;
-      }
-      if (tid == 0) sh.misc[7] = 0;
-    }
-    __syncthreads();
-    const uint32_t T = (uint32_t)sh.misc[5];
-    constexpr int KPT = SUF_CAP / SUF_THREADS;  // keys per thread (m <= SUF_CAP)
-    uint64_t kk[KPT];
-#pragma unroll
-    for (int j = 0; j < KPT; ++j) kk[j] = tid + j * SUF_THREADS < m ? sh.buf[tid + j * SUF_THREADS] : KEY_NONE;
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < KPT; ++j)
-      if (kk[j] != KEY_NONE && (uint32_t)(kk[j] >> KEY_ROW_BITS) <= T) sh.buf[atomicAdd(&sh.misc[7], 1)] = kk[j];
-    __syncthreads();
-    m = sh.misc[7];
-  }
-  if (m <= SUF_THREADS) {
-    // one key per thread: its rank among the m distinct keys (broadcast LDS reads), one scatter
-    const uint64_t ki = tid < m ? sh.buf[tid] : KEY_NONE;
-    if (tid < 4) sh.buf[m + tid] = KEY_NONE;  // padding for the 4-key reads (m <= SUF_THREADS < SUF_CAP - 4)
-    __syncthreads();
-    int rank = 0;
-    if (tid < m) {
-      for (int j = 0; j < m; j += 4) {  // four broadcast reads in flight
-        const uint64_t a = sh.buf[j], b = sh.buf[j + 1], c = sh.buf[j + 2], d = sh.buf[j + 3];
-        rank += (a < ki ? 1 : 0) + (b < ki ? 1 : 0) + (c < ki ? 1 : 0) + (d < ki ? 1 : 0);
-      }
-    }
-    __syncthreads();
-    if (tid < m) sh.buf[rank] = ki;
-    __syncthreads();
-  } else {
-    const int np2 = next_pow2(m);
-    for (int i = m + tid; i < np2; i += SUF_THREADS) sh.buf[i] = KEY_NONE;
-    __syncthreads();
-    block_bitonic_sort_u64(sh.buf, np2);
-  }
-  uint64_t* o = out + (int64_t)qi * K;
-  const uint64_t ROWM = (1ull << KEY_ROW_BITS) - 1;
-  for (int i = tid; i < K; i += SUF_THREADS) {
-    uint64_t key = KEY_NONE;
-    if (i < m) {
-      key = sh.buf[i];
-      if (!real_dist) key = ((uint64_t)((int64_t)(key >> KEY_ROW_BITS) + dfix) << KEY_ROW_BITS) | (key & ROWM);
-    }
-    o[i] = key;
-  }
-}
-
-// P(Poisson(lam) >= j) <= 1e-6: the sampled order j that an iid corpus proves with that probability
-static int sample_order(double lam, int K) {
-  double term = __builtin_exp(-lam), cdf = 0.0;
-  for (int j = 1; j < K; ++j) {
-    cdf += term;  // P(X <= j-1)
-    if (1.0 - cdf <= 1e-6) return j;
-    term *= lam / j;
-  }
-  return K;
 }
 
 int mfma_plan(int64_t n, int nq, int K, MfmaPlan* p) {
@@ -2335,7 +1807,6 @@ int mfma_plan(int64_t n, int nq, int K, MfmaPlan* p) {
   p->sample_tile_stride = ts;
   p->sample = tiles * RT;
   p->dvcols = nsc * 32;  // the dense pass writes 32 lane minima per (query, sample chunk)
-  S = p->sample;
   // thresholded pass over all n rows (K1r: one chunk per wave, MWAVES waves per workgroup slot of a CU)
   int64_t want = p->rows ? 256 * MWAVES * rows_occ : 256 / p->nqb;
   if (want < 1) want = 1;
@@ -2344,29 +1815,7 @@ int mfma_plan(int64_t n, int nq, int K, MfmaPlan* p) {
   if (cr < RT) cr = RT;
   p->chunk_rows = cr;
   p->nchunks = (int)((n + cr - 1) / cr);
-  // per-(query, chunk) list capacity: 4x the hits expected under tau_p (K * cr / S, iid rows)
-  const int64_t expect = (K * cr + S - 1) / S;
-  int capc = 64;
-  while (capc < 4 * expect && capc < 4096) capc <<= 1;
-  p->capc = capc;
-  p->j = sample_order((double)K * (double)S / (double)n, K);
-  // workspace: dv [nq][dvcols] u16 | suffix list [nq][K] | cand [nq][nchunks][capc] |
-  //            list lengths [nq][nchunks] | tau_s, tau_p, rerun [nq] | qbflag [nqb]
-  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-  p->off_suffix = al((size_t)nq * p->dvcols * sizeof(uint16_t));
-  p->off_cand = p->off_suffix + al((size_t)nq * K * sizeof(uint64_t));
-  p->off_cnt = p->off_cand + al((size_t)nq * p->nchunks * p->capc * sizeof(uint64_t));
-  p->off_tau = p->off_cnt + al((size_t)nq * p->nchunks * sizeof(int32_t));
-  p->bytes = p->off_tau + 3 * al((size_t)nq * sizeof(int32_t)) + (size_t)p->nqb * sizeof(int32_t);
-  return VRQ_OK;
-}
-
-// the same order and the same recheck for the scan of the other code sizes (hamming_mfma_dim.hip)
-int mfma_sample_order(double lam, int K) { return sample_order(lam, K); }
-int mfma_sample_check_launch(const int32_t* ccnt, int nchunks, int K, int nq, int32_t* rerun, int32_t* qbflag, int qpb,
-                             hipStream_t s) {
-  hipLaunchKernelGGL(sample_check_kernel, dim3((nq + 3) / 4), dim3(256), 0, s, ccnt, nchunks, K, nq, rerun, qbflag, qpb);
-  VRQ_LAUNCH_CHECK();
+  mfma_plan_lists(p, n, nq, K);
   return VRQ_OK;
 }
 
@@ -2381,15 +1830,7 @@ int mfma_scan_launch(const MfmaPlan& p, const uint8_t* codes, int64_t n, const u
                      uint8_t* ws, hipStream_t s, int flags) {
   constexpr int ALL = VRQ_SCAN_STAGE_PREFIX | VRQ_SCAN_STAGE_MATRIX | VRQ_SCAN_STAGE_RECHECK | VRQ_SCAN_STAGE_SUFFIX;
   const int st = (flags & ALL) ? (flags & ALL) : ALL;
-  uint16_t* dv = (uint16_t*)ws;
-  uint64_t* suffix = (uint64_t*)(ws + p.off_suffix);
-  uint64_t* cand = (uint64_t*)(ws + p.off_cand);
-  int32_t* ccnt = (int32_t*)(ws + p.off_cnt);
-  const size_t qa = ((size_t)nq * sizeof(int32_t) + 255) & ~size_t(255);
-  int32_t* tau_s = (int32_t*)(ws + p.off_tau);
-  int32_t* tau_p = (int32_t*)(ws + p.off_tau + qa);
-  int32_t* rerun = (int32_t*)(ws + p.off_tau + 2 * qa);
-  int32_t* qbflag = (int32_t*)(ws + p.off_tau + 3 * qa);
+  const MfmaWorkspace w(p, ws, nq);
   const bool sampled = p.j < K;
   const int32_t* none = nullptr;
   // the MB = 4 or MB = 2 instance of a pass
@@ -2414,13 +1855,13 @@ int mfma_scan_launch(const MfmaPlan& p, const uint8_t* codes, int64_t n, const u
                        int nch, int64_t crows, int64_t cstride, int64_t tstride, uint16_t* d, int64_t dstride) {
     const dim3 g((unsigned)((nch + MWAVES - 1) / MWAVES)), blk(MWAVES * 64);
     if (p.mb == 1)
-      hipLaunchKernelGGL(k1, g, blk, 0, s, codes, n, q, nq, tau, cand, ccnt, p.capc, crows, cstride, tstride, nch, rr,
+      hipLaunchKernelGGL(k1, g, blk, 0, s, codes, n, q, nq, tau, w.cand, w.ccnt, p.capc, crows, cstride, tstride, nch, rr,
                          qf, d, dstride);
     else if (p.mb == 2)
-      hipLaunchKernelGGL(k2, g, blk, 0, s, codes, n, q, nq, tau, cand, ccnt, p.capc, crows, cstride, tstride, nch, rr,
+      hipLaunchKernelGGL(k2, g, blk, 0, s, codes, n, q, nq, tau, w.cand, w.ccnt, p.capc, crows, cstride, tstride, nch, rr,
                          qf, d, dstride);
     else
-      hipLaunchKernelGGL(k4, g, blk, 0, s, codes, n, q, nq, tau, cand, ccnt, p.capc, crows, cstride, tstride, nch, rr,
+      hipLaunchKernelGGL(k4, g, blk, 0, s, codes, n, q, nq, tau, w.cand, w.ccnt, p.capc, crows, cstride, tstride, nch, rr,
                          qf, d, dstride);
   };
   if ((st & VRQ_SCAN_STAGE_PREFIX) && p.rows_sample) {  // dense sample pass (K1r) + per-query thresholds
@@ -2428,63 +1869,56 @@ int mfma_scan_launch(const MfmaPlan& p, const uint8_t* codes, int64_t n, const u
     if (p.mb > 2) return VRQ_EUNSUPPORTED;
     rows_pass(hamming_mfma_rows_kernel<MFMA_SAMPLE, 1>, hamming_mfma_rows_lean_kernel<MFMA_SAMPLE, 2>,
               hamming_mfma_rows_kernel<MFMA_SAMPLE, 1>, none, none, none, p.sample_chunks, p.sample_chunk_rows,
-              p.sample_stride, p.sample_tile_stride, dv, p.dvcols);
+              p.sample_stride, p.sample_tile_stride, w.dv, p.dvcols);
     VRQ_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sample_select_kernel, dim3(nq), dim3(256), 0, s, (const uint16_t*)dv, p.dvcols, q, K, p.j,
-                       tau_s, tau_p, rerun, qbflag, p.nqb);
-    VRQ_LAUNCH_CHECK();
+    const int rc = mfma_sample_select_launch(p, w, q, 128, nq, K, s);
+    if (rc != VRQ_OK) return rc;
   } else if (st & VRQ_SCAN_STAGE_PREFIX) {  // dense sample pass + per-query thresholds
     hipLaunchKernelGGL((hamming_mfma_kernel<MFMA_SAMPLE, kMbSmall>), dim3(p.sample_chunks * p.nqb_s), dim3(MWAVES * 64),
                        0, s, codes, n, (int64_t)0, q, nq, none, (uint64_t*)nullptr, (int32_t*)nullptr, 0,
                        p.sample_chunk_rows, p.sample_stride, p.sample_tile_stride, p.sample_chunks, p.nqb_s, none,
-                       none, dv, p.dvcols);
+                       none, w.dv, p.dvcols);
     VRQ_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sample_select_kernel, dim3(nq), dim3(256), 0, s, (const uint16_t*)dv, p.dvcols, q, K, p.j,
-                       tau_s, tau_p, rerun, qbflag, p.nqb);
-    VRQ_LAUNCH_CHECK();
+    const int rc = mfma_sample_select_launch(p, w, q, 128, nq, K, s);
+    if (rc != VRQ_OK) return rc;
   }
   if ((st & VRQ_SCAN_STAGE_MATRIX) && p.rows) {
     rows_pass(hamming_mfma_rows_kernel<MFMA_MAIN, 1>, hamming_mfma_rows_lean_kernel<MFMA_MAIN, 2>,
-              hamming_mfma_rows_kernel<MFMA_MAIN, 4>, (const int32_t*)(sampled ? tau_s : tau_p), none, none,
+              hamming_mfma_rows_kernel<MFMA_MAIN, 4>, (const int32_t*)(sampled ? w.tau_s : w.tau_p), none, none,
               p.nchunks, p.chunk_rows, p.chunk_rows, (int64_t)RT, (uint16_t*)nullptr, (int64_t)0);
     VRQ_LAUNCH_CHECK();
   } else if (st & VRQ_SCAN_STAGE_MATRIX) {
 #ifdef VRQ_K1M_STAMPS
-    uint16_t* mdv = dv;
+    uint16_t* mdv = w.dv;
 #else
     uint16_t* mdv = nullptr;
 #endif
     pass(hamming_mfma_swap_kernel<MFMA_MAIN, 2, 8>, hamming_mfma_swap_kernel<MFMA_MAIN, 4, 4>,
          hamming_mfma_kernel<MFMA_MAIN, kMbLarge>,
          hamming_mfma_kernel<MFMA_MAIN, kMbSmall>, p.nchunks * p.nqb,
-         (const int32_t*)(sampled ? tau_s : tau_p), cand, ccnt, p.chunk_rows, p.chunk_rows, p.nchunks, none, none,
+         (const int32_t*)(sampled ? w.tau_s : w.tau_p), w.cand, w.ccnt, p.chunk_rows, p.chunk_rows, p.nchunks, none, none,
          mdv, (int64_t)0);
     VRQ_LAUNCH_CHECK();
   }
   if ((st & VRQ_SCAN_STAGE_RECHECK) && sampled) {
     // prove C >= K per query; re-run the query blocks holding a failed query with tau_p
-    hipLaunchKernelGGL(sample_check_kernel, dim3((nq + 3) / 4), dim3(256), 0, s, (const int32_t*)ccnt, p.nchunks, K,
-                       nq, rerun, qbflag, p.qpb);
-    VRQ_LAUNCH_CHECK();
+    const int rc = mfma_sample_check_launch(p, w, nq, K, s);
+    if (rc != VRQ_OK) return rc;
     if (p.rows)
       rows_pass(hamming_mfma_rows_kernel<MFMA_RERUN, 1>, hamming_mfma_rows_lean_kernel<MFMA_RERUN, 2>,
-                hamming_mfma_rows_kernel<MFMA_RERUN, 4>, (const int32_t*)tau_p, (const int32_t*)rerun,
-                (const int32_t*)qbflag, p.nchunks, p.chunk_rows, p.chunk_rows, (int64_t)RT, (uint16_t*)nullptr,
+                hamming_mfma_rows_kernel<MFMA_RERUN, 4>, (const int32_t*)w.tau_p, (const int32_t*)w.rerun,
+                (const int32_t*)w.qbflag, p.nchunks, p.chunk_rows, p.chunk_rows, (int64_t)RT, (uint16_t*)nullptr,
                 (int64_t)0);
     else
       pass(hamming_mfma_swap_kernel<MFMA_RERUN, 2, 8>, hamming_mfma_swap_kernel<MFMA_RERUN, 4, 4>,
            hamming_mfma_kernel<MFMA_RERUN, kMbLarge>,
            hamming_mfma_kernel<MFMA_RERUN, kMbSmall>, p.nchunks * p.nqb,
-           (const int32_t*)tau_p, cand, ccnt, p.chunk_rows, p.chunk_rows, p.nchunks, (const int32_t*)rerun,
-           (const int32_t*)qbflag, (uint16_t*)nullptr, (int64_t)0);
+           (const int32_t*)w.tau_p, w.cand, w.ccnt, p.chunk_rows, p.chunk_rows, p.nchunks, (const int32_t*)w.rerun,
+           (const int32_t*)w.qbflag, (uint16_t*)nullptr, (int64_t)0);
     VRQ_LAUNCH_CHECK();
   }
-  if (st & VRQ_SCAN_STAGE_SUFFIX) {  // candidates of the whole corpus -> one sorted K-list per query
-    hipLaunchKernelGGL(suffix_topk_kernel, dim3(nq), dim3(SUF_THREADS), 0, s, codes, n, (int64_t)0, q, cand, ccnt,
-                       p.nchunks, p.capc, K, (const int32_t*)(sampled ? tau_s : tau_p), (const int32_t*)tau_p,
-                       (const int32_t*)(sampled ? rerun : nullptr), suffix);
-    VRQ_LAUNCH_CHECK();
-  }
+  // candidates of the whole corpus -> one sorted K-list per query
+  if (st & VRQ_SCAN_STAGE_SUFFIX) return mfma_suffix_launch(p, w, codes, n, 128, q, nq, K, s);
   return VRQ_OK;
 }
 

@@ -38,19 +38,13 @@
 
 #include "mfma_common.h"
 #include "mfma_fp4.h"
+#include "mfma_hits.h"
 #include "vrq_internal.h"
 #include "vrq_scan.h"
 
 namespace vrq {
 
-constexpr int MWAVES = 4;   // waves (chunks) per workgroup
-constexpr int RT = 64;      // rows per tile
-constexpr int STG = 512;    // per-wave staged hit entries
-// staged hit entry (u32): (v + dim + 1) << 14 | query-in-wave << 7 | row in the n-block, v = dist - tau(q)
-// in [-(dim + 1), -1]; list keys carry the same field: (v + dim + 1) << 40 | row
-constexpr int ENT_V_SHIFT = 14, ENT_Q_SHIFT = 7;
 constexpr int AUX_NT = 2;   // cache policy of the row DMA when each row is read once per batch
-enum { MFMA_MAIN = 0, MFMA_SAMPLE = 1, MFMA_RERUN = 2 };
 
 template <int KSD>
 struct DimCode {
@@ -77,39 +71,6 @@ struct RowsDimShape {
   static constexpr int OCC = (REGS <= 256 && 2 * (SMEM + Cd::TILE) <= 160 * 1024) ? 2 : 1;
   static_assert(SMEM * OCC <= 160 * 1024, "LDS budget");
   static_assert(2 * Cd::C < 64, "vmcnt range");
-};
-
-// the dense pass's lane minima (DenseMin of hamming_mfma.hip with the bias of the code size)
-template <bool ON, int MB, int BIAS>
-struct DenseMinD {
-  float v[MB][16];
-  __device__ __forceinline__ DenseMinD() {
-#pragma unroll
-    for (int m = 0; m < MB; ++m)
-#pragma unroll
-      for (int g = 0; g < 16; ++g) v[m][g] = __builtin_inff();
-  }
-  __device__ __forceinline__ void fold(const v16f& a, int m, int pc, bool ok) {
-    const float pcf = ok ? (float)pc : __builtin_inff();
-#pragma unroll
-    for (int g = 0; g < 16; ++g) v[m][g] = fminf(v[m][g], fmaf(-2.0f, a[g], pcf));
-  }
-  __device__ __forceinline__ void out(uint16_t* __restrict__ dv, int64_t dv_stride, int64_t col, int qbase, int h,
-                                      int nq) const {
-#pragma unroll
-    for (int m = 0; m < MB; ++m)
-#pragma unroll
-      for (int g = 0; g < 16; ++g) {
-        const int q = qbase + 32 * m + (g & 3) + 8 * (g >> 2) + 4 * h;
-        if (q < nq)
-          dv[(int64_t)q * dv_stride + col] = v[m][g] == __builtin_inff() ? (uint16_t)0xFFFF : (uint16_t)((int)v[m][g] + BIAS);
-      }
-  }
-};
-template <int MB, int BIAS>
-struct DenseMinD<false, MB, BIAS> {
-  __device__ __forceinline__ void fold(const v16f&, int, int, bool) {}
-  __device__ __forceinline__ void out(uint16_t*, int64_t, int64_t, int, int, int) const {}
 };
 
 // retire every LDS read; the N packed-row registers are its operands
@@ -283,6 +244,9 @@ __global__ __launch_bounds__(MWAVES * 64, (RowsDimShape<KSD, MB>::OCC)) void ham
 
   const int64_t qstride = (int64_t)nchunks * capc;
   uint64_t* const cbase = cand + ((int64_t)qbase * nchunks + chunk) * capc;  // + ql * qstride + pos
+  // (the hit stage stays in these two lambdas, not HitStage of mfma_hits.h as in K1r: with the shared struct
+  // every thresholded instance came out 39-40 instructions shorter and 0.8 % slower at nq = 1024 --
+  // DESIGN section 6, profiles/threshold_merge_ab.jsonl)
   int nst = 0;
   auto flush_all = [&](int64_t base_row) __attribute__((always_inline)) {  // staged hits -> lists
     if (nst > STG) {  // staging overflowed: every list of the wave -> exact rescan
@@ -323,7 +287,7 @@ __global__ __launch_bounds__(MWAVES * 64, (RowsDimShape<KSD, MB>::OCC)) void ham
       }
     }
   };
-  DenseMinD<DENSE, MB, DIMB> dmin;
+  DenseMin<DENSE, MB, DIMB> dmin;
   v16f acc[MB];
   for (int blk = 0; blk < nblk; ++blk) {
     // entering the second n-block of tile t: the next n-block's rows come from tile t + 1, which must
@@ -403,360 +367,6 @@ __global__ __launch_bounds__(MWAVES * 64, (RowsDimShape<KSD, MB>::OCC)) void ham
       const int q = qbase + i;
       if (q < nq && (!rerun || rerun[q])) ccnt[(int64_t)q * nchunks + chunk] = lcnt[i];
     }
-}
-
-// ---- thresholds from the dense sample (sample_select_kernel of hamming_mfma.hip at a runtime code size):
-// histogram of the u16 values v + dim over 2 dim + 1 bins, tau_p = d_(K) + 1, tau_s = d_(j) + 1 ----
-constexpr int kMaxDim = 2048;
-__global__ __launch_bounds__(256) void sample_select_dim_kernel(const uint16_t* __restrict__ dv, int64_t S,
-                                                                const uint8_t* __restrict__ queries, int cb, int K,
-                                                                int j, int32_t* __restrict__ tau_s,
-                                                                int32_t* __restrict__ tau_p,
-                                                                int32_t* __restrict__ rerun,
-                                                                int32_t* __restrict__ qbflag, int nqb) {
-  __shared__ uint32_t hist[2 * kMaxDim + 1 + 3];
-  __shared__ int pcq;
-  const int dim = cb * 8, NB = 2 * dim + 1;
-  const int qi = blockIdx.x, tid = threadIdx.x;
-  if (qi == 0 && qbflag)
-    for (int i = tid; i < nqb; i += 256) qbflag[i] = 0;
-  for (int i = tid; i < NB; i += 256) hist[i] = 0;
-  if (tid == 0) pcq = 0;
-  __syncthreads();
-  if (tid < cb / 4) atomicAdd(&pcq, __popc(reinterpret_cast<const uint32_t*>(queries + (int64_t)qi * cb)[tid]));
-  const uint16_t* d = dv + (int64_t)qi * S;
-  const int64_t S8 = S & ~int64_t(7);
-  constexpr int U = 8;  // 16-byte loads of 8 values, 8 in flight per thread
-  auto add8 = [&](const uint4& w) {
-    const uint32_t x[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const uint32_t lo = x[k] & 0xffff, hi = x[k] >> 16;
-      if (lo < (uint32_t)NB) atomicAdd(&hist[lo], 1u);
-      if (hi < (uint32_t)NB) atomicAdd(&hist[hi], 1u);
-    }
-  };
-  int64_t i = (int64_t)tid * 8;
-  for (; i + (U - 1) * 256 * 8 < S8; i += U * 256 * 8) {
-    uint4 w[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) w[u] = *reinterpret_cast<const uint4*>(d + i + u * 256 * 8);
-#pragma unroll
-    for (int u = 0; u < U; ++u) add8(w[u]);
-  }
-  for (; i < S8; i += 256 * 8) add8(*reinterpret_cast<const uint4*>(d + i));
-  for (int64_t i2 = S8 + tid; i2 < S; i2 += 256)
-    if (d[i2] < NB) atomicAdd(&hist[d[i2]], 1u);
-  __syncthreads();
-  if (tid < 64) {  // one wave: prefix sums over NB bins, BPL per lane
-    const int BPL = (NB + 63) / 64;
-    int loc = 0;
-    for (int k = 0; k < BPL; ++k) {
-      const int b = tid * BPL + k;
-      if (b < NB) loc += (int)hist[b];
-    }
-    int inc = loc;
-    for (int o = 1; o < 64; o <<= 1) {
-      const int y = __shfl_up(inc, o, 64);
-      if (tid >= o) inc += y;
-    }
-    int cum = inc - loc, rk = NB, rj = NB;  // k-th smallest: bin b holds it iff cum < k <= cum + hist[b]
-    for (int k = 0; k < BPL; ++k) {
-      const int b = tid * BPL + k;
-      if (b < NB) {
-        const int hh = (int)hist[b];
-        if (cum < K && cum + hh >= K) rk = b;
-        if (cum < j && cum + hh >= j) rj = b;
-        cum += hh;
-      }
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-      rk = min(rk, __shfl_xor(rk, o, 64));
-      rj = min(rj, __shfl_xor(rj, o, 64));
-    }
-    if (tid == 0) {
-      // fewer than K valid sample values (not for a planned sample): accept every row
-      const int dk = rk < NB ? rk - dim + pcq : dim;
-      const int dj = rj < NB ? rj - dim + pcq : dim;
-      tau_p[qi] = dk + 1;
-      tau_s[qi] = (j < K ? dj : dk) + 1;
-      rerun[qi] = 0;
-    }
-  }
-}
-
-// ---- suffix merge (suffix_topk_kernel of hamming_mfma.hip at a runtime code size): the per-(query,
-// chunk) lists of keys (v + dim + 1) << 40 | row -> one sorted list of K keys dist << 40 | row per query
-// (KEY_NONE padded).  Exact in every case: all lists complete and few enough -> sort them; too many ->
-// histogram of the v-field (2 dim + 2 values), keep v <= the K-th smallest; an overflowed list -> exact
-// rescan of the corpus (distance histogram of dim + 1 bins, dist == T ties in row order). ----
-constexpr int SUF_THREADS = 256;
-constexpr int SUF_CAP = 4096;
-constexpr int SUF_HB = 2 * kMaxDim + 2;  // v-field values
-struct SufDimShared {
-  uint32_t hist[SUF_HB + 2];  // (the chunk offsets of the parallel list gather live here too)
-  uint64_t buf[SUF_CAP];
-  uint32_t qw[kMaxDim / 32];
-  int32_t misc[8];
-  int32_t scan[SUF_THREADS / WAVE];
-};
-
-__device__ __forceinline__ int row_dist_dim(const uint8_t* __restrict__ codes, int64_t r, int cb, const uint32_t* qw) {
-  const uint4* p = reinterpret_cast<const uint4*>(codes + r * cb);
-  int d = 0;
-  for (int c = 0; c < cb / 16; ++c) {  // (qw: LDS, the same address in every lane)
-    const uint4 v = p[c];
-    d += __popc(v.x ^ qw[4 * c]) + __popc(v.y ^ qw[4 * c + 1]) + __popc(v.z ^ qw[4 * c + 2]) +
-         __popc(v.w ^ qw[4 * c + 3]);
-  }
-  return d;
-}
-
-// block-wide exclusive scan (SUF_THREADS threads), total in *tot
-__device__ inline int suf_dim_excl_scan(int v, int* tot, int32_t* scratch) {
-  const int l = lane_id(), w = threadIdx.x / WAVE;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < WAVE; o <<= 1) {
-    const int y = __shfl_up(x, o, WAVE);
-    if (l >= o) x += y;
-  }
-  __syncthreads();
-  if (l == WAVE - 1) scratch[w] = x;
-  __syncthreads();
-  int base = 0, all = 0;
-  for (int i = 0; i < SUF_THREADS / WAVE; ++i) {
-    const int s = scratch[i];
-    if (i < w) base += s;
-    all += s;
-  }
-  __syncthreads();
-  *tot = all;
-  return base + x - v;
-}
-
-// exact top-K of the query over rows [0, n) by brute force (one workgroup); leaves m keys (real dist)
-// in sh.buf, returns m
-__device__ int suffix_rescan_dim(const uint8_t* __restrict__ codes, int64_t n, int cb, int K, SufDimShared& sh) {
-  const int tid = threadIdx.x, dim = cb * 8;
-  for (int i = tid; i < dim + 1; i += SUF_THREADS) sh.hist[i] = 0;
-  __syncthreads();
-  for (int64_t r = tid; r < n; r += SUF_THREADS) atomicAdd(&sh.hist[row_dist_dim(codes, r, cb, sh.qw)], 1u);
-  __syncthreads();
-  if (tid == 0) {
-    int cum = 0, T = dim + 1, clt = 0;
-    for (int d = 0; d < dim + 1; ++d) {
-      if (cum + (int)sh.hist[d] >= K) {
-        T = d;
-        clt = cum;
-        break;
-      }
-      cum += (int)sh.hist[d];
-    }
-    if (T == dim + 1) clt = cum;
-    sh.misc[0] = T;
-    sh.misc[1] = clt;
-    sh.misc[2] = 0;  // dist < T appended
-    sh.misc[3] = 0;  // dist == T taken
-  }
-  __syncthreads();
-  const int T = sh.misc[0], clt = sh.misc[1];
-  const int R = K - clt;
-  for (int64_t base = 0; base < n; base += SUF_THREADS) {
-    const int64_t r = base + tid;
-    const int d = r < n ? row_dist_dim(codes, r, cb, sh.qw) : 0x7fffffff;
-    if (d < T) {
-      const int pos = atomicAdd(&sh.misc[2], 1);
-      sh.buf[pos] = ((uint64_t)(uint32_t)d << KEY_ROW_BITS) | (uint64_t)r;
-    }
-    const int eq = (d == T) ? 1 : 0;
-    if (__syncthreads_or(eq)) {
-      int tot;
-      const int pre = suf_dim_excl_scan(eq, &tot, sh.scan);  // rank among this block's eq rows, row order
-      const int rank = sh.misc[3] + pre;
-      if (eq && rank < R) sh.buf[clt + rank] = ((uint64_t)(uint32_t)d << KEY_ROW_BITS) | (uint64_t)r;
-      __syncthreads();
-      if (tid == 0) sh.misc[3] += tot;
-      __syncthreads();
-    }
-  }
-  __syncthreads();
-  const int taken = sh.misc[3] < R ? sh.misc[3] : R;
-  return clt + (taken > 0 ? taken : 0);
-}
-
-__global__ __launch_bounds__(SUF_THREADS) void suffix_topk_dim_kernel(
-    const uint8_t* __restrict__ codes, int64_t n, int cb, const uint8_t* __restrict__ queries,
-    const uint64_t* __restrict__ cand, const int32_t* __restrict__ ccnt, int nchunks, int capc, int K,
-    const int32_t* __restrict__ tau_main, const int32_t* __restrict__ tau_p, const int32_t* __restrict__ rerun,
-    uint64_t* __restrict__ out) {
-  __shared__ SufDimShared sh;
-  const int qi = blockIdx.x, tid = threadIdx.x;
-  const int dim = cb * 8, HB = 2 * dim + 2;
-  if (tid < cb / 4) sh.qw[tid] = reinterpret_cast<const uint32_t*>(queries + (int64_t)qi * cb)[tid];
-  const int32_t* cq = ccnt + (int64_t)qi * nchunks;
-  const uint64_t* Cq = cand + (int64_t)qi * nchunks * capc;
-  if (tid < 8) sh.misc[tid] = 0;
-  __syncthreads();
-  // per-chunk counts -> offsets (CPT chunks per thread)
-  const int CPT = (nchunks + SUF_THREADS - 1) / SUF_THREADS;
-  int mine = 0, over = 0;
-  for (int j = 0; j < CPT; ++j) {
-    const int c = tid * CPT + j;
-    if (c < nchunks) {
-      const int v = cq[c];
-      over |= v > capc;
-      mine += v < capc ? v : capc;
-    }
-  }
-  int total;
-  int off = suf_dim_excl_scan(mine, &total, sh.scan);
-  const bool overflow = __syncthreads_or(over) != 0;
-  // the threshold the query's lists were recorded with: dist = v-field + tau(q) - (dim + 1)
-  const int tauq = (rerun && rerun[qi]) ? tau_p[qi] : tau_main[qi];
-  const int64_t dfix = (int64_t)tauq - (dim + 1);
-  int m = -1;
-  bool real_dist = false;
-  if (!overflow && total <= SUF_CAP && nchunks < SUF_HB) {
-    // every list entry gathered by its own thread (entry e of chunk c = the largest c with coff[c] <= e)
-    int32_t* coff = reinterpret_cast<int32_t*>(sh.hist);
-    for (int j = 0; j < CPT; ++j) {
-      const int c = tid * CPT + j;
-      if (c < nchunks) {
-        const int v = cq[c];
-        coff[c] = off;
-        off += v < capc ? v : capc;
-      }
-    }
-    if (tid == 0) coff[nchunks] = total;
-    __syncthreads();
-    for (int e = tid; e < total; e += SUF_THREADS) {
-      int lo = 0, hi = nchunks;  // coff[lo] <= e < coff[hi]
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (coff[mid] <= e) lo = mid; else hi = mid;
-      }
-      sh.buf[e] = Cq[(int64_t)lo * capc + (e - coff[lo])];
-    }
-    m = total;
-  } else if (!overflow) {
-    // histogram over the v-field of every candidate, threshold T with >= K keys at v <= T
-    for (int i = tid; i < HB; i += SUF_THREADS) sh.hist[i] = 0;
-    __syncthreads();
-    for (int c = 0; c < nchunks; ++c) {
-      const int v = cq[c];
-      for (int i = tid; i < v; i += SUF_THREADS) {
-        const uint32_t f = (uint32_t)(Cq[(int64_t)c * capc + i] >> KEY_ROW_BITS);
-        atomicAdd(&sh.hist[f < (uint32_t)HB ? f : HB - 1], 1u);
-      }
-    }
-    __syncthreads();
-    if (tid == 0) {
-      int cum = 0, T = HB - 1;
-      for (int d = 0; d < HB; ++d) {
-        cum += (int)sh.hist[d];
-        if (cum >= K) {
-          T = d;
-          break;
-        }
-      }
-      sh.misc[5] = T;
-      sh.misc[6] = cum;  // keys with v <= T
-      sh.misc[7] = 0;
-    }
-    __syncthreads();
-    if (sh.misc[6] <= SUF_CAP) {
-      const uint32_t T = (uint32_t)sh.misc[5];
-      for (int c = 0; c < nchunks; ++c) {
-        const int v = cq[c];
-        for (int i = tid; i < v; i += SUF_THREADS) {
-          const uint64_t key = Cq[(int64_t)c * capc + i];
-          if ((uint32_t)(key >> KEY_ROW_BITS) <= T) sh.buf[atomicAdd(&sh.misc[7], 1)] = key;
-        }
-      }
-      __syncthreads();
-      m = sh.misc[7];
-    }
-  }
-  __syncthreads();
-  if (m < 0) {  // overflowed list, or too many candidates: exact rescan (real distances)
-    m = suffix_rescan_dim(codes, n, cb, K, sh);
-    real_dist = true;
-  }
-  __syncthreads();
-  if (!real_dist && m > SUF_THREADS) {
-    // only the keys with v <= T (T: the K-th smallest v-field) can be among the first K
-    for (int i = tid; i < HB; i += SUF_THREADS) sh.hist[i] = 0;
-    __syncthreads();
-    for (int i = tid; i < m; i += SUF_THREADS) {
-      const uint32_t f = (uint32_t)(sh.buf[i] >> KEY_ROW_BITS);
-      atomicAdd(&sh.hist[f < (uint32_t)HB ? f : HB - 1], 1u);
-    }
-    __syncthreads();
-    {  // T = the smallest v with cum(v) >= K: BPT bins per thread, one block scan
-      const int BPT = (HB + SUF_THREADS - 1) / SUF_THREADS;
-      int loc = 0;
-      for (int b = 0; b < BPT; ++b) {
-        const int d = tid * BPT + b;
-        if (d < HB) loc += (int)sh.hist[d];
-      }
-      int tot;
-      int cum = suf_dim_excl_scan(loc, &tot, sh.scan);
-      if (tid == 0) sh.misc[5] = HB - 1;  // (fewer than K keys: keep them all)
-      __syncthreads();
-      for (int b = 0; b < BPT; ++b) {
-        const int d = tid * BPT + b;
-        if (d >= HB) break;
-        const int hh = (int)sh.hist[d];
-        if (cum < K && cum + hh >= K) sh.misc[5] = d;
-        cum += hh;
-      }
-      if (tid == 0) sh.misc[7] = 0;
-    }
-    __syncthreads();
-    const uint32_t T = (uint32_t)sh.misc[5];
-    constexpr int KPT = SUF_CAP / SUF_THREADS;  // keys per thread (m <= SUF_CAP)
-    uint64_t kk[KPT];
-#pragma unroll
-    for (int j = 0; j < KPT; ++j) kk[j] = tid + j * SUF_THREADS < m ? sh.buf[tid + j * SUF_THREADS] : KEY_NONE;
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < KPT; ++j)
-      if (kk[j] != KEY_NONE && (uint32_t)(kk[j] >> KEY_ROW_BITS) <= T) sh.buf[atomicAdd(&sh.misc[7], 1)] = kk[j];
-    __syncthreads();
-    m = sh.misc[7];
-  }
-  if (m <= SUF_THREADS) {
-    // one key per thread: its rank among the m distinct keys (broadcast LDS reads), one scatter
-    const uint64_t ki = tid < m ? sh.buf[tid] : KEY_NONE;
-    if (tid < 4) sh.buf[m + tid] = KEY_NONE;  // padding for the 4-key reads
-    __syncthreads();
-    int rank = 0;
-    if (tid < m) {
-      for (int j = 0; j < m; j += 4) {
-        const uint64_t a = sh.buf[j], b = sh.buf[j + 1], c = sh.buf[j + 2], d = sh.buf[j + 3];
-        rank += (a < ki ? 1 : 0) + (b < ki ? 1 : 0) + (c < ki ? 1 : 0) + (d < ki ? 1 : 0);
-      }
-    }
-    __syncthreads();
-    if (tid < m) sh.buf[rank] = ki;
-    __syncthreads();
-  } else {
-    const int np2 = next_pow2(m);
-    for (int i = m + tid; i < np2; i += SUF_THREADS) sh.buf[i] = KEY_NONE;
-    __syncthreads();
-    block_bitonic_sort_u64(sh.buf, np2);
-  }
-  uint64_t* o = out + (int64_t)qi * K;
-  const uint64_t ROWM = (1ull << KEY_ROW_BITS) - 1;
-  for (int i = tid; i < K; i += SUF_THREADS) {
-    uint64_t key = KEY_NONE;
-    if (i < m) {
-      key = sh.buf[i];
-      if (!real_dist) key = ((uint64_t)((int64_t)(key >> KEY_ROW_BITS) + dfix) << KEY_ROW_BITS) | (key & ROWM);
-    }
-    o[i] = key;
-  }
 }
 
 namespace {
@@ -890,7 +500,6 @@ int mfma_dim_plan(int64_t n, int cb, int nq, int K, MfmaPlan* p) {
   p->sample_tile_stride = ts;
   p->sample = tiles * RT;
   p->dvcols = nsc * 32;
-  S = p->sample;
   // thresholded pass: one chunk per wave, the grid (chunks x query blocks) fills the device once at the
   // instance's occupancy
   int64_t want = 256 * MWAVES * occ_cb(cb, p->mb) / p->nqb;
@@ -899,20 +508,7 @@ int mfma_dim_plan(int64_t n, int cb, int nq, int K, MfmaPlan* p) {
   cr = (cr + RT - 1) / RT * RT;
   p->chunk_rows = cr;
   p->nchunks = (int)((n + cr - 1) / cr);
-  // per-(query, chunk) list capacity: 4x the hits expected under tau_p (K * cr / S, iid rows)
-  const int64_t expect = (K * cr + S - 1) / S;
-  int capc = 64;
-  while (capc < 4 * expect && capc < 4096) capc <<= 1;
-  p->capc = capc;
-  p->j = mfma_sample_order((double)K * (double)S / (double)n, K);
-  // workspace: dv [nq][dvcols] u16 | suffix list [nq][K] | cand [nq][nchunks][capc] |
-  //            list lengths [nq][nchunks] | tau_s, tau_p, rerun [nq] | qbflag [nqb]
-  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-  p->off_suffix = al((size_t)nq * p->dvcols * sizeof(uint16_t));
-  p->off_cand = p->off_suffix + al((size_t)nq * K * sizeof(uint64_t));
-  p->off_cnt = p->off_cand + al((size_t)nq * p->nchunks * p->capc * sizeof(uint64_t));
-  p->off_tau = p->off_cnt + al((size_t)nq * p->nchunks * sizeof(int32_t));
-  p->bytes = p->off_tau + 3 * al((size_t)nq * sizeof(int32_t)) + (size_t)p->nqb * sizeof(int32_t);
+  mfma_plan_lists(p, n, nq, K);
   return VRQ_OK;
 }
 
@@ -927,48 +523,34 @@ int mfma_dim_scan_launch(const MfmaPlan& p, const uint8_t* codes, int64_t n, int
                          uint8_t* ws, hipStream_t s, int flags) {
   constexpr int ALL = VRQ_SCAN_STAGE_PREFIX | VRQ_SCAN_STAGE_MATRIX | VRQ_SCAN_STAGE_RECHECK | VRQ_SCAN_STAGE_SUFFIX;
   const int st = (flags & ALL) ? (flags & ALL) : ALL;
-  uint16_t* dv = (uint16_t*)ws;
-  uint64_t* suffix = (uint64_t*)(ws + p.off_suffix);
-  uint64_t* cand = (uint64_t*)(ws + p.off_cand);
-  int32_t* ccnt = (int32_t*)(ws + p.off_cnt);
-  const size_t qa = ((size_t)nq * sizeof(int32_t) + 255) & ~size_t(255);
-  int32_t* tau_s = (int32_t*)(ws + p.off_tau);
-  int32_t* tau_p = (int32_t*)(ws + p.off_tau + qa);
-  int32_t* rerun = (int32_t*)(ws + p.off_tau + 2 * qa);
-  int32_t* qbflag = (int32_t*)(ws + p.off_tau + 3 * qa);
+  const MfmaWorkspace w(p, ws, nq);
   const bool sampled = p.j < K;
   if (!p.rows || !p.rows_sample) return VRQ_EINVAL;  // not a K1rd plan
   if (st & VRQ_SCAN_STAGE_PREFIX) {  // dense sample pass + per-query thresholds
     const PassArgs a{codes, n, q, nq, nullptr, nullptr, nullptr, 0, p.sample_chunk_rows, p.sample_stride,
-                     p.sample_tile_stride, p.sample_chunks, p.nqb_s, nullptr, nullptr, dv, p.dvcols};
+                     p.sample_tile_stride, p.sample_chunks, p.nqb_s, nullptr, nullptr, w.dv, p.dvcols};
     const int rc = launch_cb<MFMA_SAMPLE>(a, cb, p.mb < 2 ? p.mb : 2, s);
     if (rc != VRQ_OK) return rc;
-    hipLaunchKernelGGL(sample_select_dim_kernel, dim3(nq), dim3(256), 0, s, (const uint16_t*)dv, p.dvcols, q, cb, K,
-                       p.j, tau_s, tau_p, rerun, qbflag, p.nqb);
-    VRQ_LAUNCH_CHECK();
+    const int rc2 = mfma_sample_select_launch(p, w, q, cb, nq, K, s);
+    if (rc2 != VRQ_OK) return rc2;
   }
   if (st & VRQ_SCAN_STAGE_MATRIX) {
-    const PassArgs a{codes, n, q, nq, sampled ? tau_s : tau_p, cand, ccnt, p.capc, p.chunk_rows, p.chunk_rows,
+    const PassArgs a{codes, n, q, nq, sampled ? w.tau_s : w.tau_p, w.cand, w.ccnt, p.capc, p.chunk_rows, p.chunk_rows,
                      (int64_t)RT, p.nchunks, p.nqb, nullptr, nullptr, nullptr, 0};
     const int rc = launch_cb<MFMA_MAIN>(a, cb, p.mb, s);
     if (rc != VRQ_OK) return rc;
   }
   if ((st & VRQ_SCAN_STAGE_RECHECK) && sampled) {
     // prove C >= K per query; re-run the query blocks holding a failed query with tau_p
-    int rc = mfma_sample_check_launch(ccnt, p.nchunks, K, nq, rerun, qbflag, p.qpb, s);
+    int rc = mfma_sample_check_launch(p, w, nq, K, s);
     if (rc != VRQ_OK) return rc;
-    const PassArgs a{codes, n, q, nq, tau_p, cand, ccnt, p.capc, p.chunk_rows, p.chunk_rows,
-                     (int64_t)RT, p.nchunks, p.nqb, rerun, qbflag, nullptr, 0};
+    const PassArgs a{codes, n, q, nq, w.tau_p, w.cand, w.ccnt, p.capc, p.chunk_rows, p.chunk_rows,
+                     (int64_t)RT, p.nchunks, p.nqb, w.rerun, w.qbflag, nullptr, 0};
     rc = launch_cb<MFMA_RERUN>(a, cb, p.mb, s);
     if (rc != VRQ_OK) return rc;
   }
-  if (st & VRQ_SCAN_STAGE_SUFFIX) {  // candidates of the whole corpus -> one sorted K-list per query
-    hipLaunchKernelGGL(suffix_topk_dim_kernel, dim3(nq), dim3(SUF_THREADS), 0, s, codes, n, cb, q,
-                       (const uint64_t*)cand, (const int32_t*)ccnt, p.nchunks, p.capc, K,
-                       (const int32_t*)(sampled ? tau_s : tau_p), (const int32_t*)tau_p,
-                       (const int32_t*)(sampled ? rerun : nullptr), suffix);
-    VRQ_LAUNCH_CHECK();
-  }
+  // candidates of the whole corpus -> one sorted K-list per query
+  if (st & VRQ_SCAN_STAGE_SUFFIX) return mfma_suffix_launch(p, w, codes, n, cb, q, nq, K, s);
   return VRQ_OK;
 }
 

@@ -81,10 +81,32 @@ bool mfma_use(int64_t n, int nq, int K, int flags);
 int mfma_scan_launch(const MfmaPlan& p, const uint8_t* codes, int64_t n, const uint8_t* q, int nq, int K,
                      uint8_t* ws, hipStream_t s, int flags);
 
-// helpers of the plan and the recheck that the scan of the other code sizes shares
-int mfma_sample_order(double lam, int K);
-int mfma_sample_check_launch(const int32_t* ccnt, int nchunks, int K, int nq, int32_t* rerun, int32_t* qbflag, int qpb,
-                             hipStream_t s);
+// ---- what the matrix-core scans of every code size share (mfma_threshold.hip): the tail of a plan, the
+// view of its workspace, and the launches of the threshold, recheck and suffix stages (cb: code bytes) ----
+int mfma_sample_order(double lam, int K);  // the sampled order j an iid corpus proves with probability 1 - 1e-6
+// capc, j, the workspace offsets and bytes, from the chunk_rows, nchunks, nqb, sample and dvcols already filled in
+void mfma_plan_lists(MfmaPlan* p, int64_t n, int nq, int K);
+struct MfmaWorkspace {  // the arrays of a plan's workspace
+  uint16_t* dv;         // [nq][dvcols] lane minima of the dense sample pass
+  uint64_t *suffix, *cand;  // sorted K-lists [nq][K]; candidate lists [nq][nchunks][capc]
+  int32_t *ccnt, *tau_s, *tau_p, *rerun, *qbflag;  // list lengths [nq][nchunks]; [nq] each; [nqb]
+  MfmaWorkspace(const MfmaPlan& p, uint8_t* ws, int nq) {
+    const size_t qa = ((size_t)nq * sizeof(int32_t) + 255) & ~size_t(255);
+    dv = (uint16_t*)ws;
+    suffix = (uint64_t*)(ws + p.off_suffix);
+    cand = (uint64_t*)(ws + p.off_cand);
+    ccnt = (int32_t*)(ws + p.off_cnt);
+    tau_s = (int32_t*)(ws + p.off_tau);
+    tau_p = (int32_t*)(ws + p.off_tau + qa);
+    rerun = (int32_t*)(ws + p.off_tau + 2 * qa);
+    qbflag = (int32_t*)(ws + p.off_tau + 3 * qa);
+  }
+};
+int mfma_sample_select_launch(const MfmaPlan& p, const MfmaWorkspace& w, const uint8_t* q, int cb, int nq, int K,
+                              hipStream_t s);
+int mfma_sample_check_launch(const MfmaPlan& p, const MfmaWorkspace& w, int nq, int K, hipStream_t s);
+int mfma_suffix_launch(const MfmaPlan& p, const MfmaWorkspace& w, const uint8_t* codes, int64_t n, int cb,
+                       const uint8_t* q, int nq, int K, hipStream_t s);
 
 // ---- K1rd: the row-split matrix-core scan for the other code sizes (hamming_mfma_dim.hip): cb = 32, 48,
 // 64, 96, 192, 256.  Same four stages, same workspace layout and the same constants as the 1024-bit scan;
