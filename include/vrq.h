@@ -217,17 +217,66 @@ int vrq_scan_sample_plan(int64_t n, int32_t dim, int32_t nq, int32_t K, int32_t 
  * single-index semantics of CohereEnhancedVectorDB.py:267-322 exactly):
  *   global top-K by (dist, global row) -> stable sort by s2 desc -> first K3
  *   -> stable sort by s3 desc -> first k.
- * Inputs are the VRQ_SEARCH_SHARD outputs of S shards stacked [S, nq, K]
- * (counts i32[S, nq]); shard s must own a contiguous global row range below
- * shard s+1's.  out_src (nullable) i32[nq, k] receives s*K + p, the position of
- * each result in the stacked inputs (to fetch per-candidate payloads such as
+ * Inputs are the VRQ_SEARCH_SHARD / vrq_shard_search3 outputs of S shards stacked
+ * [S, nq, K] (counts i32[S, nq]); shard s must own a contiguous global row range
+ * below shard s+1's.  out_src (nullable) i32[nq, k] receives s*K + p, the position
+ * of each result in the stacked inputs (to fetch per-candidate payloads such as
  * external ids).
+ * The merge takes no dim and serves every dim of vrq_dim_supported: it orders
+ * candidates by their (dist, row) keys, and every distance up to 2048 is covered.
+ * Limits: K <= 1024, nshards <= 4096.
  * ------------------------------------------------------------------------- */
 int vrq_merge_shards(int32_t nshards, int32_t nq, int32_t K, const int32_t* counts,
                      const int64_t* rows, const int32_t* dist, const double* s2,
                      const double* s3, int32_t k, int32_t K3, int32_t* out_count,
                      int64_t* out_rows, int32_t* out_dist, double* out_binary,
                      double* out_cosine, int32_t* out_src, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Row-sharded search at every embedding dim and for the two-phase classes (additive to ABI version 1;
+ * VRQ_SEARCH_SHARD keeps its "1024 only" contract on vrq_search3* and is still refused by vrq_search2*).
+ * One process per GPU owns a contiguous global row range [row_offset, row_offset + n); each runs the
+ * per-shard call with the GLOBAL K (the global top-K may sit in one shard), the outputs are all-gathered
+ * and every rank runs the merge.
+ * Both per-shard calls: outputs [nq, K] = the shard's exact Phase-I top-K in FAISS (dist, row) order, rows
+ *   as row_offset + local row, every candidate with its score(s) and no sort by score;
+ *   out_count i32[nq] = min(K, n); missing slots -1 / INT32_MAX / NaN.  flags: 0, VRQ_SEARCH_SCAN_VALU or
+ *   VRQ_SEARCH_SCAN_MFMA as vrq_search3_dim_scan takes them (identical results on every scan); any other
+ *   bit returns VRQ_EUNSUPPORTED.  Supported: every dim of vrq_dim_supported, K <= 1024.  Workspace:
+ *   vrq_shard_search{3,2}_workspace_size = vrq_search3_dim_workspace_size.  n, K or nq = 0 behave as in
+ *   vrq_search3_dim_finish with kout = K.  Every argument is checked before anything is launched.
+ * vrq_shard_search3: the arguments of vrq_search3_dim without k and K3; out_binary = s2 and out_cosine = s3
+ *   of all K candidates (the scores vrq_search3_dim gives the same rows, bit for bit).  At dim == 1024 it
+ *   forwards to vrq_search3 with VRQ_SEARCH_SHARD (bit-identical); at the other dims it runs the scan
+ *   vrq_search3_dim_scan runs for the shape and flags, then the shard mode of the runtime-dim finish.
+ *   Merged by vrq_merge_shards.
+ * vrq_shard_search2: the arguments of vrq_search2 without k; out_score = the vrq_rescore_dequant score of
+ *   `mode` (every mode vrq_search2 accepts, VRQ_RESCORE_F32 and VRQ_RESCORE_SIGNED_BINARY included) of all
+ *   K candidates, bit-identical to vrq_search2's.  Merged by vrq_merge_shards2.
+ * vrq_merge_shards2: the merge of the stacked vrq_shard_search2 outputs [S, nq, K] (counts i32[S, nq];
+ *   shard s owns a contiguous global row range below shard s+1's): global top-K by (dist, global row) ->
+ *   stable sort by score descending over that order (-0.0 ties +0.0) -> first k, which is exactly the
+ *   single-index semantics of CohereVectorDBBinary.py:215-239 / VectorDBInt8Global.py:224-252, so the
+ *   result equals vrq_search2 over the whole corpus.  Outputs [nq, k]; out_count = min(k, candidates);
+ *   out_src (nullable) i32[nq, k] = s*K + p as in vrq_merge_shards (missing -1).  Limits as there.
+ * Not sharded: VRQ_ENC_BIN_INT16 (VectorDBInt16 ranks by Phase I alone); a rescore_row that points into
+ *   another shard (an id added twice must live in one shard).
+ * ------------------------------------------------------------------------- */
+size_t vrq_shard_search3_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K);
+int vrq_shard_search3(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
+                      int64_t n, int32_t dim, int64_t row_offset, const float* qf, const uint8_t* qb,
+                      int32_t nq, int32_t K, int32_t flags, int32_t* out_count, int64_t* out_rows,
+                      int32_t* out_dist, double* out_binary, double* out_cosine,
+                      void* workspace, size_t workspace_bytes, void* stream);
+size_t vrq_shard_search2_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K);
+int vrq_shard_search2(int32_t mode, const uint8_t* codes, const void* q, const double* minmax, double limit,
+                      const int64_t* rescore_row, int64_t n, int32_t dim, int64_t row_offset, const float* qf,
+                      const uint8_t* qb, int32_t nq, int32_t K, int32_t flags, int32_t* out_count,
+                      int64_t* out_rows, int32_t* out_dist, double* out_score,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int vrq_merge_shards2(int32_t nshards, int32_t nq, int32_t K, const int32_t* counts, const int64_t* rows,
+                      const int32_t* dist, const double* score, int32_t k, int32_t* out_count,
+                      int64_t* out_rows, int32_t* out_dist, double* out_score, int32_t* out_src, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Stand-alone Phase II / Phase III candidate rescoring (the per-candidate

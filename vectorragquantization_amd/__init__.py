@@ -8,8 +8,8 @@ quantise/packbits encode path, as hand-written HIP kernels behind a C ABI
 from ._native import VrqNativeError, load as load_native  # noqa: F401
 
 __all__ = ["VrqNativeError", "load_native", "CohereEnhancedVectorDB", "BinaryIndexIDMap2", "encode",
-           "ShardedSearch", "CohereVectorDBFloat", "VectorDBInt8Global", "VectorDBInt16Global", "VectorDBInt4Global",
-           "VectorDBInt8", "VectorDBInt4", "VectorDBInt16", "CohereVectorDBInt8", "CohereVectorDBBinary"]
+           "ShardedSearch", "ShardedSearch2", "CohereVectorDBFloat", "VectorDBInt8Global", "VectorDBInt16Global",
+           "VectorDBInt4Global", "VectorDBInt8", "VectorDBInt4", "VectorDBInt16", "CohereVectorDBInt8", "CohereVectorDBBinary"]
 
 _VECTORDB = ("VectorDBInt8Global", "VectorDBInt16Global", "VectorDBInt4Global", "VectorDBInt8", "VectorDBInt4",
              "VectorDBInt16", "CohereVectorDBInt8")
@@ -34,7 +34,7 @@ def __getattr__(name):  # lazy: importing the package must not require a GPU
     if name == "CohereVectorDBFloat":
         from .flat import CohereVectorDBFloat
         return CohereVectorDBFloat
-    if name == "ShardedSearch":
-        from .dist import ShardedSearch
-        return ShardedSearch
+    if name in ("ShardedSearch", "ShardedSearch2"):
+        from . import dist
+        return getattr(dist, name)
     raise AttributeError(name)

@@ -78,6 +78,13 @@ SIGNATURES = {
     "vrq_scan_plan": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _P]),
     "vrq_scan_sample_plan": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _P]),
     "vrq_merge_shards": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "vrq_shard_search3_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
+    "vrq_shard_search3": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I64, _P, _P, _I32, _I32, _I32,
+                                    _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "vrq_shard_search2_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
+    "vrq_shard_search2": (C.c_int, [_I32, _P, _P, _P, _D, _P, _I64, _I32, _I64, _P, _P, _I32, _I32, _I32,
+                                    _P, _P, _P, _P, _P, _SZ, _P]),
+    "vrq_merge_shards2": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P]),
     "vrq_rescore_binary": (C.c_int, [_P, _I32, _I32, _P, _I64, _P, _I32, _P, _P]),
     "vrq_rescore_int8_cosine": (C.c_int, [_P, _I32, _I32, _P, _P, _I64, _P, _I32, _P, _P]),
     "vrq_encode": (C.c_int, [_I32, _P, _I64, _I32, _D, _P, _P, _P, _P]),

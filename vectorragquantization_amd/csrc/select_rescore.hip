@@ -604,7 +604,8 @@ __device__ void phase2_nibble_tables_dim(const float* __restrict__ q, const uint
 }
 
 // K2 for the other dims: merge of the K1d lists (histogram over every distance up to 2048) + Phase II +
-// Phase III + the stable sorts.  mode: 0 = full 3-phase; 1 = Phase I only.
+// Phase III + the stable sorts.  mode: 0 = full 3-phase; 1 = Phase I only; 2 = shard (all Kp candidates,
+// s2 + s3, Phase-I order), as at 1024.
 template <class SH>
 __global__ __launch_bounds__(SEL_THREADS, SH::kKM <= KSMALL ? 4 : 1) void select_rescore_dim_kernel(
     const uint64_t* __restrict__ lists, int nlp, int K, int dim, const uint8_t* __restrict__ codes,
@@ -622,6 +623,19 @@ __global__ __launch_bounds__(SEL_THREADS, SH::kKM <= KSMALL ? 4 : 1) void select
   const float* q = qf + (int64_t)qi * dim;
   __shared__ double qtab[QT_NIB * 16];
   phase2_nibble_tables_dim(q, codes, fa.remap, Kp, dim / 8, sh, qtab);
+  if (mode == 2) {
+    // Phase III of every candidate, one wave per row (j, hence the row, is wave-uniform): the same
+    // phase3_cos_dim call as below, so a shard's s3 is the single index's bit for bit
+    for (int j = w; j < Kp; j += SEL_THREADS / WAVE) {
+      int64_t row = (int64_t)(sh.sel[j] & ROW_MASK);
+      if (fa.remap) row = fa.remap[row];
+      const double c = phase3_cos_dim(q, x8 + row * dim, norms[row], dim);
+      if (l == 0) sh.s3[j] = c;
+    }
+    __syncthreads();
+    write_phase1_order(Kp, true, fa, qi, sh);
+    return;
+  }
   // Phase III of the K3 survivors of the Phase-II sort, one wave per row; finish_query then finds its
   // scores in sh.s3 (by Phase-I rank) and repeats the cheap Phase-II sort
   stable_desc_order(sh.s2, Kp, sh);
@@ -657,6 +671,7 @@ struct Finish2Args {
   int64_t* out_rows;
   int32_t* out_dist;
   double* out_score;
+  bool shard;  // vrq_shard_search2: all Kp candidates in Phase-I order with their scores, [nq][K], no sort
 };
 
 template <class SH>
@@ -675,6 +690,17 @@ __global__ __launch_bounds__(SEL_THREADS, SH::kKM <= KSMALL ? 4 : 1) void select
     if (l == 0) sh.s2[j] = sc;
   }
   __syncthreads();
+  if (fa.shard) {  // (the same for every thread of the grid)
+    for (int i = tid; i < K; i += SEL_THREADS) {
+      const int64_t o = (int64_t)qi * K + i;
+      const bool live = i < Kp;
+      fa.out_rows[o] = live ? (int64_t)(sh.sel[i] & ROW_MASK) + fa.row_offset : -1;
+      fa.out_dist[o] = live ? (int32_t)(sh.sel[i] >> KEY_ROW_BITS) : DIST_NONE;
+      fa.out_score[o] = live ? sh.s2[i] : __builtin_nan("");
+    }
+    if (tid == 0) fa.out_count[qi] = Kp;
+    return;
+  }
   stable_desc_order(sh.s2, Kp, sh);  // sh.sidx[0..Kp) = Phase-I ranks by score desc, ties in Phase-I order
   const int m = fa.k < Kp ? fa.k : Kp;
   for (int i = tid; i < fa.k; i += SEL_THREADS) {
@@ -694,8 +720,10 @@ __global__ __launch_bounds__(SEL_THREADS, SH::kKM <= KSMALL ? 4 : 1) void select
   if (tid == 0) fa.out_count[qi] = m;
 }
 
-// Shard merge: the lists are the shards' (dist, global row) candidates (VRQ_SEARCH_SHARD
-// outputs stacked [S][nq][K]); the payload carried to the finish step is s2/s3.
+// Shard merge: the lists are the shards' (dist, global row) candidates (VRQ_SEARCH_SHARD /
+// vrq_shard_search3 outputs stacked [S][nq][K]); the payload carried to the finish step is s2/s3.
+// The merge never reads the embedding dim: a distance up to 2048 fits the 24 key bits above
+// KEY_ROW_BITS, and the host launches the instances whose histogram covers every such distance.
 struct ShardKeys {
   const int32_t* counts;
   const int64_t* rows;
@@ -732,6 +760,39 @@ __global__ __launch_bounds__(SEL_THREADS) void merge_shards_kernel(int S, int K,
   FinishArgs a = fa;
   a.row_offset = 0;
   finish_query(Kp, true, a, qi, sh);
+}
+
+// Shard merge of the two-phase search (vrq_shard_search2 outputs stacked [S][nq][K], one score per
+// candidate): global top-K by (dist, global row), the stable sort by score descending over that order,
+// the first k -- the tail of select_rescore2_kernel on the gathered candidates.
+template <class SH>
+__global__ __launch_bounds__(SEL_THREADS) void merge_shards2_kernel(
+    int S, int K, const int32_t* __restrict__ counts, const int64_t* __restrict__ rows,
+    const int32_t* __restrict__ dist, const double* __restrict__ score, int nq, int k,
+    int32_t* __restrict__ out_count, int64_t* __restrict__ out_rows, int32_t* __restrict__ out_dist,
+    double* __restrict__ out_score, int32_t* __restrict__ out_src) {
+  __shared__ SH sh;
+  const int qi = blockIdx.x;
+  const int tid = threadIdx.x;
+  const ShardKeys L{counts, rows, dist, nq, qi, K};
+  const int Kp = select_topk(L, S, K, sh);
+  for (int j = tid; j < Kp; j += SEL_THREADS) {
+    const int i = sh.pay[j];
+    const int s = i / K, p = i - s * K;
+    sh.s2[j] = score[((int64_t)s * nq + qi) * K + p];
+  }
+  __syncthreads();
+  stable_desc_order(sh.s2, Kp, sh);
+  const int m = k < Kp ? k : Kp;
+  for (int i = tid; i < k; i += SEL_THREADS) {
+    const int64_t o = (int64_t)qi * k + i;
+    const int r = i < m ? sh.sidx[i] : 0;
+    out_rows[o] = i < m ? (int64_t)(sh.sel[r] & ROW_MASK) : -1;
+    out_dist[o] = i < m ? (int32_t)(sh.sel[r] >> KEY_ROW_BITS) : DIST_NONE;
+    out_score[o] = i < m ? sh.s2[r] : __builtin_nan("");
+    if (out_src) out_src[o] = i < m ? sh.pay[r] : -1;
+  }
+  if (tid == 0) out_count[qi] = m;
 }
 
 // The two scores of one row for one query, one wave: at 1024 dims from the lane-resident query slice
@@ -811,6 +872,21 @@ static int launch_select(hipStream_t s, int nq, const void* ws, const Phase1Rout
   else
     hipLaunchKernelGGL(select_rescore_dim_kernel<SelDimBig>, grid, block, 0, s, lists, r.nl, K, dim, codes, x8, norms,
                        qf, mode, fa);
+  VRQ_LAUNCH_CHECK();
+  return VRQ_OK;
+}
+
+// K2b on the lists a route's scan left in `ws` (a matrix-core scan's sorted list is the single list of
+// the merge); the small-LDS instance when the shape fits it.
+static int launch_select2(hipStream_t s, int nq, const void* ws, const Phase1Route& r, int K, int dim,
+                          const float* qf, const Finish2Args& fa) {
+  const uint64_t* lists = (const uint64_t*)((const uint8_t*)ws + r.off_lists);
+  if (K <= KSMALL && r.nl <= LSMALL)
+    hipLaunchKernelGGL(select_rescore2_kernel<Sel2Small>, dim3(nq), dim3(SEL_THREADS), 0, s, lists, r.nl, K, dim, qf,
+                       fa);
+  else
+    hipLaunchKernelGGL(select_rescore2_kernel<Sel2Big>, dim3(nq), dim3(SEL_THREADS), 0, s, lists, r.nl, K, dim, qf,
+                       fa);
   VRQ_LAUNCH_CHECK();
   return VRQ_OK;
 }
@@ -896,7 +972,8 @@ int vrq_hamming_topk(const uint8_t* codes, int64_t n, int32_t code_bytes, int64_
   return launch_select(s, nq, workspace, r, k, code_bytes * 8, nullptr, nullptr, nullptr, nullptr, 1, fa);
 }
 
-// The staged three-phase search at every dim of vrq_dim_supported.  The sharded mode is 1024-only.
+// The staged three-phase search at every dim of vrq_dim_supported.  VRQ_SEARCH_SHARD stays 1024-only on
+// these entry points (their ABI-1 contract); the other dims shard through vrq_shard_search3.
 int vrq_search3_dim_scan(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq, int32_t K,
                          int32_t flags, void* workspace, size_t workspace_bytes, void* stream) {
   VRQ_CHECK_ARG(n >= 0 && nq >= 0 && K >= 0);
@@ -993,6 +1070,39 @@ int vrq_search3(const uint8_t* codes, const int8_t* x8, const double* norms, con
                          out_rows, out_dist, out_binary, out_cosine, workspace, workspace_bytes, stream);
 }
 
+// ---- the per-shard call of the row-sharded three-phase search, every dim of vrq_dim_supported ----
+size_t vrq_shard_search3_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K) {
+  return vrq_search3_dim_workspace_size(n, dim, nq, K);
+}
+
+int vrq_shard_search3(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
+                      int64_t n, int32_t dim, int64_t row_offset, const float* qf, const uint8_t* qb, int32_t nq,
+                      int32_t K, int32_t flags, int32_t* out_count, int64_t* out_rows, int32_t* out_dist,
+                      double* out_binary, double* out_cosine, void* workspace, size_t workspace_bytes, void* stream) {
+  VRQ_CHECK_ARG(n >= 0 && nq >= 0 && K >= 0);
+  VRQ_CHECK_ARG(out_count && out_rows && out_dist && out_binary && out_cosine);
+  if (!vrq_dim_supported(dim) || K > KMAX) return VRQ_EUNSUPPORTED;
+  if (flags & ~(VRQ_SEARCH_SCAN_VALU | VRQ_SEARCH_SCAN_MFMA)) return VRQ_EUNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  if (nq == 0) return VRQ_OK;
+  if (n == 0 || K == 0) return fill_empty(nq, K, out_count, out_rows, out_dist, out_binary, out_cosine, s);
+  VRQ_CHECK_ARG(codes && qb && workspace && qf && x8 && norms);
+  if (dim == DIM)  // the ABI-1 sharded mode (k and K3 are not read there)
+    return vrq_search3(codes, x8, norms, rescore_row, n, dim, row_offset, qf, qb, nq, K, K, K,
+                       flags | VRQ_SEARCH_SHARD, out_count, out_rows, out_dist, out_binary, out_cosine, workspace,
+                       workspace_bytes, stream);
+  // the scan of the shape without the shard bit, exactly as vrq_search3_dim_scan runs it, then the shard
+  // mode of the runtime-dim finish on the lists it left
+  Phase1Route r;
+  int rc = route_checked(n, dim / 8, nq, K, flags, workspace_bytes, &r);
+  if (rc != VRQ_OK) return rc;
+  rc = phase1_launch(r, codes, n, dim / 8, qb, nq, K, workspace, s, flags);
+  if (rc != VRQ_OK) return rc;
+  const FinishArgs fa = finish_args(x8, norms, rescore_row, row_offset, 0, 0, out_count, out_rows, out_dist,
+                                    out_binary, out_cosine, nullptr, K);
+  return launch_select(s, nq, workspace, r, K, dim, codes, x8, norms, qf, 2, fa);
+}
+
 // ---- introspection: the answers are read out of the route ----
 int vrq_scan_kind(int64_t n, int32_t dim, int32_t nq, int32_t K, int32_t flags, int64_t* prefix_rows) {
   if (n < 1 || nq < 1 || K < 1) return VRQ_EINVAL;
@@ -1060,12 +1170,37 @@ int vrq_merge_shards(int32_t nshards, int32_t nq, int32_t K, const int32_t* coun
   VRQ_CHECK_ARG(counts && rows && dist && s2 && s3);
   const FinishArgs fa = finish_args(nullptr, nullptr, nullptr, 0, k, K3, out_count, out_rows, out_dist, out_binary,
                                     out_cosine, out_src, k);
+  // (the call has no dim: the instances with a bin for every distance up to 2048 serve all of them)
   if (K <= KSMALL && nshards <= LSMALL)
-    hipLaunchKernelGGL(merge_shards_kernel<SelSmall>, dim3(nq), dim3(SEL_THREADS), 0, s, nshards, K, counts, rows,
+    hipLaunchKernelGGL(merge_shards_kernel<SelDimSmall>, dim3(nq), dim3(SEL_THREADS), 0, s, nshards, K, counts, rows,
                        dist, s2, s3, nq, fa);
   else
-    hipLaunchKernelGGL(merge_shards_kernel<SelBig>, dim3(nq), dim3(SEL_THREADS), 0, s, nshards, K, counts, rows,
+    hipLaunchKernelGGL(merge_shards_kernel<SelDimBig>, dim3(nq), dim3(SEL_THREADS), 0, s, nshards, K, counts, rows,
                        dist, s2, s3, nq, fa);
+  VRQ_LAUNCH_CHECK();
+  return VRQ_OK;
+}
+
+int vrq_merge_shards2(int32_t nshards, int32_t nq, int32_t K, const int32_t* counts, const int64_t* rows,
+                      const int32_t* dist, const double* score, int32_t k, int32_t* out_count, int64_t* out_rows,
+                      int32_t* out_dist, double* out_score, int32_t* out_src, void* stream) {
+  VRQ_CHECK_ARG(nshards >= 1 && nq >= 0 && K >= 0 && k >= 0);
+  VRQ_CHECK_ARG(out_count && out_rows && out_dist && out_score);
+  if (K > KMAX || nshards > MAX_LISTS) return VRQ_EUNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  if (nq == 0) return VRQ_OK;
+  if (K == 0 || k == 0) {
+    if (out_src && k && hipMemsetAsync(out_src, 0xff, sizeof(int32_t) * (size_t)nq * k, s) != hipSuccess)
+      return VRQ_EHIP;  // -1
+    return fill_empty(nq, k, out_count, out_rows, out_dist, out_score, nullptr, s);
+  }
+  VRQ_CHECK_ARG(counts && rows && dist && score);
+  if (K <= KSMALL && nshards <= LSMALL)
+    hipLaunchKernelGGL(merge_shards2_kernel<Sel2Small>, dim3(nq), dim3(SEL_THREADS), 0, s, nshards, K, counts, rows,
+                       dist, score, nq, k, out_count, out_rows, out_dist, out_score, out_src);
+  else
+    hipLaunchKernelGGL(merge_shards2_kernel<Sel2Big>, dim3(nq), dim3(SEL_THREADS), 0, s, nshards, K, counts, rows,
+                       dist, score, nq, k, out_count, out_rows, out_dist, out_score, out_src);
   VRQ_LAUNCH_CHECK();
   return VRQ_OK;
 }
@@ -1131,17 +1266,9 @@ int vrq_search2_finish(int32_t mode, const uint8_t* codes, const void* q, const 
   Phase1Route r;
   const int rc = route_checked(n, dim / 8, nq, K, flags, workspace_bytes, &r);
   if (rc != VRQ_OK) return rc;
-  // (a matrix-core scan's sorted list is the single list of the merge)
-  const uint64_t* lists = (const uint64_t*)((const uint8_t*)workspace + r.off_lists);
-  const Finish2Args fa{mode, q, minmax, limit, rescore_row, row_offset, k, out_count, out_rows, out_dist, out_score};
-  if (K <= KSMALL && r.nl <= LSMALL)
-    hipLaunchKernelGGL(select_rescore2_kernel<Sel2Small>, dim3(nq), dim3(SEL_THREADS), 0, s, lists, r.nl, K, dim, qf,
-                       fa);
-  else
-    hipLaunchKernelGGL(select_rescore2_kernel<Sel2Big>, dim3(nq), dim3(SEL_THREADS), 0, s, lists, r.nl, K, dim, qf,
-                       fa);
-  VRQ_LAUNCH_CHECK();
-  return VRQ_OK;
+  const Finish2Args fa{mode, q, minmax, limit, rescore_row, row_offset, k, out_count, out_rows, out_dist, out_score,
+                       false};
+  return launch_select2(s, nq, workspace, r, K, dim, qf, fa);
 }
 
 int vrq_search2(int32_t mode, const uint8_t* codes, const void* q, const double* minmax, double limit,
@@ -1162,6 +1289,35 @@ int vrq_search2(int32_t mode, const uint8_t* codes, const void* q, const double*
   }
   return vrq_search2_finish(mode, codes, q, minmax, limit, rescore_row, n, dim, row_offset, qf, nq, k, K, flags,
                             out_count, out_rows, out_dist, out_score, workspace, workspace_bytes, stream);
+}
+
+// ---- the per-shard call of the row-sharded two-phase search ----
+size_t vrq_shard_search2_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K) {
+  return vrq_search3_dim_workspace_size(n, dim, nq, K);
+}
+
+int vrq_shard_search2(int32_t mode, const uint8_t* codes, const void* q, const double* minmax, double limit,
+                      const int64_t* rescore_row, int64_t n, int32_t dim, int64_t row_offset, const float* qf,
+                      const uint8_t* qb, int32_t nq, int32_t K, int32_t flags, int32_t* out_count, int64_t* out_rows,
+                      int32_t* out_dist, double* out_score, void* workspace, size_t workspace_bytes, void* stream) {
+  VRQ_CHECK_ARG(search2_mode_ok(mode));
+  VRQ_CHECK_ARG(n >= 0 && nq >= 0 && K >= 0);
+  VRQ_CHECK_ARG(out_count && out_rows && out_dist && out_score);
+  if (!vrq_dim_supported(dim) || K > KMAX) return VRQ_EUNSUPPORTED;
+  if (flags & ~(VRQ_SEARCH_SCAN_VALU | VRQ_SEARCH_SCAN_MFMA)) return VRQ_EUNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  if (nq == 0) return VRQ_OK;
+  if (n == 0 || K == 0) return fill_empty(nq, K, out_count, out_rows, out_dist, out_score, nullptr, s);
+  VRQ_CHECK_ARG(codes && qb && workspace && qf && q);
+  if (mode == VRQ_ENC_INT8_LOCAL || mode == VRQ_ENC_INT4_LOCAL) VRQ_CHECK_ARG(minmax);
+  Phase1Route r;
+  int rc = route_checked(n, dim / 8, nq, K, flags, workspace_bytes, &r);
+  if (rc != VRQ_OK) return rc;
+  rc = phase1_launch(r, codes, n, dim / 8, qb, nq, K, workspace, s, flags);
+  if (rc != VRQ_OK) return rc;
+  const Finish2Args fa{mode, q, minmax, limit, rescore_row, row_offset, K, out_count, out_rows, out_dist, out_score,
+                       true};
+  return launch_select2(s, nq, workspace, r, K, dim, qf, fa);
 }
 
 }  // extern "C"

@@ -1,11 +1,14 @@
-"""Row-sharded three-phase search over several MI355X (one process per GPU).
+"""Row-sharded search over several MI355X (one process per GPU): the three-phase search
+(``ShardedSearch``) and the two-phase search of the ``CohereVectorDBBinary`` / ``VectorDBInt*``
+classes (``ShardedSearch2``), at every embedding dim of ``vrq_dim_supported``.
 
 The reference is single-process; sharding is this
 build's only scaling axis.  Rank r owns a contiguous global row range
 ``[row0, row0 + m)`` (codes, int8 rows, norms, external ids).  A query batch is
 replicated to every rank and searched in three steps:
 
-1. local ``vrq_search3`` in ``VRQ_SEARCH_SHARD`` mode: the shard's exact top-K
+1. local ``vrq_shard_search3`` (at 1024 dims: ``vrq_search3`` in ``VRQ_SEARCH_SHARD``
+   mode): the shard's exact top-K
    (K = the GLOBAL ``binary_k``, because the global top-K may sit in one shard)
    by (dist, global row), each with its Phase-II and Phase-III score;
 2. ONE ``all_gather_into_tensor`` (RCCL over xGMI with the ``nccl`` backend) of
@@ -15,6 +18,14 @@ replicated to every rank and searched in three steps:
    stable sort by s2 -> first K3 -> stable sort by s3 -> first k, which is
    exactly the single-index semantics of ``CohereEnhancedVectorDB.py:267-322``,
    so results are identical for 1/2/4/8 ranks.
+
+``ShardedSearch2`` is the same three steps with one score per candidate: ``vrq_shard_search2``,
+one all-gather of 28-byte records, ``vrq_merge_shards2`` (global top-K -> stable sort by score ->
+first k: ``CohereVectorDBBinary.py:215-239``, ``VectorDBInt8Global.py:224-252``).
+
+Not sharded: ``mode="bin16"`` (``VectorDBInt16`` ranks by Phase I alone), a ``rescore_row`` that
+crosses shards (an id added twice must live in one shard), class-level ``add_documents``, and
+``CohereVectorDBFloat`` (``merge_topk_shards`` covers the exhaustive paths through ``row_offset``).
 """
 from __future__ import annotations
 
@@ -22,7 +33,8 @@ import torch
 import torch.distributed as dist
 
 from . import _native as N
-from .enhanced import SearchBatch, search3
+from .enhanced import SearchBatch
+from .quant import _SEARCH2_MODES, merge_shards2
 
 # packed per-candidate record: row i64 | doc id i64 | s2 f64 | s3 f64 | dist i32  (36 B)
 _REC = 36
@@ -71,6 +83,120 @@ def gather_candidates(local: torch.Tensor, group=None) -> torch.Tensor:
     out = torch.empty((world * src.numel(),), dtype=src.dtype, device=src.device)
     dist.all_gather_into_tensor(out, src, group=group)
     return out.to(local.device) if stage else out
+
+
+# packed per-candidate record of the two-phase search: row i64 | doc id i64 | score f64 | dist i32  (28 B)
+_REC2 = 28
+
+
+def pack_candidates2(count: torch.Tensor, rows: torch.Tensor, ids: torch.Tensor, dist_: torch.Tensor,
+                     score: torch.Tensor) -> torch.Tensor:
+    """``pack_candidates`` for the one-score candidates of ``vrq_shard_search2``."""
+    parts = [count.to(torch.int32).contiguous().view(torch.uint8).reshape(-1),
+             rows.contiguous().view(torch.uint8).reshape(-1),
+             ids.contiguous().view(torch.uint8).reshape(-1),
+             score.contiguous().view(torch.uint8).reshape(-1),
+             dist_.to(torch.int32).contiguous().view(torch.uint8).reshape(-1)]
+    return torch.cat(parts)
+
+
+def unpack_candidates2(buf: torch.Tensor, S: int, nq: int, K: int):
+    """Inverse of ``pack_candidates2`` for S stacked ranks -> (count, rows, ids, dist, score) [S, nq(, K)]."""
+    b = buf.reshape(S, 4 * nq + _REC2 * nq * K)
+    o = 0
+
+    def take(nbytes, dtype, shape):
+        nonlocal o
+        t = b[:, o:o + nbytes].contiguous().view(dtype).reshape(S, *shape)
+        o += nbytes
+        return t
+
+    cnt = take(4 * nq, torch.int32, (nq,))
+    rows = take(8 * nq * K, torch.int64, (nq, K))
+    ids = take(8 * nq * K, torch.int64, (nq, K))
+    sc = take(8 * nq * K, torch.float64, (nq, K))
+    d = take(4 * nq * K, torch.int32, (nq, K))
+    return cnt, rows, ids, d, sc
+
+
+def _workspace(ws, size_fn, n: int, qf: torch.Tensor, K: int, dev):
+    """``ws`` if it holds a shard call of this shape, else a new buffer that does."""
+    need = size_fn(n, qf.shape[1], qf.shape[0], K) if n and K and qf.shape[0] else 0
+    if n and K and qf.shape[0] and need == 0:
+        raise N.VrqNativeError(f"sharded search: unsupported shape n={n} dim={qf.shape[1]} nq={qf.shape[0]} K={K} "
+                               "(dims: vrq_dim_supported)")
+    if ws is None or ws.numel() < need:
+        ws = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev)
+    return ws
+
+
+def _local_ids(ids: torch.Tensor, rows: torch.Tensor, row0: int) -> torch.Tensor:
+    """External ids of a shard's global candidate rows (padding stays -1; no id table: the row)."""
+    loc = (rows - row0).clamp_min(0)
+    return torch.where(rows >= 0, ids[loc] if ids.numel() else rows, rows)
+
+
+def shard_search3(codes: torch.Tensor, x8: torch.Tensor, norms: torch.Tensor, qf: torch.Tensor, qb: torch.Tensor,
+                  K: int, flags: int = 0, row_offset: int = 0, rescore_row: torch.Tensor | None = None,
+                  workspace: torch.Tensor | None = None):
+    """Thin wrapper of ``vrq_shard_search3`` (every dim of ``vrq_dim_supported``): one shard's exact Phase-I
+    top-K in (dist, row) order with both scores; returns (count, rows, dist, s2, s3) device tensors [nq, K]."""
+    dev = qf.device
+    nq, dim = qf.shape
+    n = codes.shape[0]
+    if n and (x8.shape[0] != n or norms.shape[0] != n):
+        # the ABI indexes x8 / norms by code row and cannot see their lengths
+        raise N.VrqNativeError(f"vrq_shard_search3: {n} code rows but {x8.shape[0]} int8 rows and "
+                               f"{norms.shape[0]} norms")
+    if rescore_row is not None and rescore_row.shape[0] != n:
+        raise N.VrqNativeError(f"vrq_shard_search3: rescore_row has {rescore_row.shape[0]} entries for {n} rows")
+    if n and (codes.shape[1] * 8 != dim or qb.shape != (nq, dim // 8) or x8.shape[1] != dim):
+        raise N.VrqNativeError(f"vrq_shard_search3: {codes.shape[1]}-byte codes but queries of dim {dim} / codes "
+                               f"{tuple(qb.shape)}, int8 rows of dim {x8.shape[1]}")
+    lib = N.load()
+    workspace = _workspace(workspace, lib.vrq_shard_search3_workspace_size, n, qf, K, dev)
+    cnt = torch.empty((nq,), dtype=torch.int32, device=dev)
+    rows = torch.empty((nq, K), dtype=torch.int64, device=dev)
+    dist_ = torch.empty((nq, K), dtype=torch.int32, device=dev)
+    s2 = torch.empty((nq, K), dtype=torch.float64, device=dev)
+    s3 = torch.empty((nq, K), dtype=torch.float64, device=dev)
+    rc = lib.vrq_shard_search3(N.ptr(codes) if n else 0, N.ptr(x8) if n else 0, N.ptr(norms) if n else 0,
+                               N.ptr(rescore_row), n, dim, row_offset, N.ptr(qf), N.ptr(qb), nq, K, flags,
+                               N.ptr(cnt), N.ptr(rows), N.ptr(dist_), N.ptr(s2), N.ptr(s3), N.ptr(workspace),
+                               workspace.numel(), N.stream_handle(dev))
+    N.check(rc, "vrq_shard_search3")
+    return cnt, rows, dist_, s2, s3
+
+
+def shard_search2(mode: str, codes: torch.Tensor, q: torch.Tensor, qf: torch.Tensor, qb: torch.Tensor, K: int,
+                  minmax: torch.Tensor | None = None, limit: float = 0.0, flags: int = 0, row_offset: int = 0,
+                  rescore_row: torch.Tensor | None = None, workspace: torch.Tensor | None = None):
+    """Thin wrapper of ``vrq_shard_search2``: one shard's exact Phase-I top-K in (dist, row) order with the
+    rescoring score of ``mode`` (a ``quant.search2`` mode name); returns (count, rows, dist, score) [nq, K]."""
+    if mode not in _SEARCH2_MODES:
+        raise ValueError(f"unknown search2 mode {mode!r}")
+    dev = qf.device
+    nq, dim = qf.shape
+    n = codes.shape[0]
+    if n and (codes.shape[1] * 8 != dim or qb.shape != (nq, dim // 8)):
+        raise N.VrqNativeError(f"vrq_shard_search2: {codes.shape[1]}-byte codes but queries of dim {dim} / codes "
+                               f"{tuple(qb.shape)}")
+    if n and (q is None or q.shape[0] != n or (minmax is not None and minmax.shape[0] != n) or
+              (rescore_row is not None and rescore_row.shape[0] != n)):
+        # the ABI indexes q / minmax / rescore_row by candidate row and cannot see their lengths
+        raise N.VrqNativeError(f"vrq_shard_search2: {n} code rows but {None if q is None else q.shape[0]} stored rows")
+    lib = N.load()
+    workspace = _workspace(workspace, lib.vrq_shard_search2_workspace_size, n, qf, K, dev)
+    cnt = torch.empty((nq,), dtype=torch.int32, device=dev)
+    rows = torch.empty((nq, K), dtype=torch.int64, device=dev)
+    dist_ = torch.empty((nq, K), dtype=torch.int32, device=dev)
+    score = torch.empty((nq, K), dtype=torch.float64, device=dev)
+    rc = lib.vrq_shard_search2(_SEARCH2_MODES[mode], N.ptr(codes) if n else 0, N.ptr(q) if n else 0,
+                               N.ptr(minmax) if n else 0, float(limit), N.ptr(rescore_row), n, dim, row_offset,
+                               N.ptr(qf), N.ptr(qb), nq, K, flags, N.ptr(cnt), N.ptr(rows), N.ptr(dist_),
+                               N.ptr(score), N.ptr(workspace), workspace.numel(), N.stream_handle(dev))
+    N.check(rc, f"vrq_shard_search2({mode})")
+    return cnt, rows, dist_, score
 
 
 def merge_shards(cnt, rows, d, s2, s3, k: int, K3: int):
@@ -135,17 +261,12 @@ class ShardedSearch:
 
     def local(self, qf, qb, k, binary_oversample, int8_oversample):
         K = min(k * binary_oversample, self.n_total)
-        lib = N.load()
-        need = lib.vrq_search3_workspace_size(self.codes.shape[0], qf.shape[1], qf.shape[0], K) \
-            if self.codes.shape[0] and K else 0
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty((max(need, 8),), dtype=torch.uint8, device=self.device)
+        self._ws = _workspace(self._ws, N.load().vrq_shard_search3_workspace_size, self.codes.shape[0], qf, K,
+                              self.device)
         with torch.cuda.device(self.device):
-            cnt, rows, d, s2, s3 = search3(self.codes, self.x8, self.norms, qf, qb, k, K,
-                                           k * int8_oversample, N.VRQ_SEARCH_SHARD, self.row0, None, self._ws)
-        loc = (rows - self.row0).clamp_min(0)
-        ids = torch.where(rows >= 0, self.ids[loc] if self.ids.numel() else rows, rows)
-        return K, cnt, rows, ids, d, s2, s3
+            cnt, rows, d, s2, s3 = shard_search3(self.codes, self.x8, self.norms, qf, qb, K, 0, self.row0, None,
+                                                 self._ws)
+        return K, cnt, rows, _local_ids(self.ids, rows, self.row0), d, s2, s3
 
     def search_vectors(self, qf, qb, k: int = 10, binary_oversample: int = 10,
                        int8_oversample: int = 3) -> SearchBatch:
@@ -159,3 +280,43 @@ class ShardedSearch:
         oid = torch.where(src >= 0, torch.gather(flat_ids, 1, src.clamp_min(0).to(torch.int64)),
                           torch.full_like(orow, -1))
         return SearchBatch(oc, oid, orow, od, o2, o3)
+
+
+class ShardedSearch2:
+    """One rank's shard of a row-sharded two-phase corpus (``CohereVectorDBBinary``, ``VectorDBInt*``,
+    ``CohereVectorDBInt8``) + the collective search.  ``mode`` is a ``quant.search2`` rescoring mode
+    (``int8g`` ... ``int4``, ``f32``, ``sbin``), ``q`` the shard's stored rows of that mode (for ``sbin``
+    normally ``codes`` itself), ``minmax`` / ``limit`` as there."""
+
+    def __init__(self, mode: str, codes: torch.Tensor, q: torch.Tensor, ids: torch.Tensor, row0: int, n_total: int,
+                 minmax: torch.Tensor | None = None, limit: float = 0.0, group=None):
+        if mode not in _SEARCH2_MODES:
+            raise ValueError(f"unknown search2 mode {mode!r}")
+        self.mode, self.codes, self.q, self.ids = mode, codes, q, ids
+        self.minmax, self.limit = minmax, float(limit)
+        self.row0, self.n_total, self.group = int(row0), int(n_total), group
+        self.device = codes.device
+        self._ws = None
+
+    def local(self, qf, qb, k, binary_oversample):
+        K = min(k * binary_oversample, self.n_total)
+        self._ws = _workspace(self._ws, N.load().vrq_shard_search2_workspace_size, self.codes.shape[0], qf, K,
+                              self.device)
+        with torch.cuda.device(self.device):
+            cnt, rows, d, sc = shard_search2(self.mode, self.codes, self.q, qf, qb, K, self.minmax, self.limit, 0,
+                                             self.row0, None, self._ws)
+        return K, cnt, rows, _local_ids(self.ids, rows, self.row0), d, sc
+
+    def search_vectors(self, qf, qb, k: int = 10, binary_oversample: int = 10):
+        """-> (count i32[nq], ids i64[nq, k], rows i64[nq, k], dist i32[nq, k], score f64[nq, k]), equal to
+        ``quant.search2`` over the whole corpus (padding -1 / INT32_MAX / NaN)."""
+        K, cnt, rows, ids, d, sc = self.local(qf, qb, k, binary_oversample)
+        nq = qf.shape[0]
+        S = dist.get_world_size(self.group)
+        allb = gather_candidates(pack_candidates2(cnt, rows, ids, d, sc), self.group)
+        gc, gr, gi, gd, gs = unpack_candidates2(allb, S, nq, K)
+        oc, orow, od, osc, src = merge_shards2(gc, gr, gd, gs, k)
+        flat_ids = gi.permute(1, 0, 2).reshape(nq, S * K)  # [nq, S*K] in (shard, pos) order
+        oid = torch.where(src >= 0, torch.gather(flat_ids, 1, src.clamp_min(0).to(torch.int64)),
+                          torch.full_like(orow, -1))
+        return oc, oid, orow, od, osc

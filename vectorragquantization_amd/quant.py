@@ -173,6 +173,26 @@ def search2(mode: str, codes: torch.Tensor, q: torch.Tensor, qf: torch.Tensor, q
     return rows, dist, score
 
 
+def merge_shards2(cnt, rows, dist, score, k: int):
+    """``vrq_merge_shards2`` on the stacked [S, nq, K] outputs of ``vrq_shard_search2`` (``cnt`` [S, nq]) ->
+    (count, rows, dist, score, src): the two-phase result of the whole corpus, ``src`` = shard * K + position
+    of each result in the stacked inputs (-1 for padding)."""
+    S, nq, K = rows.shape
+    dev = rows.device
+    oc = torch.empty((nq,), dtype=torch.int32, device=dev)
+    orow = torch.empty((nq, k), dtype=torch.int64, device=dev)
+    od = torch.empty((nq, k), dtype=torch.int32, device=dev)
+    osc = torch.empty((nq, k), dtype=torch.float64, device=dev)
+    src = torch.empty((nq, k), dtype=torch.int32, device=dev)
+    cnt, rows, dist, score = (t.contiguous() for t in (cnt, rows, dist, score))  # held until the launch returns
+    lib = N.load()
+    with torch.cuda.device(dev):
+        rc = lib.vrq_merge_shards2(S, nq, K, N.ptr(cnt), N.ptr(rows), N.ptr(dist), N.ptr(score), k, N.ptr(oc),
+                                   N.ptr(orow), N.ptr(od), N.ptr(osc), N.ptr(src), N.stream_handle(dev))
+    N.check(rc, "vrq_merge_shards2")
+    return oc, orow, od, osc, src
+
+
 def int8_row_norms(x8: torch.Tensor) -> torch.Tensor:
     """float64 ``np.linalg.norm`` of every int8 row (``CohereEnhancedVectorDB.py:308``)."""
     x8 = x8.contiguous()
