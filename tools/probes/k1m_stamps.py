@@ -1,7 +1,12 @@
 """K1m per-workgroup timeline (diagnostic build tools/probes/var/lib_k1m_stamps.so, -DVRQ_K1M_STAMPS): for
 each (n, nq) the PREFIX stage once, then the MATRIX stage several times; per workgroup the s_memrealtime
 (100 MHz) stamps of its start, of its main-loop start (after the prologue) and of its end, and its
-XCC / HW_ID.  Prints the spread of starts, prologue lengths, loop lengths and ends (us)."""
+XCC / HW_ID.  Prints the spread of starts, prologue lengths, loop lengths and ends (us).
+
+The build also brackets the tile boundary on wave 0 of every workgroup with the shader clock: from after the
+last MFMA of a tile to after the first MFMA of the next has issued, summed over the workgroup's tiles.
+`boundary_cycles` is that sum per boundary (percentiles over the workgroups, and the first workgroup of each
+XCC); `tile_cycles` the loop's length per tile at the reported clock, for scale."""
 import argparse
 import json
 import os
@@ -36,15 +41,22 @@ for c in a.cases.split(","):
         lib.vrq_search3_scan(N.ptr(codes), n, 1024, N.ptr(qb), nq, 100, f | N.VRQ_SCAN_STAGE_MATRIX, N.ptr(ws), ws.numel(), st)
         torch.cuda.synchronize()
     grid = int(info[3]) * ((nq + (512 if nq >= 512 else 256) - 1) // (512 if nq >= 512 else 256))
-    s = ws[:grid * 32].view(torch.int64).view(grid, 4).cpu().numpy()
+    s = ws[:grid * 64].view(torch.int64).view(grid, 8).cpu().numpy()
     t0 = s[:, 0].min()
     start, loop, end = (s[:, 0] - t0) / 100.0, (s[:, 1] - s[:, 0]) / 100.0, (s[:, 2] - t0) / 100.0
     body = (s[:, 2] - s[:, 1]) / 100.0
     xcc = (s[:, 3] >> 32) & 0xF
     q = lambda v: [round(float(np.percentile(v, p)), 1) for p in (0, 10, 50, 90, 100)]
+    nbound, bsum = (s[:, 4] >> 32) & 0xFFFFFFFF, s[:, 4] & 0xFFFFFFFF
+    bc = bsum[nbound > 0] / nbound[nbound > 0]
+    first = {int(x): int(np.flatnonzero((xcc == x) & (nbound > 0))[0]) for x in np.unique(xcc[nbound > 0])}
     print(json.dumps({"n": n, "nq": nq, "workgroups": grid, "start_us_pct0_10_50_90_100": q(start),
                       "prologue_us": q(loop), "loop_us": q(body), "end_us": q(end),
                       "kernel_span_us": round(float(end.max()), 1),
+                      "boundary_cycles_pct0_10_50_90_100": q(bc),
+                      "boundary_cycles_first_wg_per_xcc": {x: round(float(bsum[i] / nbound[i]), 1) for x, i in first.items()},
+                      "tiles_per_wg_median": float(np.median(nbound + 1)),
+                      "loop_us_per_tile_median": round(float(np.median(body / (nbound + 1))), 4),
                       "per_xcc_end_max_us": {int(x): round(float(end[xcc == x].max()), 1) for x in np.unique(xcc)},
                       "per_xcc_start_max_us": {int(x): round(float(start[xcc == x].max()), 1) for x in np.unique(xcc)}}),
           flush=True)

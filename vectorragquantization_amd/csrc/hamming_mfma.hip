@@ -54,8 +54,8 @@ constexpr int NRING = BAHEAD < 4 ? 4 : 8;   // B fragment ring (power of two > B
 #ifndef VRQ_K1M_NSR  // A/B builds: M-blocks per wave whose accumulator seeds stay in registers (capped at MB)
 #define VRQ_K1M_NSR 4
 #endif
-#ifndef VRQ_K1M_DMA_AHEAD  // A/B builds: K1m refills a packed slot one iteration earlier (two tiles of DMA lead)
-#define VRQ_K1M_DMA_AHEAD 0
+#ifndef VRQ_K1M_DMA_SHADOW  // A/B builds: 0 issues the steady tiles' LDS-DMA before group 0, not in its gaps
+#define VRQ_K1M_DMA_SHADOW 1
 #endif
 // M-blocks (32 queries each) per wave: MB = 4 for large batches (512 queries per workgroup, each
 // B fragment feeds 4 MFMAs), MB = 2 below (256 per workgroup)
@@ -100,6 +100,18 @@ constexpr int ENT_V_BIAS = 1025;
 // one M-block per group, four ds_read_b128); the asynchronous hit flush (gi = 20+MB and 24+MB).  The
 // M-blocks m < NSR take their seeds from registers as the C operand of the n-block's first MFMA and
 // have no re-seed group.
+//
+// The tile boundary (last MFMA of tile t -> first MFMA of tile t+1) is a serial stretch with the matrix
+// pipe idle, so nothing is computed from t there.  The ring slots of tiles t, t+1, t+2 and the LDS-DMA
+// source of tile t + NPK are scalar state stepped in the empty slots of group NG - 1; tiles whose refill
+// exists and is whole ("steady": all but the chunk's last NPK tiles and the refill of a partial last tile)
+// issue that refill in the empty slots of group 0 -- one piece after each of two MFMAs, scalar base + lane
+// offset -- and end on the constant vmcnt wait; only the other tiles run the clamped-row DMA form and the
+// counted wait ladder.  Between the MFMAs of two steady tiles remain: the two waits, the > 64-hits test,
+// the barrier, the back edge, the flushed-store and steady tests, two address forms, the two row-popcount
+// reads and the first B read.  The hit extraction, the synchronous flush and the partial-tile DMA are marked
+// unlikely and laid out after the loop body, so a tile's 128 MFMAs are contiguous and the no-hit path
+// falls through.
 
 // The per-group LDS wait of the schedule above.  Group gi consumes the B fragment read at the top of
 // group gi - BAHEAD; DS operations complete in order, so the wait may leave in flight exactly the DS
@@ -184,7 +196,7 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
     uint32_t d0 = doff0;
     asm volatile("" : "+v"(d0));
     const uint32_t doff[GPW] = {d0, (d0 + 1024u) ^ 64u};
-    if (tr0 + RT <= row1) {
+    if (__builtin_expect(tr0 + RT <= row1, 1)) {
       const uint8_t* base = codes + tr0 * 128;
 #pragma unroll
       for (int i = 0; i < GPW; ++i)
@@ -199,6 +211,16 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
                                          (__attribute__((address_space(3))) void*)(buf + (w * GPW + i) * 1024), 16, 0, 0);
       }
     }
+  };
+  // The same for a steady tile of the loop (below): always whole, so piece i goes from a carried scalar
+  // source pointer + the per-lane offset into the carried packed slot -- no multiply, no row test.
+  auto issue_piece = [&](const uint8_t* base, uint32_t slot_off, auto I) __attribute__((always_inline)) {
+    constexpr int i = decltype(I)::value;
+    uint32_t d0 = doff0;
+    asm volatile("" : "+v"(d0));
+    const uint32_t d = i == 0 ? d0 : (d0 + 1024u) ^ 64u;
+    __builtin_amdgcn_global_load_lds(base + d, (__attribute__((address_space(3))) void*)(pk + slot_off + (w * GPW + i) * 1024),
+                                     16, 0, 0);
   };
   const uint32_t pk0 = lds_addr(pk), ub0 = lds_addr(ub), pcr0 = lds_addr(pcr);
   const uint32_t lc0 = lds_addr(lcnt), stg0 = lds_addr(stg);
@@ -331,15 +353,16 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
   // end-of-tile vmcnt wait never waits on a store issued after a DMA.  Entries past 64 (and a
   // stage overflow) take the synchronous path at the end of the tile.
   int fe = 0, fpos = 0, nfl = 0;
-  int64_t fbase = 0;
   auto fkey = [&](int e, int64_t base_row) __attribute__((always_inline)) {
     return ((uint64_t)(uint32_t)(e >> ENT_V_SHIFT) << KEY_ROW_BITS) | (uint64_t)(base_row + (e & 127));
   };
-  auto store_flushed = [&]() __attribute__((always_inline)) {
-    if (nfl) {
+  // (called at the top of iteration t and after the loop with t = ntiles: the entries were staged in iteration
+  // t - 1, relative to tile t - 2; the base row is formed here, on the hit path, not carried through the loop)
+  auto store_flushed = [&](int t) __attribute__((always_inline)) {
+    if (__builtin_expect(nfl != 0, 0)) {
       const int ql = (fe >> ENT_Q_SHIFT) & 127;
 #ifndef VRQ_K1M_PROBE_NOSTORE  // timing-only probe builds (lists left incomplete)
-      if (l < nfl && fpos < capc) cbase[ql * qstride + fpos] = fkey(fe, fbase);
+      if (l < nfl && fpos < capc) cbase[ql * qstride + fpos] = fkey(fe, row0 + (int64_t)(t - 2) * RT);
 #endif
       nfl = 0;
     }
@@ -400,8 +423,14 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
     uint32_t m16 = 0, mmid = 0, mhi = 0;
 #pragma unroll
     for (int g = 0; g < 7; ++g) m16 |= (a[g] > hp ? 1u : 0u) << g;
+    // (one piece at a time: scheduled together, the three pieces' per-bit temporaries need more registers
+    // than the tile loop leaves free, and this rare path must not be the one that spills)
+    asm volatile("" : "+v"(m16));
+    VRQ_SCHED_FENCE();
 #pragma unroll
     for (int g = 7; g < 14; ++g) mmid |= (a[g] > hp ? 1u : 0u) << (g - 7);
+    asm volatile("" : "+v"(mmid));
+    VRQ_SCHED_FENCE();
 #pragma unroll
     for (int g = 14; g < 16; ++g) mhi |= (a[g] > hp ? 1u : 0u) << (g - 14);
     asm volatile("" : "+v"(mmid), "+v"(mhi));
@@ -482,27 +511,44 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
   // ntiles >= 1 (row0 < row1 above): no zero-trip path on which the seed and B-fragment reads issued
   // above would stay in flight into the epilogue (tests/isa_check.py follows every static path)
   __builtin_assume(ntiles > 0);
-  int st_prev = 0;  // VRQ_K1M_DMA_AHEAD: the previous iteration issued list stores
-  (void)st_prev;
-  for (int t = 0; t < ntiles; ++t) {
-#if VRQ_K1M_DMA_AHEAD
-    // the packed slot of tile t+1 is free once tile t+1 was unpacked (iteration t-1): tile t+5 goes there
-    // now, one iteration earlier than a refill of tile t's own slot (iteration 0 also issues tile 4 into
-    // tile 0's slot, unpacked in the prologue) -- two tile-times of DMA lead for the end-of-tile wait
-    const int st_now = nfl != 0 ? 1 : 0;  // wave-uniform: this iteration issues list stores
-    store_flushed();                       // previous tile's first 64 hits
-    if (t == 0 && NPK < ntiles) issue(NPK);
-    if (t + NPK + 1 < ntiles) issue(t + NPK + 1);
-#else
-    store_flushed();                       // previous tile's first 64 hits
-    if (t + NPK < ntiles) issue(t + NPK);  // into the slot of tile t (unpacked in iteration t-2)
+  // Loop-carried tile state, all scalar, advanced in the MFMA shadow of the tile's last group (gi = NG - 1)
+  // so that nothing is recomputed from t between the last MFMA of a tile and the first of the next:
+  //   ru0, ru1, ru2  the unpacked / row-popcount ring slots of tiles t, t+1, t+2 (a rotation: (t+3) % NUB = t % NUB)
+  //   pko         the packed ring offset of tile t, which is also tile t + NPK's
+  //   dsrc        the first byte of tile t + NPK in the corpus
+  // Tiles t < nsteady are steady: their refill t + NPK exists and is a whole tile, so they take the uniform
+  // DMA form from dsrc and the constant end-of-tile wait.  The others -- the chunk's last NPK tiles and the
+  // one that refills a partial last tile -- keep the general forms (issue, wait_tiles).
+  const int nwhole = strided ? ntiles : nrows / RT;
+  const int nsteady = nwhole > NPK ? nwhole - NPK : 0;
+  int ru0 = 0, ru1 = 1, ru2 = 2;
+  uint32_t pko = 0;
+  const int64_t dstep = tile_stride * 128;
+  const uint8_t* dsrc = codes + (row0 + (int64_t)NPK * tile_stride) * 128;
+#ifdef VRQ_K1M_STAMPS
+  // tile-boundary bracket (shader clock, low 32 bits): st_a after the last MFMA of a tile, st_b after the
+  // first MFMA of the next one has issued; st_bsum sums st_b - st_a over the workgroup's boundaries
+  uint32_t st_a = 0, st_b = 0, st_bsum = 0;
 #endif
-    const uint32_t blt = bl0 + (uint32_t)((t % NUB) * UBT);
-    const uint32_t bln = bl0 + (uint32_t)(((t + 1) % NUB) * UBT);
-    const uint32_t ubw = ub0 + (uint32_t)(((t + 2) % NUB) * UBT);
-    const uint32_t pks = pk0 + (uint32_t)(((t + 2) % NPK) * PKT);
+  for (int t = 0; t < ntiles; ++t) {
+    store_flushed(t);  // previous tile's first 64 hits (before the DMA: see the end-of-tile wait)
+    // tile t + NPK into the slot of tile t (unpacked in iteration t-2)
+    const bool steady = t < nsteady;
+    if (__builtin_expect(steady, 1)) {
+      if constexpr (!VRQ_K1M_DMA_SHADOW) {
+        issue_piece(dsrc, pko, std::integral_constant<int, 0>{});
+        issue_piece(dsrc, pko, std::integral_constant<int, 1>{});
+      }
+    } else if (t + NPK < ntiles) {
+      issue(t + NPK);
+    }
+    const uint32_t blt = bl0 + (uint32_t)(ru0 * UBT);
+    const uint32_t bln = bl0 + (uint32_t)(ru1 * UBT);
+    const uint32_t ubw = ub0 + (uint32_t)(ru2 * UBT);
+    const uint32_t pks = pk0 + (pko ^ (uint32_t)(2 * PKT));  // (t + 2) % NPK
+    static_assert(NPK == 4 && NUB == 3, "ring walks: slot of t + 2 by XOR, unpacked slots by rotation");
     int pcv[2];
-    const uint32_t pcra = pcr0 + (uint32_t)(((t % NUB) * RT + ri) * 4);
+    const uint32_t pcra = pcr0 + (uint32_t)((ru0 * RT + ri) * 4);
     lds_read32_imm<0>(pcv[0], pcra);
     lds_read32_imm<32 * 4>(pcv[1], pcra);
     v2i pv;
@@ -612,7 +658,7 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
             pc0 += __builtin_amdgcn_update_dpp(0, pc0, 0x4E, 0xf, 0xf, false);  // quad_perm [2,3,0,1]
             // every lane of the quad writes the same sum (no exec-masked branch: the counted waits
             // above assume this write is issued on every path)
-            lds_write32(pcr0 + (uint32_t)(((t + 2) % NUB) * RT * 4 + pr * 4), pc0);
+            lds_write32(pcr0 + (uint32_t)(ru2 * RT * 4 + pr * 4), pc0);
           }
         }
         if constexpr (SEED) {  // one 16-byte piece of M-block sm's seeds per slot, into its accumulator
@@ -632,6 +678,28 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
             block_dense(acc[nbk ^ 1][j - 2], j - 2, pcr_, lr);
           }
         }
+        // the steady refill DMA, one piece in each of two of group 0's empty slots (after the list stores
+        // at the top of the iteration, like the general form: the end-of-tile vmcnt accounting is the same)
+        if constexpr (VRQ_K1M_DMA_SHADOW && gi == 0 && (k == 0 || k == 2)) {
+          if (__builtin_expect(steady, 1)) issue_piece(dsrc, pko, std::integral_constant<int, k / 2>{});
+        }
+        if constexpr (gi == NG - 1) {
+          // the loop-carried tile state steps to tile t + 1 here, in the last group's otherwise empty slots
+          // (every address of this tile was formed from it before group 0, the popcount write in group 28)
+          if constexpr (k == 0) {
+            const int r = ru0;
+            ru0 = ru1;
+            ru1 = ru2;
+            ru2 = r;
+            asm volatile("" : "+s"(ru0), "+s"(ru1), "+s"(ru2));
+          } else if constexpr (k == 1) {
+            pko = (pko + (uint32_t)PKT) & (uint32_t)(NPK * PKT - 1);
+            asm volatile("" : "+s"(pko));
+          } else if constexpr (k == 2) {
+            dsrc += dstep;
+            asm volatile("" : "+s"(dsrc));
+          }
+        }
         if constexpr (k == 3) {
           // async flush, step 1 (after the last hit extraction of the tile, group 16 + 3 + MB): the
           // stage's first 64 entries; step 2, four groups (>= 4 LDS operations) later: list positions
@@ -645,7 +713,7 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
           if constexpr (!DENSE && j == 3 + MB) {
             // (anyhit is assigned by every n-block's test of M-block MB-1 before this point; which M-blocks
             // hold the candidates is worked out here, off the no-hit path)
-            if (anyhit) {
+            if (__builtin_expect(anyhit != 0, 0)) {
               const int pcr_ = nbk == 0 ? pcvP : pcv[0];
               const int lr = (nbk == 0 ? (t - 1) * RT + 32 : t * RT) + ri;
               const int pc = row_pc(pcr_, lr);
@@ -674,6 +742,9 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
         // point IR-level sinking moves them past the scheduling fences
         asm volatile("" : "+v"(acc[nbk][m]));
         VRQ_SCHED_FENCE();
+#ifdef VRQ_K1M_STAMPS
+        if constexpr (gi == 0 && m == 0) st_b = (uint32_t)__builtin_amdgcn_s_memtime();
+#endif
         if constexpr (MB == 4) {
           slot(std::integral_constant<int, m>{});
         } else {
@@ -685,39 +756,35 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
       VRQ_SCHED_FENCE();
     });
     pcvP = pcv[1];
+#ifdef VRQ_K1M_STAMPS
+    const uint32_t st_an = (uint32_t)__builtin_amdgcn_s_memtime();
+#endif
     // packed tile t+3 (unpacked next iteration) landed; this wave's LDS writes done
     {
 #ifndef VRQ_K1M_PROBE_NOVMWAIT  // timing-only probe builds (wrong results)
-#if VRQ_K1M_DMA_AHEAD
-      // issued after tile t+3's DMA: the k tiles after it and the list stores of this iteration and the
-      // previous one (each store instruction sits before its iteration's DMA; rare-path stores are drained)
-      const int last = t + NPK + 1 < ntiles ? t + NPK + 1 : ntiles - 1;
-      const int k = last - (t + 3), ns = st_prev + st_now;
-      if (k <= 0) wait_vm<0>();
-      else if (k == 1) {
-        if (ns == 0) wait_vm<GPW>(); else if (ns == 1) wait_vm<GPW + 1>(); else wait_vm<GPW + 2>();
+      // a steady tile: tile t + NPK was issued this iteration, one tile may stay in flight.  (vmcnt counts
+      // in issue order and the list stores sit before their iteration's DMA, so none is left behind it.)
+      if (__builtin_expect(steady, 1)) {
+        wait_vm<GPW>();
       } else {
-        if (ns == 0) wait_vm<2 * GPW>(); else if (ns == 1) wait_vm<2 * GPW + 1>(); else wait_vm<2 * GPW + 2>();
+        const int last = t + NPK < ntiles ? t + NPK : ntiles - 1;  // last tile issued so far
+        wait_tiles(last - (t + 3));
       }
-      st_prev = st_now;
-#else
-      const int last = t + NPK < ntiles ? t + NPK : ntiles - 1;  // last tile issued so far
-      wait_tiles(last - (t + 3));
-#endif
 #endif
     }
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fpos), "+v"(fe)::"memory");
-    fbase = row0 + (int64_t)(t - 1) * RT;
-    if (nst > 64) {  // rare: more than 64 hits in one tile
-      flush_from(64, fbase);
-      if (VRQ_K1M_DMA_AHEAD) wait_vm<0>();  // (drained: the next waits count only the per-tile stores)
-    }
+#ifdef VRQ_K1M_STAMPS
+    if (t > 0) st_bsum += st_b - st_a;  // (this tile's st_b, the previous tile's st_a: retired by the wait above)
+    st_a = st_an;
+#endif
+    if (__builtin_expect(nst > 64, 0))  // rare: more than 64 hits in one tile
+      flush_from(64, row0 + (int64_t)(t - 1) * RT);
     nst = 0;
 #ifndef VRQ_K1M_PROBE_NOBARRIER  // timing-only probe builds (wrong results)
     barrier_all();  // B_{t+1}
 #endif
   }
-  store_flushed();
+  store_flushed(ntiles);
   if (ntiles > 0) {  // n-block 1 of the last tile
     const int lr = (ntiles - 1) * RT + 32 + ri;
     const int pc = row_pc(pcvP, lr);
@@ -734,11 +801,12 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
   wait_lgkm0();
 #ifdef VRQ_K1M_STAMPS
   if (!DENSE && threadIdx.x == 0) {  // the MAIN pass gets the workspace head as `dv` in this build
-    uint64_t* stp = reinterpret_cast<uint64_t*>(dv) + 4 * (int64_t)L;
+    uint64_t* stp = reinterpret_cast<uint64_t*>(dv) + 8 * (int64_t)L;
     stp[0] = st_start;
     stp[1] = st_loop;
     stp[2] = __builtin_amdgcn_s_memrealtime();
     stp[3] = ((uint64_t)__builtin_amdgcn_s_getreg(63508) << 32) | (uint32_t)__builtin_amdgcn_s_getreg(63492);
+    stp[4] = ((uint64_t)(uint32_t)(ntiles - 1) << 32) | st_bsum;  // boundaries, their summed shader clocks
   }
 #endif
   if constexpr (DENSE)
