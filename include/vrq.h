@@ -465,6 +465,65 @@ int vrq_flat_ip_topk_dim(const float* xf, const int8_t* x8, const double* inv_sc
                          int32_t* out_count, int64_t* out_rows, double* out_scores, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Search with more than 1024 Phase-I candidates (additive to ABI version 1; every function above keeps
+ * its K <= 1024 contract and its VRQ_EUNSUPPORTED beyond it).  FAISS IndexBinaryFlat::search takes any k,
+ * and K = min(k * binary_oversample, ntotal) passes 1024 at k = 103 with the default oversample of 10.
+ * vrq_hamming_topk_large / vrq_search3_large / vrq_search2_large: the arguments, outputs and semantics of
+ *   vrq_hamming_topk / vrq_search3_dim / vrq_search2 -- Phase I = the K smallest rows by (dist, row), missing
+ *   slots INT32_MAX / -1 / NaN; scores from rescore_row[r] when given; Phase II a stable sort by score
+ *   descending over the Phase-I order (-0.0 ties +0.0); the three-phase call then takes the first
+ *   min(K3, candidates), scores Phase III, sorts stably by it descending and keeps the first k; out_count =
+ *   min(k, K, n), or min(K, n) with VRQ_SEARCH_PHASE1_ONLY -- with scores bit-identical to
+ *   vrq_rescore_binary_dim / vrq_rescore_int8_cosine_dim / vrq_rescore_dequant for the same (query, row).
+ *   Supported: every dim of vrq_dim_supported, 1 <= K <= VRQ_K_LARGE_MAX, 0 <= k <= VRQ_K_LARGE_MAX, any
+ *   K3 >= 0, 1 <= n < 2^32.  K <= 1024 is accepted on purpose: there every output equals the call above's,
+ *   bit for bit.  flags: vrq_search3_large 0 or VRQ_SEARCH_PHASE1_ONLY, vrq_search2_large 0; any other bit
+ *   returns VRQ_EUNSUPPORTED.  n, nq, K or k = 0 behave as in vrq_search3_dim_finish / vrq_search2 (counts 0,
+ *   padding written, nothing scanned).  Every argument and the workspace size are checked before anything
+ *   is launched.  Not sharded: vrq_shard_search* and vrq_merge_shards* keep K <= 1024.
+ * Phase I is the counting scan K1h: a Hamming distance is an integer in [0, dim], so per-(query, chunk)
+ *   histograms give the threshold distance T with count(dist < T) < K <= count(dist <= T), and a second
+ *   pass writes every row below T and the first K - count(dist < T) rows at T, in row order.  The finish
+ *   sorts the K keys and the (score, rank) pairs in LDS; 8192 pairs take 96 KiB, hence VRQ_K_LARGE_MAX.
+ * vrq_scan_large_plan (host-only; tests and tools): info i64[8] = rows per chunk (a multiple of 64), chunks,
+ *   queries per workgroup of the count kernel, rows of the bounding prefix (always 0: the count adds every
+ *   distance; a bound from a row prefix was measured and bought nothing), workspace offset of the
+ *   per-(query, chunk) counts (histograms u32 [min(nq, 512)][chunks][dim + 1], then the chunk prefixes), of the per-query T / count(dist < T) pairs (i32 [nq][2]), of the K-lists (u64 dist << 40 | row,
+ *   [nq][K], all-ones padded), and the workspace bytes = the three *_large_workspace_size (pure functions of
+ *   the shape; 0 for an unsupported one).  VRQ_EINVAL for an empty shape or a null info, VRQ_EUNSUPPORTED as
+ *   the search calls.
+ * ------------------------------------------------------------------------- */
+#define VRQ_K_LARGE_MAX 8192
+/* vrq_scan_large: the Phase-I scan the three calls above start with, alone or a subset of its stages (for
+ * callers that time them): `stages` = 0 (all) or a mask of VRQ_LARGE_STAGE_*; issuing COUNT, THRESHOLD, EMIT
+ * in that order on one stream and workspace is exactly the full scan.  Leaves the K-lists at the plan's
+ * offset (row order within the dist < T part and within the dist == T part, all-ones padded).  Shapes,
+ * return codes and the workspace as the search calls; any other bit returns VRQ_EUNSUPPORTED; n, nq or
+ * K = 0 returns VRQ_OK and does nothing. */
+#define VRQ_LARGE_STAGE_COUNT 1      /* histograms of the distances per (query, chunk) over every row */
+#define VRQ_LARGE_STAGE_THRESHOLD 2  /* per query: T, count(dist < T), the chunk prefixes, the list padding */
+#define VRQ_LARGE_STAGE_EMIT 4       /* second pass: the rows of the K-lists at their final positions */
+int vrq_scan_large(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq, int32_t K,
+                   int32_t stages, void* workspace, size_t workspace_bytes, void* stream);
+size_t vrq_hamming_topk_large_workspace_size(int64_t n, int32_t code_bytes, int32_t nq, int32_t k);
+int vrq_hamming_topk_large(const uint8_t* codes, int64_t n, int32_t code_bytes, int64_t row_offset,
+                           const uint8_t* queries, int32_t nq, int32_t k, int32_t* out_dist,
+                           int64_t* out_rows, void* workspace, size_t workspace_bytes, void* stream);
+size_t vrq_search3_large_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K);
+int vrq_search3_large(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
+                      int64_t n, int32_t dim, int64_t row_offset, const float* qf, const uint8_t* qb, int32_t nq,
+                      int32_t k, int32_t K, int32_t K3, int32_t flags, int32_t* out_count, int64_t* out_rows,
+                      int32_t* out_dist, double* out_binary, double* out_cosine, void* workspace,
+                      size_t workspace_bytes, void* stream);
+size_t vrq_search2_large_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K);
+int vrq_search2_large(int32_t mode, const uint8_t* codes, const void* q, const double* minmax, double limit,
+                      const int64_t* rescore_row, int64_t n, int32_t dim, int64_t row_offset, const float* qf,
+                      const uint8_t* qb, int32_t nq, int32_t k, int32_t K, int32_t flags, int32_t* out_count,
+                      int64_t* out_rows, int32_t* out_dist, double* out_score, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int vrq_scan_large_plan(int64_t n, int32_t dim, int32_t nq, int32_t K, int64_t* info);
+
 #ifdef __cplusplus
 }
 #endif

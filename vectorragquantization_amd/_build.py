@@ -20,7 +20,8 @@ LIB = os.path.join(PKG, "libvrq.so")
 PROBE_LIB = os.path.join(PKG, "libvrq_probe.so")
 OBJDIR = os.path.join(PKG, "_obj")
 SOURCES = ["hamming_scan.hip", "hamming_mfma.hip", "select_rescore.hip", "encode.hip", "gemm_topk.hip", "dequant.hip",
-           "search_dim.hip", "exhaustive_dim.hip", "hamming_mfma_dim.hip", "mfma_threshold.hip", "scan_route.hip"]
+           "search_dim.hip", "exhaustive_dim.hip", "hamming_mfma_dim.hip", "mfma_threshold.hip", "scan_route.hip",
+           "hamming_count.hip"]
 # sources without device code: their objects carry no gfx950 bundle, so they are kept apart (_obj/host/) from
 # the objects whose disassembly the tests read
 HOST_ONLY = {"scan_route.hip"}

@@ -37,6 +37,11 @@ VRQ_GEMM_SCAN_EXACT = 256  # _dim entry points: the exact exhaustive scan (K5d) 
 VRQ_RESCORE_F32 = 16  # vrq_rescore_dequant: compare_float32 rows
 VRQ_RESCORE_SIGNED_BINARY = 17  # vrq_rescore_dequant / vrq_search2: packed sign codes as +-1 rows
 VRQ_ENC_SIGNED_BINARY = 7
+VRQ_K_LARGE_MAX = 8192  # the *_large entry points (K1h, the counting scan); 1024 for every other search
+VRQ_K_MAX = 1024
+VRQ_LARGE_STAGE_COUNT = 1
+VRQ_LARGE_STAGE_THRESHOLD = 2
+VRQ_LARGE_STAGE_EMIT = 4
 VRQ_SCAN_KIND_VALU = 0
 VRQ_SCAN_KIND_MFMA = 1
 VRQ_SCAN_PLAN_K1RD = 3  # info[0] of vrq_scan_plan at the dims other than 1024
@@ -96,6 +101,16 @@ SIGNATURES = {
                               _P, _P, _P, _P, _P, _SZ, _P]),
     "vrq_search2_finish": (C.c_int, [_I32, _P, _P, _P, _D, _P, _I64, _I32, _I64, _P, _I32, _I32, _I32, _I32,
                                      _P, _P, _P, _P, _P, _SZ, _P]),
+    "vrq_hamming_topk_large_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
+    "vrq_hamming_topk_large": (C.c_int, [_P, _I64, _I32, _I64, _P, _I32, _I32, _P, _P, _P, _SZ, _P]),
+    "vrq_search3_large_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
+    "vrq_search3_large": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32,
+                                    _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "vrq_search2_large_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
+    "vrq_search2_large": (C.c_int, [_I32, _P, _P, _P, _D, _P, _I64, _I32, _I64, _P, _P, _I32, _I32, _I32, _I32,
+                                    _P, _P, _P, _P, _P, _SZ, _P]),
+    "vrq_scan_large_plan": (C.c_int, [_I64, _I32, _I32, _I32, _P]),
+    "vrq_scan_large": (C.c_int, [_P, _I64, _I32, _P, _I32, _I32, _I32, _P, _SZ, _P]),
     "vrq_gemm_topk_workspace_size": (_SZ, [_I32, _I64, _I32, _I32, _I32]),
     "vrq_gemm_topk_pieces": (C.c_int, []),
     "vrq_gemm_topk_plan": (C.c_int, [_I32, _I64, _I32, _I32, _I32, _P]),
@@ -193,6 +208,15 @@ def gemm_topk_dim_workspace(lib, mode: int, n: int, dim: int, nq: int, k: int, f
             return 0
         need = max(need, int(info[5]))
     return need
+
+
+def large_k(K: int, what: str) -> bool:
+    """Whether a search with K Phase-I candidates takes the *_large call (K1h, 1024 < K <= VRQ_K_LARGE_MAX);
+    raises for a K beyond that."""
+    if K > VRQ_K_LARGE_MAX:
+        raise VrqNativeError(f"{what}: K = {K} Phase-I candidates (k * binary_oversample) exceed the limit "
+                             f"of {VRQ_K_LARGE_MAX}")
+    return K > VRQ_K_MAX
 
 
 def check(rc: int, what: str) -> None:

@@ -891,6 +891,221 @@ static int launch_select2(hipStream_t s, int nq, const void* ws, const Phase1Rou
   return VRQ_OK;
 }
 
+// ---------------------------------------------------------------------------
+// The large finish (vrq_*_large, K up to VRQ_K_LARGE_MAX): the K-lists the counting scan K1h left hold the
+// exact top-K of each query, not yet in distance order.  The per-query state no longer fits LDS next to the
+// sort, so scores live in the workspace and the finish is a chain of launches on it:
+//   large_sort_kernel    sorts the K keys ascending (= FAISS (dist, row) order) in LDS, counts the candidates
+//                        (Phase-I-only calls write their outputs here)
+//   large_score_kernel   one wave per (query, candidate) over the whole grid: the stand-alone rescoring's
+//                        Scorer1024 / ScorerDim / dequant_dot, so scores are bit-identical to
+//                        vrq_rescore_*_dim / vrq_rescore_dequant (and to vrq_search3_dim / vrq_search2)
+//   large_order_kernel   sorts the pairs (descending-score image, position) lexicographically in LDS -- the
+//                        stable order -- and either keeps the order of the first K3 (three-phase, after Phase
+//                        II) or writes the first k outputs
+// 8192 pairs of (u64, i32) take 96 KiB of LDS: that is where VRQ_K_LARGE_MAX comes from.
+// ---------------------------------------------------------------------------
+constexpr int LARGE_THREADS = 1024;
+
+template <int CAP>
+__global__ __launch_bounds__(LARGE_THREADS) void large_sort_kernel(uint64_t* __restrict__ lists, int K,
+                                                                   int32_t* __restrict__ kp, bool write_out,
+                                                                   int64_t row_offset, int32_t* __restrict__ out_count,
+                                                                   int64_t* __restrict__ out_rows,
+                                                                   int32_t* __restrict__ out_dist) {
+  __shared__ uint64_t keys[CAP];
+  __shared__ int32_t cnt;
+  const int q = blockIdx.x, tid = threadIdx.x;
+  uint64_t* list = lists + (int64_t)q * K;
+  const int np2 = next_pow2(K);
+  for (int i = tid; i < np2; i += LARGE_THREADS) keys[i] = i < K ? list[i] : KEY_NONE;
+  if (tid == 0) cnt = 0;
+  block_bitonic_sort_u64(keys, np2);
+  for (int i = tid; i < K; i += LARGE_THREADS)  // the valid keys are a prefix: KEY_NONE is the largest key
+    if (keys[i] != KEY_NONE && (i + 1 == K || keys[i + 1] == KEY_NONE)) cnt = i + 1;
+  __syncthreads();
+  const int Kp = cnt;
+  for (int i = tid; i < K; i += LARGE_THREADS) {
+    const uint64_t key = keys[i];
+    list[i] = key;
+    if (write_out) {
+      const int64_t o = (int64_t)q * K + i;
+      out_rows[o] = i < Kp ? (int64_t)(key & ROW_MASK) + row_offset : -1;
+      out_dist[o] = i < Kp ? (int32_t)(key >> KEY_ROW_BITS) : DIST_NONE;
+    }
+  }
+  if (tid == 0) {
+    kp[q] = Kp;
+    if (write_out && out_count) out_count[q] = Kp;
+  }
+}
+
+// what a large_score_kernel launch scores: Phase II (binary), Phase III (cosine) or the two-phase score
+struct LargeScoreArgs {
+  int which;  // 0 binary, 1 int8 cosine, 2 dequant_dot of `mode`
+  const uint64_t* lists;
+  const int32_t* kp;
+  const int32_t* ord;  // position -> Phase-I rank (Phase III: the Phase-II order), or null (identity)
+  int K, limit;        // positions [0, min(kp, limit)) are scored
+  const int64_t* remap;
+  const uint8_t* codes;
+  const int8_t* x8;
+  const double* norms;
+  int mode;
+  const void* dq;
+  const double* minmax;
+  double dlimit;
+  double* out;  // [nq][K] by position
+};
+
+template <class Scorer>
+__global__ __launch_bounds__(256) void large_score_kernel(const float* __restrict__ qf, int dim, int bpq,
+                                                          LargeScoreArgs a) {
+  const int q = blockIdx.x / bpq;
+  const int i = (blockIdx.x - q * bpq) * (256 / WAVE) + threadIdx.x / WAVE;  // wave-uniform
+  const int kpq = a.kp[q];
+  const int m = kpq < a.limit ? kpq : a.limit;
+  if (i >= m) return;
+  const int64_t base = (int64_t)q * a.K;
+  const int r = a.ord ? a.ord[base + i] : i;
+  int64_t row = (int64_t)(a.lists[base + r] & ROW_MASK);
+  if (a.remap) row = a.remap[row];
+  double v;
+  if (a.which == 2) {
+    v = dequant_dot(a.mode, qf + (int64_t)q * dim, dim, a.dq, a.minmax, a.dlimit, row);
+  } else {
+    const Scorer sc(qf, q, dim);
+    v = a.which == 0 ? sc.binary(a.codes, row) : sc.cosine(a.x8, row, a.norms[row]);
+  }
+  if (lane_id() == 0) a.out[base + i] = v;
+}
+
+struct LargeOrderArgs {
+  const double* sc;    // scores to sort, [nq][K] by position
+  const int32_t* kp;
+  int K, limit;        // the first min(kp, limit) positions take part
+  int32_t* ord_out;    // non-null: keep the order of the first `keep` (position -> Phase-I rank) and stop
+  int keep;
+  // the final write (ord_out == null)
+  const int32_t* ord;  // sorted position -> Phase-I rank (three-phase), or null (the position is the rank)
+  const uint64_t* lists;
+  const double* s2;    // [nq][K] by Phase-I rank
+  int64_t row_offset;
+  int k;
+  int32_t* out_count;
+  int64_t* out_rows;
+  int32_t* out_dist;
+  double* out_s2;
+  double* out_s3;      // three-phase only: a.sc of the position
+};
+
+template <int CAP>
+__global__ __launch_bounds__(LARGE_THREADS) void large_order_kernel(LargeOrderArgs a) {
+  __shared__ uint64_t skey[CAP];
+  __shared__ int32_t sidx[CAP];
+  const int q = blockIdx.x, tid = threadIdx.x;
+  const int64_t base = (int64_t)q * a.K;
+  const int kpq = a.kp[q];
+  const int m = kpq < a.limit ? kpq : a.limit;
+  const int np2 = next_pow2(m > 1 ? m : 1);
+  for (int i = tid; i < np2; i += LARGE_THREADS) {
+    skey[i] = i < m ? desc_key_f64(a.sc[base + i]) : KEY_NONE;
+    sidx[i] = i < m ? i : 0x7fffffff;
+  }
+  // bitonic on (skey, sidx) lexicographic: the stable order (stable_desc_order)
+  for (int size = 2; size <= np2; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      __syncthreads();
+      for (int i = tid; i < (np2 >> 1); i += LARGE_THREADS) {
+        const int lo = ((i / stride) * stride * 2) + (i % stride);
+        const int hi = lo + stride;
+        const bool up = (lo & size) == 0;
+        const uint64_t ka = skey[lo], kb = skey[hi];
+        const int ia = sidx[lo], ib = sidx[hi];
+        const bool gt = (ka > kb) || (ka == kb && ia > ib);
+        if (gt == up) {
+          skey[lo] = kb;
+          skey[hi] = ka;
+          sidx[lo] = ib;
+          sidx[hi] = ia;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (a.ord_out) {
+    const int keep = a.keep < m ? a.keep : m;
+    for (int i = tid; i < keep; i += LARGE_THREADS) a.ord_out[base + i] = sidx[i];
+    return;
+  }
+  const int mo = a.k < m ? a.k : m;
+  for (int i = tid; i < a.k; i += LARGE_THREADS) {
+    const int64_t o = (int64_t)q * a.k + i;
+    if (i < mo) {
+      const int j = sidx[i];
+      const int r = a.ord ? a.ord[base + j] : j;
+      const uint64_t key = a.lists[base + r];
+      a.out_rows[o] = (int64_t)(key & ROW_MASK) + a.row_offset;
+      a.out_dist[o] = (int32_t)(key >> KEY_ROW_BITS);
+      a.out_s2[o] = a.s2[base + r];
+      if (a.out_s3) a.out_s3[o] = a.sc[base + j];
+    } else {
+      a.out_rows[o] = -1;
+      a.out_dist[o] = DIST_NONE;
+      a.out_s2[o] = __builtin_nan("");
+      if (a.out_s3) a.out_s3[o] = __builtin_nan("");
+    }
+  }
+  if (tid == 0) a.out_count[q] = mo;
+}
+
+static int large_sort_launch(hipStream_t s, int nq, uint64_t* lists, int K, int32_t* kp, bool write_out,
+                             int64_t row_offset, int32_t* out_count, int64_t* out_rows, int32_t* out_dist) {
+  const dim3 grid(nq), block(LARGE_THREADS);
+  if (K <= 1024)
+    hipLaunchKernelGGL(large_sort_kernel<1024>, grid, block, 0, s, lists, K, kp, write_out, row_offset, out_count,
+                       out_rows, out_dist);
+  else if (K <= 2048)
+    hipLaunchKernelGGL(large_sort_kernel<2048>, grid, block, 0, s, lists, K, kp, write_out, row_offset, out_count,
+                       out_rows, out_dist);
+  else if (K <= 4096)
+    hipLaunchKernelGGL(large_sort_kernel<4096>, grid, block, 0, s, lists, K, kp, write_out, row_offset, out_count,
+                       out_rows, out_dist);
+  else
+    hipLaunchKernelGGL(large_sort_kernel<VRQ_K_LARGE_MAX>, grid, block, 0, s, lists, K, kp, write_out, row_offset,
+                       out_count, out_rows, out_dist);
+  VRQ_LAUNCH_CHECK();
+  return VRQ_OK;
+}
+
+static int large_score_launch(hipStream_t s, int nq, const float* qf, int dim, const LargeScoreArgs& a) {
+  const int m = a.K < a.limit ? a.K : a.limit;
+  if (m < 1) return VRQ_OK;
+  const int bpq = (m + 256 / WAVE - 1) / (256 / WAVE);
+  const dim3 grid((unsigned)((int64_t)nq * bpq));
+  if (dim == DIM)
+    hipLaunchKernelGGL(large_score_kernel<Scorer1024>, grid, dim3(256), 0, s, qf, dim, bpq, a);
+  else
+    hipLaunchKernelGGL(large_score_kernel<ScorerDim>, grid, dim3(256), 0, s, qf, dim, bpq, a);
+  VRQ_LAUNCH_CHECK();
+  return VRQ_OK;
+}
+
+static int large_order_launch(hipStream_t s, int nq, const LargeOrderArgs& a) {
+  const int m = a.K < a.limit ? a.K : a.limit;  // entries sorted at the most
+  const dim3 grid(nq), block(LARGE_THREADS);
+  if (m <= 1024)
+    hipLaunchKernelGGL(large_order_kernel<1024>, grid, block, 0, s, a);
+  else if (m <= 2048)
+    hipLaunchKernelGGL(large_order_kernel<2048>, grid, block, 0, s, a);
+  else if (m <= 4096)
+    hipLaunchKernelGGL(large_order_kernel<4096>, grid, block, 0, s, a);
+  else
+    hipLaunchKernelGGL(large_order_kernel<VRQ_K_LARGE_MAX>, grid, block, 0, s, a);
+  VRQ_LAUNCH_CHECK();
+  return VRQ_OK;
+}
+
 }  // namespace vrq
 
 using namespace vrq;
@@ -1318,6 +1533,213 @@ int vrq_shard_search2(int32_t mode, const uint8_t* codes, const void* q, const d
   const Finish2Args fa{mode, q, minmax, limit, rescore_row, row_offset, K, out_count, out_rows, out_dist, out_score,
                        true};
   return launch_select2(s, nq, workspace, r, K, dim, qf, fa);
+}
+
+// ---- K up to VRQ_K_LARGE_MAX: the counting scan K1h (hamming_count.hip) + the large finish ----
+int vrq_scan_large_plan(int64_t n, int32_t dim, int32_t nq, int32_t K, int64_t* info) {
+  if (!info || n < 1 || nq < 1 || K < 1) return VRQ_EINVAL;
+  if (!vrq_dim_supported(dim)) return VRQ_EUNSUPPORTED;
+  LargePlan p;
+  const int rc = large_plan(n, dim / 8, nq, K, &p);
+  if (rc != VRQ_OK) return rc;
+  info[0] = p.chunk_rows;
+  info[1] = p.nchunks;
+  info[2] = p.qg;
+  info[3] = 0;  // (no bounding prefix: every distance is counted)
+  info[4] = (int64_t)p.off_hist;
+  info[5] = (int64_t)p.off_tc;
+  info[6] = (int64_t)p.off_lists;
+  info[7] = (int64_t)p.bytes;
+  return VRQ_OK;
+}
+
+size_t vrq_search3_large_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K) {
+  LargePlan p;
+  return vrq_dim_supported(dim) && large_plan(n, dim / 8, nq, K, &p) == VRQ_OK ? p.bytes : 0;
+}
+
+size_t vrq_search2_large_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K) {
+  return vrq_search3_large_workspace_size(n, dim, nq, K);
+}
+
+size_t vrq_hamming_topk_large_workspace_size(int64_t n, int32_t code_bytes, int32_t nq, int32_t k) {
+  return code_bytes > 0 && code_bytes <= 256 ? vrq_search3_large_workspace_size(n, code_bytes * 8, nq, k) : 0;
+}
+
+// the plan of a call that scans (n, nq, K >= 1) and the workspace check, before anything is launched
+static int large_plan_checked(int64_t n, int cb, int nq, int K, size_t workspace_bytes, LargePlan* p) {
+  const int rc = large_plan(n, cb, nq, K, p);
+  if (rc != VRQ_OK) return rc;
+  return workspace_bytes < p->bytes ? VRQ_EWORKSPACE : VRQ_OK;
+}
+
+int vrq_scan_large(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq, int32_t K,
+                   int32_t stages, void* workspace, size_t workspace_bytes, void* stream) {
+  VRQ_CHECK_ARG(n >= 0 && nq >= 0 && K >= 0);
+  if (!vrq_dim_supported(dim) || K > VRQ_K_LARGE_MAX) return VRQ_EUNSUPPORTED;
+  if (stages & ~kLargeStageAll) return VRQ_EUNSUPPORTED;
+  if (nq == 0 || n == 0 || K == 0) return VRQ_OK;
+  VRQ_CHECK_ARG(codes && qb && workspace);
+  LargePlan p;
+  const int rc = large_plan_checked(n, dim / 8, nq, K, workspace_bytes, &p);
+  if (rc != VRQ_OK) return rc;
+  return large_scan_launch(p, codes, n, dim / 8, qb, nq, K, (uint8_t*)workspace, (hipStream_t)stream, stages);
+}
+
+int vrq_hamming_topk_large(const uint8_t* codes, int64_t n, int32_t code_bytes, int64_t row_offset,
+                           const uint8_t* queries, int32_t nq, int32_t k, int32_t* out_dist, int64_t* out_rows,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+  VRQ_CHECK_ARG(n >= 0 && nq >= 0 && k >= 0 && out_dist && out_rows);
+  if (code_bytes <= 0 || code_bytes > 256 || !vrq_dim_supported(code_bytes * 8) || k > VRQ_K_LARGE_MAX)
+    return VRQ_EUNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  if (nq == 0) return VRQ_OK;
+  if (n == 0 || k == 0) return fill_empty(nq, k, nullptr, out_rows, out_dist, nullptr, nullptr, s);
+  VRQ_CHECK_ARG(codes && queries && workspace);
+  LargePlan p;
+  int rc = large_plan_checked(n, code_bytes, nq, k, workspace_bytes, &p);
+  if (rc != VRQ_OK) return rc;
+  uint8_t* ws = (uint8_t*)workspace;
+  rc = large_scan_launch(p, codes, n, code_bytes, queries, nq, k, ws, s, 0);
+  if (rc != VRQ_OK) return rc;
+  return large_sort_launch(s, nq, (uint64_t*)(ws + p.off_lists), k, (int32_t*)(ws + p.off_kp), true, row_offset,
+                           nullptr, out_rows, out_dist);
+}
+
+int vrq_search3_large(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
+                      int64_t n, int32_t dim, int64_t row_offset, const float* qf, const uint8_t* qb, int32_t nq,
+                      int32_t k, int32_t K, int32_t K3, int32_t flags, int32_t* out_count, int64_t* out_rows,
+                      int32_t* out_dist, double* out_binary, double* out_cosine, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+  VRQ_CHECK_ARG(n >= 0 && nq >= 0 && k >= 0 && K >= 0 && K3 >= 0);
+  VRQ_CHECK_ARG(out_count && out_rows && out_dist);
+  if (!vrq_dim_supported(dim) || K > VRQ_K_LARGE_MAX || k > VRQ_K_LARGE_MAX) return VRQ_EUNSUPPORTED;
+  if (flags & ~VRQ_SEARCH_PHASE1_ONLY) return VRQ_EUNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  const bool p1 = flags & VRQ_SEARCH_PHASE1_ONLY;
+  const int kout = p1 ? K : k;
+  if (nq == 0) return VRQ_OK;
+  if (!p1) VRQ_CHECK_ARG(out_binary && out_cosine);
+  if (n == 0 || K == 0 || (!p1 && k == 0))
+    return fill_empty(nq, kout, out_count, out_rows, out_dist, out_binary, out_cosine, s);
+  VRQ_CHECK_ARG(codes && qb && workspace);
+  if (!p1) VRQ_CHECK_ARG(qf && x8 && norms);
+  LargePlan p;
+  int rc = large_plan_checked(n, dim / 8, nq, K, workspace_bytes, &p);
+  if (rc != VRQ_OK) return rc;
+  uint8_t* ws = (uint8_t*)workspace;
+  uint64_t* lists = (uint64_t*)(ws + p.off_lists);
+  int32_t* kp = (int32_t*)(ws + p.off_kp);
+  int32_t* ord = (int32_t*)(ws + p.off_ord);
+  double* s2 = (double*)(ws + p.off_s2);
+  double* s3 = (double*)(ws + p.off_s3);
+  rc = large_scan_launch(p, codes, n, dim / 8, qb, nq, K, ws, s, 0);
+  if (rc != VRQ_OK) return rc;
+  rc = large_sort_launch(s, nq, lists, K, kp, p1, row_offset, out_count, out_rows, out_dist);
+  if (rc != VRQ_OK || p1) return rc;
+  // Phase II of every candidate, its stable order, the first K3
+  LargeScoreArgs sa{};
+  sa.which = 0;
+  sa.lists = lists;
+  sa.kp = kp;
+  sa.K = K;
+  sa.limit = K;
+  sa.remap = rescore_row;
+  sa.codes = codes;
+  sa.x8 = x8;
+  sa.norms = norms;
+  sa.out = s2;
+  rc = large_score_launch(s, nq, qf, dim, sa);
+  if (rc != VRQ_OK) return rc;
+  LargeOrderArgs oa{};
+  oa.sc = s2;
+  oa.kp = kp;
+  oa.K = K;
+  oa.limit = K;
+  oa.ord_out = ord;
+  oa.keep = K3;
+  rc = large_order_launch(s, nq, oa);
+  if (rc != VRQ_OK) return rc;
+  // Phase III of those, by position in the Phase-II order; its stable order, the first k
+  sa.which = 1;
+  sa.ord = ord;
+  sa.limit = K3;
+  sa.out = s3;
+  rc = large_score_launch(s, nq, qf, dim, sa);
+  if (rc != VRQ_OK) return rc;
+  LargeOrderArgs fa{};
+  fa.sc = s3;
+  fa.kp = kp;
+  fa.K = K;
+  fa.limit = K3;
+  fa.ord = ord;
+  fa.lists = lists;
+  fa.s2 = s2;
+  fa.row_offset = row_offset;
+  fa.k = k;
+  fa.out_count = out_count;
+  fa.out_rows = out_rows;
+  fa.out_dist = out_dist;
+  fa.out_s2 = out_binary;
+  fa.out_s3 = out_cosine;
+  return large_order_launch(s, nq, fa);
+}
+
+int vrq_search2_large(int32_t mode, const uint8_t* codes, const void* q, const double* minmax, double limit,
+                      const int64_t* rescore_row, int64_t n, int32_t dim, int64_t row_offset, const float* qf,
+                      const uint8_t* qb, int32_t nq, int32_t k, int32_t K, int32_t flags, int32_t* out_count,
+                      int64_t* out_rows, int32_t* out_dist, double* out_score, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+  VRQ_CHECK_ARG(search2_mode_ok(mode));
+  VRQ_CHECK_ARG(n >= 0 && nq >= 0 && k >= 0 && K >= 0);
+  VRQ_CHECK_ARG(out_count && out_rows && out_dist && out_score);
+  if (!vrq_dim_supported(dim) || K > VRQ_K_LARGE_MAX || k > VRQ_K_LARGE_MAX) return VRQ_EUNSUPPORTED;
+  if (mode == VRQ_RESCORE_SIGNED_BINARY && dim % 128 != 0) return VRQ_EUNSUPPORTED;
+  if (flags) return VRQ_EUNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  if (nq == 0) return VRQ_OK;
+  if (n == 0 || K == 0 || k == 0) return fill_empty(nq, k, out_count, out_rows, out_dist, out_score, nullptr, s);
+  VRQ_CHECK_ARG(codes && qb && workspace && qf && q);
+  if (mode == VRQ_ENC_INT8_LOCAL || mode == VRQ_ENC_INT4_LOCAL) VRQ_CHECK_ARG(minmax);
+  LargePlan p;
+  int rc = large_plan_checked(n, dim / 8, nq, K, workspace_bytes, &p);
+  if (rc != VRQ_OK) return rc;
+  uint8_t* ws = (uint8_t*)workspace;
+  uint64_t* lists = (uint64_t*)(ws + p.off_lists);
+  int32_t* kp = (int32_t*)(ws + p.off_kp);
+  double* s2 = (double*)(ws + p.off_s2);
+  rc = large_scan_launch(p, codes, n, dim / 8, qb, nq, K, ws, s, 0);
+  if (rc != VRQ_OK) return rc;
+  rc = large_sort_launch(s, nq, lists, K, kp, false, 0, nullptr, nullptr, nullptr);
+  if (rc != VRQ_OK) return rc;
+  LargeScoreArgs sa{};
+  sa.which = 2;
+  sa.lists = lists;
+  sa.kp = kp;
+  sa.K = K;
+  sa.limit = K;
+  sa.remap = rescore_row;
+  sa.mode = mode;
+  sa.dq = q;
+  sa.minmax = minmax;
+  sa.dlimit = limit;
+  sa.out = s2;
+  rc = large_score_launch(s, nq, qf, dim, sa);
+  if (rc != VRQ_OK) return rc;
+  LargeOrderArgs fa{};
+  fa.sc = s2;
+  fa.kp = kp;
+  fa.K = K;
+  fa.limit = K;
+  fa.lists = lists;
+  fa.s2 = s2;
+  fa.row_offset = row_offset;
+  fa.k = k;
+  fa.out_count = out_count;
+  fa.out_rows = out_rows;
+  fa.out_dist = out_dist;
+  fa.out_s2 = out_score;
+  return large_order_launch(s, nq, fa);
 }
 
 }  // extern "C"

@@ -144,4 +144,32 @@ int phase1_launch(const Phase1Route& r, const uint8_t* codes, int64_t n, int cb,
 // the largest `bytes` of the routes any flags can select (a pure function of the shape); 0: no route
 size_t phase1_workspace_bytes(int64_t n, int cb, int nq, int K);
 
+// ---- K1h: the counting scan for K up to VRQ_K_LARGE_MAX (hamming_count.hip).  Distances are integers in
+// [0, dim]: per-(query, chunk) histograms -> per-query threshold T and c_lt = count(dist < T) -> a second
+// pass that writes every row below T and the first K - c_lt rows at T, in row order, at positions that
+// the chunk prefixes fix.  The vrq_*_large entry points run it, then the large finish (select_rescore.hip). ----
+constexpr int kLargeMaxChunks = 1024;          // chunk prefixes of the threshold stage live in LDS
+constexpr int64_t kLargeHistBytes = 64 << 20;  // cap of the per-chunk histograms of one query batch
+constexpr int kLargeQueryBatch = 512;          // queries per pass of the scan (bounds the histograms)
+
+struct LargePlan {
+  int qg;               // queries per workgroup of the count kernel
+  int nw;               // waves per workgroup of the count kernel
+  int64_t chunk_rows;   // multiple of 64, <= 2^30
+  int nchunks;
+  // workspace: histograms u32 [qb][chunks][dim + 1] and chunk prefixes i32 [nq][nchunks][4] (the counts
+  // region), T / c_lt pairs i32 [nq][2], K-lists u64 [nq][K], then the
+  // finish's scratch: s2 f64 [nq][K], s3 f64 [nq][K], Phase-II order i32 [nq][K], candidates i32 [nq]
+  size_t off_hist, off_prefix, off_tc, off_lists, off_s2, off_s3, off_ord, off_kp, bytes;
+};
+// VRQ_EINVAL for an empty shape, VRQ_EUNSUPPORTED for a code size or K outside the path
+int large_plan(int64_t n, int cb, int nq, int K, LargePlan* p);
+// the whole scan (count, threshold, emit): leaves the K-lists at off_lists, KEY_NONE padded, the
+// dist < T part and the dist == T part each in row order.  stages: a mask of kLargeStage* (none = all).
+constexpr int kLargeStageCount = VRQ_LARGE_STAGE_COUNT, kLargeStageThreshold = VRQ_LARGE_STAGE_THRESHOLD,
+              kLargeStageEmit = VRQ_LARGE_STAGE_EMIT,
+              kLargeStageAll = kLargeStageCount | kLargeStageThreshold | kLargeStageEmit;
+int large_scan_launch(const LargePlan& p, const uint8_t* codes, int64_t n, int cb, const uint8_t* q, int nq, int K,
+                      uint8_t* ws, hipStream_t s, int stages);
+
 }  // namespace vrq

@@ -108,10 +108,20 @@ def gemm_topk(mode: str, qf: torch.Tensor, k: int, codes: torch.Tensor | None = 
     return cnt, rows, scores
 
 
+def search3_call(K: int, flags: int = 0) -> str:
+    """The entry point ``search3`` takes for K Phase-I candidates: ``vrq_search3_large`` (the counting scan
+    K1h) for 1024 < K <= ``VRQ_K_LARGE_MAX`` outside the sharded mode, else ``vrq_search3_dim``; its workspace
+    size is ``<name>_workspace_size``."""
+    if not flags & N.VRQ_SEARCH_SHARD and N.large_k(K, "search3"):
+        return "vrq_search3_large"
+    return "vrq_search3_dim"
+
+
 def search3(codes: torch.Tensor, x8: torch.Tensor, norms: torch.Tensor, qf: torch.Tensor, qb: torch.Tensor,
             k: int, K: int, K3: int, flags: int = 0, row_offset: int = 0, rescore_row: torch.Tensor | None = None,
             workspace: torch.Tensor | None = None):
-    """Thin wrapper of ``vrq_search3``; returns (count, rows, dist, s2, s3) device tensors."""
+    """Thin wrapper of ``vrq_search3``; returns (count, rows, dist, s2, s3) device tensors.  More than 1024
+    Phase-I candidates (up to ``VRQ_K_LARGE_MAX``) take ``vrq_search3_large`` (not with ``VRQ_SEARCH_SHARD``)."""
     dev = qf.device
     nq = qf.shape[0]
     n = codes.shape[0]
@@ -128,14 +138,15 @@ def search3(codes: torch.Tensor, x8: torch.Tensor, norms: torch.Tensor, qf: torc
     if rescore_row is not None and rescore_row.shape[0] != n:
         raise N.VrqNativeError(f"vrq_search3: rescore_row has {rescore_row.shape[0]} entries for {n} rows")
     lib = N.load()
-    need = lib.vrq_search3_dim_workspace_size(n, dim, nq, K) if n and nq and K else 0
+    name = search3_call(K, flags)
+    need = getattr(lib, name + "_workspace_size")(n, dim, nq, K) if n and nq and K else 0
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev)
-    rc = lib.vrq_search3_dim(N.ptr(codes) if n else 0, N.ptr(x8) if n else 0, N.ptr(norms) if n else 0,
-                             N.ptr(rescore_row), n, dim, row_offset, N.ptr(qf), N.ptr(qb), nq, k, K, K3, flags,
-                             N.ptr(cnt), N.ptr(rows), N.ptr(dist), N.ptr(s2), N.ptr(s3), N.ptr(workspace),
-                             workspace.numel(), N.stream_handle(dev))
-    N.check(rc, "vrq_search3_dim")
+    rc = getattr(lib, name)(N.ptr(codes) if n else 0, N.ptr(x8) if n else 0, N.ptr(norms) if n else 0,
+                            N.ptr(rescore_row), n, dim, row_offset, N.ptr(qf), N.ptr(qb), nq, k, K, K3, flags,
+                            N.ptr(cnt), N.ptr(rows), N.ptr(dist), N.ptr(s2), N.ptr(s3), N.ptr(workspace),
+                            workspace.numel(), N.stream_handle(dev))
+    N.check(rc, name)
     return cnt, rows, dist, s2, s3
 
 
@@ -338,7 +349,8 @@ class CohereEnhancedVectorDB:
         if self._ws is None or self._ws.device != self.device:
             self._ws = torch.empty((8,), dtype=torch.uint8, device=self.device)
         lib = N.load()
-        need = lib.vrq_search3_dim_workspace_size(n, self.embedding_dim, qf.shape[0], K) if n and K else 0
+        size_of = getattr(lib, search3_call(K) + "_workspace_size")     # of the call search3 takes for this K
+        need = size_of(n, self.embedding_dim, qf.shape[0], K) if n and K else 0
         if self._ws.numel() < need:
             self._ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):

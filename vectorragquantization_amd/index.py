@@ -159,12 +159,14 @@ class BinaryIndexIDMap2:
         R = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         lib = N.load()
         n = self.ntotal
-        ws_bytes = lib.vrq_hamming_topk_workspace_size(n, self.code_size, nq, k) if n and nq and k else 0
+        # more than 1024 neighbours: the counting scan (K1h), up to VRQ_K_LARGE_MAX
+        name = "vrq_hamming_topk_large" if N.large_k(k, "BinaryIndexIDMap2.search") else "vrq_hamming_topk"
+        ws_bytes = getattr(lib, name + "_workspace_size")(n, self.code_size, nq, k) if n and nq and k else 0
         ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
-            rc = lib.vrq_hamming_topk(N.ptr(self.codes) if n else 0, n, self.code_size, 0, N.ptr(q), nq, k,
-                                      N.ptr(D), N.ptr(R), N.ptr(ws), ws.numel(), N.stream_handle(self.device))
-        N.check(rc, "vrq_hamming_topk")
+            rc = getattr(lib, name)(N.ptr(self.codes) if n else 0, n, self.code_size, 0, N.ptr(q), nq, k,
+                                    N.ptr(D), N.ptr(R), N.ptr(ws), ws.numel(), N.stream_handle(self.device))
+        N.check(rc, name)
         return D, R
 
     def reconstruct(self, key) -> np.ndarray:

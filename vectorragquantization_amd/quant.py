@@ -105,10 +105,12 @@ def vectordb_search(mode: str, codes: torch.Tensor, q: torch.Tensor, qf: torch.T
     lib = N.load()
     dist = torch.empty((nq, K), dtype=torch.int32, device=dev)
     rows = torch.empty((nq, K), dtype=torch.int64, device=dev)
-    ws = torch.empty((max(8, lib.vrq_hamming_topk_workspace_size(n, cb, nq, K)),), dtype=torch.uint8, device=dev)
+    # more than 1024 candidates: the counting scan (K1h), up to VRQ_K_LARGE_MAX
+    name = "vrq_hamming_topk_large" if N.large_k(K, "vectordb_search") else "vrq_hamming_topk"
+    ws = torch.empty((max(8, getattr(lib, name + "_workspace_size")(n, cb, nq, K)),), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        N.check(lib.vrq_hamming_topk(N.ptr(codes), n, cb, 0, N.ptr(qb), nq, K, N.ptr(dist), N.ptr(rows), N.ptr(ws),
-                                     ws.numel(), N.stream_handle(dev)), "vrq_hamming_topk")
+        N.check(getattr(lib, name)(N.ptr(codes), n, cb, 0, N.ptr(qb), nq, K, N.ptr(dist), N.ptr(rows), N.ptr(ws),
+                                   ws.numel(), N.stream_handle(dev)), name)
     if mode == "bin16":
         kk = min(k, K)
         return rows[:, :kk], dist[:, :kk], dist[:, :kk].to(torch.float64)
@@ -163,13 +165,17 @@ def search2(mode: str, codes: torch.Tensor, q: torch.Tensor, qf: torch.Tensor, q
         # the ABI indexes q / minmax / rescore_row by candidate row and cannot see their lengths
         raise N.VrqNativeError(f"search2: {n} code rows but {None if q is None else q.shape[0]} stored rows")
     lib = N.load()
+    # more than 1024 candidates: vrq_search2_large (the counting scan K1h; it takes no scan flags)
+    name = "vrq_search2_large" if N.large_k(K, "search2") else "vrq_search2"
+    if name == "vrq_search2_large" and flags:
+        raise N.VrqNativeError(f"search2: flags {flags} with K = {K} > {N.VRQ_K_MAX} (vrq_search2_large takes none)")
     count = torch.empty((nq,), dtype=torch.int32, device=dev)
-    ws = torch.empty((max(8, lib.vrq_search2_workspace_size(n, d, nq, K)),), dtype=torch.uint8, device=dev)
+    ws = torch.empty((max(8, getattr(lib, name + "_workspace_size")(n, d, nq, K)),), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        N.check(lib.vrq_search2(_SEARCH2_MODES[mode], N.ptr(codes), N.ptr(q), N.ptr(minmax), float(limit),
-                                N.ptr(rescore_row), n, d, 0, N.ptr(qf), N.ptr(qb), nq, kk, K, flags, N.ptr(count),
-                                N.ptr(rows), N.ptr(dist), N.ptr(score), N.ptr(ws), ws.numel(),
-                                N.stream_handle(dev)), f"vrq_search2({mode})")
+        N.check(getattr(lib, name)(_SEARCH2_MODES[mode], N.ptr(codes), N.ptr(q), N.ptr(minmax), float(limit),
+                                   N.ptr(rescore_row), n, d, 0, N.ptr(qf), N.ptr(qb), nq, kk, K, flags, N.ptr(count),
+                                   N.ptr(rows), N.ptr(dist), N.ptr(score), N.ptr(ws), ws.numel(),
+                                   N.stream_handle(dev)), f"{name}({mode})")
     return rows, dist, score
 
 
