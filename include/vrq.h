@@ -481,7 +481,7 @@ int vrq_flat_ip_topk_dim(const float* xf, const int8_t* x8, const double* inv_sc
  *   bit for bit.  flags: vrq_search3_large 0 or VRQ_SEARCH_PHASE1_ONLY, vrq_search2_large 0; any other bit
  *   returns VRQ_EUNSUPPORTED.  n, nq, K or k = 0 behave as in vrq_search3_dim_finish / vrq_search2 (counts 0,
  *   padding written, nothing scanned).  Every argument and the workspace size are checked before anything
- *   is launched.  Not sharded: vrq_shard_search* and vrq_merge_shards* keep K <= 1024.
+ *   is launched.  Sharded through the vrq_shard_search*_large / vrq_merge_shards*_large calls below.
  * Phase I is the counting scan K1h: a Hamming distance is an integer in [0, dim], so per-(query, chunk)
  *   histograms give the threshold distance T with count(dist < T) < K <= count(dist <= T), and a second
  *   pass writes every row below T and the first K - count(dist < T) rows at T, in row order.  The finish
@@ -523,6 +523,60 @@ int vrq_search2_large(int32_t mode, const uint8_t* codes, const void* q, const d
                       int64_t* out_rows, int32_t* out_dist, double* out_score, void* workspace,
                       size_t workspace_bytes, void* stream);
 int vrq_scan_large_plan(int64_t n, int32_t dim, int32_t nq, int32_t K, int64_t* info);
+
+/* ---------------------------------------------------------------------------
+ * Row-sharded search with more than 1024 Phase-I candidates (additive to ABI version 1; vrq_shard_search3,
+ * vrq_shard_search2, vrq_merge_shards and vrq_merge_shards2 keep their K <= 1024 contract).
+ * vrq_shard_search3_large / vrq_shard_search2_large: the arguments and outputs of vrq_shard_search3 /
+ *   vrq_shard_search2.  Outputs [nq, K]: the shard's exact Phase-I top-K in FAISS (dist, row) order, rows as
+ *   row_offset + local row, every candidate with its score(s) -- s2 and s3 for the three-phase call, the
+ *   vrq_rescore_dequant score of `mode` (every mode vrq_search2_large accepts) for the two-phase call -- taken
+ *   from rescore_row[r] when given; no sort by score; out_count = min(K, n); missing slots -1 / INT32_MAX / NaN.
+ *   Scores are bit-identical to vrq_rescore_binary_dim / vrq_rescore_int8_cosine_dim / vrq_rescore_dequant for
+ *   the same (query, row), hence to the single-index *_large calls.  Supported: every dim of
+ *   vrq_dim_supported, 1 <= K <= VRQ_K_LARGE_MAX, 1 <= n < 2^32; flags must be 0 (the counting scan takes no
+ *   scan flags): any bit returns VRQ_EUNSUPPORTED.  n, nq or K = 0 behave as in the *_large search calls.
+ *   Every argument and the workspace size (= vrq_search3_large_workspace_size) are checked before anything is
+ *   launched.  Route: K1h, the sort of the K keys, one scoring launch per score kind over all K positions.
+ * vrq_merge_shards_large / vrq_merge_shards2_large: the arguments, outputs and semantics of vrq_merge_shards /
+ *   vrq_merge_shards2 plus a workspace of vrq_merge_shards_large_workspace_size(nshards, nq, K) bytes (one
+ *   pure function for both; 0 for an unsupported shape).  Inputs: the stacked per-shard outputs [S, nq, K]
+ *   with counts i32[S, nq]; each shard's list ascending in (dist, row) and shard s owning a contiguous global
+ *   row range below shard s + 1's, as the per-shard calls leave them.  Three-phase: global top-K by (dist,
+ *   global row) -> stable sort by s2 descending -> first min(K3, candidates) -> stable sort by s3 descending ->
+ *   first k.  Two-phase: global top-K -> stable sort by score descending (-0.0 ties +0.0) -> first k.
+ *   out_src (nullable) i32[nq, k] = s * K + p of each result in the stacked inputs, -1 for missing.
+ *   Supported: 1 <= K <= VRQ_K_LARGE_MAX, 0 <= k <= VRQ_K_LARGE_MAX, any K3 >= 0, nshards <= 4096 (s * K + p
+ *   < 2^25), distances in [0, 2048]; K <= 1024 is accepted on purpose and equals the merges above bit for bit.
+ *   VRQ_EINVAL for null pointers or negative sizes, VRQ_EUNSUPPORTED past the limits, VRQ_EWORKSPACE for a
+ *   short workspace, all before any launch.  The result equals vrq_search3_large / vrq_search2_large over the
+ *   whole corpus, bit for bit.
+ *   The global (dist, row) order of such inputs is their (dist, shard, position) order, so nothing is sorted:
+ *   a histogram of the distances gives every distance's first global rank, and shard after shard each entry's
+ *   rank is that plus its offset in its shard's run of equal distances; ranks below K are the result.
+ * ------------------------------------------------------------------------- */
+size_t vrq_shard_search3_large_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K);
+int vrq_shard_search3_large(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
+                            int64_t n, int32_t dim, int64_t row_offset, const float* qf, const uint8_t* qb,
+                            int32_t nq, int32_t K, int32_t flags, int32_t* out_count, int64_t* out_rows,
+                            int32_t* out_dist, double* out_binary, double* out_cosine, void* workspace,
+                            size_t workspace_bytes, void* stream);
+size_t vrq_shard_search2_large_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K);
+int vrq_shard_search2_large(int32_t mode, const uint8_t* codes, const void* q, const double* minmax, double limit,
+                            const int64_t* rescore_row, int64_t n, int32_t dim, int64_t row_offset, const float* qf,
+                            const uint8_t* qb, int32_t nq, int32_t K, int32_t flags, int32_t* out_count,
+                            int64_t* out_rows, int32_t* out_dist, double* out_score, void* workspace,
+                            size_t workspace_bytes, void* stream);
+size_t vrq_merge_shards_large_workspace_size(int32_t nshards, int32_t nq, int32_t K);
+int vrq_merge_shards_large(int32_t nshards, int32_t nq, int32_t K, const int32_t* counts, const int64_t* rows,
+                           const int32_t* dist, const double* s2, const double* s3, int32_t k, int32_t K3,
+                           int32_t* out_count, int64_t* out_rows, int32_t* out_dist, double* out_binary,
+                           double* out_cosine, int32_t* out_src, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int vrq_merge_shards2_large(int32_t nshards, int32_t nq, int32_t K, const int32_t* counts, const int64_t* rows,
+                            const int32_t* dist, const double* score, int32_t k, int32_t* out_count,
+                            int64_t* out_rows, int32_t* out_dist, double* out_score, int32_t* out_src,
+                            void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

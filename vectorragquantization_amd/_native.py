@@ -109,6 +109,17 @@ SIGNATURES = {
     "vrq_search2_large_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
     "vrq_search2_large": (C.c_int, [_I32, _P, _P, _P, _D, _P, _I64, _I32, _I64, _P, _P, _I32, _I32, _I32, _I32,
                                     _P, _P, _P, _P, _P, _SZ, _P]),
+    "vrq_shard_search3_large_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
+    "vrq_shard_search3_large": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I64, _P, _P, _I32, _I32, _I32,
+                                          _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "vrq_shard_search2_large_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
+    "vrq_shard_search2_large": (C.c_int, [_I32, _P, _P, _P, _D, _P, _I64, _I32, _I64, _P, _P, _I32, _I32, _I32,
+                                          _P, _P, _P, _P, _P, _SZ, _P]),
+    "vrq_merge_shards_large_workspace_size": (_SZ, [_I32, _I32, _I32]),
+    "vrq_merge_shards_large": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P,
+                                         _P, _SZ, _P]),
+    "vrq_merge_shards2_large": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _SZ,
+                                          _P]),
     "vrq_scan_large_plan": (C.c_int, [_I64, _I32, _I32, _I32, _P]),
     "vrq_scan_large": (C.c_int, [_P, _I64, _I32, _P, _I32, _I32, _I32, _P, _SZ, _P]),
     "vrq_gemm_topk_workspace_size": (_SZ, [_I32, _I64, _I32, _I32, _I32]),

@@ -956,6 +956,7 @@ struct LargeScoreArgs {
   const double* minmax;
   double dlimit;
   double* out;  // [nq][K] by position
+  bool pad;     // positions [min(kp, limit), K) get NaN (the per-shard calls score into the caller's arrays)
 };
 
 template <class Scorer>
@@ -965,8 +966,11 @@ __global__ __launch_bounds__(256) void large_score_kernel(const float* __restric
   const int i = (blockIdx.x - q * bpq) * (256 / WAVE) + threadIdx.x / WAVE;  // wave-uniform
   const int kpq = a.kp[q];
   const int m = kpq < a.limit ? kpq : a.limit;
-  if (i >= m) return;
   const int64_t base = (int64_t)q * a.K;
+  if (i >= m) {
+    if (a.pad && i < a.K && lane_id() == 0) a.out[base + i] = __builtin_nan("");
+    return;
+  }
   const int r = a.ord ? a.ord[base + i] : i;
   int64_t row = (int64_t)(a.lists[base + r] & ROW_MASK);
   if (a.remap) row = a.remap[row];
@@ -986,6 +990,8 @@ struct LargeOrderArgs {
   int K, limit;        // the first min(kp, limit) positions take part
   int32_t* ord_out;    // non-null: keep the order of the first `keep` (position -> Phase-I rank) and stop
   int keep;
+  const double* carry_in;  // with ord_out, non-null (shard merge): carry_out[position] = carry_in[Phase-I rank]
+  double* carry_out;
   // the final write (ord_out == null)
   const int32_t* ord;  // sorted position -> Phase-I rank (three-phase), or null (the position is the rank)
   const uint64_t* lists;
@@ -997,6 +1003,8 @@ struct LargeOrderArgs {
   int32_t* out_dist;
   double* out_s2;
   double* out_s3;      // three-phase only: a.sc of the position
+  const int32_t* src;  // shard merge: shard * K + position of each Phase-I rank in the stacked inputs ...
+  int32_t* out_src;    // ... written per output when non-null (-1 padded)
 };
 
 template <int CAP>
@@ -1035,7 +1043,10 @@ __global__ __launch_bounds__(LARGE_THREADS) void large_order_kernel(LargeOrderAr
   __syncthreads();
   if (a.ord_out) {
     const int keep = a.keep < m ? a.keep : m;
-    for (int i = tid; i < keep; i += LARGE_THREADS) a.ord_out[base + i] = sidx[i];
+    for (int i = tid; i < keep; i += LARGE_THREADS) {
+      a.ord_out[base + i] = sidx[i];
+      if (a.carry_in) a.carry_out[base + i] = a.carry_in[base + sidx[i]];
+    }
     return;
   }
   const int mo = a.k < m ? a.k : m;
@@ -1049,11 +1060,13 @@ __global__ __launch_bounds__(LARGE_THREADS) void large_order_kernel(LargeOrderAr
       a.out_dist[o] = (int32_t)(key >> KEY_ROW_BITS);
       a.out_s2[o] = a.s2[base + r];
       if (a.out_s3) a.out_s3[o] = a.sc[base + j];
+      if (a.out_src) a.out_src[o] = a.src[base + r];
     } else {
       a.out_rows[o] = -1;
       a.out_dist[o] = DIST_NONE;
       a.out_s2[o] = __builtin_nan("");
       if (a.out_s3) a.out_s3[o] = __builtin_nan("");
+      if (a.out_src) a.out_src[o] = -1;
     }
   }
   if (tid == 0) a.out_count[q] = mo;
@@ -1104,6 +1117,179 @@ static int large_order_launch(hipStream_t s, int nq, const LargeOrderArgs& a) {
     hipLaunchKernelGGL(large_order_kernel<VRQ_K_LARGE_MAX>, grid, block, 0, s, a);
   VRQ_LAUNCH_CHECK();
   return VRQ_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The large shard merge (vrq_merge_shards*_large): the global top-K of S stacked K-lists, K up to
+// VRQ_K_LARGE_MAX.  S * K keys do not fit LDS (512 KiB at S = 8, K = 8192), and they need not be sorted:
+// every shard's list is ascending in (dist, row) and shard s owns the rows below shard s + 1's, so the global
+// (dist, row) order is the (dist, shard, position) order, and a distance is an integer in [0, 2048].  One
+// workgroup per query:
+//   histogram   the entries of one distance are a run inside each shard's list, so the run's head subtracts
+//               its position from the bin and its tail adds its position + 1: two LDS atomics per (shard,
+//               distance) instead of one per entry on an address all 64 lanes of a wave share
+//   prefix      cursor[d] = count(dist < d): the global rank of the first entry at distance d
+//   ranks       shard after shard: an entry's global rank is cursor[d] + its offset in its run; ranks below
+//               min(K, entries) are the result -- every entry below T, and of those at T the first
+//               K - count(dist < T) in (shard, position) order -- and go, with their scores and their index
+//               s * K + p in the stacked inputs, straight to their slot in the workspace; then the run's
+//               tail advances cursor[d] by the run length
+// The stable sorts and the final write are large_order_kernel's.  An entry past its shard's count, with a
+// negative row or a distance outside [0, 2048] takes no part (the first two as in merge_shards_kernel); lists
+// that are not ascending give ranks that collide, never a store outside [0, K).
+// ---------------------------------------------------------------------------
+constexpr int MERGE_BINS = 2049;
+
+struct MergeSelectArgs {
+  int S, K, nq;
+  const int32_t* counts;  // [S][nq]
+  const int64_t* rows;    // [S][nq][K] global rows
+  const int32_t* dist;
+  const double* s2;       // the score of the two-phase merge
+  const double* s3;       // null for the two-phase merge
+  uint64_t* keys;         // [nq][K] by global rank, KEY_NONE padded
+  int32_t* src;           // [nq][K] s * K + p, -1 padded
+  double* w2;             // [nq][K] by global rank
+  double* w3;
+  int32_t* kp;            // [nq] min(K, entries)
+};
+
+// the distance of entry p of a shard's list, -1 where the entry takes no part
+__device__ __forceinline__ int merge_dist_at(const MergeSelectArgs& a, int64_t base, int p, int cnt) {
+  if (p < 0 || p >= cnt) return -1;
+  const int d = a.dist[base + p];
+  return a.rows[base + p] >= 0 && (uint32_t)d < (uint32_t)MERGE_BINS ? d : -1;
+}
+
+template <int PER>  // entries of one shard per thread: K <= PER * LARGE_THREADS
+__global__ __launch_bounds__(LARGE_THREADS) void merge_select_kernel(MergeSelectArgs a) {
+  __shared__ int32_t cursor[MERGE_BINS];    // the histogram, then the next global rank of every distance
+  __shared__ int32_t runstart[MERGE_BINS];  // position of the head of the current shard's run
+  __shared__ int32_t scratch[LARGE_THREADS];
+  const int q = blockIdx.x, tid = threadIdx.x;
+  for (int b = tid; b < MERGE_BINS; b += LARGE_THREADS) cursor[b] = 0;
+  __syncthreads();
+  for (int s = 0; s < a.S; ++s) {
+    const int c = a.counts[(int64_t)s * a.nq + q];
+    const int cnt = c < 0 ? 0 : c < a.K ? c : a.K;
+    const int64_t base = ((int64_t)s * a.nq + q) * a.K;
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+      const int p = tid + j * LARGE_THREADS;
+      const int d = merge_dist_at(a, base, p, cnt);
+      if (d < 0) continue;
+      if (merge_dist_at(a, base, p - 1, cnt) != d) atomicSub(&cursor[d], p);
+      if (merge_dist_at(a, base, p + 1, cnt) != d) atomicAdd(&cursor[d], p + 1);
+    }
+  }
+  __syncthreads();
+  // exclusive prefix over the bins: BPT consecutive bins per thread, a workgroup scan of the thread sums
+  constexpr int BPT = (MERGE_BINS + LARGE_THREADS - 1) / LARGE_THREADS;
+  int h[BPT], local = 0;
+#pragma unroll
+  for (int b = 0; b < BPT; ++b) {
+    const int i = tid * BPT + b;
+    h[b] = i < MERGE_BINS ? cursor[i] : 0;
+    local += h[b];
+  }
+  scratch[tid] = local;
+  __syncthreads();
+  for (int o = 1; o < LARGE_THREADS; o <<= 1) {
+    const int y = tid >= o ? scratch[tid - o] : 0;
+    __syncthreads();
+    scratch[tid] += y;
+    __syncthreads();
+  }
+  int cum = scratch[tid] - local;
+  const int total = scratch[LARGE_THREADS - 1];
+#pragma unroll
+  for (int b = 0; b < BPT; ++b) {
+    const int i = tid * BPT + b;
+    if (i < MERGE_BINS) cursor[i] = cum;
+    cum += h[b];
+  }
+  const int want = total < a.K ? total : a.K;
+  const int64_t ob = (int64_t)q * a.K;
+  __syncthreads();
+  for (int s = 0; s < a.S; ++s) {
+    const int c = a.counts[(int64_t)s * a.nq + q];
+    const int cnt = c < 0 ? 0 : c < a.K ? c : a.K;
+    const int64_t base = ((int64_t)s * a.nq + q) * a.K;
+    int dv[PER];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+      const int p = tid + j * LARGE_THREADS;
+      dv[j] = merge_dist_at(a, base, p, cnt);
+      if (dv[j] >= 0 && merge_dist_at(a, base, p - 1, cnt) != dv[j]) runstart[dv[j]] = p;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+      const int p = tid + j * LARGE_THREADS;
+      if (dv[j] < 0) continue;
+      const int rank = cursor[dv[j]] + p - runstart[dv[j]];
+      if ((uint32_t)rank < (uint32_t)want) {
+        a.keys[ob + rank] = ((uint64_t)(uint32_t)dv[j] << KEY_ROW_BITS) | ((uint64_t)a.rows[base + p] & ROW_MASK);
+        a.src[ob + rank] = s * a.K + p;
+        a.w2[ob + rank] = a.s2[base + p];
+        if (a.s3) a.w3[ob + rank] = a.s3[base + p];
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+      const int p = tid + j * LARGE_THREADS;
+      if (dv[j] >= 0 && merge_dist_at(a, base, p + 1, cnt) != dv[j]) cursor[dv[j]] += p - runstart[dv[j]] + 1;
+    }
+    __syncthreads();
+  }
+  for (int i = want + tid; i < a.K; i += LARGE_THREADS) {
+    a.keys[ob + i] = KEY_NONE;
+    a.src[ob + i] = -1;
+  }
+  if (tid == 0) a.kp[q] = want;
+}
+
+static int merge_select_launch(hipStream_t s, const MergeSelectArgs& a) {
+  const dim3 grid(a.nq), block(LARGE_THREADS);
+  if (a.K <= LARGE_THREADS)
+    hipLaunchKernelGGL(merge_select_kernel<1>, grid, block, 0, s, a);
+  else if (a.K <= 2 * LARGE_THREADS)
+    hipLaunchKernelGGL(merge_select_kernel<2>, grid, block, 0, s, a);
+  else if (a.K <= 4 * LARGE_THREADS)
+    hipLaunchKernelGGL(merge_select_kernel<4>, grid, block, 0, s, a);
+  else
+    hipLaunchKernelGGL(merge_select_kernel<VRQ_K_LARGE_MAX / LARGE_THREADS>, grid, block, 0, s, a);
+  VRQ_LAUNCH_CHECK();
+  return VRQ_OK;
+}
+
+// workspace of a large merge: everything is [nq][K] but the counts
+struct MergePlan {
+  size_t off_keys, off_src, off_w2, off_w3, off_w3p, off_ord, off_kp, bytes;
+};
+
+static bool merge_plan(int nshards, int nq, int K, MergePlan* p) {
+  if (nshards < 1 || nshards > MAX_LISTS || nq < 1 || K < 1 || K > VRQ_K_LARGE_MAX) return false;
+  const auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
+  const size_t m = (size_t)nq * K;
+  size_t off = 0;
+  p->off_keys = off;
+  off = al(off + m * sizeof(uint64_t));
+  p->off_src = off;
+  off = al(off + m * sizeof(int32_t));
+  p->off_w2 = off;
+  off = al(off + m * sizeof(double));
+  p->off_w3 = off;
+  off = al(off + m * sizeof(double));
+  p->off_w3p = off;  // s3 by position in the Phase-II order
+  off = al(off + m * sizeof(double));
+  p->off_ord = off;
+  off = al(off + m * sizeof(int32_t));
+  p->off_kp = off;
+  off = al(off + (size_t)nq * sizeof(int32_t));
+  p->bytes = off;
+  return true;
 }
 
 }  // namespace vrq
@@ -1739,6 +1925,215 @@ int vrq_search2_large(int32_t mode, const uint8_t* codes, const void* q, const d
   fa.out_rows = out_rows;
   fa.out_dist = out_dist;
   fa.out_s2 = out_score;
+  return large_order_launch(s, nq, fa);
+}
+
+// ---- the per-shard calls for K up to VRQ_K_LARGE_MAX: K1h, the sort, the scores of every candidate ----
+size_t vrq_shard_search3_large_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K) {
+  return vrq_search3_large_workspace_size(n, dim, nq, K);
+}
+
+size_t vrq_shard_search2_large_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K) {
+  return vrq_search3_large_workspace_size(n, dim, nq, K);
+}
+
+// scan + sort into the caller's [nq][K] rows / dist / count; leaves `sa` ready to score every position
+static int large_shard_phase1(const LargePlan& p, const uint8_t* codes, int64_t n, int32_t dim, int64_t row_offset,
+                              const uint8_t* qb, int32_t nq, int32_t K, const int64_t* rescore_row,
+                              int32_t* out_count, int64_t* out_rows, int32_t* out_dist, uint8_t* ws, hipStream_t s,
+                              LargeScoreArgs* sa) {
+  uint64_t* lists = (uint64_t*)(ws + p.off_lists);
+  int32_t* kp = (int32_t*)(ws + p.off_kp);
+  int rc = large_scan_launch(p, codes, n, dim / 8, qb, nq, K, ws, s, 0);
+  if (rc != VRQ_OK) return rc;
+  rc = large_sort_launch(s, nq, lists, K, kp, true, row_offset, out_count, out_rows, out_dist);
+  sa->lists = lists;
+  sa->kp = kp;
+  sa->K = K;
+  sa->limit = K;
+  sa->remap = rescore_row;
+  sa->pad = true;
+  return rc;
+}
+
+int vrq_shard_search3_large(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
+                            int64_t n, int32_t dim, int64_t row_offset, const float* qf, const uint8_t* qb,
+                            int32_t nq, int32_t K, int32_t flags, int32_t* out_count, int64_t* out_rows,
+                            int32_t* out_dist, double* out_binary, double* out_cosine, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  VRQ_CHECK_ARG(n >= 0 && nq >= 0 && K >= 0);
+  VRQ_CHECK_ARG(out_count && out_rows && out_dist && out_binary && out_cosine);
+  if (!vrq_dim_supported(dim) || K > VRQ_K_LARGE_MAX) return VRQ_EUNSUPPORTED;
+  if (flags) return VRQ_EUNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  if (nq == 0) return VRQ_OK;
+  if (n == 0 || K == 0) return fill_empty(nq, K, out_count, out_rows, out_dist, out_binary, out_cosine, s);
+  VRQ_CHECK_ARG(codes && qb && workspace && qf && x8 && norms);
+  LargePlan p;
+  int rc = large_plan_checked(n, dim / 8, nq, K, workspace_bytes, &p);
+  if (rc != VRQ_OK) return rc;
+  LargeScoreArgs sa{};
+  rc = large_shard_phase1(p, codes, n, dim, row_offset, qb, nq, K, rescore_row, out_count, out_rows, out_dist,
+                          (uint8_t*)workspace, s, &sa);
+  if (rc != VRQ_OK) return rc;
+  sa.codes = codes;
+  sa.x8 = x8;
+  sa.norms = norms;
+  sa.which = 0;
+  sa.out = out_binary;
+  rc = large_score_launch(s, nq, qf, dim, sa);
+  if (rc != VRQ_OK) return rc;
+  sa.which = 1;
+  sa.out = out_cosine;
+  return large_score_launch(s, nq, qf, dim, sa);
+}
+
+int vrq_shard_search2_large(int32_t mode, const uint8_t* codes, const void* q, const double* minmax, double limit,
+                            const int64_t* rescore_row, int64_t n, int32_t dim, int64_t row_offset, const float* qf,
+                            const uint8_t* qb, int32_t nq, int32_t K, int32_t flags, int32_t* out_count,
+                            int64_t* out_rows, int32_t* out_dist, double* out_score, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  VRQ_CHECK_ARG(search2_mode_ok(mode));
+  VRQ_CHECK_ARG(n >= 0 && nq >= 0 && K >= 0);
+  VRQ_CHECK_ARG(out_count && out_rows && out_dist && out_score);
+  if (!vrq_dim_supported(dim) || K > VRQ_K_LARGE_MAX) return VRQ_EUNSUPPORTED;
+  if (mode == VRQ_RESCORE_SIGNED_BINARY && dim % 128 != 0) return VRQ_EUNSUPPORTED;
+  if (flags) return VRQ_EUNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  if (nq == 0) return VRQ_OK;
+  if (n == 0 || K == 0) return fill_empty(nq, K, out_count, out_rows, out_dist, out_score, nullptr, s);
+  VRQ_CHECK_ARG(codes && qb && workspace && qf && q);
+  if (mode == VRQ_ENC_INT8_LOCAL || mode == VRQ_ENC_INT4_LOCAL) VRQ_CHECK_ARG(minmax);
+  LargePlan p;
+  int rc = large_plan_checked(n, dim / 8, nq, K, workspace_bytes, &p);
+  if (rc != VRQ_OK) return rc;
+  LargeScoreArgs sa{};
+  rc = large_shard_phase1(p, codes, n, dim, row_offset, qb, nq, K, rescore_row, out_count, out_rows, out_dist,
+                          (uint8_t*)workspace, s, &sa);
+  if (rc != VRQ_OK) return rc;
+  sa.which = 2;
+  sa.mode = mode;
+  sa.dq = q;
+  sa.minmax = minmax;
+  sa.dlimit = limit;
+  sa.out = out_score;
+  return large_score_launch(s, nq, qf, dim, sa);
+}
+
+// ---- the merge of the per-shard outputs for K up to VRQ_K_LARGE_MAX ----
+size_t vrq_merge_shards_large_workspace_size(int32_t nshards, int32_t nq, int32_t K) {
+  MergePlan p;
+  return merge_plan(nshards, nq, K, &p) ? p.bytes : 0;
+}
+
+// the arguments both merges share, checked before anything is launched; *run = false: nothing to merge
+static int merge_large_checked(int32_t nshards, int32_t nq, int32_t K, int32_t k, const void* counts,
+                               const void* rows, const void* dist, const void* sc_a, const void* sc_b,
+                               const void* workspace, size_t workspace_bytes, MergePlan* p, bool* run) {
+  *run = false;
+  if (K > VRQ_K_LARGE_MAX || k > VRQ_K_LARGE_MAX || nshards > MAX_LISTS) return VRQ_EUNSUPPORTED;
+  if (nq == 0 || K == 0 || k == 0) return VRQ_OK;
+  VRQ_CHECK_ARG(counts && rows && dist && sc_a && sc_b && workspace);
+  if (!merge_plan(nshards, nq, K, p)) return VRQ_EUNSUPPORTED;
+  if (workspace_bytes < p->bytes) return VRQ_EWORKSPACE;
+  *run = true;
+  return VRQ_OK;
+}
+
+static int fill_empty_merge(int32_t nq, int32_t k, int32_t* out_count, int64_t* out_rows, int32_t* out_dist,
+                            double* out_a, double* out_b, int32_t* out_src, hipStream_t s) {
+  if (out_src && k && hipMemsetAsync(out_src, 0xff, sizeof(int32_t) * (size_t)nq * k, s) != hipSuccess)
+    return VRQ_EHIP;  // -1
+  return fill_empty(nq, k, out_count, out_rows, out_dist, out_a, out_b, s);
+}
+
+int vrq_merge_shards_large(int32_t nshards, int32_t nq, int32_t K, const int32_t* counts, const int64_t* rows,
+                           const int32_t* dist, const double* s2, const double* s3, int32_t k, int32_t K3,
+                           int32_t* out_count, int64_t* out_rows, int32_t* out_dist, double* out_binary,
+                           double* out_cosine, int32_t* out_src, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+  VRQ_CHECK_ARG(nshards >= 1 && nq >= 0 && K >= 0 && k >= 0 && K3 >= 0);
+  VRQ_CHECK_ARG(out_count && out_rows && out_dist && out_binary && out_cosine);
+  MergePlan p;
+  bool run;
+  int rc = merge_large_checked(nshards, nq, K, k, counts, rows, dist, s2, s3, workspace, workspace_bytes, &p, &run);
+  if (rc != VRQ_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (nq == 0) return VRQ_OK;
+  if (!run) return fill_empty_merge(nq, k, out_count, out_rows, out_dist, out_binary, out_cosine, out_src, s);
+  uint8_t* ws = (uint8_t*)workspace;
+  MergeSelectArgs ma{nshards, K, nq, counts, rows, dist, s2, s3, (uint64_t*)(ws + p.off_keys),
+                     (int32_t*)(ws + p.off_src), (double*)(ws + p.off_w2), (double*)(ws + p.off_w3),
+                     (int32_t*)(ws + p.off_kp)};
+  rc = merge_select_launch(s, ma);
+  if (rc != VRQ_OK) return rc;
+  // the stable order by s2 and the first K3 of it, with their s3 by position
+  int32_t* ord = (int32_t*)(ws + p.off_ord);
+  double* w3p = (double*)(ws + p.off_w3p);
+  LargeOrderArgs oa{};
+  oa.sc = ma.w2;
+  oa.kp = ma.kp;
+  oa.K = K;
+  oa.limit = K;
+  oa.ord_out = ord;
+  oa.keep = K3;
+  oa.carry_in = ma.w3;
+  oa.carry_out = w3p;
+  rc = large_order_launch(s, nq, oa);
+  if (rc != VRQ_OK) return rc;
+  LargeOrderArgs fa{};
+  fa.sc = w3p;
+  fa.kp = ma.kp;
+  fa.K = K;
+  fa.limit = K3;
+  fa.ord = ord;
+  fa.lists = ma.keys;
+  fa.s2 = ma.w2;
+  fa.k = k;
+  fa.out_count = out_count;
+  fa.out_rows = out_rows;
+  fa.out_dist = out_dist;
+  fa.out_s2 = out_binary;
+  fa.out_s3 = out_cosine;
+  fa.src = ma.src;
+  fa.out_src = out_src;
+  return large_order_launch(s, nq, fa);
+}
+
+int vrq_merge_shards2_large(int32_t nshards, int32_t nq, int32_t K, const int32_t* counts, const int64_t* rows,
+                            const int32_t* dist, const double* score, int32_t k, int32_t* out_count,
+                            int64_t* out_rows, int32_t* out_dist, double* out_score, int32_t* out_src,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+  VRQ_CHECK_ARG(nshards >= 1 && nq >= 0 && K >= 0 && k >= 0);
+  VRQ_CHECK_ARG(out_count && out_rows && out_dist && out_score);
+  MergePlan p;
+  bool run;
+  int rc =
+      merge_large_checked(nshards, nq, K, k, counts, rows, dist, score, score, workspace, workspace_bytes, &p, &run);
+  if (rc != VRQ_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (nq == 0) return VRQ_OK;
+  if (!run) return fill_empty_merge(nq, k, out_count, out_rows, out_dist, out_score, nullptr, out_src, s);
+  uint8_t* ws = (uint8_t*)workspace;
+  MergeSelectArgs ma{nshards, K, nq, counts, rows, dist, score, nullptr, (uint64_t*)(ws + p.off_keys),
+                     (int32_t*)(ws + p.off_src), (double*)(ws + p.off_w2), (double*)(ws + p.off_w3),
+                     (int32_t*)(ws + p.off_kp)};
+  rc = merge_select_launch(s, ma);
+  if (rc != VRQ_OK) return rc;
+  LargeOrderArgs fa{};
+  fa.sc = ma.w2;
+  fa.kp = ma.kp;
+  fa.K = K;
+  fa.limit = K;
+  fa.lists = ma.keys;
+  fa.s2 = ma.w2;
+  fa.k = k;
+  fa.out_count = out_count;
+  fa.out_rows = out_rows;
+  fa.out_dist = out_dist;
+  fa.out_s2 = out_score;
+  fa.src = ma.src;
+  fa.out_src = out_src;
   return large_order_launch(s, nq, fa);
 }
 

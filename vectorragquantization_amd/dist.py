@@ -23,6 +23,15 @@ replicated to every rank and searched in three steps:
 one all-gather of 28-byte records, ``vrq_merge_shards2`` (global top-K -> stable sort by score ->
 first k: ``CohereVectorDBBinary.py:215-239``, ``VectorDBInt8Global.py:224-252``).
 
+More than 1024 Phase-I candidates (``k * binary_oversample`` up to ``VRQ_K_LARGE_MAX`` = 8192; the default
+oversample of 10 passes 1024 at k = 103) take the same three steps through ``vrq_shard_search3_large`` /
+``vrq_shard_search2_large`` (the counting scan K1h, every candidate scored) and ``vrq_merge_shards_large`` /
+``vrq_merge_shards2_large``; ``shard_calls(K)`` names the calls of a K.  Packing and the all-gather are the
+same, and their size is what it is: ``nq * K * 36`` B per rank for the three-phase search and ``nq * K * 28`` B
+for the two-phase one -- 18.9 MB per rank at nq = 64, K = 8192, linear in nq -- so a large K is a small-batch
+regime, as K1h itself is.  (Exchanging per-shard distance histograms first, so that each shard scores and
+sends only its share of the global K, is the recorded follow-up: DESIGN section 10.)
+
 Not sharded: ``mode="bin16"`` (``VectorDBInt16`` ranks by Phase I alone), a ``rescore_row`` that
 crosses shards (an id added twice must live in one shard), class-level ``add_documents``, and
 ``CohereVectorDBFloat`` (``merge_topk_shards`` covers the exhaustive paths through ``row_offset``).
@@ -119,8 +128,35 @@ def unpack_candidates2(buf: torch.Tensor, S: int, nq: int, K: int):
     return cnt, rows, ids, d, sc
 
 
-def _workspace(ws, size_fn, n: int, qf: torch.Tensor, K: int, dev):
-    """``ws`` if it holds a shard call of this shape, else a new buffer that does."""
+def shard_calls(K: int, flags: int = 0) -> dict:
+    """The entry points a sharded search with K Phase-I candidates takes: today's calls up to 1024, the
+    ``_large`` calls (the counting scan K1h + the large merge) for 1024 < K <= ``VRQ_K_LARGE_MAX``; each
+    search call's workspace size is ``<name>_workspace_size``, the large merges share
+    ``vrq_merge_shards_large_workspace_size``.  Raises past the limit, and for scan flags with a large K."""
+    large = N.large_k(K, "sharded search")
+    if large and flags:
+        raise N.VrqNativeError(f"sharded search: flags {flags} with K = {K} > {N.VRQ_K_MAX} "
+                               "(the _large calls take none)")
+    sfx = "_large" if large else ""
+    return {"search3": "vrq_shard_search3" + sfx, "search2": "vrq_shard_search2" + sfx,
+            "merge3": "vrq_merge_shards" + sfx, "merge2": "vrq_merge_shards2" + sfx}
+
+
+def _merge_workspace(lib, name: str, S: int, nq: int, K: int, dev):
+    """The extra (workspace, bytes) arguments of a merge call: none for the K <= 1024 merges."""
+    if not name.endswith("_large"):
+        return (), None
+    need = lib.vrq_merge_shards_large_workspace_size(S, nq, K) if nq and K else 0
+    if nq and K and need == 0:
+        raise N.VrqNativeError(f"{name}: unsupported shape shards={S} nq={nq} K={K}")
+    ws = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev)
+    return (N.ptr(ws), ws.numel()), ws
+
+
+def _workspace(ws, kind: str, n: int, qf: torch.Tensor, K: int, dev):
+    """``ws`` if it holds the shard call (``kind``: "search3" / "search2") of this shape, else a new buffer
+    that does."""
+    size_fn = getattr(N.load(), shard_calls(K)[kind] + "_workspace_size")
     need = size_fn(n, qf.shape[1], qf.shape[0], K) if n and K and qf.shape[0] else 0
     if n and K and qf.shape[0] and need == 0:
         raise N.VrqNativeError(f"sharded search: unsupported shape n={n} dim={qf.shape[1]} nq={qf.shape[0]} K={K} "
@@ -154,17 +190,18 @@ def shard_search3(codes: torch.Tensor, x8: torch.Tensor, norms: torch.Tensor, qf
         raise N.VrqNativeError(f"vrq_shard_search3: {codes.shape[1]}-byte codes but queries of dim {dim} / codes "
                                f"{tuple(qb.shape)}, int8 rows of dim {x8.shape[1]}")
     lib = N.load()
-    workspace = _workspace(workspace, lib.vrq_shard_search3_workspace_size, n, qf, K, dev)
+    name = shard_calls(K, flags)["search3"]
+    workspace = _workspace(workspace, "search3", n, qf, K, dev)
     cnt = torch.empty((nq,), dtype=torch.int32, device=dev)
     rows = torch.empty((nq, K), dtype=torch.int64, device=dev)
     dist_ = torch.empty((nq, K), dtype=torch.int32, device=dev)
     s2 = torch.empty((nq, K), dtype=torch.float64, device=dev)
     s3 = torch.empty((nq, K), dtype=torch.float64, device=dev)
-    rc = lib.vrq_shard_search3(N.ptr(codes) if n else 0, N.ptr(x8) if n else 0, N.ptr(norms) if n else 0,
-                               N.ptr(rescore_row), n, dim, row_offset, N.ptr(qf), N.ptr(qb), nq, K, flags,
-                               N.ptr(cnt), N.ptr(rows), N.ptr(dist_), N.ptr(s2), N.ptr(s3), N.ptr(workspace),
-                               workspace.numel(), N.stream_handle(dev))
-    N.check(rc, "vrq_shard_search3")
+    rc = getattr(lib, name)(N.ptr(codes) if n else 0, N.ptr(x8) if n else 0, N.ptr(norms) if n else 0,
+                            N.ptr(rescore_row), n, dim, row_offset, N.ptr(qf), N.ptr(qb), nq, K, flags,
+                            N.ptr(cnt), N.ptr(rows), N.ptr(dist_), N.ptr(s2), N.ptr(s3), N.ptr(workspace),
+                            workspace.numel(), N.stream_handle(dev))
+    N.check(rc, name)
     return cnt, rows, dist_, s2, s3
 
 
@@ -186,21 +223,23 @@ def shard_search2(mode: str, codes: torch.Tensor, q: torch.Tensor, qf: torch.Ten
         # the ABI indexes q / minmax / rescore_row by candidate row and cannot see their lengths
         raise N.VrqNativeError(f"vrq_shard_search2: {n} code rows but {None if q is None else q.shape[0]} stored rows")
     lib = N.load()
-    workspace = _workspace(workspace, lib.vrq_shard_search2_workspace_size, n, qf, K, dev)
+    name = shard_calls(K, flags)["search2"]
+    workspace = _workspace(workspace, "search2", n, qf, K, dev)
     cnt = torch.empty((nq,), dtype=torch.int32, device=dev)
     rows = torch.empty((nq, K), dtype=torch.int64, device=dev)
     dist_ = torch.empty((nq, K), dtype=torch.int32, device=dev)
     score = torch.empty((nq, K), dtype=torch.float64, device=dev)
-    rc = lib.vrq_shard_search2(_SEARCH2_MODES[mode], N.ptr(codes) if n else 0, N.ptr(q) if n else 0,
-                               N.ptr(minmax) if n else 0, float(limit), N.ptr(rescore_row), n, dim, row_offset,
-                               N.ptr(qf), N.ptr(qb), nq, K, flags, N.ptr(cnt), N.ptr(rows), N.ptr(dist_),
-                               N.ptr(score), N.ptr(workspace), workspace.numel(), N.stream_handle(dev))
-    N.check(rc, f"vrq_shard_search2({mode})")
+    rc = getattr(lib, name)(_SEARCH2_MODES[mode], N.ptr(codes) if n else 0, N.ptr(q) if n else 0,
+                            N.ptr(minmax) if n else 0, float(limit), N.ptr(rescore_row), n, dim, row_offset,
+                            N.ptr(qf), N.ptr(qb), nq, K, flags, N.ptr(cnt), N.ptr(rows), N.ptr(dist_),
+                            N.ptr(score), N.ptr(workspace), workspace.numel(), N.stream_handle(dev))
+    N.check(rc, f"{name}({mode})")
     return cnt, rows, dist_, score
 
 
 def merge_shards(cnt, rows, d, s2, s3, k: int, K3: int):
-    """``vrq_merge_shards`` on stacked [S, nq, K] tensors -> (count, rows, dist, s2, s3, src)."""
+    """``vrq_merge_shards`` (``vrq_merge_shards_large`` for K > 1024) on stacked [S, nq, K] tensors ->
+    (count, rows, dist, s2, s3, src)."""
     S, nq, K = rows.shape
     dev = rows.device
     oc = torch.empty((nq,), dtype=torch.int32, device=dev)
@@ -211,11 +250,13 @@ def merge_shards(cnt, rows, d, s2, s3, k: int, K3: int):
     src = torch.empty((nq, k), dtype=torch.int32, device=dev)
     cnt, rows, d, s2, s3 = (t.contiguous() for t in (cnt, rows, d, s2, s3))  # held until the launch returns
     lib = N.load()
+    name = shard_calls(K)["merge3"]
     with torch.cuda.device(dev):
-        rc = lib.vrq_merge_shards(S, nq, K, N.ptr(cnt), N.ptr(rows), N.ptr(d), N.ptr(s2), N.ptr(s3), k, K3,
-                                  N.ptr(oc), N.ptr(orow), N.ptr(od), N.ptr(o2), N.ptr(o3), N.ptr(src),
-                                  N.stream_handle(dev))
-    N.check(rc, "vrq_merge_shards")
+        extra, ws = _merge_workspace(lib, name, S, nq, K, dev)  # (stream-ordered: freed after the launches)
+        rc = getattr(lib, name)(S, nq, K, N.ptr(cnt), N.ptr(rows), N.ptr(d), N.ptr(s2), N.ptr(s3), k, K3,
+                                N.ptr(oc), N.ptr(orow), N.ptr(od), N.ptr(o2), N.ptr(o3), N.ptr(src), *extra,
+                                N.stream_handle(dev))
+    N.check(rc, name)
     return oc, orow, od, o2, o3, src
 
 
@@ -261,8 +302,7 @@ class ShardedSearch:
 
     def local(self, qf, qb, k, binary_oversample, int8_oversample):
         K = min(k * binary_oversample, self.n_total)
-        self._ws = _workspace(self._ws, N.load().vrq_shard_search3_workspace_size, self.codes.shape[0], qf, K,
-                              self.device)
+        self._ws = _workspace(self._ws, "search3", self.codes.shape[0], qf, K, self.device)
         with torch.cuda.device(self.device):
             cnt, rows, d, s2, s3 = shard_search3(self.codes, self.x8, self.norms, qf, qb, K, 0, self.row0, None,
                                                  self._ws)
@@ -300,8 +340,7 @@ class ShardedSearch2:
 
     def local(self, qf, qb, k, binary_oversample):
         K = min(k * binary_oversample, self.n_total)
-        self._ws = _workspace(self._ws, N.load().vrq_shard_search2_workspace_size, self.codes.shape[0], qf, K,
-                              self.device)
+        self._ws = _workspace(self._ws, "search2", self.codes.shape[0], qf, K, self.device)
         with torch.cuda.device(self.device):
             cnt, rows, d, sc = shard_search2(self.mode, self.codes, self.q, qf, qb, K, self.minmax, self.limit, 0,
                                              self.row0, None, self._ws)

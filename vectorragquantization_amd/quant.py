@@ -180,7 +180,8 @@ def search2(mode: str, codes: torch.Tensor, q: torch.Tensor, qf: torch.Tensor, q
 
 
 def merge_shards2(cnt, rows, dist, score, k: int):
-    """``vrq_merge_shards2`` on the stacked [S, nq, K] outputs of ``vrq_shard_search2`` (``cnt`` [S, nq]) ->
+    """``vrq_merge_shards2`` (``vrq_merge_shards2_large`` for K > 1024) on the stacked [S, nq, K] outputs of
+    ``vrq_shard_search2`` (``cnt`` [S, nq]) ->
     (count, rows, dist, score, src): the two-phase result of the whole corpus, ``src`` = shard * K + position
     of each result in the stacked inputs (-1 for padding)."""
     S, nq, K = rows.shape
@@ -192,10 +193,18 @@ def merge_shards2(cnt, rows, dist, score, k: int):
     src = torch.empty((nq, k), dtype=torch.int32, device=dev)
     cnt, rows, dist, score = (t.contiguous() for t in (cnt, rows, dist, score))  # held until the launch returns
     lib = N.load()
+    # more than 1024 candidates per shard: vrq_merge_shards2_large, which takes a workspace
+    large = N.large_k(K, "merge_shards2")
+    name = "vrq_merge_shards2_large" if large else "vrq_merge_shards2"
+    extra = ()
     with torch.cuda.device(dev):
-        rc = lib.vrq_merge_shards2(S, nq, K, N.ptr(cnt), N.ptr(rows), N.ptr(dist), N.ptr(score), k, N.ptr(oc),
-                                   N.ptr(orow), N.ptr(od), N.ptr(osc), N.ptr(src), N.stream_handle(dev))
-    N.check(rc, "vrq_merge_shards2")
+        if large:
+            ws = torch.empty((max(8, lib.vrq_merge_shards_large_workspace_size(S, nq, K)),), dtype=torch.uint8,
+                             device=dev)
+            extra = (N.ptr(ws), ws.numel())
+        rc = getattr(lib, name)(S, nq, K, N.ptr(cnt), N.ptr(rows), N.ptr(dist), N.ptr(score), k, N.ptr(oc),
+                                N.ptr(orow), N.ptr(od), N.ptr(osc), N.ptr(src), *extra, N.stream_handle(dev))
+    N.check(rc, name)
     return oc, orow, od, osc, src
 
 
