@@ -406,6 +406,17 @@ int vrq_gemm_topk_plan(int32_t mode, int64_t n, int32_t dim, int32_t nq, int32_t
  * VRQ_GEMM_BINARY.  Hit rule of the MAIN pass: binary u = <a, bits> >= ceil(thr); cosine u =
  * f32(<a, x>) * (1 / f32(norm)) >= thr. */
 int vrq_gemm_topk_layout(int32_t mode, int64_t n, int32_t dim, int32_t nq, int32_t k, int64_t* info);
+/* The rest of that layout (additive; tests checking what the SAMPLE stage's query split leaves): info
+ * i64[4] = byte offsets of the per-query error bounds Delta (f64 [nq_pad], u units: |u - s'| <= Delta for
+ * every row), of alpha and of beta (f64 [nq_pad] each: a reference score s is s' = alpha s + beta in u
+ * units), and of the per-query flags the FINISH stage writes (i32 [nq]: 0 served, 2 retried, 1 left to
+ * the exact fallback).  Delta in u units, with rho = q/S - a, S = max|q| / 127 and eps = 2^-20:
+ *   VRQ_GEMM_BINARY       max(sum rho+, sum rho-) (1 + eps) + eps ||q/S||_1
+ *   VRQ_GEMM_INT8_COSINE  ||rho||_2 (1 + eps) + eps ||q/S||_2
+ *   VRQ_GEMM_FLOAT_IP     (||rho||_2 B0 + ||q/S||_2 B1) (1 + eps) + eps (||q/S||_2 + ||rho||_2) B0,
+ *                         (B0, B1) = the corpus bounds of vrq_flat_ip_prepare
+ * The SAMPLE stage sets thr = U - 2 Delta rounded down to f32, U = the k-th largest sample maximum. */
+int vrq_gemm_topk_prep_layout(int32_t mode, int64_t n, int32_t dim, int32_t nq, int32_t k, int64_t* info);
 int vrq_gemm_topk(int32_t mode, const uint8_t* codes, const int8_t* x8, const double* norms, int64_t n,
                   int32_t dim, int64_t row_offset, const float* qf, int32_t nq, int32_t k, int32_t flags,
                   int32_t* out_count, int64_t* out_rows, double* out_scores, void* workspace,

@@ -143,6 +143,30 @@ def test_gemm_plan_chunk_rows_fit_the_hit_stage():
     assert lib.vrq_gemm_topk_plan(1, 1000, 1024, 1, 10, info.ctypes.data) == N.VRQ_EUNSUPPORTED
 
 
+def test_gemm_prep_layout_completes_the_workspace_layout():
+    """vrq_gemm_topk_prep_layout reports the four offsets vrq_gemm_topk_layout leaves out (Delta, alpha,
+    beta, flags): in workspace order between the pieces and the list lengths, each array in its own
+    256-byte-aligned slot, for every mode; the same argument validation as the other two queries."""
+    lib = N.load()
+    plan, lay, prep = np.zeros(8, np.int64), np.zeros(8, np.int64), np.full(4, -1, np.int64)
+    for mode in (2, 3, 4):
+        for n, nq, k in ((1000, 1, 10), (70_001, 257, 10), (10_000_000, 1024, 1000)):
+            args = (mode, n, 1024, nq, k)
+            assert lib.vrq_gemm_topk_plan(*args, plan.ctypes.data) == N.VRQ_OK
+            assert lib.vrq_gemm_topk_layout(*args, lay.ctypes.data) == N.VRQ_OK
+            assert lib.vrq_gemm_topk_prep_layout(*args, prep.ctypes.data) == N.VRQ_OK
+            nq_pad, off_thr, off_cnt = int(lay[0]), int(lay[1]), int(lay[2])
+            off_delta, off_alpha, off_beta, off_flag = (int(x) for x in prep)
+            assert all(o % 256 == 0 for o in prep)
+            assert nq_pad * 1024 <= off_delta and off_delta + 8 * nq_pad <= off_alpha
+            assert off_alpha + 8 * nq_pad <= off_beta and off_beta + 8 * nq_pad <= off_thr
+            assert off_thr + 4 * nq_pad <= off_flag and off_flag + 4 * nq <= off_cnt < int(plan[6])
+    assert lib.vrq_gemm_topk_prep_layout(3, 1000, 1024, 1, 10, None) == N.VRQ_EINVAL
+    assert lib.vrq_gemm_topk_prep_layout(3, 1000, 512, 1, 10, prep.ctypes.data) == N.VRQ_EUNSUPPORTED
+    assert lib.vrq_gemm_topk_prep_layout(1, 1000, 1024, 1, 10, prep.ctypes.data) == N.VRQ_EUNSUPPORTED
+    assert lib.vrq_gemm_topk_prep_layout(3, 1000, 1024, 1, 1025, prep.ctypes.data) == N.VRQ_EUNSUPPORTED
+
+
 def test_no_dropped_kernel_stubs():
     """Every kernel the host code launches has its launch stub in the library: hipcc's host-side
     compile can drop a template kernel's stub without a diagnostic (a compound pointer expression

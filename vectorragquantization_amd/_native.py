@@ -126,6 +126,7 @@ SIGNATURES = {
     "vrq_gemm_topk_pieces": (C.c_int, []),
     "vrq_gemm_topk_plan": (C.c_int, [_I32, _I64, _I32, _I32, _I32, _P]),
     "vrq_gemm_topk_layout": (C.c_int, [_I32, _I64, _I32, _I32, _I32, _P]),
+    "vrq_gemm_topk_prep_layout": (C.c_int, [_I32, _I64, _I32, _I32, _I32, _P]),
     "vrq_gemm_topk": (C.c_int, [_I32, _P, _P, _P, _I64, _I32, _I64, _P, _I32, _I32, _I32, _P, _P, _P, _P, _SZ,
                                 _P]),
     "vrq_gemm_topk_dim_workspace_size": (_SZ, [_I32, _I64, _I32, _I32, _I32]),

@@ -1394,6 +1394,20 @@ extern "C" int vrq_gemm_topk_layout(int32_t mode, int64_t n, int32_t dim, int32_
   return VRQ_OK;
 }
 
+extern "C" int vrq_gemm_topk_prep_layout(int32_t mode, int64_t n, int32_t dim, int32_t nq, int32_t k,
+                                         int64_t* info) {
+  GemmPlan p;
+  if (!info) return VRQ_EINVAL;
+  if (!gemm_mode_ok(mode) || dim != DIM) return VRQ_EUNSUPPORTED;
+  const int rc = gemm_plan(n, nq, k, &p);
+  if (rc != VRQ_OK) return rc;
+  info[0] = (int64_t)p.off_delta;
+  info[1] = (int64_t)p.off_alpha;
+  info[2] = (int64_t)p.off_beta;
+  info[3] = (int64_t)p.off_flag;
+  return VRQ_OK;
+}
+
 extern "C" int vrq_gemm_topk(int32_t mode, const uint8_t* codes, const int8_t* x8, const double* norms, int64_t n,
                              int32_t dim, int64_t row_offset, const float* qf, int32_t nq, int32_t k, int32_t flags,
                              int32_t* out_count, int64_t* out_rows, double* out_scores, void* workspace,
