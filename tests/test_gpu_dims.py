@@ -386,7 +386,9 @@ def test_enhanced_db_384(tmp_path, dev):
     assert len(db2) == 700 and np.array_equal(check(db2), a)
 
 
-@pytest.mark.parametrize("cls,mode,d", [("VectorDBInt8Global", "int8g", 768), ("VectorDBInt4", "int4", 384)])
+@pytest.mark.parametrize("cls,mode,d", [("VectorDBInt8Global", "int8g", 768), ("VectorDBInt4", "int4", 384),
+                                        ("VectorDBInt8", "int8", 1536), ("VectorDBInt16Global", "int16g", 2048),
+                                        ("VectorDBInt4Global", "int4g", 2048)])
 def test_vectordb_classes_other_dims(tmp_path, dev, cls, mode, d):
     from vectorragquantization_amd import vectordb
     from vectorragquantization_amd.embed import TableProvider
@@ -399,6 +401,9 @@ def test_vectordb_classes_other_dims(tmp_path, dev, cls, mode, d):
     db.add_vectors(list(range(n)), F)
     ref = O.QuantVectorDB(mode, db.limit if db.limit is not None else 0.0, d)
     ref.add(list(range(n)), F)
+    # the codes the class stored on the device are the oracle's (ref.index.xb is O.encode_batch(mode, F,
+    # limit)[0], added once in this order): otherwise a wrong code moves both sides' candidates only by luck
+    assert np.array_equal(db.index.codes.cpu().numpy(), ref.index.xb)
     for cf in (False, True):
         ids, _, ham, sc = db.search_vectors(Q, 10, 10, cf)
         torch.cuda.synchronize()
