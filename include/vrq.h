@@ -536,6 +536,52 @@ int vrq_search2_large(int32_t mode, const uint8_t* codes, const void* q, const d
 int vrq_scan_large_plan(int64_t n, int32_t dim, int32_t nq, int32_t K, int64_t* info);
 
 /* ---------------------------------------------------------------------------
+ * Filtered search: a row allow-bitmap (additive to ABI version 1).  The nearest rows among a caller-chosen
+ * subset of the index -- a tenant, a date range, a permission set, the hits of a keyword pre-filter -- without
+ * copying that subset into an index of its own (FAISS: SearchParameters::sel = IDSelectorBitmap).
+ * vrq_hamming_topk_filtered / vrq_search3_filtered / vrq_search2_filtered / vrq_scan_filtered: the arguments
+ *   of vrq_hamming_topk_large / vrq_search3_large / vrq_search2_large / vrq_scan_large plus
+ *   allow  device pointer to ceil(n / 64) little-endian u64 words, 8-byte aligned: row r takes part iff bit
+ *          r & 63 of word r >> 6 is set (the bytes of FAISS's IDSelectorBitmap and of numpy's
+ *          packbits(mask, bitorder="little")).  Bits at positions >= n of the last word are ignored.  One
+ *          bitmap per call, shared by its queries; it is only read.
+ *   Every output equals, bit for bit, that of the *_large call on the corpus with the disallowed rows removed
+ *   in row order (the corpus remove_ids would leave), row numbers mapped back: Phase I = the min(K, allowed)
+ *   smallest allowed rows by (dist, row), padding INT32_MAX / -1 / NaN; out_count = min(k, K, allowed), or
+ *   min(K, allowed) with VRQ_SEARCH_PHASE1_ONLY.  rescore_row[r] keeps its meaning: the filter decides whether
+ *   row r is a Phase-I candidate, its scores come from row rescore_row[r] whether or not that row is allowed.
+ *   An all-ones bitmap gives the *_large outputs; with an all-zero one every count is 0 and every output
+ *   padding.  Shapes, flags, return codes and the workspace (= the *_large one: the bitmap is the caller's)
+ *   are those of the *_large calls -- any 1 <= K <= VRQ_K_LARGE_MAX at every dim of vrq_dim_supported,
+ *   n < 2^32; n, nq, K or k = 0 behave as there (and read no bitmap).  A null or misaligned allow of a
+ *   non-empty call returns VRQ_EINVAL; every argument is checked before anything is launched.
+ * Only the counting scan K1h reads the bitmap (one word per 64-row tile, a scalar load): it serves every K,
+ *   and is a VALU scan meant for small and medium batches.  There is no filtered matrix-core scan, no
+ *   per-query bitmap and no filtered sharded call.
+ * ------------------------------------------------------------------------- */
+size_t vrq_scan_filtered_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K);
+int vrq_scan_filtered(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq, int32_t K,
+                      int32_t stages, const uint64_t* allow, void* workspace, size_t workspace_bytes,
+                      void* stream);
+size_t vrq_hamming_topk_filtered_workspace_size(int64_t n, int32_t code_bytes, int32_t nq, int32_t k);
+int vrq_hamming_topk_filtered(const uint8_t* codes, int64_t n, int32_t code_bytes, int64_t row_offset,
+                              const uint8_t* queries, int32_t nq, int32_t k, const uint64_t* allow,
+                              int32_t* out_dist, int64_t* out_rows, void* workspace, size_t workspace_bytes,
+                              void* stream);
+size_t vrq_search3_filtered_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K);
+int vrq_search3_filtered(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
+                         int64_t n, int32_t dim, int64_t row_offset, const float* qf, const uint8_t* qb, int32_t nq,
+                         int32_t k, int32_t K, int32_t K3, int32_t flags, const uint64_t* allow, int32_t* out_count,
+                         int64_t* out_rows, int32_t* out_dist, double* out_binary, double* out_cosine,
+                         void* workspace, size_t workspace_bytes, void* stream);
+size_t vrq_search2_filtered_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K);
+int vrq_search2_filtered(int32_t mode, const uint8_t* codes, const void* q, const double* minmax, double limit,
+                         const int64_t* rescore_row, int64_t n, int32_t dim, int64_t row_offset, const float* qf,
+                         const uint8_t* qb, int32_t nq, int32_t k, int32_t K, int32_t flags, const uint64_t* allow,
+                         int32_t* out_count, int64_t* out_rows, int32_t* out_dist, double* out_score,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Row-sharded search with more than 1024 Phase-I candidates (additive to ABI version 1; vrq_shard_search3,
  * vrq_shard_search2, vrq_merge_shards and vrq_merge_shards2 keep their K <= 1024 contract).
  * vrq_shard_search3_large / vrq_shard_search2_large: the arguments and outputs of vrq_shard_search3 /

@@ -122,6 +122,16 @@ SIGNATURES = {
                                           _P]),
     "vrq_scan_large_plan": (C.c_int, [_I64, _I32, _I32, _I32, _P]),
     "vrq_scan_large": (C.c_int, [_P, _I64, _I32, _P, _I32, _I32, _I32, _P, _SZ, _P]),
+    "vrq_scan_filtered_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
+    "vrq_scan_filtered": (C.c_int, [_P, _I64, _I32, _P, _I32, _I32, _I32, _P, _P, _SZ, _P]),
+    "vrq_hamming_topk_filtered_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
+    "vrq_hamming_topk_filtered": (C.c_int, [_P, _I64, _I32, _I64, _P, _I32, _I32, _P, _P, _P, _P, _SZ, _P]),
+    "vrq_search3_filtered_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
+    "vrq_search3_filtered": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _P,
+                                       _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "vrq_search2_filtered_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
+    "vrq_search2_filtered": (C.c_int, [_I32, _P, _P, _P, _D, _P, _I64, _I32, _I64, _P, _P, _I32, _I32, _I32, _I32,
+                                       _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "vrq_gemm_topk_workspace_size": (_SZ, [_I32, _I64, _I32, _I32, _I32]),
     "vrq_gemm_topk_pieces": (C.c_int, []),
     "vrq_gemm_topk_plan": (C.c_int, [_I32, _I64, _I32, _I32, _I32, _P]),
@@ -229,6 +239,15 @@ def large_k(K: int, what: str) -> bool:
         raise VrqNativeError(f"{what}: K = {K} Phase-I candidates (k * binary_oversample) exceed the limit "
                              f"of {VRQ_K_LARGE_MAX}")
     return K > VRQ_K_MAX
+
+
+def filtered_k(K: int, flags: int, what: str) -> None:
+    """A search with a row bitmap takes the *_filtered call (K1h) for every K up to VRQ_K_LARGE_MAX: raises for
+    a K beyond that, and for the sharded mode and the scan flags, which the counting scan does not take."""
+    large_k(K, what)
+    if flags & ~VRQ_SEARCH_PHASE1_ONLY:
+        raise VrqNativeError(f"{what}: flags {flags} with a row filter (the filtered calls take no "
+                             "VRQ_SEARCH_SHARD and no scan flags)")
 
 
 def check(rc: int, what: str) -> None:

@@ -111,11 +111,26 @@ __device__ __forceinline__ int xcd_linear_block() {
   return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
 }
 
+// The filtered instances (FILTER; vrq_*_filtered): `allow` holds one bit per row, bit r & 63 of the u64 word
+// r >> 6.  Chunks start at multiples of 64 rows, so the filter of a 64-row tile is the one aligned word
+// (row0 >> 6) + tile: a wave-uniform address, read like the query words through the constant address space
+// (the bitmap is read-only for the kernel's lifetime).  That makes it a scalar load on the lgkm counter; a
+// vector load would join the ring's DMA pieces on the vm counter and break the wait_vmcnt<C> accounting.
+// A disallowed row is a dead lane of both passes, exactly like a row past the ragged last tile.  `allow` is
+// the last kernel argument and the threshold's minimum is compiled into the filtered instance only, so the
+// unfiltered count and emit instances are, instruction for instruction, what they were without the FILTER axis
+// (the threshold's differs in the LDS offsets of its arrays alone).
+__device__ __forceinline__ uint64_t allow_word(const uint64_t* allow, int64_t row0, int tile) {
+  typedef const __attribute__((address_space(4))) uint64_t* const_u64_ptr;
+  const int idx = __builtin_amdgcn_readfirstlane((int)(row0 >> 6) + tile);  // n < 2^32: below 2^26
+  return ((const_u64_ptr)(uintptr_t)allow)[idx];
+}
+
 // ---- count: histogram of the distances per (query, chunk) over rows [0, n) ----
-template <int CB>
+template <int CB, bool FILTER>
 __global__ __launch_bounds__(64 * large_waves(CB)) void hamming_count_kernel(
     const uint8_t* __restrict__ codes, int64_t n, const uint8_t* __restrict__ queries, int nq, int64_t chunk_rows,
-    int nchunks, int nqg, uint32_t* __restrict__ hist_out) {
+    int nchunks, int nqg, uint32_t* __restrict__ hist_out, const uint64_t* __restrict__ allow) {
   using Ring = TileRing<CB>;
   constexpr int C = Ring::C, NW = large_waves(CB), QG = large_qg(CB), BINS = CB * 8 + 1;
   __shared__ __attribute__((aligned(16))) uint8_t ring[NW * 2 * Ring::TILE];
@@ -147,7 +162,12 @@ __global__ __launch_bounds__(64 * large_waves(CB)) void hamming_count_kernel(
     v4u rv[C];
     tr.read(i & 1, rv);
     if (i + 2 < ntw) tr.issue(w + (i + 2) * NW, i & 1);  // (the slot's reads are retired)
-    const bool live = (w + i * NW) * 64 + l < nrows;
+    bool live = (w + i * NW) * 64 + l < nrows;
+    if constexpr (FILTER) {
+      const uint64_t word = allow_word(allow, row0, w + i * NW);
+      if (word == 0) continue;  // no allowed row in this tile (wave-uniform; its loads were issued and waited)
+      live = live && ((word >> l) & 1);
+    }
     for (int j = 0; j < nqa; ++j) {
       const uint32_t d = Ring::distance(rv, queries, q0 + j);
       if (live) atomicAdd(&hist[j * BINS + d], 1u);
@@ -181,8 +201,10 @@ __device__ inline int thr_excl_scan(int v, int* tot, int32_t* scratch) {
   return incl - v;
 }
 
-// hist u32 [nq][nchunks][bins].  want = min(K, n).  Writes tc[q] = (T, c_lt), prefix[q][chunk] = (lt prefix,
+// hist u32 [nq][nchunks][bins].  want = min(K, n); a filtered scan (FILTER) lowers it to the total of the
+// histograms, the number of allowed rows (an unfiltered scan's total is n).  Writes tc[q] = (T, c_lt), prefix[q][chunk] = (lt prefix,
 // eq prefix, lt count, eq count) and the KEY_NONE padding of the K-list past `want`.
+template <bool FILTER>
 __global__ __launch_bounds__(THR_THREADS) void large_threshold_kernel(const uint32_t* __restrict__ hist, int nchunks,
                                                                       int bins, int want, int K,
                                                                       int32_t* __restrict__ tc,
@@ -216,6 +238,9 @@ __global__ __launch_bounds__(THR_THREADS) void large_threshold_kernel(const uint
   }
   int all;
   int cum = thr_excl_scan(local, &all, scratch);
+  if constexpr (FILTER) {
+    if ((uint32_t)all < (uint32_t)want) want = all;  // fewer allowed rows than K
+  }
   for (int b = 0; b < BPT; ++b) {
     const int i = tid * BPT + b;
     if (i >= bins) break;
@@ -274,13 +299,14 @@ __global__ __launch_bounds__(THR_THREADS) void large_threshold_kernel(const uint
 }
 
 // ---- emit: one wave per (chunk, LARGE_QE queries), rows in order ----
-template <int CB>
+template <int CB, bool FILTER>
 __global__ __launch_bounds__(64) void hamming_emit_kernel(const uint8_t* __restrict__ codes, int64_t n,
                                                           const uint8_t* __restrict__ queries, int nq, int K,
                                                           int64_t chunk_rows, int nchunks, int nqg,
                                                           const int32_t* __restrict__ tc,
                                                           const int32_t* __restrict__ prefix,
-                                                          uint64_t* __restrict__ lists) {
+                                                          uint64_t* __restrict__ lists,
+                                                          const uint64_t* __restrict__ allow) {
   using Ring = TileRing<CB>;
   constexpr int C = Ring::C, QE = LARGE_QE;
   __shared__ __attribute__((aligned(16))) uint8_t ring[2 * Ring::TILE];
@@ -322,7 +348,12 @@ __global__ __launch_bounds__(64) void hamming_emit_kernel(const uint8_t* __restr
     tr.read(i & 1, rv);
     if (i + 2 < ntiles) tr.issue(i + 2, i & 1);
     const int local = i * 64 + l;
-    const bool live = local < nrows;
+    bool live = local < nrows;
+    if constexpr (FILTER) {
+      const uint64_t word = allow_word(allow, row0, i);
+      if (word == 0) continue;  // (wave-uniform, as in the count kernel)
+      live = live && ((word >> l) & 1);
+    }
 #pragma unroll
     for (int j = 0; j < QE; ++j) {
       if (j < nqa) {
@@ -415,20 +446,31 @@ int large_plan(int64_t n, int cb, int nq, int K, LargePlan* p) {
 
 template <int CB>
 static int count_launch(const uint8_t* codes, int64_t n, const uint8_t* q, int nq, int64_t chunk_rows, int nchunks,
-                        uint32_t* hist, hipStream_t s) {
+                        const uint64_t* allow, uint32_t* hist, hipStream_t s) {
   const int nqg = (nq + large_qg(CB) - 1) / large_qg(CB);
-  hipLaunchKernelGGL((hamming_count_kernel<CB>), dim3((unsigned)(nchunks * nqg)), dim3(64 * large_waves(CB)), 0, s,
-                     codes, n, q, nq, chunk_rows, nchunks, nqg, hist);
+  const dim3 grid((unsigned)(nchunks * nqg)), block(64 * large_waves(CB));
+  if (allow)
+    hipLaunchKernelGGL((hamming_count_kernel<CB, true>), grid, block, 0, s, codes, n, q, nq, chunk_rows, nchunks,
+                       nqg, hist, allow);
+  else
+    hipLaunchKernelGGL((hamming_count_kernel<CB, false>), grid, block, 0, s, codes, n, q, nq, chunk_rows, nchunks,
+                       nqg, hist, allow);
   VRQ_LAUNCH_CHECK();
   return VRQ_OK;
 }
 
 template <int CB>
 static int emit_launch(const uint8_t* codes, int64_t n, const uint8_t* q, int nq, int K, int64_t chunk_rows,
-                       int nchunks, const int32_t* tc, const int32_t* prefix, uint64_t* lists, hipStream_t s) {
+                       int nchunks, const uint64_t* allow, const int32_t* tc, const int32_t* prefix,
+                       uint64_t* lists, hipStream_t s) {
   const int nqg = (nq + LARGE_QE - 1) / LARGE_QE;
-  hipLaunchKernelGGL((hamming_emit_kernel<CB>), dim3((unsigned)(nchunks * nqg)), dim3(64), 0, s, codes, n, q, nq, K,
-                     chunk_rows, nchunks, nqg, tc, prefix, lists);
+  const dim3 grid((unsigned)(nchunks * nqg)), block(64);
+  if (allow)
+    hipLaunchKernelGGL((hamming_emit_kernel<CB, true>), grid, block, 0, s, codes, n, q, nq, K, chunk_rows, nchunks,
+                       nqg, tc, prefix, lists, allow);
+  else
+    hipLaunchKernelGGL((hamming_emit_kernel<CB, false>), grid, block, 0, s, codes, n, q, nq, K, chunk_rows, nchunks,
+                       nqg, tc, prefix, lists, allow);
   VRQ_LAUNCH_CHECK();
   return VRQ_OK;
 }
@@ -436,28 +478,32 @@ static int emit_launch(const uint8_t* codes, int64_t n, const uint8_t* q, int nq
 // one pass (at most kLargeQueryBatch queries): the pointers are the pass's own slices
 template <int CB>
 static int large_pass(const LargePlan& p, const uint8_t* codes, int64_t n, const uint8_t* q, int nq, int K,
-                      uint32_t* hist, int32_t* prefix, int32_t* tc, uint64_t* lists, hipStream_t s, int stages) {
+                      const uint64_t* allow, uint32_t* hist, int32_t* prefix, int32_t* tc, uint64_t* lists, hipStream_t s, int stages) {
   constexpr int bins = CB * 8 + 1;
   int rc;
   if (stages & kLargeStageCount) {
-    rc = count_launch<CB>(codes, n, q, nq, p.chunk_rows, p.nchunks, hist, s);
+    rc = count_launch<CB>(codes, n, q, nq, p.chunk_rows, p.nchunks, allow, hist, s);
     if (rc != VRQ_OK) return rc;
   }
   if (stages & kLargeStageThreshold) {
     const int want = (int64_t)K < n ? K : (int)n;
-    hipLaunchKernelGGL(large_threshold_kernel, dim3(nq), dim3(THR_THREADS), 0, s, hist, p.nchunks, bins, want, K,
-                       tc, prefix, lists);
+    if (allow)
+      hipLaunchKernelGGL(large_threshold_kernel<true>, dim3(nq), dim3(THR_THREADS), 0, s, hist, p.nchunks, bins,
+                         want, K, tc, prefix, lists);
+    else
+      hipLaunchKernelGGL(large_threshold_kernel<false>, dim3(nq), dim3(THR_THREADS), 0, s, hist, p.nchunks, bins,
+                         want, K, tc, prefix, lists);
     VRQ_LAUNCH_CHECK();
   }
   if (stages & kLargeStageEmit) {
-    rc = emit_launch<CB>(codes, n, q, nq, K, p.chunk_rows, p.nchunks, tc, prefix, lists, s);
+    rc = emit_launch<CB>(codes, n, q, nq, K, p.chunk_rows, p.nchunks, allow, tc, prefix, lists, s);
     if (rc != VRQ_OK) return rc;
   }
   return VRQ_OK;
 }
 
 int large_scan_launch(const LargePlan& p, const uint8_t* codes, int64_t n, int cb, const uint8_t* q, int nq, int K,
-                      uint8_t* ws, hipStream_t s, int stages) {
+                      uint8_t* ws, hipStream_t s, int stages, const uint64_t* allow) {
   if (p.nchunks < 1 || p.nchunks > kLargeMaxChunks) return VRQ_EINVAL;  // not a K1h plan
   if (!(stages & kLargeStageAll)) stages |= kLargeStageAll;
   uint32_t* hist = (uint32_t*)(ws + p.off_hist);
@@ -469,13 +515,13 @@ int large_scan_launch(const LargePlan& p, const uint8_t* codes, int64_t n, int c
     const uint8_t* qb = q + (int64_t)b0 * cb;
     int rc;
     switch (cb) {
-      case 32: rc = large_pass<32>(p, codes, n, qb, nb, K, hist, prefix, tc, lists, s, stages); break;
-      case 48: rc = large_pass<48>(p, codes, n, qb, nb, K, hist, prefix, tc, lists, s, stages); break;
-      case 64: rc = large_pass<64>(p, codes, n, qb, nb, K, hist, prefix, tc, lists, s, stages); break;
-      case 96: rc = large_pass<96>(p, codes, n, qb, nb, K, hist, prefix, tc, lists, s, stages); break;
-      case 128: rc = large_pass<128>(p, codes, n, qb, nb, K, hist, prefix, tc, lists, s, stages); break;
-      case 192: rc = large_pass<192>(p, codes, n, qb, nb, K, hist, prefix, tc, lists, s, stages); break;
-      case 256: rc = large_pass<256>(p, codes, n, qb, nb, K, hist, prefix, tc, lists, s, stages); break;
+      case 32: rc = large_pass<32>(p, codes, n, qb, nb, K, allow, hist, prefix, tc, lists, s, stages); break;
+      case 48: rc = large_pass<48>(p, codes, n, qb, nb, K, allow, hist, prefix, tc, lists, s, stages); break;
+      case 64: rc = large_pass<64>(p, codes, n, qb, nb, K, allow, hist, prefix, tc, lists, s, stages); break;
+      case 96: rc = large_pass<96>(p, codes, n, qb, nb, K, allow, hist, prefix, tc, lists, s, stages); break;
+      case 128: rc = large_pass<128>(p, codes, n, qb, nb, K, allow, hist, prefix, tc, lists, s, stages); break;
+      case 192: rc = large_pass<192>(p, codes, n, qb, nb, K, allow, hist, prefix, tc, lists, s, stages); break;
+      case 256: rc = large_pass<256>(p, codes, n, qb, nb, K, allow, hist, prefix, tc, lists, s, stages); break;
       default: return VRQ_EUNSUPPORTED;
     }
     if (rc != VRQ_OK) return rc;

@@ -1752,6 +1752,23 @@ size_t vrq_hamming_topk_large_workspace_size(int64_t n, int32_t code_bytes, int3
   return code_bytes > 0 && code_bytes <= 256 ? vrq_search3_large_workspace_size(n, code_bytes * 8, nq, k) : 0;
 }
 
+// the filtered calls need no more: the bitmap is the caller's
+size_t vrq_search3_filtered_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K) {
+  return vrq_search3_large_workspace_size(n, dim, nq, K);
+}
+
+size_t vrq_search2_filtered_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K) {
+  return vrq_search3_large_workspace_size(n, dim, nq, K);
+}
+
+size_t vrq_hamming_topk_filtered_workspace_size(int64_t n, int32_t code_bytes, int32_t nq, int32_t k) {
+  return vrq_hamming_topk_large_workspace_size(n, code_bytes, nq, k);
+}
+
+size_t vrq_scan_filtered_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K) {
+  return vrq_search3_large_workspace_size(n, dim, nq, K);
+}
+
 // the plan of a call that scans (n, nq, K >= 1) and the workspace check, before anything is launched
 static int large_plan_checked(int64_t n, int cb, int nq, int K, size_t workspace_bytes, LargePlan* p) {
   const int rc = large_plan(n, cb, nq, K, p);
@@ -1759,22 +1776,40 @@ static int large_plan_checked(int64_t n, int cb, int nq, int K, size_t workspace
   return workspace_bytes < p->bytes ? VRQ_EWORKSPACE : VRQ_OK;
 }
 
-int vrq_scan_large(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq, int32_t K,
-                   int32_t stages, void* workspace, size_t workspace_bytes, void* stream) {
+// The filtered calls (vrq_*_filtered) are the *_large calls with a row bitmap handed to K1h: `filtered` asks
+// for the bitmap, which is checked with the other pointers a non-empty call reads, before any launch.
+static bool allow_ok(const uint64_t* allow) { return allow && ((uintptr_t)allow & 7) == 0; }
+
+static int scan_large_impl(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq, int32_t K,
+                           int32_t stages, void* workspace, size_t workspace_bytes, void* stream, bool filtered,
+                           const uint64_t* allow) {
   VRQ_CHECK_ARG(n >= 0 && nq >= 0 && K >= 0);
   if (!vrq_dim_supported(dim) || K > VRQ_K_LARGE_MAX) return VRQ_EUNSUPPORTED;
   if (stages & ~kLargeStageAll) return VRQ_EUNSUPPORTED;
   if (nq == 0 || n == 0 || K == 0) return VRQ_OK;
   VRQ_CHECK_ARG(codes && qb && workspace);
+  if (filtered) VRQ_CHECK_ARG(allow_ok(allow));
   LargePlan p;
   const int rc = large_plan_checked(n, dim / 8, nq, K, workspace_bytes, &p);
   if (rc != VRQ_OK) return rc;
-  return large_scan_launch(p, codes, n, dim / 8, qb, nq, K, (uint8_t*)workspace, (hipStream_t)stream, stages);
+  return large_scan_launch(p, codes, n, dim / 8, qb, nq, K, (uint8_t*)workspace, (hipStream_t)stream, stages,
+                           allow);
 }
 
-int vrq_hamming_topk_large(const uint8_t* codes, int64_t n, int32_t code_bytes, int64_t row_offset,
-                           const uint8_t* queries, int32_t nq, int32_t k, int32_t* out_dist, int64_t* out_rows,
-                           void* workspace, size_t workspace_bytes, void* stream) {
+int vrq_scan_large(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq, int32_t K,
+                   int32_t stages, void* workspace, size_t workspace_bytes, void* stream) {
+  return scan_large_impl(codes, n, dim, qb, nq, K, stages, workspace, workspace_bytes, stream, false, nullptr);
+}
+
+int vrq_scan_filtered(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq, int32_t K,
+                      int32_t stages, const uint64_t* allow, void* workspace, size_t workspace_bytes, void* stream) {
+  return scan_large_impl(codes, n, dim, qb, nq, K, stages, workspace, workspace_bytes, stream, true, allow);
+}
+
+static int hamming_topk_large_impl(const uint8_t* codes, int64_t n, int32_t code_bytes, int64_t row_offset,
+                                   const uint8_t* queries, int32_t nq, int32_t k, int32_t* out_dist,
+                                   int64_t* out_rows, void* workspace, size_t workspace_bytes, void* stream,
+                                   bool filtered, const uint64_t* allow) {
   VRQ_CHECK_ARG(n >= 0 && nq >= 0 && k >= 0 && out_dist && out_rows);
   if (code_bytes <= 0 || code_bytes > 256 || !vrq_dim_supported(code_bytes * 8) || k > VRQ_K_LARGE_MAX)
     return VRQ_EUNSUPPORTED;
@@ -1782,21 +1817,38 @@ int vrq_hamming_topk_large(const uint8_t* codes, int64_t n, int32_t code_bytes, 
   if (nq == 0) return VRQ_OK;
   if (n == 0 || k == 0) return fill_empty(nq, k, nullptr, out_rows, out_dist, nullptr, nullptr, s);
   VRQ_CHECK_ARG(codes && queries && workspace);
+  if (filtered) VRQ_CHECK_ARG(allow_ok(allow));
   LargePlan p;
   int rc = large_plan_checked(n, code_bytes, nq, k, workspace_bytes, &p);
   if (rc != VRQ_OK) return rc;
   uint8_t* ws = (uint8_t*)workspace;
-  rc = large_scan_launch(p, codes, n, code_bytes, queries, nq, k, ws, s, 0);
+  rc = large_scan_launch(p, codes, n, code_bytes, queries, nq, k, ws, s, 0, allow);
   if (rc != VRQ_OK) return rc;
   return large_sort_launch(s, nq, (uint64_t*)(ws + p.off_lists), k, (int32_t*)(ws + p.off_kp), true, row_offset,
                            nullptr, out_rows, out_dist);
 }
 
-int vrq_search3_large(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
-                      int64_t n, int32_t dim, int64_t row_offset, const float* qf, const uint8_t* qb, int32_t nq,
-                      int32_t k, int32_t K, int32_t K3, int32_t flags, int32_t* out_count, int64_t* out_rows,
-                      int32_t* out_dist, double* out_binary, double* out_cosine, void* workspace,
-                      size_t workspace_bytes, void* stream) {
+int vrq_hamming_topk_large(const uint8_t* codes, int64_t n, int32_t code_bytes, int64_t row_offset,
+                           const uint8_t* queries, int32_t nq, int32_t k, int32_t* out_dist, int64_t* out_rows,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+  return hamming_topk_large_impl(codes, n, code_bytes, row_offset, queries, nq, k, out_dist, out_rows, workspace,
+                                 workspace_bytes, stream, false, nullptr);
+}
+
+int vrq_hamming_topk_filtered(const uint8_t* codes, int64_t n, int32_t code_bytes, int64_t row_offset,
+                              const uint8_t* queries, int32_t nq, int32_t k, const uint64_t* allow,
+                              int32_t* out_dist, int64_t* out_rows, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+  return hamming_topk_large_impl(codes, n, code_bytes, row_offset, queries, nq, k, out_dist, out_rows, workspace,
+                                 workspace_bytes, stream, true, allow);
+}
+
+static int search3_large_impl(const uint8_t* codes, const int8_t* x8, const double* norms,
+                              const int64_t* rescore_row, int64_t n, int32_t dim, int64_t row_offset,
+                              const float* qf, const uint8_t* qb, int32_t nq, int32_t k, int32_t K, int32_t K3,
+                              int32_t flags, int32_t* out_count, int64_t* out_rows, int32_t* out_dist,
+                              double* out_binary, double* out_cosine, void* workspace, size_t workspace_bytes,
+                              void* stream, bool filtered, const uint64_t* allow) {
   VRQ_CHECK_ARG(n >= 0 && nq >= 0 && k >= 0 && K >= 0 && K3 >= 0);
   VRQ_CHECK_ARG(out_count && out_rows && out_dist);
   if (!vrq_dim_supported(dim) || K > VRQ_K_LARGE_MAX || k > VRQ_K_LARGE_MAX) return VRQ_EUNSUPPORTED;
@@ -1810,6 +1862,7 @@ int vrq_search3_large(const uint8_t* codes, const int8_t* x8, const double* norm
     return fill_empty(nq, kout, out_count, out_rows, out_dist, out_binary, out_cosine, s);
   VRQ_CHECK_ARG(codes && qb && workspace);
   if (!p1) VRQ_CHECK_ARG(qf && x8 && norms);
+  if (filtered) VRQ_CHECK_ARG(allow_ok(allow));
   LargePlan p;
   int rc = large_plan_checked(n, dim / 8, nq, K, workspace_bytes, &p);
   if (rc != VRQ_OK) return rc;
@@ -1819,7 +1872,7 @@ int vrq_search3_large(const uint8_t* codes, const int8_t* x8, const double* norm
   int32_t* ord = (int32_t*)(ws + p.off_ord);
   double* s2 = (double*)(ws + p.off_s2);
   double* s3 = (double*)(ws + p.off_s3);
-  rc = large_scan_launch(p, codes, n, dim / 8, qb, nq, K, ws, s, 0);
+  rc = large_scan_launch(p, codes, n, dim / 8, qb, nq, K, ws, s, 0, allow);
   if (rc != VRQ_OK) return rc;
   rc = large_sort_launch(s, nq, lists, K, kp, p1, row_offset, out_count, out_rows, out_dist);
   if (rc != VRQ_OK || p1) return rc;
@@ -1871,11 +1924,32 @@ int vrq_search3_large(const uint8_t* codes, const int8_t* x8, const double* norm
   return large_order_launch(s, nq, fa);
 }
 
-int vrq_search2_large(int32_t mode, const uint8_t* codes, const void* q, const double* minmax, double limit,
-                      const int64_t* rescore_row, int64_t n, int32_t dim, int64_t row_offset, const float* qf,
-                      const uint8_t* qb, int32_t nq, int32_t k, int32_t K, int32_t flags, int32_t* out_count,
-                      int64_t* out_rows, int32_t* out_dist, double* out_score, void* workspace,
+int vrq_search3_large(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
+                      int64_t n, int32_t dim, int64_t row_offset, const float* qf, const uint8_t* qb, int32_t nq,
+                      int32_t k, int32_t K, int32_t K3, int32_t flags, int32_t* out_count, int64_t* out_rows,
+                      int32_t* out_dist, double* out_binary, double* out_cosine, void* workspace,
                       size_t workspace_bytes, void* stream) {
+  return search3_large_impl(codes, x8, norms, rescore_row, n, dim, row_offset, qf, qb, nq, k, K, K3, flags,
+                            out_count, out_rows, out_dist, out_binary, out_cosine, workspace, workspace_bytes, stream,
+                            false, nullptr);
+}
+
+int vrq_search3_filtered(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
+                         int64_t n, int32_t dim, int64_t row_offset, const float* qf, const uint8_t* qb, int32_t nq,
+                         int32_t k, int32_t K, int32_t K3, int32_t flags, const uint64_t* allow, int32_t* out_count,
+                         int64_t* out_rows, int32_t* out_dist, double* out_binary, double* out_cosine,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+  return search3_large_impl(codes, x8, norms, rescore_row, n, dim, row_offset, qf, qb, nq, k, K, K3, flags,
+                            out_count, out_rows, out_dist, out_binary, out_cosine, workspace, workspace_bytes, stream,
+                            true, allow);
+}
+
+static int search2_large_impl(int32_t mode, const uint8_t* codes, const void* q, const double* minmax, double limit,
+                              const int64_t* rescore_row, int64_t n, int32_t dim, int64_t row_offset,
+                              const float* qf, const uint8_t* qb, int32_t nq, int32_t k, int32_t K, int32_t flags,
+                              int32_t* out_count, int64_t* out_rows, int32_t* out_dist, double* out_score,
+                              void* workspace, size_t workspace_bytes, void* stream, bool filtered,
+                              const uint64_t* allow) {
   VRQ_CHECK_ARG(search2_mode_ok(mode));
   VRQ_CHECK_ARG(n >= 0 && nq >= 0 && k >= 0 && K >= 0);
   VRQ_CHECK_ARG(out_count && out_rows && out_dist && out_score);
@@ -1887,6 +1961,7 @@ int vrq_search2_large(int32_t mode, const uint8_t* codes, const void* q, const d
   if (n == 0 || K == 0 || k == 0) return fill_empty(nq, k, out_count, out_rows, out_dist, out_score, nullptr, s);
   VRQ_CHECK_ARG(codes && qb && workspace && qf && q);
   if (mode == VRQ_ENC_INT8_LOCAL || mode == VRQ_ENC_INT4_LOCAL) VRQ_CHECK_ARG(minmax);
+  if (filtered) VRQ_CHECK_ARG(allow_ok(allow));
   LargePlan p;
   int rc = large_plan_checked(n, dim / 8, nq, K, workspace_bytes, &p);
   if (rc != VRQ_OK) return rc;
@@ -1894,7 +1969,7 @@ int vrq_search2_large(int32_t mode, const uint8_t* codes, const void* q, const d
   uint64_t* lists = (uint64_t*)(ws + p.off_lists);
   int32_t* kp = (int32_t*)(ws + p.off_kp);
   double* s2 = (double*)(ws + p.off_s2);
-  rc = large_scan_launch(p, codes, n, dim / 8, qb, nq, K, ws, s, 0);
+  rc = large_scan_launch(p, codes, n, dim / 8, qb, nq, K, ws, s, 0, allow);
   if (rc != VRQ_OK) return rc;
   rc = large_sort_launch(s, nq, lists, K, kp, false, 0, nullptr, nullptr, nullptr);
   if (rc != VRQ_OK) return rc;
@@ -1926,6 +2001,26 @@ int vrq_search2_large(int32_t mode, const uint8_t* codes, const void* q, const d
   fa.out_dist = out_dist;
   fa.out_s2 = out_score;
   return large_order_launch(s, nq, fa);
+}
+
+int vrq_search2_large(int32_t mode, const uint8_t* codes, const void* q, const double* minmax, double limit,
+                      const int64_t* rescore_row, int64_t n, int32_t dim, int64_t row_offset, const float* qf,
+                      const uint8_t* qb, int32_t nq, int32_t k, int32_t K, int32_t flags, int32_t* out_count,
+                      int64_t* out_rows, int32_t* out_dist, double* out_score, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+  return search2_large_impl(mode, codes, q, minmax, limit, rescore_row, n, dim, row_offset, qf, qb, nq, k, K, flags,
+                            out_count, out_rows, out_dist, out_score, workspace, workspace_bytes, stream, false,
+                            nullptr);
+}
+
+int vrq_search2_filtered(int32_t mode, const uint8_t* codes, const void* q, const double* minmax, double limit,
+                         const int64_t* rescore_row, int64_t n, int32_t dim, int64_t row_offset, const float* qf,
+                         const uint8_t* qb, int32_t nq, int32_t k, int32_t K, int32_t flags, const uint64_t* allow,
+                         int32_t* out_count, int64_t* out_rows, int32_t* out_dist, double* out_score,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+  return search2_large_impl(mode, codes, q, minmax, limit, rescore_row, n, dim, row_offset, qf, qb, nq, k, K, flags,
+                            out_count, out_rows, out_dist, out_score, workspace, workspace_bytes, stream, true,
+                            allow);
 }
 
 // ---- the per-shard calls for K up to VRQ_K_LARGE_MAX: K1h, the sort, the scores of every candidate ----

@@ -166,10 +166,12 @@ struct LargePlan {
 int large_plan(int64_t n, int cb, int nq, int K, LargePlan* p);
 // the whole scan (count, threshold, emit): leaves the K-lists at off_lists, KEY_NONE padded, the
 // dist < T part and the dist == T part each in row order.  stages: a mask of kLargeStage* (none = all).
+// allow: null, or the row bitmap of a filtered scan (u64 [ceil(n / 64)], bit r & 63 of word r >> 6: row r
+// takes part); the lists then hold the min(K, allowed) smallest allowed rows.
 constexpr int kLargeStageCount = VRQ_LARGE_STAGE_COUNT, kLargeStageThreshold = VRQ_LARGE_STAGE_THRESHOLD,
               kLargeStageEmit = VRQ_LARGE_STAGE_EMIT,
               kLargeStageAll = kLargeStageCount | kLargeStageThreshold | kLargeStageEmit;
 int large_scan_launch(const LargePlan& p, const uint8_t* codes, int64_t n, int cb, const uint8_t* q, int nq, int K,
-                      uint8_t* ws, hipStream_t s, int stages);
+                      uint8_t* ws, hipStream_t s, int stages, const uint64_t* allow = nullptr);
 
 }  // namespace vrq

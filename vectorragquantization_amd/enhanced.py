@@ -27,6 +27,7 @@ import torch
 
 from . import _native as N
 from .docstore import DocStoreError, RocksDictReader, is_rocksdict_dir
+from .filters import checked as checked_bitmap, ids_bitmap
 from .index import BinaryIndexIDMap2, _GrowBuffer, as_device_tensor
 from .quant import int8_row_norms
 
@@ -108,10 +109,14 @@ def gemm_topk(mode: str, qf: torch.Tensor, k: int, codes: torch.Tensor | None = 
     return cnt, rows, scores
 
 
-def search3_call(K: int, flags: int = 0) -> str:
+def search3_call(K: int, flags: int = 0, allow=None) -> str:
     """The entry point ``search3`` takes for K Phase-I candidates: ``vrq_search3_large`` (the counting scan
     K1h) for 1024 < K <= ``VRQ_K_LARGE_MAX`` outside the sharded mode, else ``vrq_search3_dim``; its workspace
-    size is ``<name>_workspace_size``."""
+    size is ``<name>_workspace_size``.  With a row bitmap ``allow``: ``vrq_search3_filtered`` for every K up
+    to ``VRQ_K_LARGE_MAX`` (it raises beyond, and with ``VRQ_SEARCH_SHARD`` or a scan flag)."""
+    if allow is not None:
+        N.filtered_k(K, flags, "search3")
+        return "vrq_search3_filtered"
     if not flags & N.VRQ_SEARCH_SHARD and N.large_k(K, "search3"):
         return "vrq_search3_large"
     return "vrq_search3_dim"
@@ -119,9 +124,10 @@ def search3_call(K: int, flags: int = 0) -> str:
 
 def search3(codes: torch.Tensor, x8: torch.Tensor, norms: torch.Tensor, qf: torch.Tensor, qb: torch.Tensor,
             k: int, K: int, K3: int, flags: int = 0, row_offset: int = 0, rescore_row: torch.Tensor | None = None,
-            workspace: torch.Tensor | None = None):
+            workspace: torch.Tensor | None = None, allow: torch.Tensor | None = None):
     """Thin wrapper of ``vrq_search3``; returns (count, rows, dist, s2, s3) device tensors.  More than 1024
-    Phase-I candidates (up to ``VRQ_K_LARGE_MAX``) take ``vrq_search3_large`` (not with ``VRQ_SEARCH_SHARD``)."""
+    Phase-I candidates (up to ``VRQ_K_LARGE_MAX``) take ``vrq_search3_large`` (not with ``VRQ_SEARCH_SHARD``).
+    ``allow`` (``filters.row_bitmap``): Phase I over the allowed rows only, ``vrq_search3_filtered``."""
     dev = qf.device
     nq = qf.shape[0]
     n = codes.shape[0]
@@ -138,10 +144,19 @@ def search3(codes: torch.Tensor, x8: torch.Tensor, norms: torch.Tensor, qf: torc
     if rescore_row is not None and rescore_row.shape[0] != n:
         raise N.VrqNativeError(f"vrq_search3: rescore_row has {rescore_row.shape[0]} entries for {n} rows")
     lib = N.load()
-    name = search3_call(K, flags)
+    name = search3_call(K, flags, allow)
     need = getattr(lib, name + "_workspace_size")(n, dim, nq, K) if n and nq and K else 0
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev)
+    if allow is not None:
+        allow = checked_bitmap(allow, n, dev)
+        rc = lib.vrq_search3_filtered(N.ptr(codes) if n else 0, N.ptr(x8) if n else 0, N.ptr(norms) if n else 0,
+                                      N.ptr(rescore_row), n, dim, row_offset, N.ptr(qf), N.ptr(qb), nq, k, K, K3,
+                                      flags, N.ptr(allow) if n else 0, N.ptr(cnt), N.ptr(rows), N.ptr(dist),
+                                      N.ptr(s2), N.ptr(s3), N.ptr(workspace), workspace.numel(),
+                                      N.stream_handle(dev))
+        N.check(rc, name)
+        return cnt, rows, dist, s2, s3
     rc = getattr(lib, name)(N.ptr(codes) if n else 0, N.ptr(x8) if n else 0, N.ptr(norms) if n else 0,
                             N.ptr(rescore_row), n, dim, row_offset, N.ptr(qf), N.ptr(qb), nq, k, K, K3, flags,
                             N.ptr(cnt), N.ptr(rows), N.ptr(dist), N.ptr(s2), N.ptr(s3), N.ptr(workspace),
@@ -337,8 +352,10 @@ class CohereEnhancedVectorDB:
 
     # -- search ------------------------------------------------------------------------
     def search_vectors(self, qf, qb, k: int = 10, binary_oversample: int = 10,
-                       int8_oversample: int = 3) -> SearchBatch:
-        """Batched three-phase search of float32 [nq, d] / ubinary [nq, d/8] query embeddings."""
+                       int8_oversample: int = 3, allowed_ids=None) -> SearchBatch:
+        """Batched three-phase search of float32 [nq, d] / ubinary [nq, d/8] query embeddings.
+        ``allowed_ids`` (document ids; None: all): only these documents are searched, as if the others had
+        been removed; ids the index does not hold are ignored."""
         qf = as_device_tensor(qf, torch.float32, self.device).reshape(-1, self.embedding_dim)
         qb = as_device_tensor(qb, torch.uint8, self.device).reshape(-1, self.embedding_dim // 8)
         n = self.index.ntotal
@@ -349,20 +366,26 @@ class CohereEnhancedVectorDB:
         if self._ws is None or self._ws.device != self.device:
             self._ws = torch.empty((8,), dtype=torch.uint8, device=self.device)
         lib = N.load()
-        size_of = getattr(lib, search3_call(K) + "_workspace_size")     # of the call search3 takes for this K
+        allow = ids_bitmap(self.index.id_map, allowed_ids) if allowed_ids is not None else None
+        size_of = getattr(lib, search3_call(K, 0, allow) + "_workspace_size")  # of the call search3 takes
         need = size_of(n, self.embedding_dim, qf.shape[0], K) if n and K else 0
         if self._ws.numel() < need:
             self._ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
             cnt, rows, dist, s2, s3 = search3(self.index.codes, self._x8.view(), self._norms.view(), qf, qb,
-                                              k, K, K3, 0, 0, self.index.rescore_rows(), self._ws)
+                                              k, K, K3, 0, 0, self.index.rescore_rows(), self._ws, allow)
         ids = torch.where(rows >= 0, self.index.id_map[rows.clamp_min(0)] if n else rows, rows)
         return SearchBatch(cnt, ids, rows, dist, s2, s3)
 
-    def search(self, query: str, k: int = 10, binary_oversample: int = 10, int8_oversample: int = 3) -> List[Dict]:
+    def search(self, query: str, k: int = 10, binary_oversample: int = 10, int8_oversample: int = 3,
+               allowed_ids=None) -> List[Dict]:
         if self.index.ntotal == 0:                                           # :247-249
             logger.error("No documents indexed. Please add documents before searching.")
             return []
+        if allowed_ids is not None:
+            allowed_ids = [int(i) for i in allowed_ids]
+            if not any(i in self.texts for i in allowed_ids):   # an empty set, or none of them indexed
+                return []
         emb = self.provider.embed([query], "search_query", ["float", "ubinary"])
         if not emb:
             logger.error("Query embedding generation failed.")
@@ -372,7 +395,7 @@ class CohereEnhancedVectorDB:
         except Exception as e:
             logger.error("Error processing query embeddings: %s", str(e))
             return []
-        res = self.search_vectors(qf, qb, k, binary_oversample, int8_oversample)
+        res = self.search_vectors(qf, qb, k, binary_oversample, int8_oversample, allowed_ids)
         return res.to_dicts(self.texts)[0]
 
 

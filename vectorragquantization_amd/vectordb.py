@@ -51,6 +51,7 @@ import torch
 from . import _native as N
 from . import quant as Q
 from .docstore import DocStoreError, RocksDictReader, is_rocksdict_dir
+from .filters import ids_bitmap
 from .index import BinaryIndexIDMap2, _GrowBuffer, as_device_tensor, torch_to_np
 
 logger = logging.getLogger(__name__)
@@ -302,25 +303,29 @@ class _QuantizedVectorDB:
             self.save()
 
     # -- search ------------------------------------------------------------------------
-    def search_vectors(self, query, k: int = 10, binary_oversample: int = 10, compare_float32: bool = False):
+    def search_vectors(self, query, k: int = 10, binary_oversample: int = 10, compare_float32: bool = False,
+                       allowed_ids=None):
         """Batched search of query embeddings (f32[nq, d]; i16[nq, d] for VectorDBInt16) on the device.
         Returns (doc_id i64[nq, kk], row i64[nq, kk], hamming i32[nq, kk], score f64[nq, kk]) with
-        kk = min(k, K); rows past the candidates are -1."""
+        kk = min(k, K); rows past the candidates are -1.  ``allowed_ids`` (None: all): only these documents
+        are searched (Phase I through ``vrq_hamming_topk_filtered``); ids the index does not hold are ignored."""
         n = self.index.ntotal
+        allow = ids_bitmap(self.index.id_map, allowed_ids) if allowed_ids is not None else None
         if k < 0 or binary_oversample < 0:
             raise ValueError("k and binary_oversample must be non-negative")
         qv = as_device_tensor(query, self.VEC_DTYPE, self.device).reshape(-1, self.embedding_dim)
         qb = self._codes(qv)["codes"]
         with torch.cuda.device(self.device):
             if self.HAMMING_ONLY:
-                rows, ham, sc = Q.vectordb_search("bin16", self.index.codes, None, None, qb, k, binary_oversample)
+                rows, ham, sc = Q.vectordb_search("bin16", self.index.codes, None, None, qb, k, binary_oversample,
+                                                  allow=allow)
             else:
                 mode = "f32" if compare_float32 else self.MODE
                 src = self._f.view() if compare_float32 else self._q.view()
                 rr = self.index.rescore_rows()
                 rows, ham, sc = Q.vectordb_search(mode, self.index.codes, src, qv, qb, k, binary_oversample,
                                                   self._mm.view() if self.LOCAL and not compare_float32 else None,
-                                                  self.limit, rr)
+                                                  self.limit, rr, allow)
                 if compare_float32:
                     self._check_float_rows(rows)
         ids = torch.where(rows >= 0, self.index.id_map[rows.clamp_min(0)], rows) if n else rows
@@ -336,20 +341,26 @@ class _QuantizedVectorDB:
             if e not in self._float_ids:
                 raise KeyError(str(e))
 
-    def search(self, query: str, k: int = 10, binary_oversample: int = 10, compare_float32: bool = False) -> List[Dict]:
+    def search(self, query: str, k: int = 10, binary_oversample: int = 10, compare_float32: bool = False,
+               allowed_ids=None) -> List[Dict]:
         if self.index.ntotal == 0:
             logger.error("No documents indexed. Please add documents before searching.")
             return []
+        kw = {}
+        if allowed_ids is not None:
+            kw["allowed_ids"] = allowed_ids = [int(i) for i in allowed_ids]
+            if not any(i in self.texts for i in allowed_ids):   # an empty set, or none of them indexed
+                return []
         emb = self._embed([query], "search_query")
         if not emb or query not in emb:
             logger.error("Query embedding generation failed. Returning empty results.")
             return []
         if self.HAMMING_ONLY:
-            ids, _, ham, _ = self.search_vectors(emb[query], k, binary_oversample)
+            ids, _, ham, _ = self.search_vectors(emb[query], k, binary_oversample, **kw)
             ids, ham = ids[0].cpu().numpy(), ham[0].cpu().numpy()
             return [{"doc_id": int(i), "score": int(h), "doc": self.texts.get(int(i), "N/A")}
                     for i, h in zip(ids, ham) if i != -1]
-        ids, _, _, sc = self.search_vectors(emb[query], k, binary_oversample, compare_float32)
+        ids, _, _, sc = self.search_vectors(emb[query], k, binary_oversample, compare_float32, **kw)
         ids, sc = ids[0].cpu().numpy(), sc[0].cpu().numpy()
         return [{"doc_id": int(i), "score": float(s), "doc": self.texts.get(int(i), "N/A")}
                 for i, s in zip(ids, sc) if i != -1]
