@@ -122,6 +122,24 @@ int vrq_hamming_topk(const uint8_t* codes, int64_t n, int32_t code_bytes, int64_
  * outputs [nq, kout] where kout = k (or K with VRQ_SEARCH_SHARD):
  *   out_count i32[nq]; out_rows i64; out_dist i32; out_binary f64; out_cosine f64
  * dim must be 1024 (code_bytes 128) in this ABI version.
+ *
+ * Score accuracy, every entry point of this header.  The products q_i * w_i (w = +-1, int8 or float32)
+ * are exact in float64 and are summed in float64; the ORDER of the sum differs between entry points (one
+ * wave per row and a butterfly in vrq_rescore_*, the *_large calls, vrq_gemm_topk and the exhaustive scan;
+ * nibble tables, one row per lane, in the fused finish of vrq_search3 / _dim / vrq_shard_search3; one row
+ * per lane in K5d).  Hence:
+ *   - When all non-zero |q_i| are multiples of some 2^g and wmax * sum|q_i| < 2^(g+53) (wmax = 1 for Phase
+ *     II, 128 for Phase III; at dim 1024 any float32 query whose non-zero coordinates lie within about 2^20
+ *     of each other in magnitude, 2^12 for Phase III), every partial sum is exact: s2 is THE exact dot, the float32 dot of Phase III / flat IP
+ *     its one correct rounding, and all entry points return identical bits.  "bit-identical" / "bit for
+ *     bit" statements about scores below are made under this condition.
+ *   - Otherwise each float64 sum is within gamma_(dim-1) * sum|q_i w_i| of the exact dot (gamma_m =
+ *     m u / (1 - m u), u = 2^-53), in whatever order: entry points with different orders may differ in the
+ *     last bits of s2 (and a Phase-II cut or a tie order may then fall differently), and the float32 dot is
+ *     one of the at most two float32 neighbours of the exact dot within that bound.  Entry points that
+ *     share an order stay bit-identical: the shard form and the fused finish; the *_large calls and
+ *     vrq_rescore_*_dim; the _dim forwarders and the ABI-1 calls at 1024.
+ *   tests/test_gpu_exact_scores.py checks both against exact rational arithmetic.
  * ------------------------------------------------------------------------- */
 size_t vrq_search3_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K);
 int vrq_search3(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
@@ -369,7 +387,7 @@ int vrq_int8_row_norms(const int8_t* x8, int64_t n, int32_t dim, double* out, vo
  *   VRQ_GEMM_INT8_COSINE  s = float32(q . int8) / ||int8||_2, -inf if the norm is 0 (x8, norms)
  * out_rows i64[nq, k] / out_scores f64[nq, k]: the k rows with the largest s ordered (s desc,
  * row asc) -- the reference's stable sorted(..., reverse=True) (:296, :321) over rows in index
- * order -- as row_offset + row, with their exact scores (bit-identical to vrq_search3's);
+ * order -- as row_offset + row, with their exact scores (vrq_search3's: see "Score accuracy" above);
  * out_count i32[nq] = min(k, n); unused slots -1 / NaN.  Queries must be finite.
  * Exact for every input: int8-quantised queries on v_mfma_i32_32x32x32_i8 give scores within a
  * proven per-query bound, a sampled threshold keeps every row that can reach the top-k, and the
@@ -486,10 +504,13 @@ int vrq_flat_ip_topk_dim(const float* xf, const int8_t* x8, const double* inv_sc
  *   descending over the Phase-I order (-0.0 ties +0.0); the three-phase call then takes the first
  *   min(K3, candidates), scores Phase III, sorts stably by it descending and keeps the first k; out_count =
  *   min(k, K, n), or min(K, n) with VRQ_SEARCH_PHASE1_ONLY -- with scores bit-identical to
- *   vrq_rescore_binary_dim / vrq_rescore_int8_cosine_dim / vrq_rescore_dequant for the same (query, row).
+ *   vrq_rescore_binary_dim / vrq_rescore_int8_cosine_dim / vrq_rescore_dequant for the same (query, row)
+ *   (the same scorers: for every input).
  *   Supported: every dim of vrq_dim_supported, 1 <= K <= VRQ_K_LARGE_MAX, 0 <= k <= VRQ_K_LARGE_MAX, any
  *   K3 >= 0, 1 <= n < 2^32.  K <= 1024 is accepted on purpose: there every output equals the call above's,
- *   bit for bit.  flags: vrq_search3_large 0 or VRQ_SEARCH_PHASE1_ONLY, vrq_search2_large 0; any other bit
+ *   bit for bit, under the condition of "Score accuracy" (vrq_search3_dim sums Phase II by nibble tables:
+ *   otherwise s2 may differ in its last bits, within the bound stated there; distances, Phase III scores of
+ *   the same row and the two-phase scores are equal for every input).  flags: vrq_search3_large 0 or VRQ_SEARCH_PHASE1_ONLY, vrq_search2_large 0; any other bit
  *   returns VRQ_EUNSUPPORTED.  n, nq, K or k = 0 behave as in vrq_search3_dim_finish / vrq_search2 (counts 0,
  *   padding written, nothing scanned).  Every argument and the workspace size are checked before anything
  *   is launched.  Sharded through the vrq_shard_search*_large / vrq_merge_shards*_large calls below.

@@ -215,6 +215,10 @@ def exhaustive_scores(mode: str, qf: np.ndarray, codes: np.ndarray = None, x8: n
     reference's per-candidate ddot).  ``"int8_cosine"``: ``float32(q . int8) / ||int8||``, -inf for
     a zero norm (``:302-318``), with the float32 dot taken as the correctly rounded exact dot (the
     GPU's definition; NumPy's sdot is within a few ulps of it).
+
+    The float64 GEMV below is a BLAS sum: it IS the exact dot only while every partial sum is exact (all
+    non-zero |q_i| multiples of some 2^g with 128 * sum|q_i| < 2^(g+53), which the queries of the suites that
+    call this satisfy).  ``tests/exact_score_model.py`` is the form that is exact for every input.
     """
     q64 = np.asarray(qf, dtype=np.float32).astype(np.float64)
     n = (codes if mode == "binary" else x8).shape[0]

@@ -3,7 +3,8 @@ Every comparison is exact.  Reference distances are plain torch ops on the devic
 table) with the disallowed rows pushed out of the (dist, row) sort; reference scores are the stand-alone
 vrq_rescore_*_dim / vrq_rescore_dequant calls on the Phase-I rows, ordered by NumPy stable sorts -- no kernel
 under test appears in a reference.  The defining property is checked once per entry point: the filtered call
-equals the *_large call on the gathered allowed rows, rows mapped back.
+equals the *_large call on the gathered allowed rows, rows mapped back.  The stand-alone rescoring kernels of
+the reference are pinned against exact rational arithmetic by tests/test_gpu_exact_scores.py.
 
 n = 12 325 = 3 x 4096 + 37 rows: the plan gives 4 chunks and a ragged last tile (asserted), the smallest
 shape at which chunk prefixes, the ragged tile and the last bitmap word can go wrong.  Dims 256, 384 (the

@@ -1,7 +1,9 @@
 """GPU checks of the search with more than 1024 Phase-I candidates (vrq_*_large: the counting scan K1h and
 the large finish).  Every comparison is exact.  Reference distances are plain torch ops on the device (xor +
 a byte-popcount table) ordered by (dist, row); reference scores are the stand-alone vrq_rescore_*_dim /
-vrq_rescore_dequant calls on the Phase-I rows, ordered by NumPy stable sorts -- no kernel under test."""
+vrq_rescore_dequant calls on the Phase-I rows, ordered by NumPy stable sorts -- no kernel under test.  Those
+reference kernels (vrq_rescore_binary_dim / vrq_rescore_int8_cosine_dim) are pinned against exact rational
+arithmetic by tests/test_gpu_exact_scores.py."""
 import numpy as np
 import pytest
 import torch

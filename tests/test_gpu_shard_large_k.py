@@ -2,7 +2,8 @@
 vrq_shard_search3_large / vrq_shard_search2_large and the merges vrq_merge_shards_large / vrq_merge_shards2_large.
 Every comparison is exact.  The references are those of tests/test_gpu_large_k.py (torch ops for Phase I, the
 stand-alone rescoring calls and NumPy stable sorts for the rest) and the single-index vrq_search3_large /
-vrq_search2_large over the whole corpus."""
+vrq_search2_large over the whole corpus.  The stand-alone rescoring kernels of the reference are pinned against
+exact rational arithmetic by tests/test_gpu_exact_scores.py."""
 import numpy as np
 import pytest
 import torch

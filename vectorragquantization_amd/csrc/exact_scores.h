@@ -1,8 +1,18 @@
 // exact_scores.h -- the reference's Phase-II / Phase-III scores of ONE row for one query, one
 // wave per (query, row), shared by the fused search finish (select_rescore.hip) and the
-// exhaustive matrix-core scorer (gemm_topk.hip), so both produce bit-identical scores.
+// exhaustive matrix-core scorer (gemm_topk.hip).
 //   Phase II  (CohereEnhancedVectorDB.py:283-293): float(q . (2*unpackbits(code)-1)), float64
 //   Phase III (CohereEnhancedVectorDB.py:302-318): float32(q . int8) / ||int8||, -inf if 0
+// Accuracy.  Every product (f32 x +-1, f32 x int8, f32 x f32) is exact in float64; the float64 sum of the
+// dim products is exact, in any order, when all non-zero |q_i| are multiples of some 2^g and
+// wmax * sum|q_i| < 2^(g+53) (wmax = 1 for Phase II, 128 for Phase III) -- at dim 1024 every float32 query
+// whose non-zero |q_i| lie within about 2^20 of each other (2^12 for Phase III).  Under that condition the wave order (phase2_dot,
+// phase3_cos, flat_ip) and the nibble order (phase2_nibbles, phase2_nibble_tables) return the same bits, the
+// exact dot, and the float32 dot is its one correct rounding.  Otherwise each order returns a float64 sum
+// within gamma_(dim-1) * sum|q_i w_i| of the exact dot (gamma_m = m u / (1 - m u), u = 2^-53): two orders may
+// differ in the last bits, and the float32 dot is one of the (at most two) float32 neighbours of the exact dot
+// within that bound.  Paths that share an order are bit-identical for every input.  Checked against exact
+// rational arithmetic by tests/test_gpu_exact_scores.py.
 #pragma once
 
 #include "vrq_internal.h"
@@ -48,8 +58,8 @@ __device__ __forceinline__ double phase3_from(const float (&qv)[DPL], const int4
     const int8_t x = (int8_t)((w[i >> 2] >> (8 * (i & 3))) & 0xff);
     s += (double)qv[i] * (double)x;  // exact product
   }
-  s = wave_sum_f64(s);                // exact sum
-  const float f = (float)s;           // one rounding: correctly rounded float32 dot
+  s = wave_sum_f64(s);                // exact sum under the header's condition, else within its bound
+  const float f = (float)s;           // one rounding: the correctly rounded float32 dot when the sum is exact
   return nrm == 0.0 ? -__builtin_inf() : (double)f / nrm;
 }
 __device__ __forceinline__ double phase3_cos(const float (&qv)[DPL], const int8_t* __restrict__ xrow, double nrm) {
@@ -86,9 +96,10 @@ __device__ __forceinline__ double flat_ip(const float (&qv)[DPL], const float* _
 }
 
 // Phase II by nibble tables (one row per thread): tab[p * 16 + v] = sum over the 4 dims 4p .. 4p+3 of
-// nibble p (packbits MSB first) of (bit of v ? q : -q), in float64 -- exact, as every partial sum of the
-// reference's float32 x +-1 products is -- so the 256-term sum over a code's nibbles is the same exact
-// value as phase2_dot.  phase2_table fills the 32 KiB table with a block's `nthreads` threads.
+// nibble p (packbits MSB first) of (bit of v ? q : -q), in float64, then the 256-term sum over a code's
+// nibbles in nibble order.  Under the header's condition every partial sum is exact and the result is
+// phase2_dot's, bit for bit; otherwise the two orders agree within the header's bound, not in the last
+// bits.  phase2_table fills the 32 KiB table with a block's `nthreads` threads.
 __device__ __forceinline__ void phase2_table(const float* __restrict__ q, double* tab, int tid, int nthreads) {
   for (int e = tid; e < 256 * 16; e += nthreads) {
     const int p = e >> 4, v = e & 15;

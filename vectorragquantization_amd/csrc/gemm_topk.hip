@@ -2,7 +2,7 @@
 // queries against the WHOLE corpus on the matrix cores (v_mfma_i32_32x32x32_i8), with the top-k
 // fused in: the nq x n score matrix is never stored.
 //
-// Reference scores (exact_scores.h, bit-identical to the fused search's):
+// Reference scores (exact_scores.h: the fused search's, bit for bit under the condition stated there):
 //   VRQ_GEMM_BINARY       s = float(q . (2*unpackbits(code)-1)), float64   CohereEnhancedVectorDB.py:283-293
 //   VRQ_GEMM_INT8_COSINE  s = float32(q . int8) / ||int8||, -inf if 0      CohereEnhancedVectorDB.py:302-318
 // Result per query: the k rows with the largest s, ordered (s desc, row asc) -- the reference's
@@ -811,7 +811,7 @@ struct Rows {
 };
 
 // The exact score of one row in two halves: the lane's load of the row (so a wave can keep several
-// candidates' loads in flight) and the arithmetic (exact_scores.h, bit-identical to the fused search).
+// candidates' loads in flight) and the arithmetic (exact_scores.h, the fused search's Phase III).
 template <int PH>
 struct RowSlice {
   int4 x;      // Phase III: the lane's 16 int8 values

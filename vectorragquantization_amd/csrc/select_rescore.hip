@@ -10,12 +10,16 @@
 //   :302-318  s3 = float(qf . int8) / np.linalg.norm(int8); -inf if norm == 0
 //   :321-322  stable sort by s3 desc, first k
 // Numerics: Phase II is accumulated in float64 -- every product is +-q_i
-// (exact) and the partial sums of float32 embedding values fit in 53 bits, so
-// the sum is exact and equals NumPy's ddot bit for bit.  Phase III: the f32
-// x int8 products are exact in float64 and so is their sum; rounding it once
-// to float32 gives the correctly rounded float32 dot (NumPy's sdot rounds per
-// BLAS summation order, <= a few ulp away: the 1e-5 tolerance of the north
-// star).  The norm is sqrt of an exact integer sum (correctly rounded, equal
+// (exact); when the non-zero |q_i| are multiples of some 2^g with
+// sum|q_i| < 2^(g+53) (coordinates within ~2^20 of each other at dim 1024) the
+// partial sums fit in 53 bits, so the sum is exact in any order and equals
+// NumPy's ddot bit for bit; otherwise it is within gamma_(dim-1) * sum|q_i| of
+// the exact dot and its last bits depend on the order (exact_scores.h).
+// Phase III: the f32 x int8 products are exact in float64 and, under the same
+// condition with 128 * sum|q_i|, so is their sum; rounding it once to float32
+// gives the correctly rounded float32 dot (NumPy's sdot rounds per BLAS
+// summation order, <= a few ulp away: the 1e-5 tolerance of the north star).
+// The norm is sqrt of an exact integer sum (correctly rounded, equal
 // to np.linalg.norm) and the division is IEEE double, as in the reference.
 #include "dequant_dot.h"
 #include "exact_scores.h"
@@ -407,9 +411,10 @@ __device__ void write_phase1_order(int Kp, bool with_scores, const FinishArgs& a
 
 // Phase II (:283-293) of the Kp candidates sh.sel[0..Kp) -> sh.s2, one candidate per lane.  The score is
 // a sum of 256 nibble terms: for nibble p of the packed code (dims 4p..4p+3, MSB first) and its value v,
-// T[p][v] = sum_b (bit b of v ? q[4p+b] : -q[4p+b]) -- exact in float64, like every partial sum of the
-// reference's float32 x +-1 products -- so s2 = sum_p T[p][v_p] is the same exact value as the wave-wide
-// ddot of phase2_dot, with 256 LDS lookups per candidate instead of 1024 products spread over a wave.
+// T[p][v] = sum_b (bit b of v ? q[4p+b] : -q[4p+b]) in float64, and s2 = sum_p T[p][v_p] in nibble order.
+// Under the condition of exact_scores.h (all |q_i| multiples of 2^g, sum|q_i| < 2^(g+53)) every partial sum is
+// exact and s2 is the value of the wave-wide ddot of phase2_dot, bit for bit; otherwise the two orders agree
+// within gamma_1023 * sum|q_i|, not in the last bits -- with 256 LDS lookups per candidate instead of 1024 products spread over a wave.
 // The tables cover QT_NIB nibbles at a time (16 KiB of LDS: four workgroups of the small instance per CU).
 constexpr int QT_NIB = 128;
 template <class SH>
@@ -551,7 +556,8 @@ __device__ __forceinline__ double phase2_dot_dim(const float* __restrict__ q, co
 }
 
 // Phase II of the Kp candidates by nibble tables, as phase2_nibble_tables, over cb = dim / 8 code bytes in
-// passes of up to 64 bytes (cb is a multiple of 16; the last pass of a 48-, 96- or 192-byte code is shorter).
+// passes of up to 64 bytes (cb is a multiple of 16: the only pass of a 32- or 48-byte code and the second pass
+// of a 96-byte code are shorter).  The same statement holds against phase2_dot_dim.
 template <class SH>
 __device__ void phase2_nibble_tables_dim(const float* __restrict__ q, const uint8_t* __restrict__ codes,
                                          const int64_t* __restrict__ remap, int Kp, int cb, SH& sh, double* qtab) {
@@ -899,7 +905,9 @@ static int launch_select2(hipStream_t s, int nq, const void* ws, const Phase1Rou
 //                        (Phase-I-only calls write their outputs here)
 //   large_score_kernel   one wave per (query, candidate) over the whole grid: the stand-alone rescoring's
 //                        Scorer1024 / ScorerDim / dequant_dot, so scores are bit-identical to
-//                        vrq_rescore_*_dim / vrq_rescore_dequant (and to vrq_search3_dim / vrq_search2)
+//                        vrq_rescore_*_dim / vrq_rescore_dequant and to vrq_search2 for every input, and to
+//                        vrq_search3_dim's Phase III; to its Phase II (nibble order) under the condition
+//                        of exact_scores.h, within its bound otherwise
 //   large_order_kernel   sorts the pairs (descending-score image, position) lexicographically in LDS -- the
 //                        stable order -- and either keeps the order of the first K3 (three-phase, after Phase
 //                        II) or writes the first k outputs
