@@ -63,26 +63,12 @@ def _phase1(codes_t, qb, K, dev, row_offset=0):
 
 
 def _paths(codes_t, qb, K):
-    """Which fallback paths a query took: run PREFIX + MATRIX + RECHECK through the stage-split ABI and read
-    the per-(query, chunk) list lengths (> capc: overflowed, rescanned exactly by the suffix stage) and the
-    per-query re-run flags from the workspace (offsets from vrq_scan_plan).  -> (overflowed[nq], rerun[nq])"""
-    from vectorragquantization_amd import _native as N
-    lib = N.load()
-    n, nq = codes_t.shape[0], qb.shape[0]
-    flags = N.VRQ_SEARCH_PHASE1_ONLY
-    info = _plan(n, nq, K)
-    ws = torch.zeros((int(info[11]),), dtype=torch.uint8, device=codes_t.device)
+    """Which fallback paths a query took (scan_paths of test_gpu_lists.py, the one reader of the workspace's
+    list lengths and re-run flags).  -> (overflowed[nq], rerun[nq])"""
+    from tests.test_gpu_lists import scan_paths
     q_t = torch.from_numpy(np.ascontiguousarray(qb)).to(codes_t.device)
-    st = N.stream_handle(codes_t.device)
-    for stage in (N.VRQ_SCAN_STAGE_PREFIX, N.VRQ_SCAN_STAGE_MATRIX, N.VRQ_SCAN_STAGE_RECHECK):
-        N.check(lib.vrq_search3_scan(N.ptr(codes_t), n, 1024, N.ptr(q_t), nq, K, flags | stage, N.ptr(ws), ws.numel(),
-                                     st), "scan stage")
-    torch.cuda.synchronize()
-    nch, capc, off_cnt, off_tau = (int(info[i]) for i in (3, 4, 6, 7))
-    cnt = ws[off_cnt:off_cnt + 4 * nq * nch].view(torch.int32).view(nq, nch).cpu().numpy()
-    qa = (4 * nq + 255) & ~255
-    rerun = ws[off_tau + 2 * qa:off_tau + 2 * qa + 4 * nq].view(torch.int32).cpu().numpy()
-    return (cnt > capc).any(axis=1), rerun != 0
+    ovf, rerun, _, _ = scan_paths(codes_t, q_t, K)
+    return ovf, rerun
 
 
 def _flip(rng, rows, nflip):

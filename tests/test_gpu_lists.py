@@ -150,6 +150,24 @@ def check_scan_lists(codes, qb, K, allow_overflow=False):
     return info
 
 
+def scan_paths(codes, qb, K):
+    """Which fallback paths the queries of (codes, qb: device tensors) take: PREFIX + MATRIX + RECHECK through
+    the stage-split ABI, then from the workspace the queries with a list longer than capc (overflowed:
+    rescanned exactly by the suffix stage), the per-query re-run flags and the per-query-block flags of the
+    re-run launch (after the three per-query arrays at off_tau), plus the plan's sampled order j.
+    -> (overflowed[nq], rerun[nq], qbflag[nqb], j), NumPy."""
+    from vectorragquantization_amd import _native as N
+    nq = qb.shape[0]
+    info, ws = _scan_stages(codes, qb, K, (N.VRQ_SCAN_STAGE_PREFIX, N.VRQ_SCAN_STAGE_MATRIX,
+                                           N.VRQ_SCAN_STAGE_RECHECK))
+    nch, capc, off_cnt, off_tau, j, nbytes = (int(info[i]) for i in (3, 4, 6, 7, 9, 11))
+    cnt = ws[off_cnt:off_cnt + 4 * nq * nch].view(torch.int32).view(nq, nch)
+    qa = _al(4 * nq)
+    rerun = ws[off_tau + 2 * qa:off_tau + 2 * qa + 4 * nq].view(torch.int32)
+    qbflag = ws[off_tau + 3 * qa:nbytes].view(torch.int32)
+    return (cnt > capc).any(dim=1).cpu().numpy(), (rerun != 0).cpu().numpy(), qbflag.cpu().numpy(), j
+
+
 @pytest.mark.parametrize("nq", [8, 64, 128, 1024])
 def test_scan_sample_lane_minima_exact(dev, nq):
     """Every lane minimum of the dense sample pass (K1r's own for <= 64 queries, K1m's MB = 2 instance

@@ -6,13 +6,20 @@ that are not multiples of the 256-query workgroup, K = 1 and K = 128 (the path's
 ties, the candidate-list overflow that triggers the exact rescan (including dist == T ties
 taken in row order), the stage-split ABI, and the full three-phase search agreeing between
 the two scans bit for bit.
+
+The three fallbacks that keep the scans exact -- the re-run with tau_p, the candidate-list overflow and
+the hit-stage overflow, both with their exact rescan -- return the same top-K as the fast path, so each
+test of one also asserts from the workspace (scan_paths of test_gpu_lists.py: list lengths, re-run flags,
+query-block flags) that its queries took the path it names.
 """
 import numpy as np
 import pytest
 import torch
 
 from oracle import oracle_np as O
+from tests import k1s_cases as C
 from tests.conftest import oracle_knn
+from tests.test_gpu_lists import check_scan_lists, scan_paths
 
 pytestmark = pytest.mark.gpu
 
@@ -93,6 +100,8 @@ def test_mfma_heavy_ties(dev, oracle_lib, nq):
     base = rng.integers(0, 256, (25, 128), dtype=np.uint8)
     codes = base[rng.integers(0, 25, 120_000)]            # every distance occurs thousands of times
     qb = np.concatenate([base[:4], rng.integers(0, 256, (nq - 4, 128), dtype=np.uint8)])
+    ovf, rerun, _, j = scan_paths(_t(codes, dev), _t(qb, dev), 100)
+    print(f"heavy ties nq={nq}: j={j}, {int(ovf.sum())} of {nq} queries overflowed, {int(rerun.sum())} re-ran")
     for K in (1, 100, 128):
         D0, I0 = oracle_knn(oracle_lib, codes, qb, K)
         _, D1, I1 = _phase1(codes, qb, K, dev, "mfma", row_offset=5_000_000)
@@ -116,6 +125,9 @@ def test_mfma_candidate_overflow_exact_rescan(dev, oracle_lib, nq):
     suffix[copies] = qb[0]
     codes[S:] = suffix
     qb[2] = codes[S + 17]                                 # another query, near the suffix too
+    ovf, rerun, _, _ = scan_paths(_t(codes, dev), _t(qb, dev), K)
+    print(f"candidate overflow nq={nq}: {int(ovf.sum())} of {nq} queries overflowed, {int(rerun.sum())} re-ran")
+    assert ovf[0], "query 0's lists must overflow"
     D0, I0 = oracle_knn(oracle_lib, codes, qb, K)
     _, D1, I1 = _phase1(codes, qb, K, dev, "mfma")
     assert np.array_equal(D0, D1)
@@ -173,20 +185,36 @@ def test_mfma_and_valu_three_phase_identical(dev):
 
 @pytest.mark.parametrize("nq", [200, 64, 40, 600])  # K1m MB = 2; the lean MB = 2 K1r (full and partial); K1s
 def test_mfma_hit_staging_overflow(dev, oracle_lib, nq):
-    """Up to 64 queries (one wave's worth) and the whole suffix clustered around one code: every tile
-    gives a wave thousands of hits, more than its LDS staging holds, so the lists are marked overflowed
-    and those queries are rescanned exactly; the other queries keep the fast path.  At 40 and 64 queries
-    this runs the lean K1r kernel's per-n-block stage overflow, spare-slot clamp and capc + 1 marking."""
+    """Up to 64 heavy queries (one wave's worth) at distance exactly 10 from every row of the suffix: the
+    heavy queries are `base` with 4 flips among bits 0..511, the suffix rows `base` with 6 flips among bits
+    512..1023.  Their threshold is 11 (the sample's K-th lane minimum is 10; j = K at this size), every
+    suffix row hits, and a wave gets 64 hits per suffix row: 2048 or more per 32-row block against the 512
+    its LDS stage holds.  The stage overflows, the lists are marked (capc + 1) and those queries are
+    rescanned exactly: the first K suffix rows in row order.  The other queries are uniform and at least
+    512 from `base` (complemented where nearer), so no suffix row is ever their candidate and they keep the
+    fast path.  At 40 and 64 queries this runs the lean K1r kernel's per-n-block stage overflow, spare-slot
+    clamp and marking (all its queries are heavy); at 200 K1m MB = 2 marks its first wave's 64 queries.
+    K1s (600) marks from the query block in which the stage overflowed to the workgroup's last: the heavy
+    queries are blocks 0 and 1, so all 512 queries of workgroup 0 and none of workgroup 1
+    (test_gpu_k1s_edges.py floods a late block, where the earlier blocks must stay unmarked)."""
     rng = np.random.default_rng(17)
     n, K = 100_000, 100
     S = 32_768
     base = rng.integers(0, 256, (1, 128), dtype=np.uint8)
     codes = rng.integers(0, 256, (n, 128), dtype=np.uint8)
-    codes[S:] = _near(rng, np.repeat(base, n - S, axis=0), 6)
+    codes[S:] = C.flip(rng, np.repeat(base, n - S, axis=0), 6, 512, 1024)
     qb = rng.integers(0, 256, (nq, 128), dtype=np.uint8)
+    near = np.unpackbits(qb ^ base, axis=1).sum(1) < 512
+    qb[near] = ~qb[near]
     nh = min(nq, 64)
-    qb[:nh] = _near(rng, np.repeat(base, nh, axis=0), 4)
+    qb[:nh] = C.flip(rng, np.repeat(base, nh, axis=0), 4, 0, 512)
     D0, I0 = oracle_knn(oracle_lib, codes, qb, K)
+    assert (D0[:nh] == 10).all() and (I0[:nh] == S + np.arange(K)).all()
+    ovf, rerun, _, j = scan_paths(_t(codes, dev), _t(qb, dev), K)
+    print(f"stage overflow nq={nq}: j={j}, {int(ovf.sum())} of {nq} queries overflowed, {int(rerun.sum())} re-ran")
+    marked = min(nq, C.SQPB) if _plan(n, nq, K)[0] == 2 else nh
+    assert ovf[:nh].all(), "every heavy query's lists must be marked overflowed"
+    assert ovf[:marked].all() and not ovf[marked:].any()
     _, D1, I1 = _phase1(codes, qb, K, dev, "mfma")
     assert np.array_equal(D0, D1)
     assert np.array_equal(I0, I1)
@@ -201,33 +229,64 @@ def _sample_rows(n, nq, K=100):
     N.check(N.load().vrq_scan_sample_plan(n, 1024, nq, K, 0, info.ctypes.data), "sample plan")
     chunks, crows, ts = int(info[1]), int(info[2]), int(info[4])
     tiles = chunks * (crows // 64)
-    return (np.arange(tiles)[:, None] * ts + np.arange(64)[None, :]).reshape(-1)
+    return (np.arange(tiles)[:, None] * ts + np.arange(64)[None, :]).reshape(-1), ts, crows // 64
 
 
-@pytest.mark.parametrize("nq", [300, 100, 50, 600])
+def _plan(n, nq, K):
+    """vrq_scan_plan of the matrix-core scan: [kind, M-blocks, chunk rows, chunks, capc, ..., j at 9, ...]."""
+    from vectorragquantization_amd import _native as N
+    info = np.zeros(12, np.int64)
+    N.check(N.load().vrq_scan_plan(n, 1024, nq, K, N.VRQ_SEARCH_SCAN_MFMA, info.ctypes.data), "plan")
+    return [int(x) for x in info]
+
+
+# K1r MB = 1, the lean MB = 2, MB = 4; K1m MB = 2 (two 256-query blocks); K1s with two and three workgroups
+@pytest.mark.parametrize("nq", [20, 50, 100, 300, 600, 1100])
 def test_mfma_sampled_threshold_rerun(dev, oracle_lib, nq):
-    """The thresholded pass runs with the sampled tau_s = d_(j)+1 (j < K) of the dense sample.
-    Queries 0 and nq - 10 (two different 256-query blocks at nq = 300; the one block of the
-    row-split kernel at nq = 100) get 70 near copies (dist <= 20) on sample
-    rows and 40 more at dist 30 off the sample, none elsewhere: d_(j) falls among the near
-    copies, the dist-30 copies miss tau_s, the check finds C = 70 < K and the re-run with tau_p
-    must recover the first 30 of them in row order.  The other queries take the fast path."""
+    """The thresholded pass runs with the sampled tau_s = d_(j) + 1 (j < K) of the dense sample and the
+    planted queries must re-run with tau_p.  n = 300 007: the sample is 65 536 rows, so j = 48 (at 100 000
+    rows and below the sample is two thirds of the corpus, j = K and nothing can re-run).
+    Two planted queries -- 0 and nq - 10 (two different 256-query blocks at nq = 300; the one block of the
+    row-split kernel up to 100); 5 and 1090 at nq = 1100, i.e. workgroups 0 and 2 of K1s, the second one
+    local query 66 of the ragged last workgroup -- get 70 near copies (dist <= 20) on sample rows, in at least
+    j distinct lanes of the sample pass, and 40 more at dist 30 off the sample, none elsewhere: the j-th lane
+    minimum falls among the near copies, the dist-30 copies miss tau_s, the check finds C = 70 < K and the
+    re-run with tau_p must recover the first 30 of them in row order.  The other queries take the fast path:
+    at nq = 1100 the middle workgroup's flag stays 0 and the re-run launch skips it.  The lists after the
+    re-run are then checked entry by entry (check_scan_lists: tau_p for the re-run queries, tau_s for the
+    others, whose lists and counts the masked re-run must leave alone)."""
     rng = np.random.default_rng(23)
-    n, K = 100_000, 100
+    n, K = 300_007, 100
+    j = _plan(n, nq, K)[9]
+    assert j < K and j <= 60, "the plan must take a sampled threshold that the 70 near copies cover"
     codes = rng.integers(0, 256, (n, 128), dtype=np.uint8)
     qb = _near(rng, codes[rng.integers(0, n, nq)], 50)
-    samp = _sample_rows(n, nq)
+    samp, ts, T = _sample_rows(n, nq)
+    assert samp.max() < n
     off = np.setdiff1d(np.arange(n), samp)
-    for q in (0, nq - 10):
-        near = rng.choice(samp, 70, replace=False)
+    planted = [5, 1090] if nq == 1100 else [0, nq - 10]
+    near_all = rng.choice(samp, 140, replace=False)        # disjoint row sets for the two queries
+    far_all = rng.choice(off, 80, replace=False)
+    for i, q in enumerate(planted):
+        near = near_all[70 * i:70 * (i + 1)]
+        assert np.unique(C.sample_lanes(near, ts, T)).size >= j, "the near copies must fill j lanes of the sample"
         codes[near] = _near(rng, np.repeat(qb[q:q + 1], 70, axis=0), int(rng.integers(5, 21)))
-        far = rng.choice(off, 40, replace=False)
+        far = far_all[40 * i:40 * (i + 1)]
         codes[far] = _near(rng, np.repeat(qb[q:q + 1], 40, axis=0), 30)
     D0, I0 = oracle_knn(oracle_lib, codes, qb, K)
+    for q in planted:
+        assert (D0[q] == 30).sum() == 30
+    codes_t, qb_t = _t(codes, dev), _t(qb, dev)
+    ovf, rerun, qbflag, jj = scan_paths(codes_t, qb_t, K)
+    print(f"sampled re-run nq={nq}: j={jj}, {int(rerun.sum())} of {nq} queries re-ran, {int(ovf.sum())} overflowed, "
+          f"query-block flags {qbflag.tolist()}")
+    assert jj == j and rerun[planted].all(), "the planted queries must fail tau_s and re-run with tau_p"
+    if nq == 1100:
+        assert qbflag.tolist() == [1, 0, 1]
     _, D1, I1 = _phase1(codes, qb, K, dev, "mfma")
-    assert (D0[0] == 30).sum() == 30 and (D0[nq - 10] == 30).sum() == 30
     assert np.array_equal(D0, D1)
     assert np.array_equal(I0, I1)
+    check_scan_lists(codes_t, qb_t, K)
 
 
 @pytest.mark.parametrize("nq", [40, 130, 520])
@@ -244,6 +303,8 @@ def test_mfma_cluster_ordered_corpus(dev, oracle_lib, nq):
     flips = rng.random(bits.shape) < rng.uniform(0.01, 0.06, (bits.shape[0], 1))
     codes = np.packbits(bits ^ flips, axis=1)
     qb = _near(rng, centres[rng.integers(0, ncl, nq)], 12)
+    ovf, rerun, _, j = scan_paths(_t(codes, dev), _t(qb, dev), 100)
+    print(f"cluster order nq={nq}: j={j}, {int(ovf.sum())} of {nq} queries overflowed, {int(rerun.sum())} re-ran")
     D0, I0 = oracle_knn(oracle_lib, codes, qb, 100)
     c, D1, I1 = _phase1(codes, qb, 100, dev, "mfma")
     assert np.array_equal(c, np.full(nq, 100))
