@@ -577,8 +577,8 @@ int vrq_scan_large_plan(int64_t n, int32_t dim, int32_t nq, int32_t K, int64_t* 
  *   n < 2^32; n, nq, K or k = 0 behave as there (and read no bitmap).  A null or misaligned allow of a
  *   non-empty call returns VRQ_EINVAL; every argument is checked before anything is launched.
  * Only the counting scan K1h reads the bitmap (one word per 64-row tile, a scalar load): it serves every K,
- *   and is a VALU scan meant for small and medium batches.  There is no filtered matrix-core scan, no
- *   per-query bitmap and no filtered sharded call.
+ *   and is a VALU scan meant for small and medium batches (for big ones: the vrq_*_batch calls below).  There
+ *   is no per-query bitmap and no filtered sharded call.
  * ------------------------------------------------------------------------- */
 size_t vrq_scan_filtered_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K);
 int vrq_scan_filtered(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq, int32_t K,
@@ -601,6 +601,62 @@ int vrq_search2_filtered(int32_t mode, const uint8_t* codes, const void* q, cons
                          const uint8_t* qb, int32_t nq, int32_t k, int32_t K, int32_t flags, const uint64_t* allow,
                          int32_t* out_count, int64_t* out_rows, int32_t* out_dist, double* out_score,
                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * The counting scan on the matrix cores: large-K and filtered search for big batches (additive to ABI
+ * version 1).  K1hm (hamming_count_mfma.hip) runs the count and the emit stage of the counting scan on
+ * v_mfma_f32_32x32x64_f8f6f4, at every dim of vrq_dim_supported, with and without the row bitmap; the
+ * threshold stage and the finish are K1h's.  The *_large and *_filtered calls above keep running K1h.
+ * vrq_hamming_topk_batch / vrq_search3_batch / vrq_search2_batch / vrq_scan_batch: the arguments of the
+ *   *_filtered call plus
+ *   engine  VRQ_LARGE_ENGINE_AUTO (the engine vrq_large_engine names), _VALU (K1h: exactly the *_large /
+ *           *_filtered call) or _MFMA (K1hm, for any non-empty shape the *_large calls accept); any other
+ *           value returns VRQ_EINVAL.
+ *   allow   may be null here: an unfiltered search.  A misaligned non-null allow returns VRQ_EINVAL.
+ *   For every input, every output is bit-identical, whichever engine runs, to the *_large call (allow null)
+ *   or the *_filtered call with the same arguments; after vrq_scan_batch the T / count(dist < T) pairs and the
+ *   K-lists in the workspace are bit-identical between the engines too (the dist < T part and the dist == T part
+ *   each in row order, all-ones padded), each at its own plan's offset, and so are the histograms summed over
+ *   the chunks: an engine's plan fixes its chunks, so the per-chunk arrays agree only where the plans do.  Shapes, flags (0 / VRQ_SEARCH_PHASE1_ONLY as in
+ *   the *_large calls), stage masks, empty shapes and return codes are those of the *_filtered calls; the
+ *   workspace (vrq_*_batch_workspace_size: a pure function of the shape, 0 for an unsupported one) covers
+ *   either engine.  Every argument is checked before anything is launched.
+ * vrq_large_engine (host-only): the engine AUTO takes for a shape, VRQ_LARGE_ENGINE_VALU or _MFMA, from a
+ *   measured minimum batch per code size (tools/batch_bench.py); VRQ_EINVAL / VRQ_EUNSUPPORTED as
+ *   vrq_scan_large_plan.
+ * vrq_scan_batch_plan (host-only; tests and tools): info i64[10] = the engine that will run, rows per chunk
+ *   (a multiple of 64), chunks, queries per wave of the count kernel (K1h: per workgroup), query blocks of a
+ *   pass, rows a count workgroup scans between two flushes of its 16-bit bins (0: it never flushes), the
+ *   workspace offsets of the histograms (u32 [min(nq, 512)][chunks][dim + 1]), of the T / count(dist < T) pairs
+ *   and of the K-lists, and the workspace bytes.  With VRQ_LARGE_ENGINE_VALU the chunks and offsets are
+ *   vrq_scan_large_plan's.
+ * ------------------------------------------------------------------------- */
+#define VRQ_LARGE_ENGINE_AUTO 0
+#define VRQ_LARGE_ENGINE_VALU 1 /* K1h: exactly the *_large / *_filtered call */
+#define VRQ_LARGE_ENGINE_MFMA 2 /* K1hm, any non-empty shape the *_large calls accept */
+int vrq_large_engine(int64_t n, int32_t dim, int32_t nq, int32_t K, int32_t filtered);
+int vrq_scan_batch_plan(int64_t n, int32_t dim, int32_t nq, int32_t K, int32_t engine, int64_t* info);
+size_t vrq_scan_batch_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K);
+int vrq_scan_batch(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq, int32_t K,
+                   int32_t stages, const uint64_t* allow, void* workspace, size_t workspace_bytes, void* stream,
+                   int32_t engine);
+size_t vrq_hamming_topk_batch_workspace_size(int64_t n, int32_t code_bytes, int32_t nq, int32_t k);
+int vrq_hamming_topk_batch(const uint8_t* codes, int64_t n, int32_t code_bytes, int64_t row_offset,
+                           const uint8_t* queries, int32_t nq, int32_t k, const uint64_t* allow, int32_t* out_dist,
+                           int64_t* out_rows, void* workspace, size_t workspace_bytes, void* stream,
+                           int32_t engine);
+size_t vrq_search3_batch_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K);
+int vrq_search3_batch(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
+                      int64_t n, int32_t dim, int64_t row_offset, const float* qf, const uint8_t* qb, int32_t nq,
+                      int32_t k, int32_t K, int32_t K3, int32_t flags, const uint64_t* allow, int32_t* out_count,
+                      int64_t* out_rows, int32_t* out_dist, double* out_binary, double* out_cosine,
+                      void* workspace, size_t workspace_bytes, void* stream, int32_t engine);
+size_t vrq_search2_batch_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K);
+int vrq_search2_batch(int32_t mode, const uint8_t* codes, const void* q, const double* minmax, double limit,
+                      const int64_t* rescore_row, int64_t n, int32_t dim, int64_t row_offset, const float* qf,
+                      const uint8_t* qb, int32_t nq, int32_t k, int32_t K, int32_t flags, const uint64_t* allow,
+                      int32_t* out_count, int64_t* out_rows, int32_t* out_dist, double* out_score,
+                      void* workspace, size_t workspace_bytes, void* stream, int32_t engine);
 
 /* ---------------------------------------------------------------------------
  * Row-sharded search with more than 1024 Phase-I candidates (additive to ABI version 1; vrq_shard_search3,

@@ -21,7 +21,7 @@ PROBE_LIB = os.path.join(PKG, "libvrq_probe.so")
 OBJDIR = os.path.join(PKG, "_obj")
 SOURCES = ["hamming_scan.hip", "hamming_mfma.hip", "select_rescore.hip", "encode.hip", "gemm_topk.hip", "dequant.hip",
            "search_dim.hip", "exhaustive_dim.hip", "hamming_mfma_dim.hip", "mfma_threshold.hip", "scan_route.hip",
-           "hamming_count.hip"]
+           "hamming_count.hip", "hamming_count_mfma.hip"]
 # sources without device code: their objects carry no gfx950 bundle, so they are kept apart (_obj/host/) from
 # the objects whose disassembly the tests read
 HOST_ONLY = {"scan_route.hip"}
@@ -32,7 +32,8 @@ CFLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"--offload-arch={A
 # them there; the AGPR form costs 16 v_accvgpr moves per accumulator use)
 EXTRA = {"hamming_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
          "gemm_topk.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
-         "hamming_mfma_dim.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
+         "hamming_mfma_dim.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+         "hamming_count_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 
 
 def _hipcc() -> str:

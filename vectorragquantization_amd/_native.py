@@ -132,6 +132,18 @@ SIGNATURES = {
     "vrq_search2_filtered_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
     "vrq_search2_filtered": (C.c_int, [_I32, _P, _P, _P, _D, _P, _I64, _I32, _I64, _P, _P, _I32, _I32, _I32, _I32,
                                        _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "vrq_large_engine": (C.c_int, [_I64, _I32, _I32, _I32, _I32]),
+    "vrq_scan_batch_plan": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _P]),
+    "vrq_scan_batch_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
+    "vrq_scan_batch": (C.c_int, [_P, _I64, _I32, _P, _I32, _I32, _I32, _P, _P, _SZ, _P, _I32]),
+    "vrq_hamming_topk_batch_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
+    "vrq_hamming_topk_batch": (C.c_int, [_P, _I64, _I32, _I64, _P, _I32, _I32, _P, _P, _P, _P, _SZ, _P, _I32]),
+    "vrq_search3_batch_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
+    "vrq_search3_batch": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _P,
+                                    _P, _P, _P, _P, _P, _P, _SZ, _P, _I32]),
+    "vrq_search2_batch_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
+    "vrq_search2_batch": (C.c_int, [_I32, _P, _P, _P, _D, _P, _I64, _I32, _I64, _P, _P, _I32, _I32, _I32, _I32,
+                                    _P, _P, _P, _P, _P, _P, _SZ, _P, _I32]),
     "vrq_gemm_topk_workspace_size": (_SZ, [_I32, _I64, _I32, _I32, _I32]),
     "vrq_gemm_topk_pieces": (C.c_int, []),
     "vrq_gemm_topk_plan": (C.c_int, [_I32, _I64, _I32, _I32, _I32, _P]),
@@ -248,6 +260,38 @@ def filtered_k(K: int, flags: int, what: str) -> None:
     if flags & ~VRQ_SEARCH_PHASE1_ONLY:
         raise VrqNativeError(f"{what}: flags {flags} with a row filter (the filtered calls take no "
                              "VRQ_SEARCH_SHARD and no scan flags)")
+
+
+VRQ_LARGE_ENGINE_AUTO, VRQ_LARGE_ENGINE_VALU, VRQ_LARGE_ENGINE_MFMA = 0, 1, 2
+_ENGINES = {"auto": VRQ_LARGE_ENGINE_AUTO, "valu": VRQ_LARGE_ENGINE_VALU, "mfma": VRQ_LARGE_ENGINE_MFMA}
+
+
+def batch_engine(engine, K: int, flags: int, what: str):
+    """The ``engine=`` argument of the search wrappers: ``None`` (today's route: returns None) or "auto" /
+    "valu" / "mfma", the VRQ_LARGE_ENGINE_* value of the *_batch call the search then takes -- the counting
+    scan, K1h or K1hm, for every K up to VRQ_K_LARGE_MAX, with or without a row bitmap.  Raises for a K
+    beyond that, for an unknown name, and for the sharded mode and the scan flags."""
+    if engine is None:
+        return None
+    if engine not in _ENGINES:
+        raise VrqNativeError(f"{what}: engine {engine!r} (None, 'auto', 'mfma' or 'valu')")
+    large_k(K, what)
+    if flags & ~VRQ_SEARCH_PHASE1_ONLY:
+        raise VrqNativeError(f"{what}: flags {flags} with engine={engine!r} (the batch calls take no "
+                             "VRQ_SEARCH_SHARD and no scan flags)")
+    return _ENGINES[engine]
+
+
+def batch_call(base: str, engine, K: int, flags: int = 0, allow=None) -> str:
+    """The entry point a search wrapper takes for ``base`` ("vrq_search3", "vrq_search2", "vrq_hamming_topk"):
+    ``<base>_batch`` with an ``engine``, else ``<base>_filtered`` with a bitmap, ``<base>_large`` for
+    K > 1024, ``base``."""
+    if batch_engine(engine, K, flags, base) is not None:
+        return base + "_batch"
+    if allow is not None:
+        filtered_k(K, flags, base)
+        return base + "_filtered"
+    return base + "_large" if large_k(K, base) else base
 
 
 def check(rc: int, what: str) -> None:

@@ -126,11 +126,12 @@ class CohereVectorDBBinary(_QuantizedVectorDB):
 
     # -- search ------------------------------------------------------------------------------
     def search_vectors(self, query, k: int = 10, binary_oversample: int = 10, compare_float32: bool = False,
-                       allowed_ids=None):
+                       allowed_ids=None, engine=None):
         """Batched search of float32 query embeddings (f32[nq, d]) on the device, one ``vrq_search2`` call.
         Returns (doc_id i64[nq, kk], row i64[nq, kk], hamming i32[nq, kk], score f64[nq, kk]) with
         kk = min(k, K); rows past the candidates are -1.  ``allowed_ids`` (None: all): only these documents
-        are searched (``vrq_search2_filtered``); ids the index does not hold are ignored."""
+        are searched (``vrq_search2_filtered``); ids the index does not hold are ignored.  ``engine`` ("auto",
+        "mfma", "valu"; default None): ``vrq_search2_batch``, the counting scan on the named engine."""
         if k < 0 or binary_oversample < 0:
             raise ValueError("k and binary_oversample must be non-negative")
         qv = as_device_tensor(query, torch.float32, self.device).reshape(-1, self.embedding_dim)
@@ -140,7 +141,7 @@ class CohereVectorDBBinary(_QuantizedVectorDB):
         with torch.cuda.device(self.device):
             rows, ham, sc = Q.search2("f32" if compare_float32 else "sbin", codes,
                                       self._f.view() if compare_float32 else codes, qv, qb, k, binary_oversample,
-                                      rescore_row=self.index.rescore_rows(), allow=allow)
+                                      rescore_row=self.index.rescore_rows(), allow=allow, engine=engine)
         if compare_float32:
             self._check_float_rows(rows)
         ids = torch.where(rows >= 0, self.index.id_map[rows.clamp_min(0)], rows) if self.index.ntotal else rows

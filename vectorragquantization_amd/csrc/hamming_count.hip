@@ -400,29 +400,24 @@ static int large_qg_of(int cb) {
 
 static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
-int large_plan(int64_t n, int cb, int nq, int K, LargePlan* p) {
-  if (n < 1 || nq < 1 || K < 1) return VRQ_EINVAL;
-  if (!large_code_bytes_supported(cb) || K > VRQ_K_LARGE_MAX || n >= (int64_t(1) << 32)) return VRQ_EUNSUPPORTED;
-  const int64_t bins = (int64_t)cb * 8 + 1;
-  p->qg = large_qg_of(cb);
-  p->nw = large_waves(cb);
-  const int qb = nq < kLargeQueryBatch ? nq : kLargeQueryBatch;  // queries of one pass
-  const int64_t nqg = (qb + p->qg - 1) / p->qg;
-  // query groups x chunks near kTargetWaves / nw workgroups, chunks of at least kMinChunkRows rows
-  int64_t want = kTargetWaves / p->nw / nqg;
+// rows per chunk (a multiple of 64) for about `want` chunks: at least kMinChunkRows rows; at most kLargeMaxChunks
+// chunks and kLargeHistBytes of histograms per pass of qb queries, but chunks of at most 2^30 rows
+int64_t large_chunk_rows(int64_t n, int64_t want, int qb, int64_t bins) {
   if (want < 1) want = 1;
   int64_t rows = (n + want - 1) / want;
   if (rows < kMinChunkRows) rows = kMinChunkRows;
-  // at most kLargeMaxChunks chunks and kLargeHistBytes of histograms per pass, but chunks of at most 2^30 rows
   int64_t maxc = kLargeHistBytes / (qb * bins * 4);
   if (maxc > kLargeMaxChunks) maxc = kLargeMaxChunks;
   const int64_t minc = (n + (int64_t(1) << 30) - 1) >> 30;
   if (maxc < minc) maxc = minc;
   if (maxc < 1) maxc = 1;
   if (rows < (n + maxc - 1) / maxc) rows = (n + maxc - 1) / maxc;
-  rows = (rows + 63) & ~int64_t(63);
-  p->chunk_rows = rows;
-  p->nchunks = (int)((n + rows - 1) / rows);
+  return (rows + 63) & ~int64_t(63);
+}
+
+// the chunks and the workspace layout of a plan whose chunk_rows is set (shared by K1h and K1hm)
+void large_layout(LargePlan* p, int64_t n, int nq, int qb, int K, int64_t bins) {
+  p->nchunks = (int)((n + p->chunk_rows - 1) / p->chunk_rows);
   size_t off = 0;
   p->off_hist = off;
   off = align256(off + (size_t)qb * p->nchunks * bins * 4);
@@ -441,6 +436,19 @@ int large_plan(int64_t n, int cb, int nq, int K, LargePlan* p) {
   p->off_kp = off;
   off = align256(off + (size_t)nq * sizeof(int32_t));
   p->bytes = off;
+}
+
+int large_plan(int64_t n, int cb, int nq, int K, LargePlan* p) {
+  if (n < 1 || nq < 1 || K < 1) return VRQ_EINVAL;
+  if (!large_code_bytes_supported(cb) || K > VRQ_K_LARGE_MAX || n >= (int64_t(1) << 32)) return VRQ_EUNSUPPORTED;
+  const int64_t bins = (int64_t)cb * 8 + 1;
+  p->qg = large_qg_of(cb);
+  p->nw = large_waves(cb);
+  const int qb = nq < kLargeQueryBatch ? nq : kLargeQueryBatch;  // queries of one pass
+  const int64_t nqg = (qb + p->qg - 1) / p->qg;
+  // query groups x chunks near kTargetWaves / nw workgroups
+  p->chunk_rows = large_chunk_rows(n, kTargetWaves / p->nw / nqg, qb, bins);
+  large_layout(p, n, nq, qb, K, bins);
   return VRQ_OK;
 }
 
@@ -475,6 +483,18 @@ static int emit_launch(const uint8_t* codes, int64_t n, const uint8_t* q, int nq
   return VRQ_OK;
 }
 
+int large_threshold_launch(const uint32_t* hist, int nq, int nchunks, int bins, int want, int K, bool filtered,
+                           int32_t* tc, int32_t* prefix, uint64_t* lists, hipStream_t s) {
+  if (filtered)
+    hipLaunchKernelGGL(large_threshold_kernel<true>, dim3(nq), dim3(THR_THREADS), 0, s, hist, nchunks, bins, want,
+                       K, tc, prefix, lists);
+  else
+    hipLaunchKernelGGL(large_threshold_kernel<false>, dim3(nq), dim3(THR_THREADS), 0, s, hist, nchunks, bins, want,
+                       K, tc, prefix, lists);
+  VRQ_LAUNCH_CHECK();
+  return VRQ_OK;
+}
+
 // one pass (at most kLargeQueryBatch queries): the pointers are the pass's own slices
 template <int CB>
 static int large_pass(const LargePlan& p, const uint8_t* codes, int64_t n, const uint8_t* q, int nq, int K,
@@ -487,13 +507,8 @@ static int large_pass(const LargePlan& p, const uint8_t* codes, int64_t n, const
   }
   if (stages & kLargeStageThreshold) {
     const int want = (int64_t)K < n ? K : (int)n;
-    if (allow)
-      hipLaunchKernelGGL(large_threshold_kernel<true>, dim3(nq), dim3(THR_THREADS), 0, s, hist, p.nchunks, bins,
-                         want, K, tc, prefix, lists);
-    else
-      hipLaunchKernelGGL(large_threshold_kernel<false>, dim3(nq), dim3(THR_THREADS), 0, s, hist, p.nchunks, bins,
-                         want, K, tc, prefix, lists);
-    VRQ_LAUNCH_CHECK();
+    rc = large_threshold_launch(hist, nq, p.nchunks, bins, want, K, allow != nullptr, tc, prefix, lists, s);
+    if (rc != VRQ_OK) return rc;
   }
   if (stages & kLargeStageEmit) {
     rc = emit_launch<CB>(codes, n, q, nq, K, p.chunk_rows, p.nchunks, allow, tc, prefix, lists, s);

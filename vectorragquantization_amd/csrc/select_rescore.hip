@@ -1788,19 +1788,38 @@ static int large_plan_checked(int64_t n, int cb, int nq, int K, size_t workspace
 // for the bitmap, which is checked with the other pointers a non-empty call reads, before any launch.
 static bool allow_ok(const uint64_t* allow) { return allow && ((uintptr_t)allow & 7) == 0; }
 
+// The batch calls (vrq_*_batch) are the same calls again with a choice of the scan's engine: `engine` is -1 for
+// a *_large / *_filtered call (K1h, its own workspace size) and a VRQ_LARGE_ENGINE_* value for a *_batch call
+// (the workspace covers either engine).  A *_batch call is filtered iff its bitmap is not null.
+static bool engine_ok(int engine) { return engine >= -1 && engine <= VRQ_LARGE_ENGINE_MFMA; }
+
+static int large_route_checked(int64_t n, int cb, int nq, int K, int engine, bool filtered, size_t workspace_bytes,
+                               BatchPlan* bp) {
+  if (engine < 0) {
+    *bp = BatchPlan{};
+    bp->engine = VRQ_LARGE_ENGINE_VALU;
+    return large_plan_checked(n, cb, nq, K, workspace_bytes, &bp->lp);
+  }
+  (void)filtered;  // (AUTO's choice does not depend on it: one table entry per code size serves both kinds)
+  const int rc = batch_plan(n, cb, nq, K, engine, bp);
+  if (rc != VRQ_OK) return rc;
+  return workspace_bytes < bp->need ? VRQ_EWORKSPACE : VRQ_OK;
+}
+
 static int scan_large_impl(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq, int32_t K,
                            int32_t stages, void* workspace, size_t workspace_bytes, void* stream, bool filtered,
-                           const uint64_t* allow) {
+                           const uint64_t* allow, int engine = -1) {
+  VRQ_CHECK_ARG(engine_ok(engine));
   VRQ_CHECK_ARG(n >= 0 && nq >= 0 && K >= 0);
   if (!vrq_dim_supported(dim) || K > VRQ_K_LARGE_MAX) return VRQ_EUNSUPPORTED;
   if (stages & ~kLargeStageAll) return VRQ_EUNSUPPORTED;
   if (nq == 0 || n == 0 || K == 0) return VRQ_OK;
   VRQ_CHECK_ARG(codes && qb && workspace);
   if (filtered) VRQ_CHECK_ARG(allow_ok(allow));
-  LargePlan p;
-  const int rc = large_plan_checked(n, dim / 8, nq, K, workspace_bytes, &p);
+  BatchPlan bp;
+  const int rc = large_route_checked(n, dim / 8, nq, K, engine, filtered, workspace_bytes, &bp);
   if (rc != VRQ_OK) return rc;
-  return large_scan_launch(p, codes, n, dim / 8, qb, nq, K, (uint8_t*)workspace, (hipStream_t)stream, stages,
+  return batch_scan_launch(bp, codes, n, dim / 8, qb, nq, K, (uint8_t*)workspace, (hipStream_t)stream, stages,
                            allow);
 }
 
@@ -1817,7 +1836,8 @@ int vrq_scan_filtered(const uint8_t* codes, int64_t n, int32_t dim, const uint8_
 static int hamming_topk_large_impl(const uint8_t* codes, int64_t n, int32_t code_bytes, int64_t row_offset,
                                    const uint8_t* queries, int32_t nq, int32_t k, int32_t* out_dist,
                                    int64_t* out_rows, void* workspace, size_t workspace_bytes, void* stream,
-                                   bool filtered, const uint64_t* allow) {
+                                   bool filtered, const uint64_t* allow, int engine = -1) {
+  VRQ_CHECK_ARG(engine_ok(engine));
   VRQ_CHECK_ARG(n >= 0 && nq >= 0 && k >= 0 && out_dist && out_rows);
   if (code_bytes <= 0 || code_bytes > 256 || !vrq_dim_supported(code_bytes * 8) || k > VRQ_K_LARGE_MAX)
     return VRQ_EUNSUPPORTED;
@@ -1826,11 +1846,12 @@ static int hamming_topk_large_impl(const uint8_t* codes, int64_t n, int32_t code
   if (n == 0 || k == 0) return fill_empty(nq, k, nullptr, out_rows, out_dist, nullptr, nullptr, s);
   VRQ_CHECK_ARG(codes && queries && workspace);
   if (filtered) VRQ_CHECK_ARG(allow_ok(allow));
-  LargePlan p;
-  int rc = large_plan_checked(n, code_bytes, nq, k, workspace_bytes, &p);
+  BatchPlan bp;
+  int rc = large_route_checked(n, code_bytes, nq, k, engine, filtered, workspace_bytes, &bp);
   if (rc != VRQ_OK) return rc;
+  const LargePlan& p = bp.lp;
   uint8_t* ws = (uint8_t*)workspace;
-  rc = large_scan_launch(p, codes, n, code_bytes, queries, nq, k, ws, s, 0, allow);
+  rc = batch_scan_launch(bp, codes, n, code_bytes, queries, nq, k, ws, s, 0, allow);
   if (rc != VRQ_OK) return rc;
   return large_sort_launch(s, nq, (uint64_t*)(ws + p.off_lists), k, (int32_t*)(ws + p.off_kp), true, row_offset,
                            nullptr, out_rows, out_dist);
@@ -1856,7 +1877,8 @@ static int search3_large_impl(const uint8_t* codes, const int8_t* x8, const doub
                               const float* qf, const uint8_t* qb, int32_t nq, int32_t k, int32_t K, int32_t K3,
                               int32_t flags, int32_t* out_count, int64_t* out_rows, int32_t* out_dist,
                               double* out_binary, double* out_cosine, void* workspace, size_t workspace_bytes,
-                              void* stream, bool filtered, const uint64_t* allow) {
+                              void* stream, bool filtered, const uint64_t* allow, int engine = -1) {
+  VRQ_CHECK_ARG(engine_ok(engine));
   VRQ_CHECK_ARG(n >= 0 && nq >= 0 && k >= 0 && K >= 0 && K3 >= 0);
   VRQ_CHECK_ARG(out_count && out_rows && out_dist);
   if (!vrq_dim_supported(dim) || K > VRQ_K_LARGE_MAX || k > VRQ_K_LARGE_MAX) return VRQ_EUNSUPPORTED;
@@ -1871,16 +1893,17 @@ static int search3_large_impl(const uint8_t* codes, const int8_t* x8, const doub
   VRQ_CHECK_ARG(codes && qb && workspace);
   if (!p1) VRQ_CHECK_ARG(qf && x8 && norms);
   if (filtered) VRQ_CHECK_ARG(allow_ok(allow));
-  LargePlan p;
-  int rc = large_plan_checked(n, dim / 8, nq, K, workspace_bytes, &p);
+  BatchPlan bp;
+  int rc = large_route_checked(n, dim / 8, nq, K, engine, filtered, workspace_bytes, &bp);
   if (rc != VRQ_OK) return rc;
+  const LargePlan& p = bp.lp;
   uint8_t* ws = (uint8_t*)workspace;
   uint64_t* lists = (uint64_t*)(ws + p.off_lists);
   int32_t* kp = (int32_t*)(ws + p.off_kp);
   int32_t* ord = (int32_t*)(ws + p.off_ord);
   double* s2 = (double*)(ws + p.off_s2);
   double* s3 = (double*)(ws + p.off_s3);
-  rc = large_scan_launch(p, codes, n, dim / 8, qb, nq, K, ws, s, 0, allow);
+  rc = batch_scan_launch(bp, codes, n, dim / 8, qb, nq, K, ws, s, 0, allow);
   if (rc != VRQ_OK) return rc;
   rc = large_sort_launch(s, nq, lists, K, kp, p1, row_offset, out_count, out_rows, out_dist);
   if (rc != VRQ_OK || p1) return rc;
@@ -1957,7 +1980,8 @@ static int search2_large_impl(int32_t mode, const uint8_t* codes, const void* q,
                               const float* qf, const uint8_t* qb, int32_t nq, int32_t k, int32_t K, int32_t flags,
                               int32_t* out_count, int64_t* out_rows, int32_t* out_dist, double* out_score,
                               void* workspace, size_t workspace_bytes, void* stream, bool filtered,
-                              const uint64_t* allow) {
+                              const uint64_t* allow, int engine = -1) {
+  VRQ_CHECK_ARG(engine_ok(engine));
   VRQ_CHECK_ARG(search2_mode_ok(mode));
   VRQ_CHECK_ARG(n >= 0 && nq >= 0 && k >= 0 && K >= 0);
   VRQ_CHECK_ARG(out_count && out_rows && out_dist && out_score);
@@ -1970,14 +1994,15 @@ static int search2_large_impl(int32_t mode, const uint8_t* codes, const void* q,
   VRQ_CHECK_ARG(codes && qb && workspace && qf && q);
   if (mode == VRQ_ENC_INT8_LOCAL || mode == VRQ_ENC_INT4_LOCAL) VRQ_CHECK_ARG(minmax);
   if (filtered) VRQ_CHECK_ARG(allow_ok(allow));
-  LargePlan p;
-  int rc = large_plan_checked(n, dim / 8, nq, K, workspace_bytes, &p);
+  BatchPlan bp;
+  int rc = large_route_checked(n, dim / 8, nq, K, engine, filtered, workspace_bytes, &bp);
   if (rc != VRQ_OK) return rc;
+  const LargePlan& p = bp.lp;
   uint8_t* ws = (uint8_t*)workspace;
   uint64_t* lists = (uint64_t*)(ws + p.off_lists);
   int32_t* kp = (int32_t*)(ws + p.off_kp);
   double* s2 = (double*)(ws + p.off_s2);
-  rc = large_scan_launch(p, codes, n, dim / 8, qb, nq, K, ws, s, 0, allow);
+  rc = batch_scan_launch(bp, codes, n, dim / 8, qb, nq, K, ws, s, 0, allow);
   if (rc != VRQ_OK) return rc;
   rc = large_sort_launch(s, nq, lists, K, kp, false, 0, nullptr, nullptr, nullptr);
   if (rc != VRQ_OK) return rc;
@@ -2029,6 +2054,98 @@ int vrq_search2_filtered(int32_t mode, const uint8_t* codes, const void* q, cons
   return search2_large_impl(mode, codes, q, minmax, limit, rescore_row, n, dim, row_offset, qf, qb, nq, k, K, flags,
                             out_count, out_rows, out_dist, out_score, workspace, workspace_bytes, stream, true,
                             allow);
+}
+
+// ---- the batch calls: the *_large / *_filtered calls with the scan's engine chosen (K1h or K1hm) ----
+// (the bitmap's alignment is checked where the *_filtered calls check theirs: after the empty-shape returns)
+static bool batch_engine_ok(int32_t engine) {
+  return engine >= VRQ_LARGE_ENGINE_AUTO && engine <= VRQ_LARGE_ENGINE_MFMA;
+}
+
+int vrq_large_engine(int64_t n, int32_t dim, int32_t nq, int32_t K, int32_t filtered) {
+  if (n < 1 || nq < 1 || K < 1) return VRQ_EINVAL;
+  if (!vrq_dim_supported(dim)) return VRQ_EUNSUPPORTED;
+  (void)filtered;  // one minimum batch per code size serves both kinds of scan, so the plan call needs no such axis
+  BatchPlan p;
+  const int rc = batch_plan(n, dim / 8, nq, K, VRQ_LARGE_ENGINE_AUTO, &p);
+  return rc != VRQ_OK ? rc : p.engine;
+}
+
+size_t vrq_search3_batch_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K) {
+  BatchPlan p;
+  return vrq_dim_supported(dim) && batch_plan(n, dim / 8, nq, K, VRQ_LARGE_ENGINE_AUTO, &p) == VRQ_OK
+             ? p.need
+             : 0;
+}
+
+size_t vrq_search2_batch_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K) {
+  return vrq_search3_batch_workspace_size(n, dim, nq, K);
+}
+
+size_t vrq_scan_batch_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K) {
+  return vrq_search3_batch_workspace_size(n, dim, nq, K);
+}
+
+size_t vrq_hamming_topk_batch_workspace_size(int64_t n, int32_t code_bytes, int32_t nq, int32_t k) {
+  return code_bytes > 0 && code_bytes <= 256 ? vrq_search3_batch_workspace_size(n, code_bytes * 8, nq, k) : 0;
+}
+
+int vrq_scan_batch_plan(int64_t n, int32_t dim, int32_t nq, int32_t K, int32_t engine, int64_t* info) {
+  if (!info || n < 1 || nq < 1 || K < 1 || !batch_engine_ok(engine)) return VRQ_EINVAL;
+  if (!vrq_dim_supported(dim)) return VRQ_EUNSUPPORTED;
+  BatchPlan p;
+  const int rc = batch_plan(n, dim / 8, nq, K, engine, &p);
+  if (rc != VRQ_OK) return rc;
+  info[0] = p.engine;
+  info[1] = p.lp.chunk_rows;
+  info[2] = p.lp.nchunks;
+  info[3] = p.qpw;
+  info[4] = p.nqb;
+  info[5] = p.flush_rows;
+  info[6] = (int64_t)p.lp.off_hist;
+  info[7] = (int64_t)p.lp.off_tc;
+  info[8] = (int64_t)p.lp.off_lists;
+  info[9] = (int64_t)p.need;
+  return VRQ_OK;
+}
+
+int vrq_scan_batch(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq, int32_t K,
+                   int32_t stages, const uint64_t* allow, void* workspace, size_t workspace_bytes, void* stream,
+                   int32_t engine) {
+  VRQ_CHECK_ARG(batch_engine_ok(engine));
+  return scan_large_impl(codes, n, dim, qb, nq, K, stages, workspace, workspace_bytes, stream, allow != nullptr,
+                         allow, engine);
+}
+
+int vrq_hamming_topk_batch(const uint8_t* codes, int64_t n, int32_t code_bytes, int64_t row_offset,
+                           const uint8_t* queries, int32_t nq, int32_t k, const uint64_t* allow, int32_t* out_dist,
+                           int64_t* out_rows, void* workspace, size_t workspace_bytes, void* stream,
+                           int32_t engine) {
+  VRQ_CHECK_ARG(batch_engine_ok(engine));
+  return hamming_topk_large_impl(codes, n, code_bytes, row_offset, queries, nq, k, out_dist, out_rows, workspace,
+                                 workspace_bytes, stream, allow != nullptr, allow, engine);
+}
+
+int vrq_search3_batch(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
+                      int64_t n, int32_t dim, int64_t row_offset, const float* qf, const uint8_t* qb, int32_t nq,
+                      int32_t k, int32_t K, int32_t K3, int32_t flags, const uint64_t* allow, int32_t* out_count,
+                      int64_t* out_rows, int32_t* out_dist, double* out_binary, double* out_cosine,
+                      void* workspace, size_t workspace_bytes, void* stream, int32_t engine) {
+  VRQ_CHECK_ARG(batch_engine_ok(engine));
+  return search3_large_impl(codes, x8, norms, rescore_row, n, dim, row_offset, qf, qb, nq, k, K, K3, flags,
+                            out_count, out_rows, out_dist, out_binary, out_cosine, workspace, workspace_bytes, stream,
+                            allow != nullptr, allow, engine);
+}
+
+int vrq_search2_batch(int32_t mode, const uint8_t* codes, const void* q, const double* minmax, double limit,
+                      const int64_t* rescore_row, int64_t n, int32_t dim, int64_t row_offset, const float* qf,
+                      const uint8_t* qb, int32_t nq, int32_t k, int32_t K, int32_t flags, const uint64_t* allow,
+                      int32_t* out_count, int64_t* out_rows, int32_t* out_dist, double* out_score,
+                      void* workspace, size_t workspace_bytes, void* stream, int32_t engine) {
+  VRQ_CHECK_ARG(batch_engine_ok(engine));
+  return search2_large_impl(mode, codes, q, minmax, limit, rescore_row, n, dim, row_offset, qf, qb, nq, k, K, flags,
+                            out_count, out_rows, out_dist, out_score, workspace, workspace_bytes, stream,
+                            allow != nullptr, allow, engine);
 }
 
 // ---- the per-shard calls for K up to VRQ_K_LARGE_MAX: K1h, the sort, the scores of every candidate ----

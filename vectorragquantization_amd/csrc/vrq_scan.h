@@ -173,5 +173,32 @@ constexpr int kLargeStageCount = VRQ_LARGE_STAGE_COUNT, kLargeStageThreshold = V
               kLargeStageAll = kLargeStageCount | kLargeStageThreshold | kLargeStageEmit;
 int large_scan_launch(const LargePlan& p, const uint8_t* codes, int64_t n, int cb, const uint8_t* q, int nq, int K,
                       uint8_t* ws, hipStream_t s, int stages, const uint64_t* allow = nullptr);
+// what large_plan and K1hm's plan share: the chunk length under the path's caps, and the chunk count and workspace
+// layout of a plan whose chunk_rows is set
+int64_t large_chunk_rows(int64_t n, int64_t want, int qb, int64_t bins);
+void large_layout(LargePlan* p, int64_t n, int nq, int qb, int K, int64_t bins);
+// the threshold stage of one pass (nq <= kLargeQueryBatch queries), shared by K1h and K1hm
+int large_threshold_launch(const uint32_t* hist, int nq, int nchunks, int bins, int want, int K, bool filtered,
+                           int32_t* tc, int32_t* prefix, uint64_t* lists, hipStream_t s);
+
+// ---- K1hm: the count and emit stages of the counting scan on the matrix cores (hamming_count_mfma.hip), and
+// the choice between the two engines that the vrq_*_batch entry points make.  A K1hm plan keeps K1h's
+// workspace layout and meaning (lp: chunk rows, chunks and every offset), with its own chunking. ----
+struct BatchPlan {
+  int engine;          // VRQ_LARGE_ENGINE_VALU (K1h: lp is large_plan's) or VRQ_LARGE_ENGINE_MFMA
+  LargePlan lp;
+  int mb;              // M-blocks per wave (K1h: 0)
+  int qpw;             // queries per wave of the count kernel: 32 mb, 16 at 256 code bytes (K1h: lp.qg)
+  int nqb;             // query blocks of a full pass of the count kernel
+  int passes;          // passes of at most kLargeQueryBatch queries
+  int64_t flush_rows;  // rows a count workgroup scans between two flushes of its u16 bins; 0: it never flushes
+  size_t need;         // workspace bytes of a vrq_*_batch call: the larger of the two engines'
+};
+// the measured AUTO threshold (INT32_MAX: forced only): one entry per code size, valid with and without a bitmap
+int large_mfma_min_queries(int cb);
+// engine: VRQ_LARGE_ENGINE_*; AUTO is resolved.  VRQ_EINVAL for an engine outside them, else as large_plan
+int batch_plan(int64_t n, int cb, int nq, int K, int engine, BatchPlan* p);
+int batch_scan_launch(const BatchPlan& p, const uint8_t* codes, int64_t n, int cb, const uint8_t* q, int nq, int K,
+                      uint8_t* ws, hipStream_t s, int stages, const uint64_t* allow);
 
 }  // namespace vrq

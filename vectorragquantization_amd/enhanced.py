@@ -124,10 +124,12 @@ def search3_call(K: int, flags: int = 0, allow=None) -> str:
 
 def search3(codes: torch.Tensor, x8: torch.Tensor, norms: torch.Tensor, qf: torch.Tensor, qb: torch.Tensor,
             k: int, K: int, K3: int, flags: int = 0, row_offset: int = 0, rescore_row: torch.Tensor | None = None,
-            workspace: torch.Tensor | None = None, allow: torch.Tensor | None = None):
+            workspace: torch.Tensor | None = None, allow: torch.Tensor | None = None, engine: str | None = None):
     """Thin wrapper of ``vrq_search3``; returns (count, rows, dist, s2, s3) device tensors.  More than 1024
     Phase-I candidates (up to ``VRQ_K_LARGE_MAX``) take ``vrq_search3_large`` (not with ``VRQ_SEARCH_SHARD``).
-    ``allow`` (``filters.row_bitmap``): Phase I over the allowed rows only, ``vrq_search3_filtered``."""
+    ``allow`` (``filters.row_bitmap``): Phase I over the allowed rows only, ``vrq_search3_filtered``.
+    ``engine`` ("auto", "mfma", "valu"; default None = the routes above): ``vrq_search3_batch``, the counting
+    scan on the named engine for every K up to ``VRQ_K_LARGE_MAX``, with or without ``allow``."""
     dev = qf.device
     nq = qf.shape[0]
     n = codes.shape[0]
@@ -144,10 +146,21 @@ def search3(codes: torch.Tensor, x8: torch.Tensor, norms: torch.Tensor, qf: torc
     if rescore_row is not None and rescore_row.shape[0] != n:
         raise N.VrqNativeError(f"vrq_search3: rescore_row has {rescore_row.shape[0]} entries for {n} rows")
     lib = N.load()
-    name = search3_call(K, flags, allow)
+    eng = N.batch_engine(engine, K, flags, "search3")
+    name = N.batch_call("vrq_search3", engine, K, flags, allow) if eng is not None else search3_call(K, flags, allow)
     need = getattr(lib, name + "_workspace_size")(n, dim, nq, K) if n and nq and K else 0
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev)
+    if eng is not None:
+        if allow is not None:
+            allow = checked_bitmap(allow, n, dev)
+        rc = getattr(lib, name)(N.ptr(codes) if n else 0, N.ptr(x8) if n else 0, N.ptr(norms) if n else 0,
+                                   N.ptr(rescore_row), n, dim, row_offset, N.ptr(qf), N.ptr(qb), nq, k, K, K3,
+                                   flags, N.ptr(allow) if n else 0, N.ptr(cnt), N.ptr(rows), N.ptr(dist),
+                                   N.ptr(s2), N.ptr(s3), N.ptr(workspace), workspace.numel(),
+                                   N.stream_handle(dev), eng)
+        N.check(rc, name)
+        return cnt, rows, dist, s2, s3
     if allow is not None:
         allow = checked_bitmap(allow, n, dev)
         rc = lib.vrq_search3_filtered(N.ptr(codes) if n else 0, N.ptr(x8) if n else 0, N.ptr(norms) if n else 0,
@@ -352,7 +365,7 @@ class CohereEnhancedVectorDB:
 
     # -- search ------------------------------------------------------------------------
     def search_vectors(self, qf, qb, k: int = 10, binary_oversample: int = 10,
-                       int8_oversample: int = 3, allowed_ids=None) -> SearchBatch:
+                       int8_oversample: int = 3, allowed_ids=None, engine=None) -> SearchBatch:
         """Batched three-phase search of float32 [nq, d] / ubinary [nq, d/8] query embeddings.
         ``allowed_ids`` (document ids; None: all): only these documents are searched, as if the others had
         been removed; ids the index does not hold are ignored."""
@@ -367,18 +380,19 @@ class CohereEnhancedVectorDB:
             self._ws = torch.empty((8,), dtype=torch.uint8, device=self.device)
         lib = N.load()
         allow = ids_bitmap(self.index.id_map, allowed_ids) if allowed_ids is not None else None
-        size_of = getattr(lib, search3_call(K, 0, allow) + "_workspace_size")  # of the call search3 takes
+        name = N.batch_call("vrq_search3", engine, K, 0, allow) if engine is not None else search3_call(K, 0, allow)
+        size_of = getattr(lib, name + "_workspace_size")  # of the call search3 takes
         need = size_of(n, self.embedding_dim, qf.shape[0], K) if n and K else 0
         if self._ws.numel() < need:
             self._ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
             cnt, rows, dist, s2, s3 = search3(self.index.codes, self._x8.view(), self._norms.view(), qf, qb,
-                                              k, K, K3, 0, 0, self.index.rescore_rows(), self._ws, allow)
+                                              k, K, K3, 0, 0, self.index.rescore_rows(), self._ws, allow, engine)
         ids = torch.where(rows >= 0, self.index.id_map[rows.clamp_min(0)] if n else rows, rows)
         return SearchBatch(cnt, ids, rows, dist, s2, s3)
 
     def search(self, query: str, k: int = 10, binary_oversample: int = 10, int8_oversample: int = 3,
-               allowed_ids=None) -> List[Dict]:
+               allowed_ids=None, engine=None) -> List[Dict]:
         if self.index.ntotal == 0:                                           # :247-249
             logger.error("No documents indexed. Please add documents before searching.")
             return []
@@ -395,7 +409,7 @@ class CohereEnhancedVectorDB:
         except Exception as e:
             logger.error("Error processing query embeddings: %s", str(e))
             return []
-        res = self.search_vectors(qf, qb, k, binary_oversample, int8_oversample, allowed_ids)
+        res = self.search_vectors(qf, qb, k, binary_oversample, int8_oversample, allowed_ids, engine)
         return res.to_dicts(self.texts)[0]
 
 

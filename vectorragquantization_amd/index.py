@@ -145,23 +145,40 @@ class BinaryIndexIDMap2:
                 self._dup = True
             self._rev[e] = base + j
 
-    def search(self, q, k: int, allow=None):
+    def search(self, q, k: int, allow=None, engine=None):
         """(D i32[nq,k], L i64[nq,k]) on the host, like ``faiss.Index.search``; ``allow``: a row bitmap
-        (``filters.row_bitmap`` / ``filters.ids_bitmap``), FAISS's ``SearchParameters(sel=IDSelectorBitmap)``."""
-        D, R = self.search_device(q, k, allow)
+        (``filters.row_bitmap`` / ``filters.ids_bitmap``), FAISS's ``SearchParameters(sel=IDSelectorBitmap)``;
+        ``engine``: as ``search_device``."""
+        D, R = self.search_device(q, k, allow, engine)
         L = torch.where(R >= 0, self.id_map[R.clamp_min(0)] if self.ntotal else R, R)
         return D.cpu().numpy(), L.cpu().numpy()
 
-    def search_device(self, q, k: int, allow=None):
+    def search_device(self, q, k: int, allow=None, engine=None):
         """Phase I on device -> (dist i32[nq,k], internal row i64[nq,k]) device tensors.  With ``allow``
         (int64[ceil(ntotal / 64)], bit r & 63 of word r >> 6: row r takes part) only the allowed rows are
-        searched: ``vrq_hamming_topk_filtered``, the counting scan, for every k up to VRQ_K_LARGE_MAX."""
+        searched: ``vrq_hamming_topk_filtered``, the counting scan, for every k up to VRQ_K_LARGE_MAX.
+        ``engine`` ("auto", "mfma", "valu"; default None = the routes above): ``vrq_hamming_topk_batch``, the
+        counting scan on the named engine for every k up to VRQ_K_LARGE_MAX, with or without ``allow``."""
         q = as_device_tensor(q, torch.uint8, self.device).reshape(-1, self.code_size)
         nq = q.shape[0]
         D = torch.empty((nq, k), dtype=torch.int32, device=self.device)
         R = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         lib = N.load()
         n = self.ntotal
+        eng = N.batch_engine(engine, k, 0, "BinaryIndexIDMap2.search")
+        if eng is not None:
+            if allow is not None:
+                from .filters import checked
+                allow = checked(allow, n, self.device)
+            name = N.batch_call("vrq_hamming_topk", engine, k, 0, allow)
+            ws_bytes = getattr(lib, name + "_workspace_size")(n, self.code_size, nq, k) if n and nq and k else 0
+            ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=self.device)
+            with torch.cuda.device(self.device):
+                rc = getattr(lib, name)(N.ptr(self.codes) if n else 0, n, self.code_size, 0, N.ptr(q), nq, k,
+                                        N.ptr(allow) if n else 0, N.ptr(D), N.ptr(R), N.ptr(ws), ws.numel(),
+                                        N.stream_handle(self.device), eng)
+            N.check(rc, name)
+            return D, R
         if allow is not None:
             from .filters import checked
             N.filtered_k(k, 0, "BinaryIndexIDMap2.search")

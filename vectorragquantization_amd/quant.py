@@ -88,7 +88,7 @@ def dequantize(mode: str, q, minmax=None, limit: float = 0.0, dim: int = None, d
 
 def vectordb_search(mode: str, codes: torch.Tensor, q: torch.Tensor, qf: torch.Tensor, qb: torch.Tensor, k: int = 10,
                     binary_oversample: int = 10, minmax: torch.Tensor = None, limit: float = 0.0,
-                    rescore_row: torch.Tensor = None, allow: torch.Tensor = None):
+                    rescore_row: torch.Tensor = None, allow: torch.Tensor = None, engine: str = None):
     """``VectorDBInt{4,8,16}{,Global}.search`` for a query batch (e.g. VectorDBInt8Global.py:205-252):
     Phase I Hamming top-``k * binary_oversample`` over the ubinary codes (``vrq_hamming_topk``, FAISS
     order), Phase II ``float(np.dot(query_float, doc_emb))`` (``vrq_rescore_dequant``), Python's stable
@@ -99,6 +99,8 @@ def vectordb_search(mode: str, codes: torch.Tensor, q: torch.Tensor, qf: torch.T
     reference's ``doc_db[str(id)]`` lookup returns (the last add of a duplicated id).
     ``allow`` (``filters.row_bitmap``): Phase I over the allowed rows only (``vrq_hamming_topk_filtered``, the
     counting scan, for every K up to VRQ_K_LARGE_MAX), then the same rescoring.
+    ``engine`` ("auto", "mfma", "valu"; default None = the routes above): Phase I through
+    ``vrq_hamming_topk_batch``, the counting scan on the named engine, with or without ``allow``.
     Returns (rows i64[nq, k], hamming i32[nq, k], score f64[nq, k]) on the device; rows past the
     corpus are -1 (score NaN)."""
     dev = codes.device
@@ -108,7 +110,17 @@ def vectordb_search(mode: str, codes: torch.Tensor, q: torch.Tensor, qf: torch.T
     lib = N.load()
     dist = torch.empty((nq, K), dtype=torch.int32, device=dev)
     rows = torch.empty((nq, K), dtype=torch.int64, device=dev)
-    if allow is not None:
+    eng = N.batch_engine(engine, K, 0, "vectordb_search")
+    if eng is not None:
+        if allow is not None:
+            allow = checked_bitmap(allow, n, dev)
+        name = N.batch_call("vrq_hamming_topk", engine, K, 0, allow)
+        ws = torch.empty((max(8, getattr(lib, name + "_workspace_size")(n, cb, nq, K)),), dtype=torch.uint8,
+                         device=dev)
+        with torch.cuda.device(dev):
+            N.check(getattr(lib, name)(N.ptr(codes), n, cb, 0, N.ptr(qb), nq, K, N.ptr(allow), N.ptr(dist),
+                                               N.ptr(rows), N.ptr(ws), ws.numel(), N.stream_handle(dev), eng), name)
+    elif allow is not None:
         N.filtered_k(K, 0, "vectordb_search")
         allow = checked_bitmap(allow, n, dev)
         name = "vrq_hamming_topk_filtered"
@@ -153,7 +165,7 @@ _SEARCH2_MODES = {**_DEQ_MODES, "f32": N.VRQ_RESCORE_F32, "sbin": N.VRQ_RESCORE_
 
 def search2(mode: str, codes: torch.Tensor, q: torch.Tensor, qf: torch.Tensor, qb: torch.Tensor, k: int = 10,
             binary_oversample: int = 10, minmax: torch.Tensor = None, limit: float = 0.0,
-            rescore_row: torch.Tensor = None, flags: int = 0, allow: torch.Tensor = None):
+            rescore_row: torch.Tensor = None, flags: int = 0, allow: torch.Tensor = None, engine: str = None):
     """The two-phase search of ``vectordb_search`` as ONE fused call (``vrq_search2``: the Phase-I scan and
     a finish kernel that merges, rescores, sorts and cuts; ``CohereVectorDBBinary.py:215-239`` and the same
     loop of the ``VectorDBInt*`` classes).  ``mode`` is a ``vectordb_search`` rescoring mode (``int8g`` ...
@@ -161,7 +173,9 @@ def search2(mode: str, codes: torch.Tensor, q: torch.Tensor, qf: torch.Tensor, q
     rows.  ``flags``: 0, ``VRQ_SEARCH_SCAN_VALU`` or ``VRQ_SEARCH_SCAN_MFMA``.  Same return contract as
     ``vectordb_search``: (rows i64[nq, kk], hamming i32[nq, kk], score f64[nq, kk]) on the device,
     kk = min(k, K); rows past the corpus are -1 (score NaN).  ``allow`` (``filters.row_bitmap``): Phase I over
-    the allowed rows only, ``vrq_search2_filtered`` for every K up to VRQ_K_LARGE_MAX (no flags)."""
+    the allowed rows only, ``vrq_search2_filtered`` for every K up to VRQ_K_LARGE_MAX (no flags).
+    ``engine`` ("auto", "mfma", "valu"; default None = the routes above): ``vrq_search2_batch``, the counting
+    scan on the named engine for every K up to VRQ_K_LARGE_MAX, with or without ``allow`` (no flags)."""
     if mode not in _SEARCH2_MODES:
         raise ValueError(f"unknown search2 mode {mode!r}")
     dev = codes.device
@@ -181,6 +195,21 @@ def search2(mode: str, codes: torch.Tensor, q: torch.Tensor, qf: torch.Tensor, q
         # the ABI indexes q / minmax / rescore_row by candidate row and cannot see their lengths
         raise N.VrqNativeError(f"search2: {n} code rows but {None if q is None else q.shape[0]} stored rows")
     lib = N.load()
+    eng = N.batch_engine(engine, K, flags, "search2")
+    if eng is not None:
+        if flags:
+            raise N.VrqNativeError(f"search2: flags {flags} with engine={engine!r} (vrq_search2_batch takes none)")
+        if allow is not None:
+            allow = checked_bitmap(allow, n, dev)
+        name = N.batch_call("vrq_search2", engine, K, flags, allow)
+        count = torch.empty((nq,), dtype=torch.int32, device=dev)
+        ws = torch.empty((max(8, getattr(lib, name + "_workspace_size")(n, d, nq, K)),), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            N.check(getattr(lib, name)(_SEARCH2_MODES[mode], N.ptr(codes), N.ptr(q), N.ptr(minmax), float(limit),
+                                          N.ptr(rescore_row), n, d, 0, N.ptr(qf), N.ptr(qb), nq, kk, K, 0,
+                                          N.ptr(allow), N.ptr(count), N.ptr(rows), N.ptr(dist), N.ptr(score),
+                                          N.ptr(ws), ws.numel(), N.stream_handle(dev), eng), f"{name}({mode})")
+        return rows, dist, score
     if allow is not None:
         N.filtered_k(K, flags, "search2")
         if flags:

@@ -304,11 +304,12 @@ class _QuantizedVectorDB:
 
     # -- search ------------------------------------------------------------------------
     def search_vectors(self, query, k: int = 10, binary_oversample: int = 10, compare_float32: bool = False,
-                       allowed_ids=None):
+                       allowed_ids=None, engine=None):
         """Batched search of query embeddings (f32[nq, d]; i16[nq, d] for VectorDBInt16) on the device.
         Returns (doc_id i64[nq, kk], row i64[nq, kk], hamming i32[nq, kk], score f64[nq, kk]) with
         kk = min(k, K); rows past the candidates are -1.  ``allowed_ids`` (None: all): only these documents
-        are searched (Phase I through ``vrq_hamming_topk_filtered``); ids the index does not hold are ignored."""
+        are searched (Phase I through ``vrq_hamming_topk_filtered``); ids the index does not hold are ignored.
+        ``engine`` ("auto", "mfma", "valu"; default None): Phase I through ``vrq_hamming_topk_batch``."""
         n = self.index.ntotal
         allow = ids_bitmap(self.index.id_map, allowed_ids) if allowed_ids is not None else None
         if k < 0 or binary_oversample < 0:
@@ -318,14 +319,14 @@ class _QuantizedVectorDB:
         with torch.cuda.device(self.device):
             if self.HAMMING_ONLY:
                 rows, ham, sc = Q.vectordb_search("bin16", self.index.codes, None, None, qb, k, binary_oversample,
-                                                  allow=allow)
+                                                  allow=allow, engine=engine)
             else:
                 mode = "f32" if compare_float32 else self.MODE
                 src = self._f.view() if compare_float32 else self._q.view()
                 rr = self.index.rescore_rows()
                 rows, ham, sc = Q.vectordb_search(mode, self.index.codes, src, qv, qb, k, binary_oversample,
                                                   self._mm.view() if self.LOCAL and not compare_float32 else None,
-                                                  self.limit, rr, allow)
+                                                  self.limit, rr, allow, engine)
                 if compare_float32:
                     self._check_float_rows(rows)
         ids = torch.where(rows >= 0, self.index.id_map[rows.clamp_min(0)], rows) if n else rows
@@ -342,11 +343,11 @@ class _QuantizedVectorDB:
                 raise KeyError(str(e))
 
     def search(self, query: str, k: int = 10, binary_oversample: int = 10, compare_float32: bool = False,
-               allowed_ids=None) -> List[Dict]:
+               allowed_ids=None, engine=None) -> List[Dict]:
         if self.index.ntotal == 0:
             logger.error("No documents indexed. Please add documents before searching.")
             return []
-        kw = {}
+        kw = {} if engine is None else {"engine": engine}
         if allowed_ids is not None:
             kw["allowed_ids"] = allowed_ids = [int(i) for i in allowed_ids]
             if not any(i in self.texts for i in allowed_ids):   # an empty set, or none of them indexed
