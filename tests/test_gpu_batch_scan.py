@@ -210,3 +210,39 @@ def test_more_rows_in_a_chunk_than_between_two_flushes(dev):
     lists = ws[p[8]:p[8] + nq * K * 8].cpu().numpy().view(np.uint64).reshape(nq, K)
     for j, b in enumerate((0, 4, 256)):
         assert lists[j].tolist() == [(b << 40) + r for r in range(K)]
+
+
+@pytest.mark.parametrize("engine", ["valu", "mfma"])
+def test_stages_issued_apart_over_two_passes_leave_what_one_call_leaves(dev, engine):
+    """The pass loop of the counting-scan route, which both engines share: COUNT, THRESHOLD and EMIT as three calls
+    leave the (T, c_lt) pairs and the K-lists of all 513 queries that one call with stages = 0 leaves on a second
+    workspace.  513 queries are two passes, the second of one query; 70 000 rows at 384 dims are several chunks;
+    every third row is allowed.  The histograms region holds one pass (run() above), so after the COUNT call its
+    slot 0 holds the counts of query 512, not of query 0: query 512 is a copy of query 0 here, which makes the two
+    the same words and the stages separable, while the pairs, chunk prefixes and lists of the two queries still
+    live in their own slices (b0 = 0 and b0 = 512) and are all compared."""
+    N, lib = _N()
+    eng = {"valu": N.VRQ_LARGE_ENGINE_VALU, "mfma": N.VRQ_LARGE_ENGINE_MFMA}[engine]
+    dim, n, nq, K = 384, 70_000, 513, 1025
+    p = plan(n, dim, nq, K, eng)
+    chunks, off_tc, off_lists, need = p[2], p[7], p[8], p[9]
+    assert p[0] == eng and chunks > 1
+    codes, q = M.random_case(n, dim, nq, 513)
+    q[512] = q[0]
+    c_t, q_t = torch.from_numpy(codes).to(dev), torch.from_numpy(q).to(dev)
+    a_t = torch.from_numpy(M.pack(np.arange(n) % 3 == 0)).to(dev)
+    left = []
+    for fill, stages in ((0xA5, STAGES), (0x5A, (0,))):
+        ws = torch.full((need,), fill, dtype=torch.uint8, device=dev)
+        for st in stages:
+            N.check(lib.vrq_scan_batch(N.ptr(c_t), n, dim, N.ptr(q_t), nq, K, st, N.ptr(a_t), N.ptr(ws), ws.numel(),
+                                       N.stream_handle(dev), eng), "vrq_scan_batch")
+        torch.cuda.synchronize()
+        left.append((ws[off_tc:off_tc + nq * 8].cpu().numpy().view(np.int32).reshape(nq, 2),
+                     ws[off_lists:off_lists + nq * K * 8].cpu().numpy().view(np.uint64).reshape(nq, K)))
+    (tc3, lists3), (tc1, lists1) = left
+    assert np.array_equal(tc3, tc1) and np.array_equal(lists3, lists1)
+    # not vacuous: every list is full of allowed rows (nothing of the prefill is left), cut among ties at T
+    rows = lists1 & np.uint64((1 << 40) - 1)
+    assert (rows < n).all() and (rows % 3 == 0).all() and ((lists1 >> np.uint64(40)) <= tc1[:, :1].astype(np.uint64)).all()
+    assert (tc1[:, 1] < K).all() and np.array_equal(lists1[512], lists1[0]) and not np.array_equal(lists1[1], lists1[0])

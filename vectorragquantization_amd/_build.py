@@ -21,10 +21,10 @@ PROBE_LIB = os.path.join(PKG, "libvrq_probe.so")
 OBJDIR = os.path.join(PKG, "_obj")
 SOURCES = ["hamming_scan.hip", "hamming_mfma.hip", "select_rescore.hip", "encode.hip", "gemm_topk.hip", "dequant.hip",
            "search_dim.hip", "exhaustive_dim.hip", "hamming_mfma_dim.hip", "mfma_threshold.hip", "scan_route.hip",
-           "hamming_count.hip", "hamming_count_mfma.hip"]
+           "hamming_count.hip", "hamming_count_mfma.hip", "count_route.hip"]
 # sources without device code: their objects carry no gfx950 bundle, so they are kept apart (_obj/host/) from
 # the objects whose disassembly the tests read
-HOST_ONLY = {"scan_route.hip"}
+HOST_ONLY = {"scan_route.hip", "count_route.hip"}
 ARCH = os.environ.get("VRQ_OFFLOAD_ARCH", "gfx950")
 CFLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"--offload-arch={ARCH}",
           "-Wall", "-Wno-unused-function", "-Wno-unused-variable"]

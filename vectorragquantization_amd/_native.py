@@ -286,12 +286,47 @@ def batch_call(base: str, engine, K: int, flags: int = 0, allow=None) -> str:
     """The entry point a search wrapper takes for ``base`` ("vrq_search3", "vrq_search2", "vrq_hamming_topk"):
     ``<base>_batch`` with an ``engine``, else ``<base>_filtered`` with a bitmap, ``<base>_large`` for
     K > 1024, ``base``."""
-    if batch_engine(engine, K, flags, base) is not None:
-        return base + "_batch"
-    if allow is not None:
-        filtered_k(K, flags, base)
-        return base + "_filtered"
-    return base + "_large" if large_k(K, base) else base
+    return SearchCall(base, K, flags, allow, engine).name
+
+
+class SearchCall:
+    """The route of a search wrapper to its entry point, and the one place that sizes its workspace and makes
+    the call.  ``name`` is ``<base>_batch`` with an ``engine``, else ``<base>_filtered`` with a bitmap ``allow``,
+    ``<base>_large`` for K > 1024, else ``plain`` (default ``base``); ``engine`` is the resolved
+    VRQ_LARGE_ENGINE_* value (None outside the batch calls).  ``what`` names the caller in the errors
+    ``batch_engine`` / ``filtered_k`` / ``large_k`` raise (default ``base``)."""
+
+    def __init__(self, base: str, K: int, flags: int = 0, allow=None, engine=None, what: str = None,
+                 plain: str = None):
+        what = what or base
+        self.engine = batch_engine(engine, K, flags, what)
+        if self.engine is not None:
+            self.name = base + "_batch"
+        elif allow is not None:
+            filtered_k(K, flags, what)
+            self.name = base + "_filtered"
+        else:
+            self.name = base + "_large" if large_k(K, what) else plain or base
+        self.bitmap = self.engine is not None or allow is not None  # the call has a bitmap argument
+
+    def workspace_bytes(self, lib, n: int, width: int, nq: int, K: int) -> int:
+        """``<name>_workspace_size`` (``width``: dim, or code bytes for vrq_hamming_topk*); 0 for an empty shape."""
+        return getattr(lib, self.name + "_workspace_size")(n, width, nq, K) if n and nq and K else 0
+
+    def workspace(self, lib, n: int, width: int, nq: int, K: int, device, have=None):
+        """``have`` where it is large enough, else a new uint8 tensor of max(8, workspace_bytes) bytes."""
+        import torch
+        need = self.workspace_bytes(lib, n, width, nq, K)
+        if have is not None and have.numel() >= need:
+            return have
+        return torch.empty((max(8, need),), dtype=torch.uint8, device=device)
+
+    def __call__(self, lib, head: tuple, tail: tuple, allow, ws, device, label: str = None) -> None:
+        """``name(*head, [allow,] *tail, ws, bytes, stream[, engine])``: the bitmap's pointer goes between the
+        inputs and the outputs of a *_filtered / *_batch call, the engine ends a *_batch call.  Raises unless
+        VRQ_OK."""
+        args = head + ((ptr(allow),) if self.bitmap else ()) + tail + (ptr(ws), ws.numel(), stream_handle(device))
+        check(getattr(lib, self.name)(*args, *(() if self.engine is None else (self.engine,))), label or self.name)
 
 
 def check(rc: int, what: str) -> None:

@@ -382,105 +382,45 @@ __global__ __launch_bounds__(64) void hamming_emit_kernel(const uint8_t* __restr
 }
 
 // ---------------------------------------------------------------------------
-// host side
+// host side: the tables the plan reads and the stages of one pass (the plan and the loop over passes and
+// stages are the counting-scan route's, count_route.hip)
 // ---------------------------------------------------------------------------
-static bool large_code_bytes_supported(int cb) { return cb == 128 || dim_code_bytes_supported(cb); }
-
-static int large_qg_of(int cb) {
-  switch (cb) {
-    case 32: return large_qg(32);
-    case 48: return large_qg(48);
-    case 64: return large_qg(64);
-    case 96: return large_qg(96);
-    case 128: return large_qg(128);
-    case 192: return large_qg(192);
-    default: return large_qg(256);
-  }
+int large_qg_of(int cb) {
+  return count_code_bytes(cb, [](auto CB) -> int { return large_qg(decltype(CB)::value); });
 }
 
-static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
+int large_waves_of(int cb) { return large_waves(cb); }
 
-// rows per chunk (a multiple of 64) for about `want` chunks: at least kMinChunkRows rows; at most kLargeMaxChunks
-// chunks and kLargeHistBytes of histograms per pass of qb queries, but chunks of at most 2^30 rows
-int64_t large_chunk_rows(int64_t n, int64_t want, int qb, int64_t bins) {
-  if (want < 1) want = 1;
-  int64_t rows = (n + want - 1) / want;
-  if (rows < kMinChunkRows) rows = kMinChunkRows;
-  int64_t maxc = kLargeHistBytes / (qb * bins * 4);
-  if (maxc > kLargeMaxChunks) maxc = kLargeMaxChunks;
-  const int64_t minc = (n + (int64_t(1) << 30) - 1) >> 30;
-  if (maxc < minc) maxc = minc;
-  if (maxc < 1) maxc = 1;
-  if (rows < (n + maxc - 1) / maxc) rows = (n + maxc - 1) / maxc;
-  return (rows + 63) & ~int64_t(63);
+int large_count_launch(int cb, const CountPassArgs& a, hipStream_t s) {
+  return count_code_bytes(cb, [&](auto CBc) -> int {
+    constexpr int CB = decltype(CBc)::value;
+    const int nqg = (a.nq + large_qg(CB) - 1) / large_qg(CB);
+    const dim3 grid((unsigned)(a.nchunks * nqg)), block(64 * large_waves(CB));
+    if (a.allow)
+      hipLaunchKernelGGL((hamming_count_kernel<CB, true>), grid, block, 0, s, a.codes, a.n, a.q, a.nq, a.chunk_rows,
+                         a.nchunks, nqg, a.hist, a.allow);
+    else
+      hipLaunchKernelGGL((hamming_count_kernel<CB, false>), grid, block, 0, s, a.codes, a.n, a.q, a.nq, a.chunk_rows,
+                         a.nchunks, nqg, a.hist, a.allow);
+    VRQ_LAUNCH_CHECK();
+    return VRQ_OK;
+  });
 }
 
-// the chunks and the workspace layout of a plan whose chunk_rows is set (shared by K1h and K1hm)
-void large_layout(LargePlan* p, int64_t n, int nq, int qb, int K, int64_t bins) {
-  p->nchunks = (int)((n + p->chunk_rows - 1) / p->chunk_rows);
-  size_t off = 0;
-  p->off_hist = off;
-  off = align256(off + (size_t)qb * p->nchunks * bins * 4);
-  p->off_prefix = off;
-  off = align256(off + (size_t)nq * p->nchunks * 4 * sizeof(int32_t));
-  p->off_tc = off;
-  off = align256(off + (size_t)nq * 2 * sizeof(int32_t));
-  p->off_lists = off;
-  off = align256(off + (size_t)nq * K * sizeof(uint64_t));
-  p->off_s2 = off;
-  off = align256(off + (size_t)nq * K * sizeof(double));
-  p->off_s3 = off;
-  off = align256(off + (size_t)nq * K * sizeof(double));
-  p->off_ord = off;
-  off = align256(off + (size_t)nq * K * sizeof(int32_t));
-  p->off_kp = off;
-  off = align256(off + (size_t)nq * sizeof(int32_t));
-  p->bytes = off;
-}
-
-int large_plan(int64_t n, int cb, int nq, int K, LargePlan* p) {
-  if (n < 1 || nq < 1 || K < 1) return VRQ_EINVAL;
-  if (!large_code_bytes_supported(cb) || K > VRQ_K_LARGE_MAX || n >= (int64_t(1) << 32)) return VRQ_EUNSUPPORTED;
-  const int64_t bins = (int64_t)cb * 8 + 1;
-  p->qg = large_qg_of(cb);
-  p->nw = large_waves(cb);
-  const int qb = nq < kLargeQueryBatch ? nq : kLargeQueryBatch;  // queries of one pass
-  const int64_t nqg = (qb + p->qg - 1) / p->qg;
-  // query groups x chunks near kTargetWaves / nw workgroups
-  p->chunk_rows = large_chunk_rows(n, kTargetWaves / p->nw / nqg, qb, bins);
-  large_layout(p, n, nq, qb, K, bins);
-  return VRQ_OK;
-}
-
-template <int CB>
-static int count_launch(const uint8_t* codes, int64_t n, const uint8_t* q, int nq, int64_t chunk_rows, int nchunks,
-                        const uint64_t* allow, uint32_t* hist, hipStream_t s) {
-  const int nqg = (nq + large_qg(CB) - 1) / large_qg(CB);
-  const dim3 grid((unsigned)(nchunks * nqg)), block(64 * large_waves(CB));
-  if (allow)
-    hipLaunchKernelGGL((hamming_count_kernel<CB, true>), grid, block, 0, s, codes, n, q, nq, chunk_rows, nchunks,
-                       nqg, hist, allow);
-  else
-    hipLaunchKernelGGL((hamming_count_kernel<CB, false>), grid, block, 0, s, codes, n, q, nq, chunk_rows, nchunks,
-                       nqg, hist, allow);
-  VRQ_LAUNCH_CHECK();
-  return VRQ_OK;
-}
-
-template <int CB>
-static int emit_launch(const uint8_t* codes, int64_t n, const uint8_t* q, int nq, int K, int64_t chunk_rows,
-                       int nchunks, const uint64_t* allow, const int32_t* tc, const int32_t* prefix,
-                       uint64_t* lists, hipStream_t s) {
-  const int nqg = (nq + LARGE_QE - 1) / LARGE_QE;
-  const dim3 grid((unsigned)(nchunks * nqg)), block(64);
-  if (allow)
-    hipLaunchKernelGGL((hamming_emit_kernel<CB, true>), grid, block, 0, s, codes, n, q, nq, K, chunk_rows, nchunks,
-                       nqg, tc, prefix, lists, allow);
-  else
-    hipLaunchKernelGGL((hamming_emit_kernel<CB, false>), grid, block, 0, s, codes, n, q, nq, K, chunk_rows, nchunks,
-                       nqg, tc, prefix, lists, allow);
-  VRQ_LAUNCH_CHECK();
-  return VRQ_OK;
+int large_emit_launch(int cb, const CountPassArgs& a, hipStream_t s) {
+  return count_code_bytes(cb, [&](auto CBc) -> int {
+    constexpr int CB = decltype(CBc)::value;
+    const int nqg = (a.nq + LARGE_QE - 1) / LARGE_QE;
+    const dim3 grid((unsigned)(a.nchunks * nqg)), block(64);
+    if (a.allow)
+      hipLaunchKernelGGL((hamming_emit_kernel<CB, true>), grid, block, 0, s, a.codes, a.n, a.q, a.nq, a.K,
+                         a.chunk_rows, a.nchunks, nqg, a.tc, a.prefix, a.lists, a.allow);
+    else
+      hipLaunchKernelGGL((hamming_emit_kernel<CB, false>), grid, block, 0, s, a.codes, a.n, a.q, a.nq, a.K,
+                         a.chunk_rows, a.nchunks, nqg, a.tc, a.prefix, a.lists, a.allow);
+    VRQ_LAUNCH_CHECK();
+    return VRQ_OK;
+  });
 }
 
 int large_threshold_launch(const uint32_t* hist, int nq, int nchunks, int bins, int want, int K, bool filtered,
@@ -492,55 +432,6 @@ int large_threshold_launch(const uint32_t* hist, int nq, int nchunks, int bins, 
     hipLaunchKernelGGL(large_threshold_kernel<false>, dim3(nq), dim3(THR_THREADS), 0, s, hist, nchunks, bins, want,
                        K, tc, prefix, lists);
   VRQ_LAUNCH_CHECK();
-  return VRQ_OK;
-}
-
-// one pass (at most kLargeQueryBatch queries): the pointers are the pass's own slices
-template <int CB>
-static int large_pass(const LargePlan& p, const uint8_t* codes, int64_t n, const uint8_t* q, int nq, int K,
-                      const uint64_t* allow, uint32_t* hist, int32_t* prefix, int32_t* tc, uint64_t* lists, hipStream_t s, int stages) {
-  constexpr int bins = CB * 8 + 1;
-  int rc;
-  if (stages & kLargeStageCount) {
-    rc = count_launch<CB>(codes, n, q, nq, p.chunk_rows, p.nchunks, allow, hist, s);
-    if (rc != VRQ_OK) return rc;
-  }
-  if (stages & kLargeStageThreshold) {
-    const int want = (int64_t)K < n ? K : (int)n;
-    rc = large_threshold_launch(hist, nq, p.nchunks, bins, want, K, allow != nullptr, tc, prefix, lists, s);
-    if (rc != VRQ_OK) return rc;
-  }
-  if (stages & kLargeStageEmit) {
-    rc = emit_launch<CB>(codes, n, q, nq, K, p.chunk_rows, p.nchunks, allow, tc, prefix, lists, s);
-    if (rc != VRQ_OK) return rc;
-  }
-  return VRQ_OK;
-}
-
-int large_scan_launch(const LargePlan& p, const uint8_t* codes, int64_t n, int cb, const uint8_t* q, int nq, int K,
-                      uint8_t* ws, hipStream_t s, int stages, const uint64_t* allow) {
-  if (p.nchunks < 1 || p.nchunks > kLargeMaxChunks) return VRQ_EINVAL;  // not a K1h plan
-  if (!(stages & kLargeStageAll)) stages |= kLargeStageAll;
-  uint32_t* hist = (uint32_t*)(ws + p.off_hist);
-  for (int b0 = 0; b0 < nq; b0 += kLargeQueryBatch) {
-    const int nb = nq - b0 < kLargeQueryBatch ? nq - b0 : kLargeQueryBatch;
-    int32_t* prefix = (int32_t*)(ws + p.off_prefix) + (int64_t)b0 * p.nchunks * 4;
-    int32_t* tc = (int32_t*)(ws + p.off_tc) + (int64_t)b0 * 2;
-    uint64_t* lists = (uint64_t*)(ws + p.off_lists) + (int64_t)b0 * K;
-    const uint8_t* qb = q + (int64_t)b0 * cb;
-    int rc;
-    switch (cb) {
-      case 32: rc = large_pass<32>(p, codes, n, qb, nb, K, allow, hist, prefix, tc, lists, s, stages); break;
-      case 48: rc = large_pass<48>(p, codes, n, qb, nb, K, allow, hist, prefix, tc, lists, s, stages); break;
-      case 64: rc = large_pass<64>(p, codes, n, qb, nb, K, allow, hist, prefix, tc, lists, s, stages); break;
-      case 96: rc = large_pass<96>(p, codes, n, qb, nb, K, allow, hist, prefix, tc, lists, s, stages); break;
-      case 128: rc = large_pass<128>(p, codes, n, qb, nb, K, allow, hist, prefix, tc, lists, s, stages); break;
-      case 192: rc = large_pass<192>(p, codes, n, qb, nb, K, allow, hist, prefix, tc, lists, s, stages); break;
-      case 256: rc = large_pass<256>(p, codes, n, qb, nb, K, allow, hist, prefix, tc, lists, s, stages); break;
-      default: return VRQ_EUNSUPPORTED;
-    }
-    if (rc != VRQ_OK) return rc;
-  }
   return VRQ_OK;
 }
 

@@ -403,30 +403,18 @@ __global__ __launch_bounds__(64) void hamming_emit_mfma_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// host side
+// host side: the tables the plan reads and the stages of one pass (the plan and the loop over passes and
+// stages are the counting-scan route's, count_route.hip)
 // ---------------------------------------------------------------------------
+int large_mfma_qreal_of(int cb) { return cb == 256 ? 16 : 32; }
+// M-blocks per wave: two where 64 queries' bins and four rings fit the LDS (up to 96 code bytes)
+int large_mfma_mb_of(int cb, int qb) { return cb <= 96 && qb > 32 ? 2 : 1; }
+int64_t large_mfma_flush_rows() { return kCountFlushRows; }
+
 namespace {
 
-int qreal_of(int cb) { return cb == 256 ? 16 : 32; }
-// M-blocks per wave: two where 64 queries' bins and four rings fit the LDS (up to 96 code bytes)
-int mb_of(int cb, int qb) { return cb <= 96 && qb > 32 ? 2 : 1; }
-
-struct PassArgs {
-  const uint8_t* codes;
-  int64_t n;
-  const uint8_t* q;
-  int nq, K;
-  int64_t chunk_rows;
-  int nchunks;
-  const uint64_t* allow;
-  uint32_t* hist;
-  const int32_t* tc;
-  const int32_t* prefix;
-  uint64_t* lists;
-};
-
 template <int KS, int MB>
-int count_launch(const PassArgs& a, hipStream_t s) {
+int count_launch(const CountPassArgs& a, hipStream_t s) {
   using Cd = CountCode<KS>;
   const int qpw = Cd::QREAL * MB, nqb = (a.nq + qpw - 1) / qpw;
   const dim3 grid((unsigned)(a.nchunks * nqb)), block(64 * Cd::NW);
@@ -441,7 +429,7 @@ int count_launch(const PassArgs& a, hipStream_t s) {
 }
 
 template <int KS, int MB>
-int emit_launch(const PassArgs& a, hipStream_t s) {
+int emit_launch(const CountPassArgs& a, hipStream_t s) {
   const int qpw = 32 * MB, nqb = (a.nq + qpw - 1) / qpw;
   const dim3 grid((unsigned)(a.nchunks * nqb)), block(64);
   if (a.allow)
@@ -454,28 +442,20 @@ int emit_launch(const PassArgs& a, hipStream_t s) {
   return VRQ_OK;
 }
 
-template <int KS>
-int stage_launch(bool emit, int mb, const PassArgs& a, hipStream_t s) {
-  if (mb == 1) return emit ? emit_launch<KS, 1>(a, s) : count_launch<KS, 1>(a, s);
-  if constexpr (KS <= 12)
-    if (mb == 2) return emit ? emit_launch<KS, 2>(a, s) : count_launch<KS, 2>(a, s);
-  return VRQ_EUNSUPPORTED;  // (a plan never asks for it)
-}
-
-int stage_launch_cb(int cb, bool emit, int mb, const PassArgs& a, hipStream_t s) {
-  switch (cb) {
-    case 32: return stage_launch<4>(emit, mb, a, s);
-    case 48: return stage_launch<6>(emit, mb, a, s);
-    case 64: return stage_launch<8>(emit, mb, a, s);
-    case 96: return stage_launch<12>(emit, mb, a, s);
-    case 128: return stage_launch<16>(emit, mb, a, s);
-    case 192: return stage_launch<24>(emit, mb, a, s);
-    case 256: return stage_launch<32>(emit, mb, a, s);
-    default: return VRQ_EUNSUPPORTED;
-  }
+int stage_launch(int cb, bool emit, const CountPassArgs& a, hipStream_t s) {
+  return count_code_bytes(cb, [&](auto CB) -> int {
+    constexpr int KS = decltype(CB)::value / 8;
+    if (a.mb == 1) return emit ? emit_launch<KS, 1>(a, s) : count_launch<KS, 1>(a, s);
+    if constexpr (KS <= 12)
+      if (a.mb == 2) return emit ? emit_launch<KS, 2>(a, s) : count_launch<KS, 2>(a, s);
+    return VRQ_EUNSUPPORTED;  // (a plan never asks for it)
+  });
 }
 
 }  // namespace
+
+int large_mfma_count_launch(int cb, const CountPassArgs& a, hipStream_t s) { return stage_launch(cb, false, a, s); }
+int large_mfma_emit_launch(int cb, const CountPassArgs& a, hipStream_t s) { return stage_launch(cb, true, a, s); }
 
 // The smallest batch at which AUTO takes K1hm, per code size; INT_MAX: forced only.  One entry serves the
 // unfiltered and the filtered scan (it must hold for both), so the plan call needs no filter axis.
@@ -495,86 +475,6 @@ int large_mfma_min_queries(int cb) {
     case 256: return 16;
     default: return INT_MAX;
   }
-}
-
-// the K1hm plan of a shape large_plan accepted: K1h's caps and workspace layout, its own chunking
-static void large_mfma_plan(int64_t n, int cb, int nq, int K, BatchPlan* p) {
-  LargePlan& lp = p->lp;
-  const int64_t bins = (int64_t)cb * 8 + 1;
-  const int qb = nq < kLargeQueryBatch ? nq : kLargeQueryBatch;  // queries of one pass
-  p->engine = VRQ_LARGE_ENGINE_MFMA;
-  p->mb = mb_of(cb, qb);
-  p->qpw = qreal_of(cb) * p->mb;
-  p->nqb = (qb + p->qpw - 1) / p->qpw;
-  p->passes = (nq + kLargeQueryBatch - 1) / kLargeQueryBatch;
-  lp.qg = p->qpw;
-  lp.nw = cb <= 128 ? 4 : 2;
-  // chunks x query blocks near kTargetWaves / 4 count workgroups (one per CU at a time: the bins fill its LDS)
-  lp.chunk_rows = large_chunk_rows(n, kTargetWaves / 4 / p->nqb, qb, bins);
-  large_layout(&lp, n, nq, qb, K, bins);
-  p->flush_rows = lp.chunk_rows > kCountFlushRows ? kCountFlushRows : 0;
-}
-
-int batch_plan(int64_t n, int cb, int nq, int K, int engine, BatchPlan* p) {
-  if (engine < VRQ_LARGE_ENGINE_AUTO || engine > VRQ_LARGE_ENGINE_MFMA) return VRQ_EINVAL;
-  BatchPlan valu{}, mfma{};
-  const int rc = large_plan(n, cb, nq, K, &valu.lp);  // (the shape checks of both engines)
-  if (rc != VRQ_OK) return rc;
-  valu.engine = VRQ_LARGE_ENGINE_VALU;
-  valu.qpw = valu.lp.qg;
-  const int qb = nq < kLargeQueryBatch ? nq : kLargeQueryBatch;
-  valu.nqb = (qb + valu.lp.qg - 1) / valu.lp.qg;
-  valu.passes = (nq + kLargeQueryBatch - 1) / kLargeQueryBatch;
-  large_mfma_plan(n, cb, nq, K, &mfma);
-  if (engine == VRQ_LARGE_ENGINE_AUTO)
-    engine = nq >= large_mfma_min_queries(cb) ? VRQ_LARGE_ENGINE_MFMA : VRQ_LARGE_ENGINE_VALU;
-  *p = engine == VRQ_LARGE_ENGINE_MFMA ? mfma : valu;
-  p->need = valu.lp.bytes > mfma.lp.bytes ? valu.lp.bytes : mfma.lp.bytes;  // the workspace covers either engine
-  return VRQ_OK;
-}
-
-int batch_scan_launch(const BatchPlan& p, const uint8_t* codes, int64_t n, int cb, const uint8_t* q, int nq, int K,
-                      uint8_t* ws, hipStream_t s, int stages, const uint64_t* allow) {
-  const LargePlan& lp = p.lp;
-  if (p.engine == VRQ_LARGE_ENGINE_VALU) return large_scan_launch(lp, codes, n, cb, q, nq, K, ws, s, stages, allow);
-  if (p.engine != VRQ_LARGE_ENGINE_MFMA || lp.nchunks < 1 || lp.nchunks > kLargeMaxChunks || p.mb < 1 ||
-      lp.chunk_rows % 64 != 0)
-    return VRQ_EINVAL;  // not a K1hm plan
-  if (!(stages & kLargeStageAll)) stages |= kLargeStageAll;
-  const int bins = cb * 8 + 1;
-  const int want = (int64_t)K < n ? K : (int)n;
-  for (int b0 = 0; b0 < nq; b0 += kLargeQueryBatch) {
-    const int nb = nq - b0 < kLargeQueryBatch ? nq - b0 : kLargeQueryBatch;
-    PassArgs a;
-    a.codes = codes;
-    a.n = n;
-    a.q = q + (int64_t)b0 * cb;
-    a.nq = nb;
-    a.K = K;
-    a.chunk_rows = lp.chunk_rows;
-    a.nchunks = lp.nchunks;
-    a.allow = allow;
-    a.hist = (uint32_t*)(ws + lp.off_hist);
-    int32_t* prefix = (int32_t*)(ws + lp.off_prefix) + (int64_t)b0 * lp.nchunks * 4;
-    int32_t* tc = (int32_t*)(ws + lp.off_tc) + (int64_t)b0 * 2;
-    a.prefix = prefix;
-    a.tc = tc;
-    a.lists = (uint64_t*)(ws + lp.off_lists) + (int64_t)b0 * K;
-    int rc;
-    if (stages & kLargeStageCount) {
-      rc = stage_launch_cb(cb, false, p.mb, a, s);
-      if (rc != VRQ_OK) return rc;
-    }
-    if (stages & kLargeStageThreshold) {
-      rc = large_threshold_launch(a.hist, nb, lp.nchunks, bins, want, K, allow != nullptr, tc, prefix, a.lists, s);
-      if (rc != VRQ_OK) return rc;
-    }
-    if (stages & kLargeStageEmit) {
-      rc = stage_launch_cb(cb, true, p.mb, a, s);
-      if (rc != VRQ_OK) return rc;
-    }
-  }
-  return VRQ_OK;
 }
 
 }  // namespace vrq

@@ -1733,12 +1733,12 @@ int vrq_shard_search2(int32_t mode, const uint8_t* codes, const void* q, const d
 int vrq_scan_large_plan(int64_t n, int32_t dim, int32_t nq, int32_t K, int64_t* info) {
   if (!info || n < 1 || nq < 1 || K < 1) return VRQ_EINVAL;
   if (!vrq_dim_supported(dim)) return VRQ_EUNSUPPORTED;
-  LargePlan p;
-  const int rc = large_plan(n, dim / 8, nq, K, &p);
+  CountPlan p;
+  const int rc = count_route(n, dim / 8, nq, K, VRQ_LARGE_ENGINE_VALU, false, &p);
   if (rc != VRQ_OK) return rc;
   info[0] = p.chunk_rows;
   info[1] = p.nchunks;
-  info[2] = p.qg;
+  info[2] = p.qpw;
   info[3] = 0;  // (no bounding prefix: every distance is counted)
   info[4] = (int64_t)p.off_hist;
   info[5] = (int64_t)p.off_tc;
@@ -1747,9 +1747,15 @@ int vrq_scan_large_plan(int64_t n, int32_t dim, int32_t nq, int32_t K, int64_t* 
   return VRQ_OK;
 }
 
+// the workspace of a call of the counting scan: K1h's own (*_large, *_filtered), or either engine's (*_batch)
+static size_t count_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K, bool either) {
+  CountPlan p;
+  const int engine = either ? VRQ_LARGE_ENGINE_AUTO : VRQ_LARGE_ENGINE_VALU;
+  return vrq_dim_supported(dim) && count_route(n, dim / 8, nq, K, engine, either, &p) == VRQ_OK ? p.need : 0;
+}
+
 size_t vrq_search3_large_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K) {
-  LargePlan p;
-  return vrq_dim_supported(dim) && large_plan(n, dim / 8, nq, K, &p) == VRQ_OK ? p.bytes : 0;
+  return count_workspace_size(n, dim, nq, K, false);
 }
 
 size_t vrq_search2_large_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K) {
@@ -1777,67 +1783,61 @@ size_t vrq_scan_filtered_workspace_size(int64_t n, int32_t dim, int32_t nq, int3
   return vrq_search3_large_workspace_size(n, dim, nq, K);
 }
 
-// the plan of a call that scans (n, nq, K >= 1) and the workspace check, before anything is launched
-static int large_plan_checked(int64_t n, int cb, int nq, int K, size_t workspace_bytes, LargePlan* p) {
-  const int rc = large_plan(n, cb, nq, K, p);
+// What a call asks of the counting scan, one value per family of entry points.  The filtered calls
+// (vrq_*_filtered) are the *_large calls with a row bitmap handed to K1h; the batch calls (vrq_*_batch) are the
+// same calls again with a choice of the scan's engine, a workspace that covers either engine, and a bitmap
+// that may be null (no filter).
+struct CountCall {
+  int engine = VRQ_LARGE_ENGINE_VALU;  // VRQ_LARGE_ENGINE_*; a *_large / *_filtered call runs K1h
+  bool either = false;                 // the workspace covers either engine (*_batch)
+  bool filtered = false;               // the call reads `allow`
+  const uint64_t* allow = nullptr;
+};
+static CountCall filtered_call(const uint64_t* allow) { return {VRQ_LARGE_ENGINE_VALU, false, true, allow}; }
+static CountCall batch_call(const uint64_t* allow, int engine) { return {engine, true, allow != nullptr, allow}; }
+static bool engine_ok(int engine) { return engine >= VRQ_LARGE_ENGINE_AUTO && engine <= VRQ_LARGE_ENGINE_MFMA; }
+
+// The route of a call that scans (n, nq, K >= 1), after the other pointers a non-empty call reads: the
+// bitmap's check, the plan and the workspace check, before anything is launched.  (AUTO's choice does not
+// depend on the filter: one table entry per code size serves both kinds.)
+static int count_route_checked(int64_t n, int cb, int nq, int K, const CountCall& c, size_t workspace_bytes,
+                               CountPlan* p) {
+  if (c.filtered) VRQ_CHECK_ARG(c.allow && ((uintptr_t)c.allow & 7) == 0);
+  const int rc = count_route(n, cb, nq, K, c.engine, c.either, p);
   if (rc != VRQ_OK) return rc;
-  return workspace_bytes < p->bytes ? VRQ_EWORKSPACE : VRQ_OK;
-}
-
-// The filtered calls (vrq_*_filtered) are the *_large calls with a row bitmap handed to K1h: `filtered` asks
-// for the bitmap, which is checked with the other pointers a non-empty call reads, before any launch.
-static bool allow_ok(const uint64_t* allow) { return allow && ((uintptr_t)allow & 7) == 0; }
-
-// The batch calls (vrq_*_batch) are the same calls again with a choice of the scan's engine: `engine` is -1 for
-// a *_large / *_filtered call (K1h, its own workspace size) and a VRQ_LARGE_ENGINE_* value for a *_batch call
-// (the workspace covers either engine).  A *_batch call is filtered iff its bitmap is not null.
-static bool engine_ok(int engine) { return engine >= -1 && engine <= VRQ_LARGE_ENGINE_MFMA; }
-
-static int large_route_checked(int64_t n, int cb, int nq, int K, int engine, bool filtered, size_t workspace_bytes,
-                               BatchPlan* bp) {
-  if (engine < 0) {
-    *bp = BatchPlan{};
-    bp->engine = VRQ_LARGE_ENGINE_VALU;
-    return large_plan_checked(n, cb, nq, K, workspace_bytes, &bp->lp);
-  }
-  (void)filtered;  // (AUTO's choice does not depend on it: one table entry per code size serves both kinds)
-  const int rc = batch_plan(n, cb, nq, K, engine, bp);
-  if (rc != VRQ_OK) return rc;
-  return workspace_bytes < bp->need ? VRQ_EWORKSPACE : VRQ_OK;
+  return workspace_bytes < p->need ? VRQ_EWORKSPACE : VRQ_OK;
 }
 
 static int scan_large_impl(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq, int32_t K,
-                           int32_t stages, void* workspace, size_t workspace_bytes, void* stream, bool filtered,
-                           const uint64_t* allow, int engine = -1) {
-  VRQ_CHECK_ARG(engine_ok(engine));
+                           int32_t stages, void* workspace, size_t workspace_bytes, void* stream,
+                           const CountCall& call) {
   VRQ_CHECK_ARG(n >= 0 && nq >= 0 && K >= 0);
   if (!vrq_dim_supported(dim) || K > VRQ_K_LARGE_MAX) return VRQ_EUNSUPPORTED;
   if (stages & ~kLargeStageAll) return VRQ_EUNSUPPORTED;
   if (nq == 0 || n == 0 || K == 0) return VRQ_OK;
   VRQ_CHECK_ARG(codes && qb && workspace);
-  if (filtered) VRQ_CHECK_ARG(allow_ok(allow));
-  BatchPlan bp;
-  const int rc = large_route_checked(n, dim / 8, nq, K, engine, filtered, workspace_bytes, &bp);
+  CountPlan p;
+  const int rc = count_route_checked(n, dim / 8, nq, K, call, workspace_bytes, &p);
   if (rc != VRQ_OK) return rc;
-  return batch_scan_launch(bp, codes, n, dim / 8, qb, nq, K, (uint8_t*)workspace, (hipStream_t)stream, stages,
-                           allow);
+  return count_route_launch(p, codes, n, dim / 8, qb, nq, K, (uint8_t*)workspace, (hipStream_t)stream, stages,
+                            call.allow);
 }
 
 int vrq_scan_large(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq, int32_t K,
                    int32_t stages, void* workspace, size_t workspace_bytes, void* stream) {
-  return scan_large_impl(codes, n, dim, qb, nq, K, stages, workspace, workspace_bytes, stream, false, nullptr);
+  return scan_large_impl(codes, n, dim, qb, nq, K, stages, workspace, workspace_bytes, stream, CountCall{});
 }
 
 int vrq_scan_filtered(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq, int32_t K,
                       int32_t stages, const uint64_t* allow, void* workspace, size_t workspace_bytes, void* stream) {
-  return scan_large_impl(codes, n, dim, qb, nq, K, stages, workspace, workspace_bytes, stream, true, allow);
+  return scan_large_impl(codes, n, dim, qb, nq, K, stages, workspace, workspace_bytes, stream,
+                         filtered_call(allow));
 }
 
 static int hamming_topk_large_impl(const uint8_t* codes, int64_t n, int32_t code_bytes, int64_t row_offset,
                                    const uint8_t* queries, int32_t nq, int32_t k, int32_t* out_dist,
                                    int64_t* out_rows, void* workspace, size_t workspace_bytes, void* stream,
-                                   bool filtered, const uint64_t* allow, int engine = -1) {
-  VRQ_CHECK_ARG(engine_ok(engine));
+                                   const CountCall& call) {
   VRQ_CHECK_ARG(n >= 0 && nq >= 0 && k >= 0 && out_dist && out_rows);
   if (code_bytes <= 0 || code_bytes > 256 || !vrq_dim_supported(code_bytes * 8) || k > VRQ_K_LARGE_MAX)
     return VRQ_EUNSUPPORTED;
@@ -1845,13 +1845,11 @@ static int hamming_topk_large_impl(const uint8_t* codes, int64_t n, int32_t code
   if (nq == 0) return VRQ_OK;
   if (n == 0 || k == 0) return fill_empty(nq, k, nullptr, out_rows, out_dist, nullptr, nullptr, s);
   VRQ_CHECK_ARG(codes && queries && workspace);
-  if (filtered) VRQ_CHECK_ARG(allow_ok(allow));
-  BatchPlan bp;
-  int rc = large_route_checked(n, code_bytes, nq, k, engine, filtered, workspace_bytes, &bp);
+  CountPlan p;
+  int rc = count_route_checked(n, code_bytes, nq, k, call, workspace_bytes, &p);
   if (rc != VRQ_OK) return rc;
-  const LargePlan& p = bp.lp;
   uint8_t* ws = (uint8_t*)workspace;
-  rc = batch_scan_launch(bp, codes, n, code_bytes, queries, nq, k, ws, s, 0, allow);
+  rc = count_route_launch(p, codes, n, code_bytes, queries, nq, k, ws, s, 0, call.allow);
   if (rc != VRQ_OK) return rc;
   return large_sort_launch(s, nq, (uint64_t*)(ws + p.off_lists), k, (int32_t*)(ws + p.off_kp), true, row_offset,
                            nullptr, out_rows, out_dist);
@@ -1861,7 +1859,7 @@ int vrq_hamming_topk_large(const uint8_t* codes, int64_t n, int32_t code_bytes, 
                            const uint8_t* queries, int32_t nq, int32_t k, int32_t* out_dist, int64_t* out_rows,
                            void* workspace, size_t workspace_bytes, void* stream) {
   return hamming_topk_large_impl(codes, n, code_bytes, row_offset, queries, nq, k, out_dist, out_rows, workspace,
-                                 workspace_bytes, stream, false, nullptr);
+                                 workspace_bytes, stream, CountCall{});
 }
 
 int vrq_hamming_topk_filtered(const uint8_t* codes, int64_t n, int32_t code_bytes, int64_t row_offset,
@@ -1869,7 +1867,7 @@ int vrq_hamming_topk_filtered(const uint8_t* codes, int64_t n, int32_t code_byte
                               int32_t* out_dist, int64_t* out_rows, void* workspace, size_t workspace_bytes,
                               void* stream) {
   return hamming_topk_large_impl(codes, n, code_bytes, row_offset, queries, nq, k, out_dist, out_rows, workspace,
-                                 workspace_bytes, stream, true, allow);
+                                 workspace_bytes, stream, filtered_call(allow));
 }
 
 static int search3_large_impl(const uint8_t* codes, const int8_t* x8, const double* norms,
@@ -1877,8 +1875,7 @@ static int search3_large_impl(const uint8_t* codes, const int8_t* x8, const doub
                               const float* qf, const uint8_t* qb, int32_t nq, int32_t k, int32_t K, int32_t K3,
                               int32_t flags, int32_t* out_count, int64_t* out_rows, int32_t* out_dist,
                               double* out_binary, double* out_cosine, void* workspace, size_t workspace_bytes,
-                              void* stream, bool filtered, const uint64_t* allow, int engine = -1) {
-  VRQ_CHECK_ARG(engine_ok(engine));
+                              void* stream, const CountCall& call) {
   VRQ_CHECK_ARG(n >= 0 && nq >= 0 && k >= 0 && K >= 0 && K3 >= 0);
   VRQ_CHECK_ARG(out_count && out_rows && out_dist);
   if (!vrq_dim_supported(dim) || K > VRQ_K_LARGE_MAX || k > VRQ_K_LARGE_MAX) return VRQ_EUNSUPPORTED;
@@ -1892,18 +1889,16 @@ static int search3_large_impl(const uint8_t* codes, const int8_t* x8, const doub
     return fill_empty(nq, kout, out_count, out_rows, out_dist, out_binary, out_cosine, s);
   VRQ_CHECK_ARG(codes && qb && workspace);
   if (!p1) VRQ_CHECK_ARG(qf && x8 && norms);
-  if (filtered) VRQ_CHECK_ARG(allow_ok(allow));
-  BatchPlan bp;
-  int rc = large_route_checked(n, dim / 8, nq, K, engine, filtered, workspace_bytes, &bp);
+  CountPlan p;
+  int rc = count_route_checked(n, dim / 8, nq, K, call, workspace_bytes, &p);
   if (rc != VRQ_OK) return rc;
-  const LargePlan& p = bp.lp;
   uint8_t* ws = (uint8_t*)workspace;
   uint64_t* lists = (uint64_t*)(ws + p.off_lists);
   int32_t* kp = (int32_t*)(ws + p.off_kp);
   int32_t* ord = (int32_t*)(ws + p.off_ord);
   double* s2 = (double*)(ws + p.off_s2);
   double* s3 = (double*)(ws + p.off_s3);
-  rc = batch_scan_launch(bp, codes, n, dim / 8, qb, nq, K, ws, s, 0, allow);
+  rc = count_route_launch(p, codes, n, dim / 8, qb, nq, K, ws, s, 0, call.allow);
   if (rc != VRQ_OK) return rc;
   rc = large_sort_launch(s, nq, lists, K, kp, p1, row_offset, out_count, out_rows, out_dist);
   if (rc != VRQ_OK || p1) return rc;
@@ -1962,7 +1957,7 @@ int vrq_search3_large(const uint8_t* codes, const int8_t* x8, const double* norm
                       size_t workspace_bytes, void* stream) {
   return search3_large_impl(codes, x8, norms, rescore_row, n, dim, row_offset, qf, qb, nq, k, K, K3, flags,
                             out_count, out_rows, out_dist, out_binary, out_cosine, workspace, workspace_bytes, stream,
-                            false, nullptr);
+                            CountCall{});
 }
 
 int vrq_search3_filtered(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
@@ -1972,16 +1967,14 @@ int vrq_search3_filtered(const uint8_t* codes, const int8_t* x8, const double* n
                          void* workspace, size_t workspace_bytes, void* stream) {
   return search3_large_impl(codes, x8, norms, rescore_row, n, dim, row_offset, qf, qb, nq, k, K, K3, flags,
                             out_count, out_rows, out_dist, out_binary, out_cosine, workspace, workspace_bytes, stream,
-                            true, allow);
+                            filtered_call(allow));
 }
 
 static int search2_large_impl(int32_t mode, const uint8_t* codes, const void* q, const double* minmax, double limit,
                               const int64_t* rescore_row, int64_t n, int32_t dim, int64_t row_offset,
                               const float* qf, const uint8_t* qb, int32_t nq, int32_t k, int32_t K, int32_t flags,
                               int32_t* out_count, int64_t* out_rows, int32_t* out_dist, double* out_score,
-                              void* workspace, size_t workspace_bytes, void* stream, bool filtered,
-                              const uint64_t* allow, int engine = -1) {
-  VRQ_CHECK_ARG(engine_ok(engine));
+                              void* workspace, size_t workspace_bytes, void* stream, const CountCall& call) {
   VRQ_CHECK_ARG(search2_mode_ok(mode));
   VRQ_CHECK_ARG(n >= 0 && nq >= 0 && k >= 0 && K >= 0);
   VRQ_CHECK_ARG(out_count && out_rows && out_dist && out_score);
@@ -1993,16 +1986,14 @@ static int search2_large_impl(int32_t mode, const uint8_t* codes, const void* q,
   if (n == 0 || K == 0 || k == 0) return fill_empty(nq, k, out_count, out_rows, out_dist, out_score, nullptr, s);
   VRQ_CHECK_ARG(codes && qb && workspace && qf && q);
   if (mode == VRQ_ENC_INT8_LOCAL || mode == VRQ_ENC_INT4_LOCAL) VRQ_CHECK_ARG(minmax);
-  if (filtered) VRQ_CHECK_ARG(allow_ok(allow));
-  BatchPlan bp;
-  int rc = large_route_checked(n, dim / 8, nq, K, engine, filtered, workspace_bytes, &bp);
+  CountPlan p;
+  int rc = count_route_checked(n, dim / 8, nq, K, call, workspace_bytes, &p);
   if (rc != VRQ_OK) return rc;
-  const LargePlan& p = bp.lp;
   uint8_t* ws = (uint8_t*)workspace;
   uint64_t* lists = (uint64_t*)(ws + p.off_lists);
   int32_t* kp = (int32_t*)(ws + p.off_kp);
   double* s2 = (double*)(ws + p.off_s2);
-  rc = batch_scan_launch(bp, codes, n, dim / 8, qb, nq, K, ws, s, 0, allow);
+  rc = count_route_launch(p, codes, n, dim / 8, qb, nq, K, ws, s, 0, call.allow);
   if (rc != VRQ_OK) return rc;
   rc = large_sort_launch(s, nq, lists, K, kp, false, 0, nullptr, nullptr, nullptr);
   if (rc != VRQ_OK) return rc;
@@ -2042,8 +2033,7 @@ int vrq_search2_large(int32_t mode, const uint8_t* codes, const void* q, const d
                       int64_t* out_rows, int32_t* out_dist, double* out_score, void* workspace,
                       size_t workspace_bytes, void* stream) {
   return search2_large_impl(mode, codes, q, minmax, limit, rescore_row, n, dim, row_offset, qf, qb, nq, k, K, flags,
-                            out_count, out_rows, out_dist, out_score, workspace, workspace_bytes, stream, false,
-                            nullptr);
+                            out_count, out_rows, out_dist, out_score, workspace, workspace_bytes, stream, CountCall{});
 }
 
 int vrq_search2_filtered(int32_t mode, const uint8_t* codes, const void* q, const double* minmax, double limit,
@@ -2052,30 +2042,23 @@ int vrq_search2_filtered(int32_t mode, const uint8_t* codes, const void* q, cons
                          int32_t* out_count, int64_t* out_rows, int32_t* out_dist, double* out_score,
                          void* workspace, size_t workspace_bytes, void* stream) {
   return search2_large_impl(mode, codes, q, minmax, limit, rescore_row, n, dim, row_offset, qf, qb, nq, k, K, flags,
-                            out_count, out_rows, out_dist, out_score, workspace, workspace_bytes, stream, true,
-                            allow);
+                            out_count, out_rows, out_dist, out_score, workspace, workspace_bytes, stream,
+                            filtered_call(allow));
 }
 
 // ---- the batch calls: the *_large / *_filtered calls with the scan's engine chosen (K1h or K1hm) ----
 // (the bitmap's alignment is checked where the *_filtered calls check theirs: after the empty-shape returns)
-static bool batch_engine_ok(int32_t engine) {
-  return engine >= VRQ_LARGE_ENGINE_AUTO && engine <= VRQ_LARGE_ENGINE_MFMA;
-}
-
 int vrq_large_engine(int64_t n, int32_t dim, int32_t nq, int32_t K, int32_t filtered) {
   if (n < 1 || nq < 1 || K < 1) return VRQ_EINVAL;
   if (!vrq_dim_supported(dim)) return VRQ_EUNSUPPORTED;
   (void)filtered;  // one minimum batch per code size serves both kinds of scan, so the plan call needs no such axis
-  BatchPlan p;
-  const int rc = batch_plan(n, dim / 8, nq, K, VRQ_LARGE_ENGINE_AUTO, &p);
+  CountPlan p;
+  const int rc = count_route(n, dim / 8, nq, K, VRQ_LARGE_ENGINE_AUTO, true, &p);
   return rc != VRQ_OK ? rc : p.engine;
 }
 
 size_t vrq_search3_batch_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K) {
-  BatchPlan p;
-  return vrq_dim_supported(dim) && batch_plan(n, dim / 8, nq, K, VRQ_LARGE_ENGINE_AUTO, &p) == VRQ_OK
-             ? p.need
-             : 0;
+  return count_workspace_size(n, dim, nq, K, true);
 }
 
 size_t vrq_search2_batch_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K) {
@@ -2091,20 +2074,20 @@ size_t vrq_hamming_topk_batch_workspace_size(int64_t n, int32_t code_bytes, int3
 }
 
 int vrq_scan_batch_plan(int64_t n, int32_t dim, int32_t nq, int32_t K, int32_t engine, int64_t* info) {
-  if (!info || n < 1 || nq < 1 || K < 1 || !batch_engine_ok(engine)) return VRQ_EINVAL;
+  if (!info || n < 1 || nq < 1 || K < 1 || !engine_ok(engine)) return VRQ_EINVAL;
   if (!vrq_dim_supported(dim)) return VRQ_EUNSUPPORTED;
-  BatchPlan p;
-  const int rc = batch_plan(n, dim / 8, nq, K, engine, &p);
+  CountPlan p;
+  const int rc = count_route(n, dim / 8, nq, K, engine, true, &p);
   if (rc != VRQ_OK) return rc;
   info[0] = p.engine;
-  info[1] = p.lp.chunk_rows;
-  info[2] = p.lp.nchunks;
+  info[1] = p.chunk_rows;
+  info[2] = p.nchunks;
   info[3] = p.qpw;
   info[4] = p.nqb;
   info[5] = p.flush_rows;
-  info[6] = (int64_t)p.lp.off_hist;
-  info[7] = (int64_t)p.lp.off_tc;
-  info[8] = (int64_t)p.lp.off_lists;
+  info[6] = (int64_t)p.off_hist;
+  info[7] = (int64_t)p.off_tc;
+  info[8] = (int64_t)p.off_lists;
   info[9] = (int64_t)p.need;
   return VRQ_OK;
 }
@@ -2112,18 +2095,18 @@ int vrq_scan_batch_plan(int64_t n, int32_t dim, int32_t nq, int32_t K, int32_t e
 int vrq_scan_batch(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq, int32_t K,
                    int32_t stages, const uint64_t* allow, void* workspace, size_t workspace_bytes, void* stream,
                    int32_t engine) {
-  VRQ_CHECK_ARG(batch_engine_ok(engine));
-  return scan_large_impl(codes, n, dim, qb, nq, K, stages, workspace, workspace_bytes, stream, allow != nullptr,
-                         allow, engine);
+  VRQ_CHECK_ARG(engine_ok(engine));
+  return scan_large_impl(codes, n, dim, qb, nq, K, stages, workspace, workspace_bytes, stream,
+                         batch_call(allow, engine));
 }
 
 int vrq_hamming_topk_batch(const uint8_t* codes, int64_t n, int32_t code_bytes, int64_t row_offset,
                            const uint8_t* queries, int32_t nq, int32_t k, const uint64_t* allow, int32_t* out_dist,
                            int64_t* out_rows, void* workspace, size_t workspace_bytes, void* stream,
                            int32_t engine) {
-  VRQ_CHECK_ARG(batch_engine_ok(engine));
+  VRQ_CHECK_ARG(engine_ok(engine));
   return hamming_topk_large_impl(codes, n, code_bytes, row_offset, queries, nq, k, out_dist, out_rows, workspace,
-                                 workspace_bytes, stream, allow != nullptr, allow, engine);
+                                 workspace_bytes, stream, batch_call(allow, engine));
 }
 
 int vrq_search3_batch(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
@@ -2131,10 +2114,10 @@ int vrq_search3_batch(const uint8_t* codes, const int8_t* x8, const double* norm
                       int32_t k, int32_t K, int32_t K3, int32_t flags, const uint64_t* allow, int32_t* out_count,
                       int64_t* out_rows, int32_t* out_dist, double* out_binary, double* out_cosine,
                       void* workspace, size_t workspace_bytes, void* stream, int32_t engine) {
-  VRQ_CHECK_ARG(batch_engine_ok(engine));
+  VRQ_CHECK_ARG(engine_ok(engine));
   return search3_large_impl(codes, x8, norms, rescore_row, n, dim, row_offset, qf, qb, nq, k, K, K3, flags,
                             out_count, out_rows, out_dist, out_binary, out_cosine, workspace, workspace_bytes, stream,
-                            allow != nullptr, allow, engine);
+                            batch_call(allow, engine));
 }
 
 int vrq_search2_batch(int32_t mode, const uint8_t* codes, const void* q, const double* minmax, double limit,
@@ -2142,10 +2125,10 @@ int vrq_search2_batch(int32_t mode, const uint8_t* codes, const void* q, const d
                       const uint8_t* qb, int32_t nq, int32_t k, int32_t K, int32_t flags, const uint64_t* allow,
                       int32_t* out_count, int64_t* out_rows, int32_t* out_dist, double* out_score,
                       void* workspace, size_t workspace_bytes, void* stream, int32_t engine) {
-  VRQ_CHECK_ARG(batch_engine_ok(engine));
+  VRQ_CHECK_ARG(engine_ok(engine));
   return search2_large_impl(mode, codes, q, minmax, limit, rescore_row, n, dim, row_offset, qf, qb, nq, k, K, flags,
                             out_count, out_rows, out_dist, out_score, workspace, workspace_bytes, stream,
-                            allow != nullptr, allow, engine);
+                            batch_call(allow, engine));
 }
 
 // ---- the per-shard calls for K up to VRQ_K_LARGE_MAX: K1h, the sort, the scores of every candidate ----
@@ -2158,13 +2141,13 @@ size_t vrq_shard_search2_large_workspace_size(int64_t n, int32_t dim, int32_t nq
 }
 
 // scan + sort into the caller's [nq][K] rows / dist / count; leaves `sa` ready to score every position
-static int large_shard_phase1(const LargePlan& p, const uint8_t* codes, int64_t n, int32_t dim, int64_t row_offset,
+static int large_shard_phase1(const CountPlan& p, const uint8_t* codes, int64_t n, int32_t dim, int64_t row_offset,
                               const uint8_t* qb, int32_t nq, int32_t K, const int64_t* rescore_row,
                               int32_t* out_count, int64_t* out_rows, int32_t* out_dist, uint8_t* ws, hipStream_t s,
                               LargeScoreArgs* sa) {
   uint64_t* lists = (uint64_t*)(ws + p.off_lists);
   int32_t* kp = (int32_t*)(ws + p.off_kp);
-  int rc = large_scan_launch(p, codes, n, dim / 8, qb, nq, K, ws, s, 0);
+  int rc = count_route_launch(p, codes, n, dim / 8, qb, nq, K, ws, s, 0, nullptr);
   if (rc != VRQ_OK) return rc;
   rc = large_sort_launch(s, nq, lists, K, kp, true, row_offset, out_count, out_rows, out_dist);
   sa->lists = lists;
@@ -2189,8 +2172,8 @@ int vrq_shard_search3_large(const uint8_t* codes, const int8_t* x8, const double
   if (nq == 0) return VRQ_OK;
   if (n == 0 || K == 0) return fill_empty(nq, K, out_count, out_rows, out_dist, out_binary, out_cosine, s);
   VRQ_CHECK_ARG(codes && qb && workspace && qf && x8 && norms);
-  LargePlan p;
-  int rc = large_plan_checked(n, dim / 8, nq, K, workspace_bytes, &p);
+  CountPlan p;
+  int rc = count_route_checked(n, dim / 8, nq, K, CountCall{}, workspace_bytes, &p);
   if (rc != VRQ_OK) return rc;
   LargeScoreArgs sa{};
   rc = large_shard_phase1(p, codes, n, dim, row_offset, qb, nq, K, rescore_row, out_count, out_rows, out_dist,
@@ -2224,8 +2207,8 @@ int vrq_shard_search2_large(int32_t mode, const uint8_t* codes, const void* q, c
   if (n == 0 || K == 0) return fill_empty(nq, K, out_count, out_rows, out_dist, out_score, nullptr, s);
   VRQ_CHECK_ARG(codes && qb && workspace && qf && q);
   if (mode == VRQ_ENC_INT8_LOCAL || mode == VRQ_ENC_INT4_LOCAL) VRQ_CHECK_ARG(minmax);
-  LargePlan p;
-  int rc = large_plan_checked(n, dim / 8, nq, K, workspace_bytes, &p);
+  CountPlan p;
+  int rc = count_route_checked(n, dim / 8, nq, K, CountCall{}, workspace_bytes, &p);
   if (rc != VRQ_OK) return rc;
   LargeScoreArgs sa{};
   rc = large_shard_phase1(p, codes, n, dim, row_offset, qb, nq, K, rescore_row, out_count, out_rows, out_dist,

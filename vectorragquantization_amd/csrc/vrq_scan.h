@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/vrq.h"
 
 namespace vrq {
@@ -147,23 +149,84 @@ size_t phase1_workspace_bytes(int64_t n, int cb, int nq, int K);
 // ---- K1h: the counting scan for K up to VRQ_K_LARGE_MAX (hamming_count.hip).  Distances are integers in
 // [0, dim]: per-(query, chunk) histograms -> per-query threshold T and c_lt = count(dist < T) -> a second
 // pass that writes every row below T and the first K - c_lt rows at T, in row order, at positions that
-// the chunk prefixes fix.  The vrq_*_large entry points run it, then the large finish (select_rescore.hip). ----
+// the chunk prefixes fix.  K1hm (hamming_count_mfma.hip) is the count and the emit stage again on the matrix
+// cores; the threshold stage is shared.  The plan, the choice of the engine and the loop over passes and
+// stages are the counting-scan route's (below); an engine file exports the count and the emit stage of one
+// pass, and the measured tables the plan reads. ----
 constexpr int kLargeMaxChunks = 1024;          // chunk prefixes of the threshold stage live in LDS
 constexpr int64_t kLargeHistBytes = 64 << 20;  // cap of the per-chunk histograms of one query batch
 constexpr int kLargeQueryBatch = 512;          // queries per pass of the scan (bounds the histograms)
 
-struct LargePlan {
-  int qg;               // queries per workgroup of the count kernel
-  int nw;               // waves per workgroup of the count kernel
+// cb -> f(std::integral_constant<int, cb>) for the code sizes the counting scan has instances of
+template <class F>
+int count_code_bytes(int cb, F&& f) {
+  switch (cb) {
+    case 32: return f(std::integral_constant<int, 32>{});
+    case 48: return f(std::integral_constant<int, 48>{});
+    case 64: return f(std::integral_constant<int, 64>{});
+    case 96: return f(std::integral_constant<int, 96>{});
+    case 128: return f(std::integral_constant<int, 128>{});
+    case 192: return f(std::integral_constant<int, 192>{});
+    case 256: return f(std::integral_constant<int, 256>{});
+    default: return VRQ_EUNSUPPORTED;
+  }
+}
+
+// one pass (at most kLargeQueryBatch queries) of either engine: the pointers are the pass's own slices
+struct CountPassArgs {
+  const uint8_t* codes;
+  int64_t n;
+  const uint8_t* q;
+  int nq, K;
+  int64_t chunk_rows;
+  int nchunks;
+  int mb;                 // K1hm: M-blocks per wave
+  const uint64_t* allow;  // null, or the row bitmap of a filtered scan
+  uint32_t* hist;
+  int32_t* tc;
+  int32_t* prefix;
+  uint64_t* lists;
+};
+// K1h: queries and waves per workgroup of the count kernel, and its two stages
+int large_qg_of(int cb);
+int large_waves_of(int cb);
+int large_count_launch(int cb, const CountPassArgs& a, hipStream_t s);
+int large_emit_launch(int cb, const CountPassArgs& a, hipStream_t s);
+// the threshold stage of a pass, shared by K1h and K1hm
+int large_threshold_launch(const uint32_t* hist, int nq, int nchunks, int bins, int want, int K, bool filtered,
+                           int32_t* tc, int32_t* prefix, uint64_t* lists, hipStream_t s);
+// K1hm: the measured AUTO threshold (INT32_MAX: forced only; one entry per code size, valid with and without a
+// bitmap), M-blocks per wave for a pass of qb queries, real queries of an M-block, the rows a count workgroup
+// scans between two flushes of its u16 bins, and its two stages
+int large_mfma_min_queries(int cb);
+int large_mfma_mb_of(int cb, int qb);
+int large_mfma_qreal_of(int cb);
+int64_t large_mfma_flush_rows();
+int large_mfma_count_launch(int cb, const CountPassArgs& a, hipStream_t s);
+int large_mfma_emit_launch(int cb, const CountPassArgs& a, hipStream_t s);
+
+// ---- the counting-scan route (count_route.hip): the plan of either engine, the choice between them, the
+// workspace a call needs and the one loop over passes and stages.  The vrq_*_large, vrq_*_filtered, vrq_*_batch
+// and sharded *_large entry points (select_rescore.hip) all take their scan from here. ----
+struct CountPlan {
+  int engine;           // VRQ_LARGE_ENGINE_VALU (K1h) or VRQ_LARGE_ENGINE_MFMA (K1hm): the one that runs
+  int qpw;              // queries per workgroup of the count kernel (K1hm: per wave: 32 mb, 16 at 256 code bytes)
+  int mb;               // K1hm: M-blocks per wave (K1h: 0)
+  int nqb;              // query blocks of a full pass of the count kernel
+  int passes;           // passes of at most kLargeQueryBatch queries
   int64_t chunk_rows;   // multiple of 64, <= 2^30
   int nchunks;
+  int64_t flush_rows;   // K1hm: rows between two flushes of a count workgroup's bins; 0: it never flushes
   // workspace: histograms u32 [qb][chunks][dim + 1] and chunk prefixes i32 [nq][nchunks][4] (the counts
   // region), T / c_lt pairs i32 [nq][2], K-lists u64 [nq][K], then the
   // finish's scratch: s2 f64 [nq][K], s3 f64 [nq][K], Phase-II order i32 [nq][K], candidates i32 [nq]
   size_t off_hist, off_prefix, off_tc, off_lists, off_s2, off_s3, off_ord, off_kp, bytes;
+  size_t need;          // bytes the call's workspace must hold: `bytes`, or the larger of the two engines'
 };
-// VRQ_EINVAL for an empty shape, VRQ_EUNSUPPORTED for a code size or K outside the path
-int large_plan(int64_t n, int cb, int nq, int K, LargePlan* p);
+// engine: VRQ_LARGE_ENGINE_*; AUTO is resolved.  either: the workspace must cover either engine (a *_batch
+// call); a *_large / *_filtered call is engine VALU with K1h's own bytes.  VRQ_EINVAL for an engine outside
+// them or an empty shape, VRQ_EUNSUPPORTED for a code size or K outside the path or n >= 2^32
+int count_route(int64_t n, int cb, int nq, int K, int engine, bool either, CountPlan* p);
 // the whole scan (count, threshold, emit): leaves the K-lists at off_lists, KEY_NONE padded, the
 // dist < T part and the dist == T part each in row order.  stages: a mask of kLargeStage* (none = all).
 // allow: null, or the row bitmap of a filtered scan (u64 [ceil(n / 64)], bit r & 63 of word r >> 6: row r
@@ -171,34 +234,7 @@ int large_plan(int64_t n, int cb, int nq, int K, LargePlan* p);
 constexpr int kLargeStageCount = VRQ_LARGE_STAGE_COUNT, kLargeStageThreshold = VRQ_LARGE_STAGE_THRESHOLD,
               kLargeStageEmit = VRQ_LARGE_STAGE_EMIT,
               kLargeStageAll = kLargeStageCount | kLargeStageThreshold | kLargeStageEmit;
-int large_scan_launch(const LargePlan& p, const uint8_t* codes, int64_t n, int cb, const uint8_t* q, int nq, int K,
-                      uint8_t* ws, hipStream_t s, int stages, const uint64_t* allow = nullptr);
-// what large_plan and K1hm's plan share: the chunk length under the path's caps, and the chunk count and workspace
-// layout of a plan whose chunk_rows is set
-int64_t large_chunk_rows(int64_t n, int64_t want, int qb, int64_t bins);
-void large_layout(LargePlan* p, int64_t n, int nq, int qb, int K, int64_t bins);
-// the threshold stage of one pass (nq <= kLargeQueryBatch queries), shared by K1h and K1hm
-int large_threshold_launch(const uint32_t* hist, int nq, int nchunks, int bins, int want, int K, bool filtered,
-                           int32_t* tc, int32_t* prefix, uint64_t* lists, hipStream_t s);
-
-// ---- K1hm: the count and emit stages of the counting scan on the matrix cores (hamming_count_mfma.hip), and
-// the choice between the two engines that the vrq_*_batch entry points make.  A K1hm plan keeps K1h's
-// workspace layout and meaning (lp: chunk rows, chunks and every offset), with its own chunking. ----
-struct BatchPlan {
-  int engine;          // VRQ_LARGE_ENGINE_VALU (K1h: lp is large_plan's) or VRQ_LARGE_ENGINE_MFMA
-  LargePlan lp;
-  int mb;              // M-blocks per wave (K1h: 0)
-  int qpw;             // queries per wave of the count kernel: 32 mb, 16 at 256 code bytes (K1h: lp.qg)
-  int nqb;             // query blocks of a full pass of the count kernel
-  int passes;          // passes of at most kLargeQueryBatch queries
-  int64_t flush_rows;  // rows a count workgroup scans between two flushes of its u16 bins; 0: it never flushes
-  size_t need;         // workspace bytes of a vrq_*_batch call: the larger of the two engines'
-};
-// the measured AUTO threshold (INT32_MAX: forced only): one entry per code size, valid with and without a bitmap
-int large_mfma_min_queries(int cb);
-// engine: VRQ_LARGE_ENGINE_*; AUTO is resolved.  VRQ_EINVAL for an engine outside them, else as large_plan
-int batch_plan(int64_t n, int cb, int nq, int K, int engine, BatchPlan* p);
-int batch_scan_launch(const BatchPlan& p, const uint8_t* codes, int64_t n, int cb, const uint8_t* q, int nq, int K,
-                      uint8_t* ws, hipStream_t s, int stages, const uint64_t* allow);
+int count_route_launch(const CountPlan& p, const uint8_t* codes, int64_t n, int cb, const uint8_t* q, int nq, int K,
+                       uint8_t* ws, hipStream_t s, int stages, const uint64_t* allow);
 
 }  // namespace vrq

@@ -109,17 +109,21 @@ def gemm_topk(mode: str, qf: torch.Tensor, k: int, codes: torch.Tensor | None = 
     return cnt, rows, scores
 
 
+def search3_route(K: int, flags: int = 0, allow=None, engine=None) -> N.SearchCall:
+    """The route ``search3`` takes (``N.SearchCall`` of ``vrq_search3``, whose plain call is ``vrq_search3_dim``).
+    The sharded mode without a bitmap or an engine stays on ``vrq_search3_dim`` whatever K is: sharding keeps
+    K <= 1024, and its error is the library's."""
+    if flags & N.VRQ_SEARCH_SHARD and allow is None and engine is None:
+        K = min(K, N.VRQ_K_MAX)
+    return N.SearchCall("vrq_search3", K, flags, allow, engine, "search3", "vrq_search3_dim")
+
+
 def search3_call(K: int, flags: int = 0, allow=None) -> str:
     """The entry point ``search3`` takes for K Phase-I candidates: ``vrq_search3_large`` (the counting scan
     K1h) for 1024 < K <= ``VRQ_K_LARGE_MAX`` outside the sharded mode, else ``vrq_search3_dim``; its workspace
     size is ``<name>_workspace_size``.  With a row bitmap ``allow``: ``vrq_search3_filtered`` for every K up
     to ``VRQ_K_LARGE_MAX`` (it raises beyond, and with ``VRQ_SEARCH_SHARD`` or a scan flag)."""
-    if allow is not None:
-        N.filtered_k(K, flags, "search3")
-        return "vrq_search3_filtered"
-    if not flags & N.VRQ_SEARCH_SHARD and N.large_k(K, "search3"):
-        return "vrq_search3_large"
-    return "vrq_search3_dim"
+    return search3_route(K, flags, allow).name
 
 
 def search3(codes: torch.Tensor, x8: torch.Tensor, norms: torch.Tensor, qf: torch.Tensor, qb: torch.Tensor,
@@ -146,35 +150,13 @@ def search3(codes: torch.Tensor, x8: torch.Tensor, norms: torch.Tensor, qf: torc
     if rescore_row is not None and rescore_row.shape[0] != n:
         raise N.VrqNativeError(f"vrq_search3: rescore_row has {rescore_row.shape[0]} entries for {n} rows")
     lib = N.load()
-    eng = N.batch_engine(engine, K, flags, "search3")
-    name = N.batch_call("vrq_search3", engine, K, flags, allow) if eng is not None else search3_call(K, flags, allow)
-    need = getattr(lib, name + "_workspace_size")(n, dim, nq, K) if n and nq and K else 0
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev)
-    if eng is not None:
-        if allow is not None:
-            allow = checked_bitmap(allow, n, dev)
-        rc = getattr(lib, name)(N.ptr(codes) if n else 0, N.ptr(x8) if n else 0, N.ptr(norms) if n else 0,
-                                   N.ptr(rescore_row), n, dim, row_offset, N.ptr(qf), N.ptr(qb), nq, k, K, K3,
-                                   flags, N.ptr(allow) if n else 0, N.ptr(cnt), N.ptr(rows), N.ptr(dist),
-                                   N.ptr(s2), N.ptr(s3), N.ptr(workspace), workspace.numel(),
-                                   N.stream_handle(dev), eng)
-        N.check(rc, name)
-        return cnt, rows, dist, s2, s3
+    call = search3_route(K, flags, allow, engine)
+    workspace = call.workspace(lib, n, dim, nq, K, dev, workspace)
     if allow is not None:
         allow = checked_bitmap(allow, n, dev)
-        rc = lib.vrq_search3_filtered(N.ptr(codes) if n else 0, N.ptr(x8) if n else 0, N.ptr(norms) if n else 0,
-                                      N.ptr(rescore_row), n, dim, row_offset, N.ptr(qf), N.ptr(qb), nq, k, K, K3,
-                                      flags, N.ptr(allow) if n else 0, N.ptr(cnt), N.ptr(rows), N.ptr(dist),
-                                      N.ptr(s2), N.ptr(s3), N.ptr(workspace), workspace.numel(),
-                                      N.stream_handle(dev))
-        N.check(rc, name)
-        return cnt, rows, dist, s2, s3
-    rc = getattr(lib, name)(N.ptr(codes) if n else 0, N.ptr(x8) if n else 0, N.ptr(norms) if n else 0,
-                            N.ptr(rescore_row), n, dim, row_offset, N.ptr(qf), N.ptr(qb), nq, k, K, K3, flags,
-                            N.ptr(cnt), N.ptr(rows), N.ptr(dist), N.ptr(s2), N.ptr(s3), N.ptr(workspace),
-                            workspace.numel(), N.stream_handle(dev))
-    N.check(rc, name)
+    call(lib, (N.ptr(codes) if n else 0, N.ptr(x8) if n else 0, N.ptr(norms) if n else 0, N.ptr(rescore_row), n, dim,
+               row_offset, N.ptr(qf), N.ptr(qb), nq, k, K, K3, flags),
+         (N.ptr(cnt), N.ptr(rows), N.ptr(dist), N.ptr(s2), N.ptr(s3)), allow if n else None, workspace, dev)
     return cnt, rows, dist, s2, s3
 
 
@@ -380,11 +362,9 @@ class CohereEnhancedVectorDB:
             self._ws = torch.empty((8,), dtype=torch.uint8, device=self.device)
         lib = N.load()
         allow = ids_bitmap(self.index.id_map, allowed_ids) if allowed_ids is not None else None
-        name = N.batch_call("vrq_search3", engine, K, 0, allow) if engine is not None else search3_call(K, 0, allow)
-        size_of = getattr(lib, name + "_workspace_size")  # of the call search3 takes
-        need = size_of(n, self.embedding_dim, qf.shape[0], K) if n and K else 0
-        if self._ws.numel() < need:
-            self._ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        # sized by the route search3 itself takes
+        self._ws = search3_route(K, 0, allow, engine).workspace(lib, n, self.embedding_dim, qf.shape[0], K,
+                                                                self.device, self._ws)
         with torch.cuda.device(self.device):
             cnt, rows, dist, s2, s3 = search3(self.index.codes, self._x8.view(), self._norms.view(), qf, qb,
                                               k, K, K3, 0, 0, self.index.rescore_rows(), self._ws, allow, engine)

@@ -165,41 +165,15 @@ class BinaryIndexIDMap2:
         R = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         lib = N.load()
         n = self.ntotal
-        eng = N.batch_engine(engine, k, 0, "BinaryIndexIDMap2.search")
-        if eng is not None:
-            if allow is not None:
-                from .filters import checked
-                allow = checked(allow, n, self.device)
-            name = N.batch_call("vrq_hamming_topk", engine, k, 0, allow)
-            ws_bytes = getattr(lib, name + "_workspace_size")(n, self.code_size, nq, k) if n and nq and k else 0
-            ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=self.device)
-            with torch.cuda.device(self.device):
-                rc = getattr(lib, name)(N.ptr(self.codes) if n else 0, n, self.code_size, 0, N.ptr(q), nq, k,
-                                        N.ptr(allow) if n else 0, N.ptr(D), N.ptr(R), N.ptr(ws), ws.numel(),
-                                        N.stream_handle(self.device), eng)
-            N.check(rc, name)
-            return D, R
+        call = N.SearchCall("vrq_hamming_topk", k, 0, allow, engine, "BinaryIndexIDMap2.search")
         if allow is not None:
             from .filters import checked
-            N.filtered_k(k, 0, "BinaryIndexIDMap2.search")
             allow = checked(allow, n, self.device)
-            name = "vrq_hamming_topk_filtered"
-            ws_bytes = getattr(lib, name + "_workspace_size")(n, self.code_size, nq, k) if n and nq and k else 0
-            ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=self.device)
-            with torch.cuda.device(self.device):
-                rc = getattr(lib, name)(N.ptr(self.codes) if n else 0, n, self.code_size, 0, N.ptr(q), nq, k,
-                                        N.ptr(allow) if n else 0, N.ptr(D), N.ptr(R), N.ptr(ws), ws.numel(),
-                                        N.stream_handle(self.device))
-            N.check(rc, name)
-            return D, R
-        # more than 1024 neighbours: the counting scan (K1h), up to VRQ_K_LARGE_MAX
-        name = "vrq_hamming_topk_large" if N.large_k(k, "BinaryIndexIDMap2.search") else "vrq_hamming_topk"
-        ws_bytes = getattr(lib, name + "_workspace_size")(n, self.code_size, nq, k) if n and nq and k else 0
-        ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=self.device)
+        # more than 1024 neighbours, a bitmap or an engine: the counting scan, up to VRQ_K_LARGE_MAX
+        ws = call.workspace(lib, n, self.code_size, nq, k, self.device)
         with torch.cuda.device(self.device):
-            rc = getattr(lib, name)(N.ptr(self.codes) if n else 0, n, self.code_size, 0, N.ptr(q), nq, k,
-                                    N.ptr(D), N.ptr(R), N.ptr(ws), ws.numel(), N.stream_handle(self.device))
-        N.check(rc, name)
+            call(lib, (N.ptr(self.codes) if n else 0, n, self.code_size, 0, N.ptr(q), nq, k), (N.ptr(D), N.ptr(R)),
+                 allow if n else None, ws, self.device)
         return D, R
 
     def reconstruct(self, key) -> np.ndarray:

@@ -110,34 +110,13 @@ def vectordb_search(mode: str, codes: torch.Tensor, q: torch.Tensor, qf: torch.T
     lib = N.load()
     dist = torch.empty((nq, K), dtype=torch.int32, device=dev)
     rows = torch.empty((nq, K), dtype=torch.int64, device=dev)
-    eng = N.batch_engine(engine, K, 0, "vectordb_search")
-    if eng is not None:
-        if allow is not None:
-            allow = checked_bitmap(allow, n, dev)
-        name = N.batch_call("vrq_hamming_topk", engine, K, 0, allow)
-        ws = torch.empty((max(8, getattr(lib, name + "_workspace_size")(n, cb, nq, K)),), dtype=torch.uint8,
-                         device=dev)
-        with torch.cuda.device(dev):
-            N.check(getattr(lib, name)(N.ptr(codes), n, cb, 0, N.ptr(qb), nq, K, N.ptr(allow), N.ptr(dist),
-                                               N.ptr(rows), N.ptr(ws), ws.numel(), N.stream_handle(dev), eng), name)
-    elif allow is not None:
-        N.filtered_k(K, 0, "vectordb_search")
+    # more than 1024 candidates, a bitmap or an engine: the counting scan, up to VRQ_K_LARGE_MAX
+    call = N.SearchCall("vrq_hamming_topk", K, 0, allow, engine, "vectordb_search")
+    if allow is not None:
         allow = checked_bitmap(allow, n, dev)
-        name = "vrq_hamming_topk_filtered"
-        ws = torch.empty((max(8, lib.vrq_hamming_topk_filtered_workspace_size(n, cb, nq, K)),), dtype=torch.uint8,
-                         device=dev)
-        with torch.cuda.device(dev):
-            N.check(lib.vrq_hamming_topk_filtered(N.ptr(codes), n, cb, 0, N.ptr(qb), nq, K, N.ptr(allow),
-                                                  N.ptr(dist), N.ptr(rows), N.ptr(ws), ws.numel(),
-                                                  N.stream_handle(dev)), name)
-    else:
-        # more than 1024 candidates: the counting scan (K1h), up to VRQ_K_LARGE_MAX
-        name = "vrq_hamming_topk_large" if N.large_k(K, "vectordb_search") else "vrq_hamming_topk"
-        ws = torch.empty((max(8, getattr(lib, name + "_workspace_size")(n, cb, nq, K)),), dtype=torch.uint8,
-                         device=dev)
-        with torch.cuda.device(dev):
-            N.check(getattr(lib, name)(N.ptr(codes), n, cb, 0, N.ptr(qb), nq, K, N.ptr(dist), N.ptr(rows),
-                                       N.ptr(ws), ws.numel(), N.stream_handle(dev)), name)
+    ws = call.workspace(lib, n, cb, nq, K, dev)
+    with torch.cuda.device(dev):
+        call(lib, (N.ptr(codes), n, cb, 0, N.ptr(qb), nq, K), (N.ptr(dist), N.ptr(rows)), allow, ws, dev)
     if mode == "bin16":
         kk = min(k, K)
         return rows[:, :kk], dist[:, :kk], dist[:, :kk].to(torch.float64)
@@ -195,48 +174,19 @@ def search2(mode: str, codes: torch.Tensor, q: torch.Tensor, qf: torch.Tensor, q
         # the ABI indexes q / minmax / rescore_row by candidate row and cannot see their lengths
         raise N.VrqNativeError(f"search2: {n} code rows but {None if q is None else q.shape[0]} stored rows")
     lib = N.load()
-    eng = N.batch_engine(engine, K, flags, "search2")
-    if eng is not None:
-        if flags:
-            raise N.VrqNativeError(f"search2: flags {flags} with engine={engine!r} (vrq_search2_batch takes none)")
-        if allow is not None:
-            allow = checked_bitmap(allow, n, dev)
-        name = N.batch_call("vrq_search2", engine, K, flags, allow)
-        count = torch.empty((nq,), dtype=torch.int32, device=dev)
-        ws = torch.empty((max(8, getattr(lib, name + "_workspace_size")(n, d, nq, K)),), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            N.check(getattr(lib, name)(_SEARCH2_MODES[mode], N.ptr(codes), N.ptr(q), N.ptr(minmax), float(limit),
-                                          N.ptr(rescore_row), n, d, 0, N.ptr(qf), N.ptr(qb), nq, kk, K, 0,
-                                          N.ptr(allow), N.ptr(count), N.ptr(rows), N.ptr(dist), N.ptr(score),
-                                          N.ptr(ws), ws.numel(), N.stream_handle(dev), eng), f"{name}({mode})")
-        return rows, dist, score
+    call = N.SearchCall("vrq_search2", K, flags, allow, engine, "search2")
+    if flags and call.name != "vrq_search2":  # the counting scan takes no scan flags
+        why = f"engine={engine!r}" if call.engine is not None else \
+            "a row filter" if allow is not None else f"K = {K} > {N.VRQ_K_MAX}"
+        raise N.VrqNativeError(f"search2: flags {flags} with {why} ({call.name} takes none)")
     if allow is not None:
-        N.filtered_k(K, flags, "search2")
-        if flags:
-            raise N.VrqNativeError(f"search2: flags {flags} with a row filter (vrq_search2_filtered takes none)")
         allow = checked_bitmap(allow, n, dev)
-        name = "vrq_search2_filtered"
-        count = torch.empty((nq,), dtype=torch.int32, device=dev)
-        ws = torch.empty((max(8, lib.vrq_search2_filtered_workspace_size(n, d, nq, K)),), dtype=torch.uint8,
-                         device=dev)
-        with torch.cuda.device(dev):
-            N.check(lib.vrq_search2_filtered(_SEARCH2_MODES[mode], N.ptr(codes), N.ptr(q), N.ptr(minmax),
-                                             float(limit), N.ptr(rescore_row), n, d, 0, N.ptr(qf), N.ptr(qb), nq,
-                                             kk, K, 0, N.ptr(allow), N.ptr(count), N.ptr(rows), N.ptr(dist),
-                                             N.ptr(score), N.ptr(ws), ws.numel(), N.stream_handle(dev)),
-                    f"{name}({mode})")
-        return rows, dist, score
-    # more than 1024 candidates: vrq_search2_large (the counting scan K1h; it takes no scan flags)
-    name = "vrq_search2_large" if N.large_k(K, "search2") else "vrq_search2"
-    if name == "vrq_search2_large" and flags:
-        raise N.VrqNativeError(f"search2: flags {flags} with K = {K} > {N.VRQ_K_MAX} (vrq_search2_large takes none)")
     count = torch.empty((nq,), dtype=torch.int32, device=dev)
-    ws = torch.empty((max(8, getattr(lib, name + "_workspace_size")(n, d, nq, K)),), dtype=torch.uint8, device=dev)
+    ws = call.workspace(lib, n, d, nq, K, dev)
     with torch.cuda.device(dev):
-        N.check(getattr(lib, name)(_SEARCH2_MODES[mode], N.ptr(codes), N.ptr(q), N.ptr(minmax), float(limit),
-                                   N.ptr(rescore_row), n, d, 0, N.ptr(qf), N.ptr(qb), nq, kk, K, flags, N.ptr(count),
-                                   N.ptr(rows), N.ptr(dist), N.ptr(score), N.ptr(ws), ws.numel(),
-                                   N.stream_handle(dev)), f"{name}({mode})")
+        call(lib, (_SEARCH2_MODES[mode], N.ptr(codes), N.ptr(q), N.ptr(minmax), float(limit), N.ptr(rescore_row), n,
+                   d, 0, N.ptr(qf), N.ptr(qb), nq, kk, K, flags),
+             (N.ptr(count), N.ptr(rows), N.ptr(dist), N.ptr(score)), allow, ws, dev, f"{call.name}({mode})")
     return rows, dist, score
 
 
