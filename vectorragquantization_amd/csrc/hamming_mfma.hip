@@ -107,11 +107,31 @@ constexpr int ENT_V_BIAS = 1025;
 // exists and is whole ("steady": all but the chunk's last NPK tiles and the refill of a partial last tile)
 // issue that refill in the empty slots of group 0 -- one piece after each of two MFMAs, scalar base + lane
 // offset -- and end on the constant vmcnt wait; only the other tiles run the clamped-row DMA form and the
-// counted wait ladder.  Between the MFMAs of two steady tiles remain: the two waits, the > 64-hits test,
-// the barrier, the back edge, the flushed-store and steady tests, two address forms, the two row-popcount
-// reads and the first B read.  The hit extraction, the synchronous flush and the partial-tile DMA are marked
-// unlikely and laid out after the loop body, so a tile's 128 MFMAs are contiguous and the no-hit path
-// falls through.
+// counted wait ladder.  The two kinds run in two loops over one tile body with a compile-time STEADY: the
+// steady loop's body tests neither the mode nor t nor a row against the chunk's end (its tiles and the ones
+// before them are whole), and the first n-block has no t == 0 case in either loop (pcvP starts at the
+// popcount of a row past the chunk).  Between the MFMAs of two steady tiles remain: the two waits, the
+// > 64-hits test, the barrier, the loop test, the flushed-store test, two address forms, the two
+// row-popcount reads and the first B read.  The hit extraction and the synchronous flush are marked unlikely
+// and laid out after the loop body, so a tile's 128 MFMAs are contiguous and the no-hit path falls through.
+//
+// The counted waits.  Each group's s_waitcnt lgkmcnt and its first MFMA (M-block 0) are ONE asm statement
+// (wait_lgkm_mfma_fp4, mfma_common.h), the B fragment a plain input: a wait-only statement naming the fragment
+// as an output made the compiler pad the following MFMA with s_nop 0.  The compiler does not know that
+// statement writes M-block 0's accumulator with an MFMA, so the schedule guarantees its hazards:
+//   * the next reader of acc[.][0] is the next group's fused MFMA with C = D whole (accumulate chain: no wait
+//     state), MB MFMAs later; M-blocks >= 1 stay builtin MFMAs the compiler pads itself;
+//   * vector reads of acc[nbk][0] (the max3 tree, the hit extraction) come in the OTHER n-block's groups
+//     j >= 2: at least 2 MB MFMAs of 8 passes each behind its last write (group 15), where 12 issue slots
+//     suffice; after the loop the epilogue reads acc[1][0] behind the last group's MB - 1 builtin MFMAs, the
+//     two waits and the barrier.
+// Registers filled by LDS reads are named "+v" once, in an empty statement right behind the wait that retires
+// them (see the tile body).  The address form and the read of the packed reads are one statement each, so are
+// the M0 write and the LDS-DMA of a refill piece.  s_nop left in the steady run (tests/test_k1m_loop_shape.py):
+// one s_nop 0 between the SALU write of M0 and the first DMA piece (required wait state; the second piece's
+// address VALU fills it), two around the DPP adds of the row popcounts (VALU write -> DPP read), one s_nop 1
+// between the v_cmp that writes vcc and the v_cndmask of the flush's lane mask (thresholded instances), or
+// between the row test and its select (dense instance, two n-blocks).
 
 // The per-group LDS wait of the schedule above.  Group gi consumes the B fragment read at the top of
 // group gi - BAHEAD; DS operations complete in order, so the wait may leave in flight exactly the DS
@@ -212,17 +232,20 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
       }
     }
   };
+  const uint32_t pk0 = lds_addr(pk), ub0 = lds_addr(ub), pcr0 = lds_addr(pcr);
   // The same for a steady tile of the loop (below): always whole, so piece i goes from a carried scalar
-  // source pointer + the per-lane offset into the carried packed slot -- no multiply, no row test.
+  // source pointer + the per-lane offset into the carried packed slot -- no multiply, no row test.  One asm
+  // statement per piece (mfma_common.h): the M0 write, its one wait state and the DMA; piece 1's lane offset
+  // (doff0 + 1024) ^ 64 = (doff0 ^ 64) + 1024 is formed in that wait state.
+  const uint32_t pkw0 = pk0 + (uint32_t)(w * GPW * 1024), pkw1 = pkw0 + 1024u;  // this wave's pieces in slot 0
+  uint32_t tdma = 0;  // piece 1's address register (kept live past the next group: lds_read64_xad)
   auto issue_piece = [&](const uint8_t* base, uint32_t slot_off, auto I) __attribute__((always_inline)) {
     constexpr int i = decltype(I)::value;
-    uint32_t d0 = doff0;
-    asm volatile("" : "+v"(d0));
-    const uint32_t d = i == 0 ? d0 : (d0 + 1024u) ^ 64u;
-    __builtin_amdgcn_global_load_lds(base + d, (__attribute__((address_space(3))) void*)(pk + slot_off + (w * GPW + i) * 1024),
-                                     16, 0, 0);
+    if constexpr (i == 0)
+      lds_dma16(base, doff0, pkw0, slot_off);
+    else
+      lds_dma16_xad<64>(base, tdma, doff0, 1024u, pkw1, slot_off);
   };
-  const uint32_t pk0 = lds_addr(pk), ub0 = lds_addr(ub), pcr0 = lds_addr(pcr);
   const uint32_t lc0 = lds_addr(lcnt), stg0 = lds_addr(stg);
   // unit u of this wave = (nblk, piece) = ((4w+u) >> 3, (4w+u) & 7): lane -> tile row
   // 32*nblk + ri; piece p (dwords 4p..4p+3) holds k-steps 2p, 2p+1; lane-half h takes dword
@@ -468,13 +491,15 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
   // lane's running minima; only those leave the kernel (dense_out)
   DenseMin<DENSE, MB, 1024> dmin;
   auto block_dense = [&](const v16f& a, int m, int pc, int lr) __attribute__((always_inline)) {
-    dmin.fold(a, m, pc, lr < nrows);
+    dmin.fold(a, m, pc, (uint32_t)lr < (uint32_t)nrows);  // (lr < 0: the n-block before tile 0)
   };
 
   // ---- main loop: 32 groups per tile (schedule above) ----
   v4i ring[NRING];
   const uint32_t bl0 = ub0 + (uint32_t)(l * 16);  // + tile slot + group * 1024: this lane's B fragment
-  int pcvP = 0;  // previous tile's n-block 1 row popcount
+  // previous tile's n-block 1 row popcount.  No previous tile before tile 0: row_pc's value for a row past
+  // the chunk, a threshold of 2^29 that no accumulator reaches (and a DENSE row no minimum takes: lr < 0)
+  int pcvP = 0x40000000;
   int lmax = 0;         // this lane's running maximum over the previous n-block's accumulators (float bits)
   uint64_t anyhit = 0;  // lanes of the previous n-block that hold a candidate (wave-uniform)
   int hpb = 0;   // the previous n-block's per-lane threshold pc(r)/2, as float bits
@@ -494,6 +519,8 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
     seedr[m] = __builtin_bit_cast(v16f, x);
     acc[0][m] = acc[1][m] = seedr[m];  // (tile 0 tests acc[1] against a threshold nothing exceeds)
   });
+  if constexpr (DENSE)  // tile 0 folds acc[1] as rows before the chunk (no value): finite, so the fold is exact
+    static_for<0, MB>([&](auto M) { acc[1][decltype(M)::value] = v16f{}; });
   if constexpr (!DENSE)
     static_for<NSR, MB>([&](auto M) {
       constexpr int m = decltype(M)::value;
@@ -530,11 +557,13 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
   // first MFMA of the next one has issued; st_bsum sums st_b - st_a over the workgroup's boundaries
   uint32_t st_a = 0, st_b = 0, st_bsum = 0;
 #endif
-  for (int t = 0; t < ntiles; ++t) {
+  // One tile.  STEADY is a compile-time mode: the steady loop's body holds no test of it, of t or of a row
+  // against the chunk's end (its tiles and their predecessors are whole), the tail loop's keeps the general forms.
+  auto tile = [&](auto ST, const int t) __attribute__((always_inline)) {
+    constexpr bool STEADY = decltype(ST)::value;
     store_flushed(t);  // previous tile's first 64 hits (before the DMA: see the end-of-tile wait)
     // tile t + NPK into the slot of tile t (unpacked in iteration t-2)
-    const bool steady = t < nsteady;
-    if (__builtin_expect(steady, 1)) {
+    if constexpr (STEADY) {
       if constexpr (!VRQ_K1M_DMA_SHADOW) {
         issue_piece(dsrc, pko, std::integral_constant<int, 0>{});
         issue_piece(dsrc, pko, std::integral_constant<int, 1>{});
@@ -542,6 +571,10 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
     } else if (t + NPK < ntiles) {
       issue(t + NPK);
     }
+    // the popcount of a row the previous n-block tested: in a steady tile always a row of the chunk
+    auto tile_row_pc = [&](int pcv, int lr) __attribute__((always_inline)) {
+      if constexpr (STEADY) return pcv; else return row_pc(pcv, lr);
+    };
     const uint32_t blt = bl0 + (uint32_t)(ru0 * UBT);
     const uint32_t bln = bl0 + (uint32_t)(ru1 * UBT);
     const uint32_t ubw = ub0 + (uint32_t)(ru2 * UBT);
@@ -564,17 +597,9 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
       // packed reads of the unpack units (used 5 groups later) and of the row popcounts
       // (unit u's source is unit 0's with u XORed into the swizzled piece index, the second popcount piece
       // the first with its lowest index bit flipped: one kept address each)
-      if constexpr ((gi & 7) == 1) lds_read64(pv, xor_add<16 * (gi >> 3)>(usrc[0], pks));
-      if constexpr (gi == 12) {
-        lds_read128(pa, xor_add<0>(psrc0, pks));
-        lds_read128(pb, xor_add<16>(psrc0, pks));
-      }
-      // every LDS operation issued up to the B read of group gi - BAHEAD has completed (k1m_wait): the
-      // fragment of this group, the packed unit read 5 groups ago, the popcounts, the seeds
-      asm volatile("s_waitcnt lgkmcnt(%7)"
-                   : "+v"(ring[gi & (NRING - 1)]), "+v"(pv), "+v"(pcv[0]), "+v"(pcv[1]), "+v"(pa), "+v"(pb), "+v"(fe)
-                   : "n"(k1m_wait(gi, MB, NSR, DENSE))
-                   : "memory");
+      uint32_t tads = 0;  // the address register of this group's packed reads (lds_read64_xad)
+      if constexpr ((gi & 7) == 1) lds_read64_xad<16 * (gi >> 3)>(pv, tads, usrc[0], pks);
+      if constexpr (gi == 12) lds_read128x2_xad<0, 16>(pa, pb, tads, psrc0, pks);
       // The group's non-MFMA work is cut into four slots that sit between its MFMAs (slot k after
       // MFMA k; at MB = 2 slots 2k and 2k+1 after MFMA k): an in-order wave issues them while the
       // matrix core runs, at most ~3 vector instructions per slot, instead of one burst after the
@@ -620,10 +645,10 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
         }
         if constexpr (!DENSE && j == 1 && k == 0) {
           // the n-block's threshold pc(r)/2 as float bits (>= 0); no previous n-block before tile 0:
-          // a threshold no accumulator exceeds
+          // pcvP starts at a value whose threshold no accumulator exceeds
           const int pcr_ = nbk == 0 ? pcvP : pcv[0];
           const int lr = (nbk == 0 ? (t - 1) * RT + 32 : t * RT) + ri;
-          hpb = (nbk == 0 && t == 0) ? 0x7fffffff : __float_as_int(0.5f * (float)row_pc(pcr_, lr));
+          hpb = __float_as_int(0.5f * (float)tile_row_pc(pcr_, lr));
           asm volatile("" : "+v"(hpb));
         }
         if constexpr (UNPACK) {  // unpack_row32 of pv.x (slots 0, 1) and pv.y (slots 2, 3)
@@ -672,16 +697,15 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
           acc[nbk ^ 1][sm] = __builtin_bit_cast(v16f, x);
         }
         if constexpr (DENSE && j >= 2 && j < 2 + MB && k == 0) {
-          if (nbk == 1 || t > 0) {
-            const int pcr_ = nbk == 0 ? pcvP : pcv[0];
-            const int lr = (nbk == 0 ? (t - 1) * RT + 32 : t * RT) + ri;
-            block_dense(acc[nbk ^ 1][j - 2], j - 2, pcr_, lr);
-          }
+          // (the n-block before tile 0 has lr < 0: block_dense folds nothing)
+          const int pcr_ = nbk == 0 ? pcvP : pcv[0];
+          const int lr = (nbk == 0 ? (t - 1) * RT + 32 : t * RT) + ri;
+          block_dense(acc[nbk ^ 1][j - 2], j - 2, pcr_, lr);
         }
         // the steady refill DMA, one piece in each of two of group 0's empty slots (after the list stores
         // at the top of the iteration, like the general form: the end-of-tile vmcnt accounting is the same)
         if constexpr (VRQ_K1M_DMA_SHADOW && gi == 0 && (k == 0 || k == 2)) {
-          if (__builtin_expect(steady, 1)) issue_piece(dsrc, pko, std::integral_constant<int, k / 2>{});
+          if constexpr (STEADY) issue_piece(dsrc, pko, std::integral_constant<int, k / 2>{});
         }
         if constexpr (gi == NG - 1) {
           // the loop-carried tile state steps to tile t + 1 here, in the last group's otherwise empty slots
@@ -716,7 +740,7 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
             if (__builtin_expect(anyhit != 0, 0)) {
               const int pcr_ = nbk == 0 ? pcvP : pcv[0];
               const int lr = (nbk == 0 ? (t - 1) * RT + 32 : t * RT) + ri;
-              const int pc = row_pc(pcr_, lr);
+              const int pc = tile_row_pc(pcr_, lr);
               const float hp = 0.5f * (float)pc;
               static_for<0, MB>([&](auto M) {
                 constexpr int mm = decltype(M)::value;
@@ -729,9 +753,34 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
           }
         }
       };
-      static_for<0, MB>([&](auto M) {
-        constexpr int m = decltype(M)::value;
-        if constexpr (s == 0 && m < NSR) {  // register-resident seeds: the C operand
+      static_for<0, MB>([&](auto P) {
+        constexpr int p = decltype(P)::value, m = p;
+        if constexpr (p == 0) {
+          // The group's counted wait and its first MFMA, one statement (wait_lgkm_mfma_fp4): every LDS operation
+          // issued up to the B read of group gi - BAHEAD has completed (k1m_wait) -- the fragment of this group,
+          // the packed unit read 4 groups ago, the popcounts, the seeds.  Hazards of M-block 0's accumulator,
+          // which the compiler no longer sees written by an MFMA: see "The counted waits" above the kernel.
+          constexpr int W = k1m_wait(gi, MB, NSR, DENSE);
+          if constexpr (s == 0 && m < NSR)
+            wait_lgkm_mfma_fp4_seed<W>(acc[nbk][m], A[m][s], ring[gi & (NRING - 1)], seedr[m < NSR ? m : 0]);
+          else if constexpr (s == 0 && DENSE)
+            wait_lgkm_mfma_fp4_zero<W>(acc[nbk][m], A[m][s], ring[gi & (NRING - 1)]);
+          else  // (s == 0, m >= NSR: the seeds loaded after the block's last epilogue have landed at this wait)
+            wait_lgkm_mfma_fp4<W>(acc[nbk][m], A[m][s], ring[gi & (NRING - 1)]);
+          // The registers whose LDS reads this wait retired, named once each, right behind it: no use of them
+          // is scheduled above this point and so above the wait (asm statements keep their order).  Each sits in
+          // the group BEFORE its first consumer's, or slots away from it, so the idle state the compiler puts
+          // between an asm statement's output and its next reader never lands in an MFMA gap:
+          //   the row popcounts of this tile (read before group 0)       group 0          -> group 1
+          //   the packed unit read in group 8u + 1                        group 8u + 5     -> group 8u + 6
+          //   the packed popcount pieces read in group 12                 group 16         -> group 28
+          //   the staged entries read in group 20 + MB, slot 3            group 24 + MB    -> its slot 3
+          static_assert(k1m_wait(0, MB, NSR, DENSE) == 1, "group 0's wait leaves only the B read of group 3 in flight");
+          if constexpr (gi == 0) asm volatile("" : "+v"(pcv[0]), "+v"(pcv[1]));
+          if constexpr ((gi & 7) == 5) asm volatile("" : "+v"(pv));
+          if constexpr (gi == 16) asm volatile("" : "+v"(pa), "+v"(pb));
+          if constexpr (gi == 24 + MB && !DENSE) asm volatile("" : "+v"(fe));
+        } else if constexpr (s == 0 && m < NSR) {  // register-resident seeds: the C operand
           acc[nbk][m] = mfma_fp4(A[m][s], ring[gi & (NRING - 1)], seedr[m < NSR ? m : 0]);
         } else {
           if constexpr (s == 0 && !DENSE)  // the seeds loaded after the block's last epilogue have landed
@@ -739,20 +788,26 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
           acc[nbk][m] = mfma_fp4(A[m][s], ring[gi & (NRING - 1)], (s == 0 && DENSE) ? v16f{} : acc[nbk][m]);
         }
         // pin the accumulator here: the MFMA intrinsics are pure, and without a use at this
-        // point IR-level sinking moves them past the scheduling fences
-        asm volatile("" : "+v"(acc[nbk][m]));
+        // point IR-level sinking moves them past the scheduling fences.  (At MB = 2 a use only: the compiler
+        // pads an asm OUTPUT against its next reader unless an instruction it knows lies between, and between
+        // M-block 1's MFMAs of two groups there may be none -- the fused statement is opaque to it.)
+        if constexpr (p != 0 && MB == 2) asm_use(acc[nbk][m]);
+        if constexpr (p != 0 && MB != 2) asm volatile("" : "+v"(acc[nbk][m]));
         VRQ_SCHED_FENCE();
 #ifdef VRQ_K1M_STAMPS
-        if constexpr (gi == 0 && m == 0) st_b = (uint32_t)__builtin_amdgcn_s_memtime();
+        if constexpr (gi == 0 && p == 0) st_b = (uint32_t)__builtin_amdgcn_s_memtime();
 #endif
         if constexpr (MB == 4) {
-          slot(std::integral_constant<int, m>{});
+          slot(std::integral_constant<int, p>{});
         } else {
-          slot(std::integral_constant<int, 2 * m>{});
-          slot(std::integral_constant<int, 2 * m + 1>{});
+          slot(std::integral_constant<int, 2 * p>{});
+          slot(std::integral_constant<int, 2 * p + 1>{});
         }
         VRQ_SCHED_FENCE();
       });
+      // the address registers of this group's packed reads and of the DMA's second piece end here
+      if constexpr ((gi & 7) == 1 || gi == 12) asm_keep(tads);
+      if constexpr (STEADY && gi == (VRQ_K1M_DMA_SHADOW ? 1 : 0)) asm_keep(tdma);
       VRQ_SCHED_FENCE();
     });
     pcvP = pcv[1];
@@ -764,7 +819,7 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
 #ifndef VRQ_K1M_PROBE_NOVMWAIT  // timing-only probe builds (wrong results)
       // a steady tile: tile t + NPK was issued this iteration, one tile may stay in flight.  (vmcnt counts
       // in issue order and the list stores sit before their iteration's DMA, so none is left behind it.)
-      if (__builtin_expect(steady, 1)) {
+      if constexpr (STEADY) {
         wait_vm<GPW>();
       } else {
         const int last = t + NPK < ntiles ? t + NPK : ntiles - 1;  // last tile issued so far
@@ -783,7 +838,13 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
 #ifndef VRQ_K1M_PROBE_NOBARRIER  // timing-only probe builds (wrong results)
     barrier_all();  // B_{t+1}
 #endif
-  }
+  };
+  // The steady loop (possibly empty), then the tail loop: the chunk's last NPK tiles and the refill of a
+  // partial last tile, at least one tile (nsteady < ntiles).  Both carry ru0..2, pko, dsrc, nst, the hit
+  // stage, the accumulators, seeds, A and the B ring; nothing is recomputed at the hand-over.
+  int t = 0;
+  for (; t < nsteady; ++t) tile(std::true_type{}, t);
+  do tile(std::false_type{}, t); while (++t < ntiles);
   store_flushed(ntiles);
   if (ntiles > 0) {  // n-block 1 of the last tile
     const int lr = (ntiles - 1) * RT + 32 + ri;
