@@ -577,8 +577,8 @@ int vrq_scan_large_plan(int64_t n, int32_t dim, int32_t nq, int32_t K, int64_t* 
  *   n < 2^32; n, nq, K or k = 0 behave as there (and read no bitmap).  A null or misaligned allow of a
  *   non-empty call returns VRQ_EINVAL; every argument is checked before anything is launched.
  * Only the counting scan K1h reads the bitmap (one word per 64-row tile, a scalar load): it serves every K,
- *   and is a VALU scan meant for small and medium batches (for big ones: the vrq_*_batch calls below).  There
- *   is no per-query bitmap and no filtered sharded call.
+ *   and is a VALU scan meant for small and medium batches (for big ones: the vrq_*_batch calls below).  A
+ *   bitmap per query: the vrq_*_perquery calls further below.  There is no filtered sharded call.
  * ------------------------------------------------------------------------- */
 size_t vrq_scan_filtered_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K);
 int vrq_scan_filtered(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq, int32_t K,
@@ -657,6 +657,59 @@ int vrq_search2_batch(int32_t mode, const uint8_t* codes, const void* q, const d
                       const uint8_t* qb, int32_t nq, int32_t k, int32_t K, int32_t flags, const uint64_t* allow,
                       int32_t* out_count, int64_t* out_rows, int32_t* out_dist, double* out_score,
                       void* workspace, size_t workspace_bytes, void* stream, int32_t engine);
+
+/* ---------------------------------------------------------------------------
+ * Filtered search with a row bitmap per query (additive to ABI version 1; every call above keeps its
+ * contract).  A serving batch mixes queries of different tenants, permission sets or date ranges: these calls
+ * take a set of bitmaps and, per query, which of them filters it, on either engine of the counting scan.
+ * vrq_scan_perquery / vrq_hamming_topk_perquery / vrq_search3_perquery / vrq_search2_perquery: the arguments
+ *   of the *_batch call, `engine` included, followed by
+ *   nsets      number of bitmaps `allow` holds, >= 1.
+ *   set_words  u64 words from one bitmap to the next, >= ceil(n / 64) (bitmaps may be sized for capacity).
+ *   query_set  device i32 [nq], 4-byte aligned: query q is filtered by bitmap query_set[q].  -1: every row is
+ *              allowed (an unfiltered query).  Any other value outside [0, nsets): no row is allowed -- count 0,
+ *              every output padding; no address is ever formed from such an id.
+ *   allow      device u64, 8-byte aligned: bitmap s is the ceil(n / 64) words at allow + s * set_words, in the
+ *              format of the *_filtered calls.  Words past ceil(n / 64) of a set are never read, bits past n
+ *              are ignored; all index arithmetic is 64-bit.
+ *   For every query q and every input, row q of every output array equals, bit for bit, the *_batch call of the
+ *   same engine run on that query alone with allow + query_set[q] * set_words (a null allow for -1); hence the
+ *   result does not depend on the engine, and after vrq_scan_perquery the T / count(dist < T) pairs and the
+ *   K-lists in the workspace are bit-identical between the engines, as after vrq_scan_batch.  Shapes, flags,
+ *   stage masks, engines, empty shapes (n, nq, K or k = 0 read neither array) and return codes are those of
+ *   the *_batch calls; the workspace is vrq_*_batch_workspace_size (the bitmaps are the caller's and nothing
+ *   else is staged in global memory).  A non-empty call returns VRQ_EINVAL for a null allow or query_set, an
+ *   allow not 8-byte aligned, a query_set not 4-byte aligned, nsets < 1 or set_words < ceil(n / 64); every
+ *   argument and the workspace size are checked before anything is launched.  vrq_large_engine(...,
+ *   filtered = 1) and vrq_scan_batch_plan describe these calls unchanged: the plan, the chunks and the
+ *   workspace layout do not depend on the filter's shape.
+ * Both engines read a word per (64-row tile, resident query) as a scalar load; when every query of a count
+ *   workgroup (K1h) or wave (K1hm) names the same set they run the single-bitmap loop body, inside an instance
+ *   with a higher register use: measured at 1M rows, a batch in one set costs 1.05-1.18 times the *_batch call
+ *   with that bitmap, and mixed sets cost K1h 1.1-1.3 times and K1hm up to 6.5 times that call
+ *   (tools/perquery_bench.py, DESIGN section 5 "Per-query filters").  Not built: a filter on the sharded calls or on the
+ *   exhaustive (gemm_topk) path, and skipping the loads of tiles no query may see.
+ * ------------------------------------------------------------------------- */
+int vrq_scan_perquery(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq, int32_t K,
+                      int32_t stages, const uint64_t* allow, void* workspace, size_t workspace_bytes, void* stream,
+                      int32_t engine, int32_t nsets, int64_t set_words, const int32_t* query_set);
+int vrq_hamming_topk_perquery(const uint8_t* codes, int64_t n, int32_t code_bytes, int64_t row_offset,
+                              const uint8_t* queries, int32_t nq, int32_t k, const uint64_t* allow,
+                              int32_t* out_dist, int64_t* out_rows, void* workspace, size_t workspace_bytes,
+                              void* stream, int32_t engine, int32_t nsets, int64_t set_words,
+                              const int32_t* query_set);
+int vrq_search3_perquery(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
+                         int64_t n, int32_t dim, int64_t row_offset, const float* qf, const uint8_t* qb, int32_t nq,
+                         int32_t k, int32_t K, int32_t K3, int32_t flags, const uint64_t* allow, int32_t* out_count,
+                         int64_t* out_rows, int32_t* out_dist, double* out_binary, double* out_cosine,
+                         void* workspace, size_t workspace_bytes, void* stream, int32_t engine, int32_t nsets,
+                         int64_t set_words, const int32_t* query_set);
+int vrq_search2_perquery(int32_t mode, const uint8_t* codes, const void* q, const double* minmax, double limit,
+                         const int64_t* rescore_row, int64_t n, int32_t dim, int64_t row_offset, const float* qf,
+                         const uint8_t* qb, int32_t nq, int32_t k, int32_t K, int32_t flags, const uint64_t* allow,
+                         int32_t* out_count, int64_t* out_rows, int32_t* out_dist, double* out_score,
+                         void* workspace, size_t workspace_bytes, void* stream, int32_t engine, int32_t nsets,
+                         int64_t set_words, const int32_t* query_set);
 
 /* ---------------------------------------------------------------------------
  * Row-sharded search with more than 1024 Phase-I candidates (additive to ABI version 1; vrq_shard_search3,

@@ -144,6 +144,14 @@ SIGNATURES = {
     "vrq_search2_batch_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
     "vrq_search2_batch": (C.c_int, [_I32, _P, _P, _P, _D, _P, _I64, _I32, _I64, _P, _P, _I32, _I32, _I32, _I32,
                                     _P, _P, _P, _P, _P, _P, _SZ, _P, _I32]),
+    # the *_batch prototypes followed by (int32 nsets, int64 set_words, const int32* query_set)
+    "vrq_scan_perquery": (C.c_int, [_P, _I64, _I32, _P, _I32, _I32, _I32, _P, _P, _SZ, _P, _I32, _I32, _I64, _P]),
+    "vrq_hamming_topk_perquery": (C.c_int, [_P, _I64, _I32, _I64, _P, _I32, _I32, _P, _P, _P, _P, _SZ, _P, _I32,
+                                            _I32, _I64, _P]),
+    "vrq_search3_perquery": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _P,
+                                       _P, _P, _P, _P, _P, _P, _SZ, _P, _I32, _I32, _I64, _P]),
+    "vrq_search2_perquery": (C.c_int, [_I32, _P, _P, _P, _D, _P, _I64, _I32, _I64, _P, _P, _I32, _I32, _I32, _I32,
+                                       _P, _P, _P, _P, _P, _P, _SZ, _P, _I32, _I32, _I64, _P]),
     "vrq_gemm_topk_workspace_size": (_SZ, [_I32, _I64, _I32, _I32, _I32]),
     "vrq_gemm_topk_pieces": (C.c_int, []),
     "vrq_gemm_topk_plan": (C.c_int, [_I32, _I64, _I32, _I32, _I32, _P]),
@@ -289,18 +297,39 @@ def batch_call(base: str, engine, K: int, flags: int = 0, allow=None) -> str:
     return SearchCall(base, K, flags, allow, engine).name
 
 
+def set_words_of(allow) -> int:
+    """``set_words`` of a 2-D ``allow`` (int64 [S, words], unit stride along a row): the words from one bitmap to
+    the next.  A size-1 dimension may carry any stride, so a single set is as wide as its row."""
+    return int(allow.stride(0)) if allow.shape[0] > 1 else int(allow.shape[1])
+
+
 class SearchCall:
     """The route of a search wrapper to its entry point, and the one place that sizes its workspace and makes
     the call.  ``name`` is ``<base>_batch`` with an ``engine``, else ``<base>_filtered`` with a bitmap ``allow``,
     ``<base>_large`` for K > 1024, else ``plain`` (default ``base``); ``engine`` is the resolved
     VRQ_LARGE_ENGINE_* value (None outside the batch calls).  ``what`` names the caller in the errors
-    ``batch_engine`` / ``filtered_k`` / ``large_k`` raise (default ``base``)."""
+    ``batch_engine`` / ``filtered_k`` / ``large_k`` raise (default ``base``).
+
+    With ``query_set`` (one set id per query; ``allow`` then holds a bitmap per set, ``filters.row_bitmaps``)
+    the route is ``<base>_perquery``: a batch call with the filter's shape after the engine.  It has no earlier
+    route to preserve, so ``engine=None`` means "auto" there; its workspace is the batch call's."""
 
     def __init__(self, base: str, K: int, flags: int = 0, allow=None, engine=None, what: str = None,
-                 plain: str = None):
+                 plain: str = None, query_set=None):
         what = what or base
+        self.perquery = query_set is not None
+        if self.perquery:
+            if allow is None:
+                raise VrqNativeError(f"{what}: query_set without allow (a bitmap per set, filters.row_bitmaps)")
+            engine = "auto" if engine is None else engine
+        elif allow is not None and getattr(allow, "ndim", 1) != 1:
+            raise VrqNativeError(f"{what}: a {allow.ndim}-D allow needs query_set (one set id per query)")
         self.engine = batch_engine(engine, K, flags, what)
-        if self.engine is not None:
+        self.sized_by = None  # the call whose *_workspace_size serves this one (default: its own)
+        if self.perquery:
+            self.name = base + "_perquery"
+            self.sized_by = base + "_batch"
+        elif self.engine is not None:
             self.name = base + "_batch"
         elif allow is not None:
             filtered_k(K, flags, what)
@@ -311,7 +340,7 @@ class SearchCall:
 
     def workspace_bytes(self, lib, n: int, width: int, nq: int, K: int) -> int:
         """``<name>_workspace_size`` (``width``: dim, or code bytes for vrq_hamming_topk*); 0 for an empty shape."""
-        return getattr(lib, self.name + "_workspace_size")(n, width, nq, K) if n and nq and K else 0
+        return getattr(lib, (self.sized_by or self.name) + "_workspace_size")(n, width, nq, K) if n and nq and K else 0
 
     def workspace(self, lib, n: int, width: int, nq: int, K: int, device, have=None):
         """``have`` where it is large enough, else a new uint8 tensor of max(8, workspace_bytes) bytes."""
@@ -321,12 +350,16 @@ class SearchCall:
             return have
         return torch.empty((max(8, need),), dtype=torch.uint8, device=device)
 
-    def __call__(self, lib, head: tuple, tail: tuple, allow, ws, device, label: str = None) -> None:
-        """``name(*head, [allow,] *tail, ws, bytes, stream[, engine])``: the bitmap's pointer goes between the
-        inputs and the outputs of a *_filtered / *_batch call, the engine ends a *_batch call.  Raises unless
+    def __call__(self, lib, head: tuple, tail: tuple, allow, ws, device, label: str = None, query_set=None) -> None:
+        """``name(*head, [allow,] *tail, ws, bytes, stream[, engine[, nsets, set_words, query_set]])``: the
+        bitmap's pointer goes between the inputs and the outputs of a *_filtered / *_batch / *_perquery call, the
+        engine ends a *_batch call, the filter's shape (from the 2-D ``allow``) a *_perquery call.  Raises unless
         VRQ_OK."""
         args = head + ((ptr(allow),) if self.bitmap else ()) + tail + (ptr(ws), ws.numel(), stream_handle(device))
-        check(getattr(lib, self.name)(*args, *(() if self.engine is None else (self.engine,))), label or self.name)
+        end = () if self.engine is None else (self.engine,)
+        if self.perquery:
+            end += (int(allow.shape[0]), set_words_of(allow), ptr(query_set)) if allow is not None else (1, 0, 0)
+        check(getattr(lib, self.name)(*args, *end), label or self.name)
 
 
 def check(rc: int, what: str) -> None:

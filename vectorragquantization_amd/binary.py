@@ -31,7 +31,7 @@ import torch
 
 from . import quant as Q
 from .docstore import DocStoreError
-from .filters import ids_bitmap
+from .filters import class_filter, ids_bitmap
 from .index import _GrowBuffer, as_device_tensor
 from .vectordb import _QuantizedVectorDB
 
@@ -126,22 +126,26 @@ class CohereVectorDBBinary(_QuantizedVectorDB):
 
     # -- search ------------------------------------------------------------------------------
     def search_vectors(self, query, k: int = 10, binary_oversample: int = 10, compare_float32: bool = False,
-                       allowed_ids=None, engine=None):
+                       allowed_ids=None, engine=None, allowed_ids_per_query=None):
         """Batched search of float32 query embeddings (f32[nq, d]) on the device, one ``vrq_search2`` call.
         Returns (doc_id i64[nq, kk], row i64[nq, kk], hamming i32[nq, kk], score f64[nq, kk]) with
         kk = min(k, K); rows past the candidates are -1.  ``allowed_ids`` (None: all): only these documents
         are searched (``vrq_search2_filtered``); ids the index does not hold are ignored.  ``engine`` ("auto",
-        "mfma", "valu"; default None): ``vrq_search2_batch``, the counting scan on the named engine."""
+        "mfma", "valu"; default None): ``vrq_search2_batch``, the counting scan on the named engine.
+        ``allowed_ids_per_query`` (exclusive with ``allowed_ids``): a sequence of nq entries, each None
+        (unfiltered) or a collection of ids, one filter per query through the ``*_perquery`` call, where
+        ``engine=None`` means "auto"; an empty collection, or one of unknown ids, finds nothing."""
         if k < 0 or binary_oversample < 0:
             raise ValueError("k and binary_oversample must be non-negative")
         qv = as_device_tensor(query, torch.float32, self.device).reshape(-1, self.embedding_dim)
         qb = Q.encode("sbin", qv, device=self.device)["codes"]
         codes = self.index.codes
-        allow = ids_bitmap(self.index.id_map, allowed_ids) if allowed_ids is not None else None
+        allow, qset = class_filter(self.index.id_map, allowed_ids, allowed_ids_per_query, qv.shape[0])
         with torch.cuda.device(self.device):
             rows, ham, sc = Q.search2("f32" if compare_float32 else "sbin", codes,
                                       self._f.view() if compare_float32 else codes, qv, qb, k, binary_oversample,
-                                      rescore_row=self.index.rescore_rows(), allow=allow, engine=engine)
+                                      rescore_row=self.index.rescore_rows(), allow=allow, engine=engine,
+                                      query_set=qset)
         if compare_float32:
             self._check_float_rows(rows)
         ids = torch.where(rows >= 0, self.index.id_map[rows.clamp_min(0)], rows) if self.index.ntotal else rows

@@ -82,7 +82,7 @@ int count_route(int64_t n, int cb, int nq, int K, int engine, bool either, Count
 }
 
 int count_route_launch(const CountPlan& p, const uint8_t* codes, int64_t n, int cb, const uint8_t* q, int nq, int K,
-                       uint8_t* ws, hipStream_t s, int stages, const uint64_t* allow) {
+                       uint8_t* ws, hipStream_t s, int stages, const RowFilter& filter) {
   const bool mfma = p.engine == VRQ_LARGE_ENGINE_MFMA;
   // not a plan of this engine
   if ((!mfma && p.engine != VRQ_LARGE_ENGINE_VALU) || p.nchunks < 1 || p.nchunks > kLargeMaxChunks) return VRQ_EINVAL;
@@ -100,7 +100,8 @@ int count_route_launch(const CountPlan& p, const uint8_t* codes, int64_t n, int 
     a.chunk_rows = p.chunk_rows;
     a.nchunks = p.nchunks;
     a.mb = p.mb;
-    a.allow = allow;
+    a.filter = filter;
+    if (filter.query_set) a.filter.query_set = filter.query_set + b0;  // the pass's queries' sets
     a.hist = (uint32_t*)(ws + p.off_hist);
     a.prefix = (int32_t*)(ws + p.off_prefix) + (int64_t)b0 * p.nchunks * 4;
     a.tc = (int32_t*)(ws + p.off_tc) + (int64_t)b0 * 2;
@@ -111,7 +112,7 @@ int count_route_launch(const CountPlan& p, const uint8_t* codes, int64_t n, int 
       if (rc != VRQ_OK) return rc;
     }
     if (stages & kLargeStageThreshold) {
-      rc = large_threshold_launch(a.hist, a.nq, p.nchunks, bins, want, K, allow != nullptr, a.tc, a.prefix, a.lists, s);
+      rc = large_threshold_launch(a.hist, a.nq, p.nchunks, bins, want, K, filter.allow != nullptr, a.tc, a.prefix, a.lists, s);
       if (rc != VRQ_OK) return rc;
     }
     if (stages & kLargeStageEmit) {

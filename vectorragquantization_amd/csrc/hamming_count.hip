@@ -26,6 +26,7 @@
 // layout of K1d (search_dim.hip); a tile is copied to registers before its slot is refilled, so two tiles are
 // in flight while one is scored.  One row per lane, v_xor_b32 + v_bcnt_u32_b32 against wave-uniform query
 // words (scalar loads).  Every loop has a host-fixed trip count; no workgroup waits for another.
+#include "row_filter.h"
 #include "vrq_internal.h"
 #include "vrq_scan.h"
 #include "wave_scan.h"
@@ -120,6 +121,15 @@ __device__ __forceinline__ int xcd_linear_block() {
 // the last kernel argument and the threshold's minimum is compiled into the filtered instance only, so the
 // unfiltered count and emit instances are, instruction for instruction, what they were without the FILTER axis
 // (the threshold's differs in the LDS offsets of its arrays alone).
+//
+// The per-query instances (FILTER_SETS; vrq_*_perquery, row_filter.h): every resident query has its own word of
+// the tile, at its set's base + (row0 >> 6) + tile, still a scalar load at a wave-uniform address for the reason
+// above.  The set ids are read once at kernel entry and kept as wave-uniform offsets; `live` is the row's bit
+// of the query's own word, and a query whose word is zero skips its distance on a wave-uniform branch -- when
+// that holds for every resident query the tile does nothing, but its loads were issued and waited for as in
+// every other instance, so the ring's trip counts and wait counts are those of the unfiltered kernel.  When all
+// real queries of the workgroup name one set (a batch sorted by set), a wave-uniform test at entry takes the
+// single-word path with that set's word.  nsets, set_words and query_set follow `allow` as the last arguments.
 __device__ __forceinline__ uint64_t allow_word(const uint64_t* allow, int64_t row0, int tile) {
   typedef const __attribute__((address_space(4))) uint64_t* const_u64_ptr;
   const int idx = __builtin_amdgcn_readfirstlane((int)(row0 >> 6) + tile);  // n < 2^32: below 2^26
@@ -127,10 +137,11 @@ __device__ __forceinline__ uint64_t allow_word(const uint64_t* allow, int64_t ro
 }
 
 // ---- count: histogram of the distances per (query, chunk) over rows [0, n) ----
-template <int CB, bool FILTER>
+template <int CB, int FILTER>
 __global__ __launch_bounds__(64 * large_waves(CB)) void hamming_count_kernel(
     const uint8_t* __restrict__ codes, int64_t n, const uint8_t* __restrict__ queries, int nq, int64_t chunk_rows,
-    int nchunks, int nqg, uint32_t* __restrict__ hist_out, const uint64_t* __restrict__ allow) {
+    int nchunks, int nqg, uint32_t* __restrict__ hist_out, const uint64_t* __restrict__ allow, int nsets,
+    int64_t set_words, const int32_t* __restrict__ query_set) {
   using Ring = TileRing<CB>;
   constexpr int C = Ring::C, NW = large_waves(CB), QG = large_qg(CB), BINS = CB * 8 + 1;
   __shared__ __attribute__((aligned(16))) uint8_t ring[NW * 2 * Ring::TILE];
@@ -151,6 +162,24 @@ __global__ __launch_bounds__(64 * large_waves(CB)) void hamming_count_kernel(
   for (int i = tid; i < nqa * BINS; i += 64 * NW) hist[i] = 0;
   __syncthreads();  // (no DMA in flight yet)
 
+  // per-query sets: the bitmap offset of every resident query and its two flags (bit j of sall / snone)
+  int64_t soff[FILTER == FILTER_SETS ? QG : 1];
+  uint32_t sall = 0, snone = 0;
+  bool uniform = true;
+  if constexpr (FILTER == FILTER_SETS) {
+    const int sid0 = set_id_uniform(query_set, q0);
+#pragma unroll
+    for (int j = 0; j < QG; ++j) {
+      const bool real = j < nqa;
+      const int sid = set_id_uniform(query_set, q0 + (real ? j : 0));
+      const SetRef r = set_ref(sid, real, nsets, set_words);
+      soff[j] = r.off;
+      sall |= (uint32_t)r.all << j;
+      snone |= (uint32_t)r.none << j;
+      uniform = uniform && (!real || sid == sid0);
+    }
+  }
+
   // this wave's tiles: w, w + NW, ...
   const int ntiles = (nrows + 63) >> 6;
   const int ntw = w < ntiles ? (ntiles - w + NW - 1) / NW : 0;
@@ -163,7 +192,23 @@ __global__ __launch_bounds__(64 * large_waves(CB)) void hamming_count_kernel(
     tr.read(i & 1, rv);
     if (i + 2 < ntw) tr.issue(w + (i + 2) * NW, i & 1);  // (the slot's reads are retired)
     bool live = (w + i * NW) * 64 + l < nrows;
-    if constexpr (FILTER) {
+    if constexpr (FILTER == FILTER_SETS) {
+      const int idx = __builtin_amdgcn_readfirstlane((int)(row0 >> 6) + w + i * NW);
+      if (!uniform) {  // mixed sets: a word per resident query (slots past nqa are `none`: word 0)
+#pragma unroll
+        for (int j = 0; j < QG; ++j) {
+          const uint64_t wj = set_word(allow, soff[j], (sall >> j) & 1, (snone >> j) & 1, idx);
+          if (wj == 0) continue;  // no allowed row of this query in the tile (wave-uniform)
+          const uint32_t d = Ring::distance(rv, queries, q0 + j);
+          if (live && ((wj >> l) & 1)) atomicAdd(&hist[j * BINS + d], 1u);
+        }
+        continue;
+      }
+      const uint64_t word = set_word(allow, soff[0], sall & 1, snone & 1, idx);
+      if (word == 0) continue;
+      live = live && ((word >> l) & 1);
+    }
+    if constexpr (FILTER == FILTER_ONE) {
       const uint64_t word = allow_word(allow, row0, w + i * NW);
       if (word == 0) continue;  // no allowed row in this tile (wave-uniform; its loads were issued and waited)
       live = live && ((word >> l) & 1);
@@ -299,14 +344,16 @@ __global__ __launch_bounds__(THR_THREADS) void large_threshold_kernel(const uint
 }
 
 // ---- emit: one wave per (chunk, LARGE_QE queries), rows in order ----
-template <int CB, bool FILTER>
+template <int CB, int FILTER>
 __global__ __launch_bounds__(64) void hamming_emit_kernel(const uint8_t* __restrict__ codes, int64_t n,
                                                           const uint8_t* __restrict__ queries, int nq, int K,
                                                           int64_t chunk_rows, int nchunks, int nqg,
                                                           const int32_t* __restrict__ tc,
                                                           const int32_t* __restrict__ prefix,
                                                           uint64_t* __restrict__ lists,
-                                                          const uint64_t* __restrict__ allow) {
+                                                          const uint64_t* __restrict__ allow, int nsets,
+                                                          int64_t set_words,
+                                                          const int32_t* __restrict__ query_set) {
   using Ring = TileRing<CB>;
   constexpr int C = Ring::C, QE = LARGE_QE;
   __shared__ __attribute__((aligned(16))) uint8_t ring[2 * Ring::TILE];
@@ -338,6 +385,24 @@ __global__ __launch_bounds__(64) void hamming_emit_kernel(const uint8_t* __restr
   }
   if (!any) return;  // this chunk holds no row of these queries' K-lists (wave-uniform)
 
+  // per-query sets, as in the count kernel
+  int64_t soff[QE];
+  uint32_t sall = 0, snone = 0;
+  bool uniform = true;
+  if constexpr (FILTER == FILTER_SETS) {
+    const int sid0 = set_id_uniform(query_set, q0);
+#pragma unroll
+    for (int j = 0; j < QE; ++j) {
+      const bool real = j < nqa;
+      const int sid = set_id_uniform(query_set, q0 + (real ? j : 0));
+      const SetRef r = set_ref(sid, real, nsets, set_words);
+      soff[j] = r.off;
+      sall |= (uint32_t)r.all << j;
+      snone |= (uint32_t)r.none << j;
+      uniform = uniform && (!real || sid == sid0);
+    }
+  }
+
   const int ntiles = (nrows + 63) >> 6;
   Ring tr(ring, codes, row0, row1);
   tr.issue(0, 0);
@@ -348,8 +413,23 @@ __global__ __launch_bounds__(64) void hamming_emit_kernel(const uint8_t* __restr
     tr.read(i & 1, rv);
     if (i + 2 < ntiles) tr.issue(i + 2, i & 1);
     const int local = i * 64 + l;
-    bool live = local < nrows;
-    if constexpr (FILTER) {
+    const bool inrows = local < nrows;
+    bool live = inrows;
+    uint64_t wq[QE];  // FILTER_SETS: the tile's word of every query (all-ones bits elsewhere)
+#pragma unroll
+    for (int j = 0; j < QE; ++j) wq[j] = ~0ull;
+    if constexpr (FILTER == FILTER_SETS) {
+      const int idx = __builtin_amdgcn_readfirstlane((int)(row0 >> 6) + i);
+      uint64_t any_word = 0;
+#pragma unroll
+      for (int j = 0; j < QE; ++j) {
+        const int js = uniform ? 0 : j;
+        wq[j] = set_word(allow, soff[js], (sall >> js) & 1, (snone >> js) & 1, idx);
+        any_word |= wq[j];
+      }
+      if (any_word == 0) continue;  // (wave-uniform: slots past nqa are `none`, or copies of slot 0)
+    }
+    if constexpr (FILTER == FILTER_ONE) {
       const uint64_t word = allow_word(allow, row0, i);
       if (word == 0) continue;  // (wave-uniform, as in the count kernel)
       live = live && ((word >> l) & 1);
@@ -357,6 +437,10 @@ __global__ __launch_bounds__(64) void hamming_emit_kernel(const uint8_t* __restr
 #pragma unroll
     for (int j = 0; j < QE; ++j) {
       if (j < nqa) {
+        if constexpr (FILTER == FILTER_SETS) {
+          if (wq[j] == 0) continue;  // no allowed row of this query in the tile (wave-uniform)
+          live = inrows && ((wq[j] >> l) & 1);
+        }
         const int32_t d = (int32_t)Ring::distance(rv, queries, q0 + j);
         const bool lt = live && d < T[j], eq = live && d == T[j];
         const uint64_t mlt = __ballot(lt), meq = __ballot(eq);
@@ -396,14 +480,13 @@ int large_count_launch(int cb, const CountPassArgs& a, hipStream_t s) {
     constexpr int CB = decltype(CBc)::value;
     const int nqg = (a.nq + large_qg(CB) - 1) / large_qg(CB);
     const dim3 grid((unsigned)(a.nchunks * nqg)), block(64 * large_waves(CB));
-    if (a.allow)
-      hipLaunchKernelGGL((hamming_count_kernel<CB, true>), grid, block, 0, s, a.codes, a.n, a.q, a.nq, a.chunk_rows,
-                         a.nchunks, nqg, a.hist, a.allow);
-    else
-      hipLaunchKernelGGL((hamming_count_kernel<CB, false>), grid, block, 0, s, a.codes, a.n, a.q, a.nq, a.chunk_rows,
-                         a.nchunks, nqg, a.hist, a.allow);
-    VRQ_LAUNCH_CHECK();
-    return VRQ_OK;
+    return filter_kind(a.filter, [&](auto F) -> int {
+      hipLaunchKernelGGL((hamming_count_kernel<CB, decltype(F)::value>), grid, block, 0, s, a.codes, a.n, a.q, a.nq,
+                         a.chunk_rows, a.nchunks, nqg, a.hist, a.filter.allow, a.filter.nsets, a.filter.set_words,
+                         a.filter.query_set);
+      VRQ_LAUNCH_CHECK();
+      return VRQ_OK;
+    });
   });
 }
 
@@ -412,14 +495,13 @@ int large_emit_launch(int cb, const CountPassArgs& a, hipStream_t s) {
     constexpr int CB = decltype(CBc)::value;
     const int nqg = (a.nq + LARGE_QE - 1) / LARGE_QE;
     const dim3 grid((unsigned)(a.nchunks * nqg)), block(64);
-    if (a.allow)
-      hipLaunchKernelGGL((hamming_emit_kernel<CB, true>), grid, block, 0, s, a.codes, a.n, a.q, a.nq, a.K,
-                         a.chunk_rows, a.nchunks, nqg, a.tc, a.prefix, a.lists, a.allow);
-    else
-      hipLaunchKernelGGL((hamming_emit_kernel<CB, false>), grid, block, 0, s, a.codes, a.n, a.q, a.nq, a.K,
-                         a.chunk_rows, a.nchunks, nqg, a.tc, a.prefix, a.lists, a.allow);
-    VRQ_LAUNCH_CHECK();
-    return VRQ_OK;
+    return filter_kind(a.filter, [&](auto F) -> int {
+      hipLaunchKernelGGL((hamming_emit_kernel<CB, decltype(F)::value>), grid, block, 0, s, a.codes, a.n, a.q, a.nq,
+                         a.K, a.chunk_rows, a.nchunks, nqg, a.tc, a.prefix, a.lists, a.filter.allow, a.filter.nsets,
+                         a.filter.set_words, a.filter.query_set);
+      VRQ_LAUNCH_CHECK();
+      return VRQ_OK;
+    });
   });
 }
 

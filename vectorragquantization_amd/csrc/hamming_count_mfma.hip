@@ -26,10 +26,21 @@
 // Dead pairs never count and never hit: rows past the chunk's end, rows whose bitmap bit is clear, query
 // slots past nq (zero A fragments; their seed never accepts in emit, their adds are masked in count).
 // Every loop has a trip count fixed by the kernel arguments; no workgroup waits for another.
+//
+// Per-query sets (FILTER_SETS; row_filter.h).  Lane i of a wave keeps the bitmap offset of query slot i (WaveSets),
+// read once at kernel entry; a slot's word of a tile is a scalar load at base + v_readlane(offset), on the lgkm
+// counter like the single bitmap's word, so the ring's counted vm waits are untouched.  count: once per tile the
+// words of the wave's slots are turned into a per-lane mask "which slots allow my row" for each n-block, so
+// register g of M-block m tests bit slot_of(g, 0) of the mask shifted by 4 hh; the OR of the words plays the
+// single word's part for the tile and n-block skips.  emit: the tile loop needs the OR of the words alone (the
+// any_above pre-test keeps a per-row predicate); the (query, row) bit is applied in the rare hit path, before
+// the ballots.  When every real slot of the wave names one set, a wave-uniform test at entry takes the
+// single-word path with that set's word.
 #include <limits.h>
 
 #include "mfma_common.h"
 #include "mfma_fp4.h"
+#include "row_filter.h"
 #include "vrq_internal.h"
 #include "vrq_scan.h"
 
@@ -164,10 +175,11 @@ __device__ __forceinline__ int slot_of(int g, int hh) { return (g & 3) + 8 * (g 
 }  // namespace
 
 // ---- count ----
-template <int KS, int MB, bool FILTER>
+template <int KS, int MB, int FILTER>
 __global__ __launch_bounds__(64 * CountCode<KS>::NW) void hamming_count_mfma_kernel(
     const uint8_t* __restrict__ codes, int64_t n, const uint8_t* __restrict__ queries, int nq, int64_t chunk_rows,
-    int nchunks, int nqb, uint32_t* __restrict__ hist_out, const uint64_t* __restrict__ allow) {
+    int nchunks, int nqb, uint32_t* __restrict__ hist_out, const uint64_t* __restrict__ allow, int nsets,
+    int64_t set_words, const int32_t* __restrict__ query_set) {
   using Cd = CountCode<KS>;
   using Eng = Engine<KS, MB>;
   constexpr int C = Cd::C, NPH = Cd::NPH, NW = Cd::NW, BINS = Cd::BINS, QREAL = Cd::QREAL, NG = Cd::NG;
@@ -215,6 +227,11 @@ __global__ __launch_bounds__(64 * CountCode<KS>::NW) void hamming_count_mfma_ker
   }
   const uint32_t hist0 = lds_addr(hist);
   const int inc = h ? 0x10000 : 1;
+  WaveSets sets;  // lane i: slot i & 31 of M-block i >> 5
+  if constexpr (FILTER == FILTER_SETS) {
+    const int q = q0 + (l >> 5) * QREAL + ri;
+    sets.init(query_set, q, (l >> 5) < MB && ri < QREAL && q < nq, nsets, set_words);
+  }
 
   const int ntiles = (nrows + 63) >> 6;
   constexpr int SEGT = kCountFlushRows / 64;  // tiles between flushes
@@ -233,9 +250,33 @@ __global__ __launch_bounds__(64 * CountCode<KS>::NW) void hamming_count_mfma_ker
       e.read(i & 1, rb);
       if (i + 2 < ntw) e.issue(tile + 2 * NW, i & 1);  // (the slot's reads are retired)
       uint64_t word = ~0ull;
-      if constexpr (FILTER) {
+      if constexpr (FILTER == FILTER_ONE) {
         word = tile_allow_word(allow, row0, tile);
         if (word == 0) continue;  // no allowed row in this tile (wave-uniform; its loads were issued and waited)
+      }
+      // FILTER_SETS, mixed sets: bit s of smask[nb][m] says slot s of M-block m allows this lane's row of n-block nb
+      uint32_t smask[2][MB];
+      bool mixed = false;
+      if constexpr (FILTER == FILTER_SETS) {
+        const int idx = __builtin_amdgcn_readfirstlane((int)(row0 >> 6) + tile);
+        mixed = !sets.uniform;
+        if (mixed) {
+          word = 0;
+#pragma unroll
+          for (int m = 0; m < MB; ++m) {
+            smask[0][m] = smask[1][m] = 0;
+#pragma unroll
+            for (int sl = 0; sl < QREAL; ++sl) {
+              const uint64_t ws = sets.word(allow, 32 * m + sl, idx);
+              word |= ws;
+              smask[0][m] |= (((uint32_t)ws >> ri) & 1u) << sl;
+              smask[1][m] |= (((uint32_t)(ws >> 32) >> ri) & 1u) << sl;
+            }
+          }
+        } else {
+          word = sets.word(allow, 0, idx);
+        }
+        if (word == 0) continue;  // no allowed row of any resident query in this tile (wave-uniform)
       }
 #pragma unroll
       for (int nb = 0; nb < 2; ++nb) {
@@ -245,6 +286,22 @@ __global__ __launch_bounds__(64 * CountCode<KS>::NW) void hamming_count_mfma_ker
         const bool rlive = tile * 64 + nb * 32 + ri < nrows && ((half >> ri) & 1);
         v16f acc[MB];
         const int prow = e.block(rb[nb], seed, acc);
+        if (FILTER == FILTER_SETS && mixed) {
+          if (rlive) {
+            const float pr = (float)prow;
+#pragma unroll
+            for (int m = 0; m < MB; ++m) {
+              const uint32_t sm = smask[nb][m] >> (4 * h);  // (slots past nq are `none`: their bits are clear)
+#pragma unroll
+              for (int g = 0; g < NG; ++g)
+                if ((sm >> slot_of(g, 0)) & 1) {
+                  const int d = (int)(pr - 2.0f * acc[m][g]);
+                  lds_add32(hist0 + (uint32_t)(((m * NG + g) * BINS + d) * 4), inc);
+                }
+            }
+          }
+          continue;
+        }
         if (rlive) {
           const float pr = (float)prow;
 #pragma unroll
@@ -282,11 +339,12 @@ __global__ __launch_bounds__(64 * CountCode<KS>::NW) void hamming_count_mfma_ker
 }
 
 // ---- emit ----
-template <int KS, int MB, bool FILTER>
+template <int KS, int MB, int FILTER>
 __global__ __launch_bounds__(64) void hamming_emit_mfma_kernel(
     const uint8_t* __restrict__ codes, int64_t n, const uint8_t* __restrict__ queries, int nq, int K,
     int64_t chunk_rows, int nchunks, int nqb, const int32_t* __restrict__ tc, const int32_t* __restrict__ prefix,
-    uint64_t* __restrict__ lists, const uint64_t* __restrict__ allow) {
+    uint64_t* __restrict__ lists, const uint64_t* __restrict__ allow, int nsets, int64_t set_words,
+    const int32_t* __restrict__ query_set) {
   using Cd = CountCode<KS>;
   using Eng = Engine<KS, MB>;
   constexpr int C = Cd::C, NPH = Cd::NPH, QPW = 32 * MB;
@@ -337,6 +395,8 @@ __global__ __launch_bounds__(64) void hamming_emit_mfma_kernel(
     for (int g = 0; g < 16; ++g) seed[m][g] = 0.5f * (float)tq[32 * m + slot_of(g, h)];
   __syncthreads();  // (every plain LDS access is done before the first DMA)
   const uint32_t T0 = lds_addr(Tq), lt0 = lds_addr(ltpos), eq0 = lds_addr(eqpos);
+  WaveSets sets;  // lane i: query slot i
+  if constexpr (FILTER == FILTER_SETS) sets.init(query_set, q0 + l, l < QPW && q0 + l < nq, nsets, set_words);
 
   const int ntiles = (nrows + 63) >> 6;
   e.issue(0, 0);
@@ -347,9 +407,23 @@ __global__ __launch_bounds__(64) void hamming_emit_mfma_kernel(
     e.read(i & 1, rb);
     if (i + 2 < ntiles) e.issue(i + 2, i & 1);
     uint64_t word = ~0ull;
-    if constexpr (FILTER) {
+    if constexpr (FILTER == FILTER_ONE) {
       word = tile_allow_word(allow, row0, i);
       if (word == 0) continue;  // (wave-uniform, as in the count kernel)
+    }
+    int idx = 0;
+    bool mixed = false;
+    if constexpr (FILTER == FILTER_SETS) {
+      idx = __builtin_amdgcn_readfirstlane((int)(row0 >> 6) + i);
+      mixed = !sets.uniform;
+      if (mixed) {  // the OR of the slots' words: the per-row predicate of the pre-test
+        word = 0;
+#pragma unroll
+        for (int sl = 0; sl < QPW; ++sl) word |= sets.word(allow, sl, idx);
+      } else {
+        word = sets.word(allow, 0, idx);
+      }
+      if (word == 0) continue;
     }
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb) {
@@ -368,11 +442,17 @@ __global__ __launch_bounds__(64) void hamming_emit_mfma_kernel(
         // rare: some row of this n-block is in some list of this M-block
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
-          const bool hit = acc[m][g] > hp;
+          bool hit = acc[m][g] > hp;
           if (!__ballot(hit)) continue;
           int lo = l;  // lane-dependent values of this rare path from an opaque lane id (no hoisting)
           asm volatile("" : "+v"(lo));
           const int ql = 32 * m + slot_of(g, lo >> 5);
+          if (FILTER == FILTER_SETS && mixed) {  // the row's bit of the query's own word
+            const uint64_t wlo = sets.word(allow, 32 * m + slot_of(g, 0), idx);
+            const uint64_t whi = sets.word(allow, 32 * m + slot_of(g, 1), idx);
+            const uint32_t wh = (uint32_t)(((lo >> 5) ? whi : wlo) >> (32 * nb));
+            hit = hit && ((wh >> (lo & 31)) & 1);
+          }
           // acc = <q, r> + (T + 1 - pc(q)) / 2, so pc(r) - 2 acc = dist - T - 1 in [-(dim + 1), -1]
           const int v = prow - (int)(2.0f * acc[m][g]);
           const bool lt = hit && v < -1, eq = hit && v == -1;
@@ -418,28 +498,26 @@ int count_launch(const CountPassArgs& a, hipStream_t s) {
   using Cd = CountCode<KS>;
   const int qpw = Cd::QREAL * MB, nqb = (a.nq + qpw - 1) / qpw;
   const dim3 grid((unsigned)(a.nchunks * nqb)), block(64 * Cd::NW);
-  if (a.allow)
-    hipLaunchKernelGGL((hamming_count_mfma_kernel<KS, MB, true>), grid, block, 0, s, a.codes, a.n, a.q, a.nq,
-                       a.chunk_rows, a.nchunks, nqb, a.hist, a.allow);
-  else
-    hipLaunchKernelGGL((hamming_count_mfma_kernel<KS, MB, false>), grid, block, 0, s, a.codes, a.n, a.q, a.nq,
-                       a.chunk_rows, a.nchunks, nqb, a.hist, a.allow);
-  VRQ_LAUNCH_CHECK();
-  return VRQ_OK;
+  return filter_kind(a.filter, [&](auto F) -> int {
+    hipLaunchKernelGGL((hamming_count_mfma_kernel<KS, MB, decltype(F)::value>), grid, block, 0, s, a.codes, a.n, a.q,
+                       a.nq, a.chunk_rows, a.nchunks, nqb, a.hist, a.filter.allow, a.filter.nsets, a.filter.set_words,
+                       a.filter.query_set);
+    VRQ_LAUNCH_CHECK();
+    return VRQ_OK;
+  });
 }
 
 template <int KS, int MB>
 int emit_launch(const CountPassArgs& a, hipStream_t s) {
   const int qpw = 32 * MB, nqb = (a.nq + qpw - 1) / qpw;
   const dim3 grid((unsigned)(a.nchunks * nqb)), block(64);
-  if (a.allow)
-    hipLaunchKernelGGL((hamming_emit_mfma_kernel<KS, MB, true>), grid, block, 0, s, a.codes, a.n, a.q, a.nq, a.K,
-                       a.chunk_rows, a.nchunks, nqb, a.tc, a.prefix, a.lists, a.allow);
-  else
-    hipLaunchKernelGGL((hamming_emit_mfma_kernel<KS, MB, false>), grid, block, 0, s, a.codes, a.n, a.q, a.nq, a.K,
-                       a.chunk_rows, a.nchunks, nqb, a.tc, a.prefix, a.lists, a.allow);
-  VRQ_LAUNCH_CHECK();
-  return VRQ_OK;
+  return filter_kind(a.filter, [&](auto F) -> int {
+    hipLaunchKernelGGL((hamming_emit_mfma_kernel<KS, MB, decltype(F)::value>), grid, block, 0, s, a.codes, a.n, a.q,
+                       a.nq, a.K, a.chunk_rows, a.nchunks, nqb, a.tc, a.prefix, a.lists, a.filter.allow,
+                       a.filter.nsets, a.filter.set_words, a.filter.query_set);
+    VRQ_LAUNCH_CHECK();
+    return VRQ_OK;
+  });
 }
 
 int stage_launch(int cb, bool emit, const CountPassArgs& a, hipStream_t s) {

@@ -1786,15 +1786,25 @@ size_t vrq_scan_filtered_workspace_size(int64_t n, int32_t dim, int32_t nq, int3
 // What a call asks of the counting scan, one value per family of entry points.  The filtered calls
 // (vrq_*_filtered) are the *_large calls with a row bitmap handed to K1h; the batch calls (vrq_*_batch) are the
 // same calls again with a choice of the scan's engine, a workspace that covers either engine, and a bitmap
-// that may be null (no filter).
+// that may be null (no filter).  The per-query calls (vrq_*_perquery) are the batch calls with nsets bitmaps and
+// a set id per query in place of the one bitmap.
 struct CountCall {
   int engine = VRQ_LARGE_ENGINE_VALU;  // VRQ_LARGE_ENGINE_*; a *_large / *_filtered call runs K1h
-  bool either = false;                 // the workspace covers either engine (*_batch)
-  bool filtered = false;               // the call reads `allow`
-  const uint64_t* allow = nullptr;
+  bool either = false;                 // the workspace covers either engine (*_batch, *_perquery)
+  bool filtered = false;               // the call reads `filter.allow`
+  bool perquery = false;               // the call reads `filter.query_set`
+  RowFilter filter;
 };
-static CountCall filtered_call(const uint64_t* allow) { return {VRQ_LARGE_ENGINE_VALU, false, true, allow}; }
-static CountCall batch_call(const uint64_t* allow, int engine) { return {engine, true, allow != nullptr, allow}; }
+static CountCall filtered_call(const uint64_t* allow) {
+  return {VRQ_LARGE_ENGINE_VALU, false, true, false, RowFilter{allow, 0, 0, nullptr}};
+}
+static CountCall batch_call(const uint64_t* allow, int engine) {
+  return {engine, true, allow != nullptr, false, RowFilter{allow, 0, 0, nullptr}};
+}
+static CountCall perquery_call(const uint64_t* allow, int nsets, int64_t set_words, const int32_t* query_set,
+                               int engine) {
+  return {engine, true, true, true, RowFilter{allow, nsets, set_words, query_set}};
+}
 static bool engine_ok(int engine) { return engine >= VRQ_LARGE_ENGINE_AUTO && engine <= VRQ_LARGE_ENGINE_MFMA; }
 
 // The route of a call that scans (n, nq, K >= 1), after the other pointers a non-empty call reads: the
@@ -1802,7 +1812,11 @@ static bool engine_ok(int engine) { return engine >= VRQ_LARGE_ENGINE_AUTO && en
 // depend on the filter: one table entry per code size serves both kinds.)
 static int count_route_checked(int64_t n, int cb, int nq, int K, const CountCall& c, size_t workspace_bytes,
                                CountPlan* p) {
-  if (c.filtered) VRQ_CHECK_ARG(c.allow && ((uintptr_t)c.allow & 7) == 0);
+  if (c.filtered) VRQ_CHECK_ARG(c.filter.allow && ((uintptr_t)c.filter.allow & 7) == 0);
+  if (c.perquery) {
+    VRQ_CHECK_ARG(c.filter.query_set && ((uintptr_t)c.filter.query_set & 3) == 0);
+    VRQ_CHECK_ARG(c.filter.nsets >= 1 && c.filter.set_words >= (n + 63) / 64);
+  }
   const int rc = count_route(n, cb, nq, K, c.engine, c.either, p);
   if (rc != VRQ_OK) return rc;
   return workspace_bytes < p->need ? VRQ_EWORKSPACE : VRQ_OK;
@@ -1820,7 +1834,7 @@ static int scan_large_impl(const uint8_t* codes, int64_t n, int32_t dim, const u
   const int rc = count_route_checked(n, dim / 8, nq, K, call, workspace_bytes, &p);
   if (rc != VRQ_OK) return rc;
   return count_route_launch(p, codes, n, dim / 8, qb, nq, K, (uint8_t*)workspace, (hipStream_t)stream, stages,
-                            call.allow);
+                            call.filter);
 }
 
 int vrq_scan_large(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq, int32_t K,
@@ -1849,7 +1863,7 @@ static int hamming_topk_large_impl(const uint8_t* codes, int64_t n, int32_t code
   int rc = count_route_checked(n, code_bytes, nq, k, call, workspace_bytes, &p);
   if (rc != VRQ_OK) return rc;
   uint8_t* ws = (uint8_t*)workspace;
-  rc = count_route_launch(p, codes, n, code_bytes, queries, nq, k, ws, s, 0, call.allow);
+  rc = count_route_launch(p, codes, n, code_bytes, queries, nq, k, ws, s, 0, call.filter);
   if (rc != VRQ_OK) return rc;
   return large_sort_launch(s, nq, (uint64_t*)(ws + p.off_lists), k, (int32_t*)(ws + p.off_kp), true, row_offset,
                            nullptr, out_rows, out_dist);
@@ -1898,7 +1912,7 @@ static int search3_large_impl(const uint8_t* codes, const int8_t* x8, const doub
   int32_t* ord = (int32_t*)(ws + p.off_ord);
   double* s2 = (double*)(ws + p.off_s2);
   double* s3 = (double*)(ws + p.off_s3);
-  rc = count_route_launch(p, codes, n, dim / 8, qb, nq, K, ws, s, 0, call.allow);
+  rc = count_route_launch(p, codes, n, dim / 8, qb, nq, K, ws, s, 0, call.filter);
   if (rc != VRQ_OK) return rc;
   rc = large_sort_launch(s, nq, lists, K, kp, p1, row_offset, out_count, out_rows, out_dist);
   if (rc != VRQ_OK || p1) return rc;
@@ -1993,7 +2007,7 @@ static int search2_large_impl(int32_t mode, const uint8_t* codes, const void* q,
   uint64_t* lists = (uint64_t*)(ws + p.off_lists);
   int32_t* kp = (int32_t*)(ws + p.off_kp);
   double* s2 = (double*)(ws + p.off_s2);
-  rc = count_route_launch(p, codes, n, dim / 8, qb, nq, K, ws, s, 0, call.allow);
+  rc = count_route_launch(p, codes, n, dim / 8, qb, nq, K, ws, s, 0, call.filter);
   if (rc != VRQ_OK) return rc;
   rc = large_sort_launch(s, nq, lists, K, kp, false, 0, nullptr, nullptr, nullptr);
   if (rc != VRQ_OK) return rc;
@@ -2131,6 +2145,49 @@ int vrq_search2_batch(int32_t mode, const uint8_t* codes, const void* q, const d
                             batch_call(allow, engine));
 }
 
+// ---- the per-query calls: the batch calls with a set of bitmaps and one set id per query ----
+int vrq_scan_perquery(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq, int32_t K,
+                      int32_t stages, const uint64_t* allow, void* workspace, size_t workspace_bytes, void* stream,
+                      int32_t engine, int32_t nsets, int64_t set_words, const int32_t* query_set) {
+  VRQ_CHECK_ARG(engine_ok(engine));
+  return scan_large_impl(codes, n, dim, qb, nq, K, stages, workspace, workspace_bytes, stream,
+                         perquery_call(allow, nsets, set_words, query_set, engine));
+}
+
+int vrq_hamming_topk_perquery(const uint8_t* codes, int64_t n, int32_t code_bytes, int64_t row_offset,
+                              const uint8_t* queries, int32_t nq, int32_t k, const uint64_t* allow,
+                              int32_t* out_dist, int64_t* out_rows, void* workspace, size_t workspace_bytes,
+                              void* stream, int32_t engine, int32_t nsets, int64_t set_words,
+                              const int32_t* query_set) {
+  VRQ_CHECK_ARG(engine_ok(engine));
+  return hamming_topk_large_impl(codes, n, code_bytes, row_offset, queries, nq, k, out_dist, out_rows, workspace,
+                                 workspace_bytes, stream, perquery_call(allow, nsets, set_words, query_set, engine));
+}
+
+int vrq_search3_perquery(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
+                         int64_t n, int32_t dim, int64_t row_offset, const float* qf, const uint8_t* qb, int32_t nq,
+                         int32_t k, int32_t K, int32_t K3, int32_t flags, const uint64_t* allow, int32_t* out_count,
+                         int64_t* out_rows, int32_t* out_dist, double* out_binary, double* out_cosine,
+                         void* workspace, size_t workspace_bytes, void* stream, int32_t engine, int32_t nsets,
+                         int64_t set_words, const int32_t* query_set) {
+  VRQ_CHECK_ARG(engine_ok(engine));
+  return search3_large_impl(codes, x8, norms, rescore_row, n, dim, row_offset, qf, qb, nq, k, K, K3, flags,
+                            out_count, out_rows, out_dist, out_binary, out_cosine, workspace, workspace_bytes, stream,
+                            perquery_call(allow, nsets, set_words, query_set, engine));
+}
+
+int vrq_search2_perquery(int32_t mode, const uint8_t* codes, const void* q, const double* minmax, double limit,
+                         const int64_t* rescore_row, int64_t n, int32_t dim, int64_t row_offset, const float* qf,
+                         const uint8_t* qb, int32_t nq, int32_t k, int32_t K, int32_t flags, const uint64_t* allow,
+                         int32_t* out_count, int64_t* out_rows, int32_t* out_dist, double* out_score,
+                         void* workspace, size_t workspace_bytes, void* stream, int32_t engine, int32_t nsets,
+                         int64_t set_words, const int32_t* query_set) {
+  VRQ_CHECK_ARG(engine_ok(engine));
+  return search2_large_impl(mode, codes, q, minmax, limit, rescore_row, n, dim, row_offset, qf, qb, nq, k, K, flags,
+                            out_count, out_rows, out_dist, out_score, workspace, workspace_bytes, stream,
+                            perquery_call(allow, nsets, set_words, query_set, engine));
+}
+
 // ---- the per-shard calls for K up to VRQ_K_LARGE_MAX: K1h, the sort, the scores of every candidate ----
 size_t vrq_shard_search3_large_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K) {
   return vrq_search3_large_workspace_size(n, dim, nq, K);
@@ -2147,7 +2204,7 @@ static int large_shard_phase1(const CountPlan& p, const uint8_t* codes, int64_t 
                               LargeScoreArgs* sa) {
   uint64_t* lists = (uint64_t*)(ws + p.off_lists);
   int32_t* kp = (int32_t*)(ws + p.off_kp);
-  int rc = count_route_launch(p, codes, n, dim / 8, qb, nq, K, ws, s, 0, nullptr);
+  int rc = count_route_launch(p, codes, n, dim / 8, qb, nq, K, ws, s, 0, RowFilter{});
   if (rc != VRQ_OK) return rc;
   rc = large_sort_launch(s, nq, lists, K, kp, true, row_offset, out_count, out_rows, out_dist);
   sa->lists = lists;

@@ -172,6 +172,25 @@ int count_code_bytes(int cb, F&& f) {
   }
 }
 
+// The row filter of a counting scan.  allow == null: none.  query_set == null: the one bitmap `allow`, u64
+// [ceil(n / 64)], bit r & 63 of word r >> 6: row r takes part (nsets and set_words are not read).  Otherwise
+// `allow` holds nsets such bitmaps, bitmap s at allow + s * set_words (set_words >= ceil(n / 64)), and query q
+// is filtered by bitmap query_set[q] (device i32 [nq]): -1 allows every row, any other value outside
+// [0, nsets) allows none.
+struct RowFilter {
+  const uint64_t* allow = nullptr;
+  int nsets = 0;
+  int64_t set_words = 0;
+  const int32_t* query_set = nullptr;
+};
+// filter -> f(std::integral_constant<int, FILTER_*>) (row_filter.h: 0 off, 1 one bitmap, 2 per-query sets)
+template <class F>
+int filter_kind(const RowFilter& r, F&& f) {
+  if (!r.allow) return f(std::integral_constant<int, 0>{});
+  if (!r.query_set) return f(std::integral_constant<int, 1>{});
+  return f(std::integral_constant<int, 2>{});
+}
+
 // one pass (at most kLargeQueryBatch queries) of either engine: the pointers are the pass's own slices
 struct CountPassArgs {
   const uint8_t* codes;
@@ -181,7 +200,7 @@ struct CountPassArgs {
   int64_t chunk_rows;
   int nchunks;
   int mb;                 // K1hm: M-blocks per wave
-  const uint64_t* allow;  // null, or the row bitmap of a filtered scan
+  RowFilter filter;       // query_set is the pass's own slice
   uint32_t* hist;
   int32_t* tc;
   int32_t* prefix;
@@ -229,12 +248,11 @@ struct CountPlan {
 int count_route(int64_t n, int cb, int nq, int K, int engine, bool either, CountPlan* p);
 // the whole scan (count, threshold, emit): leaves the K-lists at off_lists, KEY_NONE padded, the
 // dist < T part and the dist == T part each in row order.  stages: a mask of kLargeStage* (none = all).
-// allow: null, or the row bitmap of a filtered scan (u64 [ceil(n / 64)], bit r & 63 of word r >> 6: row r
-// takes part); the lists then hold the min(K, allowed) smallest allowed rows.
+// filter: the row filter (above); the lists of a query then hold its min(K, allowed) smallest allowed rows.
 constexpr int kLargeStageCount = VRQ_LARGE_STAGE_COUNT, kLargeStageThreshold = VRQ_LARGE_STAGE_THRESHOLD,
               kLargeStageEmit = VRQ_LARGE_STAGE_EMIT,
               kLargeStageAll = kLargeStageCount | kLargeStageThreshold | kLargeStageEmit;
 int count_route_launch(const CountPlan& p, const uint8_t* codes, int64_t n, int cb, const uint8_t* q, int nq, int K,
-                       uint8_t* ws, hipStream_t s, int stages, const uint64_t* allow);
+                       uint8_t* ws, hipStream_t s, int stages, const RowFilter& filter);
 
 }  // namespace vrq

@@ -27,7 +27,7 @@ import torch
 
 from . import _native as N
 from .docstore import DocStoreError, RocksDictReader, is_rocksdict_dir
-from .filters import checked as checked_bitmap, ids_bitmap
+from .filters import checked as checked_bitmap, checked_filter, class_filter, ids_bitmap
 from .index import BinaryIndexIDMap2, _GrowBuffer, as_device_tensor
 from .quant import int8_row_norms
 
@@ -109,13 +109,13 @@ def gemm_topk(mode: str, qf: torch.Tensor, k: int, codes: torch.Tensor | None = 
     return cnt, rows, scores
 
 
-def search3_route(K: int, flags: int = 0, allow=None, engine=None) -> N.SearchCall:
+def search3_route(K: int, flags: int = 0, allow=None, engine=None, query_set=None) -> N.SearchCall:
     """The route ``search3`` takes (``N.SearchCall`` of ``vrq_search3``, whose plain call is ``vrq_search3_dim``).
     The sharded mode without a bitmap or an engine stays on ``vrq_search3_dim`` whatever K is: sharding keeps
     K <= 1024, and its error is the library's."""
-    if flags & N.VRQ_SEARCH_SHARD and allow is None and engine is None:
+    if flags & N.VRQ_SEARCH_SHARD and allow is None and engine is None and query_set is None:
         K = min(K, N.VRQ_K_MAX)
-    return N.SearchCall("vrq_search3", K, flags, allow, engine, "search3", "vrq_search3_dim")
+    return N.SearchCall("vrq_search3", K, flags, allow, engine, "search3", "vrq_search3_dim", query_set)
 
 
 def search3_call(K: int, flags: int = 0, allow=None) -> str:
@@ -128,12 +128,16 @@ def search3_call(K: int, flags: int = 0, allow=None) -> str:
 
 def search3(codes: torch.Tensor, x8: torch.Tensor, norms: torch.Tensor, qf: torch.Tensor, qb: torch.Tensor,
             k: int, K: int, K3: int, flags: int = 0, row_offset: int = 0, rescore_row: torch.Tensor | None = None,
-            workspace: torch.Tensor | None = None, allow: torch.Tensor | None = None, engine: str | None = None):
+            workspace: torch.Tensor | None = None, allow: torch.Tensor | None = None, engine: str | None = None,
+            query_set: torch.Tensor | None = None):
     """Thin wrapper of ``vrq_search3``; returns (count, rows, dist, s2, s3) device tensors.  More than 1024
     Phase-I candidates (up to ``VRQ_K_LARGE_MAX``) take ``vrq_search3_large`` (not with ``VRQ_SEARCH_SHARD``).
     ``allow`` (``filters.row_bitmap``): Phase I over the allowed rows only, ``vrq_search3_filtered``.
     ``engine`` ("auto", "mfma", "valu"; default None = the routes above): ``vrq_search3_batch``, the counting
-    scan on the named engine for every K up to ``VRQ_K_LARGE_MAX``, with or without ``allow``."""
+    scan on the named engine for every K up to ``VRQ_K_LARGE_MAX``, with or without ``allow``.
+    ``query_set`` (an int tensor [nq]) with a 2-D ``allow`` (``filters.row_bitmaps``): query i is filtered by bitmap
+    ``query_set[i]`` (-1: unfiltered; any other id outside the sets: no row), ``vrq_search3_perquery``, where
+    ``engine=None`` means "auto"."""
     dev = qf.device
     nq = qf.shape[0]
     n = codes.shape[0]
@@ -150,13 +154,13 @@ def search3(codes: torch.Tensor, x8: torch.Tensor, norms: torch.Tensor, qf: torc
     if rescore_row is not None and rescore_row.shape[0] != n:
         raise N.VrqNativeError(f"vrq_search3: rescore_row has {rescore_row.shape[0]} entries for {n} rows")
     lib = N.load()
-    call = search3_route(K, flags, allow, engine)
+    call = search3_route(K, flags, allow, engine, query_set)
     workspace = call.workspace(lib, n, dim, nq, K, dev, workspace)
-    if allow is not None:
-        allow = checked_bitmap(allow, n, dev)
+    allow, query_set = checked_filter(allow, query_set, n, nq, dev)
     call(lib, (N.ptr(codes) if n else 0, N.ptr(x8) if n else 0, N.ptr(norms) if n else 0, N.ptr(rescore_row), n, dim,
                row_offset, N.ptr(qf), N.ptr(qb), nq, k, K, K3, flags),
-         (N.ptr(cnt), N.ptr(rows), N.ptr(dist), N.ptr(s2), N.ptr(s3)), allow if n else None, workspace, dev)
+         (N.ptr(cnt), N.ptr(rows), N.ptr(dist), N.ptr(s2), N.ptr(s3)), allow if n else None, workspace, dev,
+         query_set=query_set)
     return cnt, rows, dist, s2, s3
 
 
@@ -347,10 +351,14 @@ class CohereEnhancedVectorDB:
 
     # -- search ------------------------------------------------------------------------
     def search_vectors(self, qf, qb, k: int = 10, binary_oversample: int = 10,
-                       int8_oversample: int = 3, allowed_ids=None, engine=None) -> SearchBatch:
+                       int8_oversample: int = 3, allowed_ids=None, engine=None,
+                       allowed_ids_per_query=None) -> SearchBatch:
         """Batched three-phase search of float32 [nq, d] / ubinary [nq, d/8] query embeddings.
         ``allowed_ids`` (document ids; None: all): only these documents are searched, as if the others had
-        been removed; ids the index does not hold are ignored."""
+        been removed; ids the index does not hold are ignored.
+        ``allowed_ids_per_query`` (exclusive with ``allowed_ids``): a sequence of nq entries, each None
+        (unfiltered) or a collection of ids, one filter per query through the ``*_perquery`` call, where
+        ``engine=None`` means "auto"; an empty collection, or one of unknown ids, finds nothing."""
         qf = as_device_tensor(qf, torch.float32, self.device).reshape(-1, self.embedding_dim)
         qb = as_device_tensor(qb, torch.uint8, self.device).reshape(-1, self.embedding_dim // 8)
         n = self.index.ntotal
@@ -361,13 +369,14 @@ class CohereEnhancedVectorDB:
         if self._ws is None or self._ws.device != self.device:
             self._ws = torch.empty((8,), dtype=torch.uint8, device=self.device)
         lib = N.load()
-        allow = ids_bitmap(self.index.id_map, allowed_ids) if allowed_ids is not None else None
+        allow, qset = class_filter(self.index.id_map, allowed_ids, allowed_ids_per_query, qf.shape[0])
         # sized by the route search3 itself takes
-        self._ws = search3_route(K, 0, allow, engine).workspace(lib, n, self.embedding_dim, qf.shape[0], K,
+        self._ws = search3_route(K, 0, allow, engine, qset).workspace(lib, n, self.embedding_dim, qf.shape[0], K,
                                                                 self.device, self._ws)
         with torch.cuda.device(self.device):
             cnt, rows, dist, s2, s3 = search3(self.index.codes, self._x8.view(), self._norms.view(), qf, qb,
-                                              k, K, K3, 0, 0, self.index.rescore_rows(), self._ws, allow, engine)
+                                              k, K, K3, 0, 0, self.index.rescore_rows(), self._ws, allow, engine,
+                                              qset)
         ids = torch.where(rows >= 0, self.index.id_map[rows.clamp_min(0)] if n else rows, rows)
         return SearchBatch(cnt, ids, rows, dist, s2, s3)
 

@@ -145,35 +145,37 @@ class BinaryIndexIDMap2:
                 self._dup = True
             self._rev[e] = base + j
 
-    def search(self, q, k: int, allow=None, engine=None):
+    def search(self, q, k: int, allow=None, engine=None, query_set=None):
         """(D i32[nq,k], L i64[nq,k]) on the host, like ``faiss.Index.search``; ``allow``: a row bitmap
         (``filters.row_bitmap`` / ``filters.ids_bitmap``), FAISS's ``SearchParameters(sel=IDSelectorBitmap)``;
-        ``engine``: as ``search_device``."""
-        D, R = self.search_device(q, k, allow, engine)
+        ``engine``, ``query_set``: as ``search_device``."""
+        D, R = self.search_device(q, k, allow, engine, query_set)
         L = torch.where(R >= 0, self.id_map[R.clamp_min(0)] if self.ntotal else R, R)
         return D.cpu().numpy(), L.cpu().numpy()
 
-    def search_device(self, q, k: int, allow=None, engine=None):
+    def search_device(self, q, k: int, allow=None, engine=None, query_set=None):
         """Phase I on device -> (dist i32[nq,k], internal row i64[nq,k]) device tensors.  With ``allow``
         (int64[ceil(ntotal / 64)], bit r & 63 of word r >> 6: row r takes part) only the allowed rows are
         searched: ``vrq_hamming_topk_filtered``, the counting scan, for every k up to VRQ_K_LARGE_MAX.
         ``engine`` ("auto", "mfma", "valu"; default None = the routes above): ``vrq_hamming_topk_batch``, the
-        counting scan on the named engine for every k up to VRQ_K_LARGE_MAX, with or without ``allow``."""
+        counting scan on the named engine for every k up to VRQ_K_LARGE_MAX, with or without ``allow``.
+        ``query_set`` (an int tensor [nq]) with a 2-D ``allow`` (``filters.row_bitmaps``: a bitmap per set): query
+        i is filtered by bitmap ``query_set[i]``, -1 meaning unfiltered and any other id outside the sets no row;
+        ``vrq_hamming_topk_perquery``, where ``engine=None`` means "auto"."""
         q = as_device_tensor(q, torch.uint8, self.device).reshape(-1, self.code_size)
         nq = q.shape[0]
         D = torch.empty((nq, k), dtype=torch.int32, device=self.device)
         R = torch.empty((nq, k), dtype=torch.int64, device=self.device)
         lib = N.load()
         n = self.ntotal
-        call = N.SearchCall("vrq_hamming_topk", k, 0, allow, engine, "BinaryIndexIDMap2.search")
-        if allow is not None:
-            from .filters import checked
-            allow = checked(allow, n, self.device)
+        call = N.SearchCall("vrq_hamming_topk", k, 0, allow, engine, "BinaryIndexIDMap2.search", query_set=query_set)
+        from .filters import checked_filter
+        allow, query_set = checked_filter(allow, query_set, n, nq, self.device)
         # more than 1024 neighbours, a bitmap or an engine: the counting scan, up to VRQ_K_LARGE_MAX
         ws = call.workspace(lib, n, self.code_size, nq, k, self.device)
         with torch.cuda.device(self.device):
             call(lib, (N.ptr(self.codes) if n else 0, n, self.code_size, 0, N.ptr(q), nq, k), (N.ptr(D), N.ptr(R)),
-                 allow if n else None, ws, self.device)
+                 allow if n else None, ws, self.device, query_set=query_set)
         return D, R
 
     def reconstruct(self, key) -> np.ndarray:

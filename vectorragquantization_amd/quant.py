@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .filters import checked as checked_bitmap
+from .filters import checked as checked_bitmap, checked_filter
 from .index import _device, as_device_tensor
 
 
@@ -88,7 +88,8 @@ def dequantize(mode: str, q, minmax=None, limit: float = 0.0, dim: int = None, d
 
 def vectordb_search(mode: str, codes: torch.Tensor, q: torch.Tensor, qf: torch.Tensor, qb: torch.Tensor, k: int = 10,
                     binary_oversample: int = 10, minmax: torch.Tensor = None, limit: float = 0.0,
-                    rescore_row: torch.Tensor = None, allow: torch.Tensor = None, engine: str = None):
+                    rescore_row: torch.Tensor = None, allow: torch.Tensor = None, engine: str = None,
+                    query_set: torch.Tensor = None):
     """``VectorDBInt{4,8,16}{,Global}.search`` for a query batch (e.g. VectorDBInt8Global.py:205-252):
     Phase I Hamming top-``k * binary_oversample`` over the ubinary codes (``vrq_hamming_topk``, FAISS
     order), Phase II ``float(np.dot(query_float, doc_emb))`` (``vrq_rescore_dequant``), Python's stable
@@ -101,6 +102,8 @@ def vectordb_search(mode: str, codes: torch.Tensor, q: torch.Tensor, qf: torch.T
     counting scan, for every K up to VRQ_K_LARGE_MAX), then the same rescoring.
     ``engine`` ("auto", "mfma", "valu"; default None = the routes above): Phase I through
     ``vrq_hamming_topk_batch``, the counting scan on the named engine, with or without ``allow``.
+    ``query_set`` (an int tensor [nq]) with a 2-D ``allow`` (``filters.row_bitmaps``): a bitmap per query
+    (-1: unfiltered), Phase I through ``vrq_hamming_topk_perquery``, where ``engine=None`` means "auto".
     Returns (rows i64[nq, k], hamming i32[nq, k], score f64[nq, k]) on the device; rows past the
     corpus are -1 (score NaN)."""
     dev = codes.device
@@ -111,12 +114,12 @@ def vectordb_search(mode: str, codes: torch.Tensor, q: torch.Tensor, qf: torch.T
     dist = torch.empty((nq, K), dtype=torch.int32, device=dev)
     rows = torch.empty((nq, K), dtype=torch.int64, device=dev)
     # more than 1024 candidates, a bitmap or an engine: the counting scan, up to VRQ_K_LARGE_MAX
-    call = N.SearchCall("vrq_hamming_topk", K, 0, allow, engine, "vectordb_search")
-    if allow is not None:
-        allow = checked_bitmap(allow, n, dev)
+    call = N.SearchCall("vrq_hamming_topk", K, 0, allow, engine, "vectordb_search", query_set=query_set)
+    allow, query_set = checked_filter(allow, query_set, n, nq, dev)
     ws = call.workspace(lib, n, cb, nq, K, dev)
     with torch.cuda.device(dev):
-        call(lib, (N.ptr(codes), n, cb, 0, N.ptr(qb), nq, K), (N.ptr(dist), N.ptr(rows)), allow, ws, dev)
+        call(lib, (N.ptr(codes), n, cb, 0, N.ptr(qb), nq, K), (N.ptr(dist), N.ptr(rows)), allow, ws, dev,
+             query_set=query_set)
     if mode == "bin16":
         kk = min(k, K)
         return rows[:, :kk], dist[:, :kk], dist[:, :kk].to(torch.float64)
@@ -144,7 +147,8 @@ _SEARCH2_MODES = {**_DEQ_MODES, "f32": N.VRQ_RESCORE_F32, "sbin": N.VRQ_RESCORE_
 
 def search2(mode: str, codes: torch.Tensor, q: torch.Tensor, qf: torch.Tensor, qb: torch.Tensor, k: int = 10,
             binary_oversample: int = 10, minmax: torch.Tensor = None, limit: float = 0.0,
-            rescore_row: torch.Tensor = None, flags: int = 0, allow: torch.Tensor = None, engine: str = None):
+            rescore_row: torch.Tensor = None, flags: int = 0, allow: torch.Tensor = None, engine: str = None,
+            query_set: torch.Tensor = None):
     """The two-phase search of ``vectordb_search`` as ONE fused call (``vrq_search2``: the Phase-I scan and
     a finish kernel that merges, rescores, sorts and cuts; ``CohereVectorDBBinary.py:215-239`` and the same
     loop of the ``VectorDBInt*`` classes).  ``mode`` is a ``vectordb_search`` rescoring mode (``int8g`` ...
@@ -154,7 +158,9 @@ def search2(mode: str, codes: torch.Tensor, q: torch.Tensor, qf: torch.Tensor, q
     kk = min(k, K); rows past the corpus are -1 (score NaN).  ``allow`` (``filters.row_bitmap``): Phase I over
     the allowed rows only, ``vrq_search2_filtered`` for every K up to VRQ_K_LARGE_MAX (no flags).
     ``engine`` ("auto", "mfma", "valu"; default None = the routes above): ``vrq_search2_batch``, the counting
-    scan on the named engine for every K up to VRQ_K_LARGE_MAX, with or without ``allow`` (no flags)."""
+    scan on the named engine for every K up to VRQ_K_LARGE_MAX, with or without ``allow`` (no flags).
+    ``query_set`` (an int tensor [nq]) with a 2-D ``allow`` (``filters.row_bitmaps``): a bitmap per query
+    (-1: unfiltered), ``vrq_search2_perquery``, where ``engine=None`` means "auto" (no flags)."""
     if mode not in _SEARCH2_MODES:
         raise ValueError(f"unknown search2 mode {mode!r}")
     dev = codes.device
@@ -174,19 +180,19 @@ def search2(mode: str, codes: torch.Tensor, q: torch.Tensor, qf: torch.Tensor, q
         # the ABI indexes q / minmax / rescore_row by candidate row and cannot see their lengths
         raise N.VrqNativeError(f"search2: {n} code rows but {None if q is None else q.shape[0]} stored rows")
     lib = N.load()
-    call = N.SearchCall("vrq_search2", K, flags, allow, engine, "search2")
+    call = N.SearchCall("vrq_search2", K, flags, allow, engine, "search2", query_set=query_set)
     if flags and call.name != "vrq_search2":  # the counting scan takes no scan flags
         why = f"engine={engine!r}" if call.engine is not None else \
             "a row filter" if allow is not None else f"K = {K} > {N.VRQ_K_MAX}"
         raise N.VrqNativeError(f"search2: flags {flags} with {why} ({call.name} takes none)")
-    if allow is not None:
-        allow = checked_bitmap(allow, n, dev)
+    allow, query_set = checked_filter(allow, query_set, n, nq, dev)
     count = torch.empty((nq,), dtype=torch.int32, device=dev)
     ws = call.workspace(lib, n, d, nq, K, dev)
     with torch.cuda.device(dev):
         call(lib, (_SEARCH2_MODES[mode], N.ptr(codes), N.ptr(q), N.ptr(minmax), float(limit), N.ptr(rescore_row), n,
                    d, 0, N.ptr(qf), N.ptr(qb), nq, kk, K, flags),
-             (N.ptr(count), N.ptr(rows), N.ptr(dist), N.ptr(score)), allow, ws, dev, f"{call.name}({mode})")
+             (N.ptr(count), N.ptr(rows), N.ptr(dist), N.ptr(score)), allow, ws, dev, f"{call.name}({mode})",
+             query_set=query_set)
     return rows, dist, score
 
 

@@ -51,7 +51,7 @@ import torch
 from . import _native as N
 from . import quant as Q
 from .docstore import DocStoreError, RocksDictReader, is_rocksdict_dir
-from .filters import ids_bitmap
+from .filters import class_filter, ids_bitmap
 from .index import BinaryIndexIDMap2, _GrowBuffer, as_device_tensor, torch_to_np
 
 logger = logging.getLogger(__name__)
@@ -304,29 +304,32 @@ class _QuantizedVectorDB:
 
     # -- search ------------------------------------------------------------------------
     def search_vectors(self, query, k: int = 10, binary_oversample: int = 10, compare_float32: bool = False,
-                       allowed_ids=None, engine=None):
+                       allowed_ids=None, engine=None, allowed_ids_per_query=None):
         """Batched search of query embeddings (f32[nq, d]; i16[nq, d] for VectorDBInt16) on the device.
         Returns (doc_id i64[nq, kk], row i64[nq, kk], hamming i32[nq, kk], score f64[nq, kk]) with
         kk = min(k, K); rows past the candidates are -1.  ``allowed_ids`` (None: all): only these documents
         are searched (Phase I through ``vrq_hamming_topk_filtered``); ids the index does not hold are ignored.
-        ``engine`` ("auto", "mfma", "valu"; default None): Phase I through ``vrq_hamming_topk_batch``."""
+        ``engine`` ("auto", "mfma", "valu"; default None): Phase I through ``vrq_hamming_topk_batch``.
+        ``allowed_ids_per_query`` (exclusive with ``allowed_ids``): a sequence of nq entries, each None
+        (unfiltered) or a collection of ids, one filter per query through the ``*_perquery`` call, where
+        ``engine=None`` means "auto"; an empty collection, or one of unknown ids, finds nothing."""
         n = self.index.ntotal
-        allow = ids_bitmap(self.index.id_map, allowed_ids) if allowed_ids is not None else None
         if k < 0 or binary_oversample < 0:
             raise ValueError("k and binary_oversample must be non-negative")
         qv = as_device_tensor(query, self.VEC_DTYPE, self.device).reshape(-1, self.embedding_dim)
         qb = self._codes(qv)["codes"]
+        allow, qset = class_filter(self.index.id_map, allowed_ids, allowed_ids_per_query, qv.shape[0])
         with torch.cuda.device(self.device):
             if self.HAMMING_ONLY:
                 rows, ham, sc = Q.vectordb_search("bin16", self.index.codes, None, None, qb, k, binary_oversample,
-                                                  allow=allow, engine=engine)
+                                                  allow=allow, engine=engine, query_set=qset)
             else:
                 mode = "f32" if compare_float32 else self.MODE
                 src = self._f.view() if compare_float32 else self._q.view()
                 rr = self.index.rescore_rows()
                 rows, ham, sc = Q.vectordb_search(mode, self.index.codes, src, qv, qb, k, binary_oversample,
                                                   self._mm.view() if self.LOCAL and not compare_float32 else None,
-                                                  self.limit, rr, allow, engine)
+                                                  self.limit, rr, allow, engine, qset)
                 if compare_float32:
                     self._check_float_rows(rows)
         ids = torch.where(rows >= 0, self.index.id_map[rows.clamp_min(0)], rows) if n else rows
