@@ -495,6 +495,49 @@ int vrq_flat_ip_topk_dim(const float* xf, const int8_t* x8, const double* inv_sc
                          size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Exhaustive int8-cosine top-k on the matrix cores at every supported embedding dim (additive to ABI
+ * version 1; vrq_gemm_topk_dim keeps running K5d with the flags it accepts).  K5md: K5's method -- one
+ * int8 query piece on v_mfma_i32_32x32x32_i8 within a proven per-query bound Delta, a sampled threshold,
+ * exact rescoring of the survivors (the scores of vrq_rescore_int8_cosine_dim, bit for bit), one retry
+ * at a raised threshold after a list overflow, an exact scan of every row for what is left -- with the
+ * k-loop length d / 32 a template axis.  Exact for every finite input; same outputs and order as
+ * vrq_gemm_topk_dim.
+ * vrq_gemm_topk_dim_mfma: the arguments of vrq_gemm_topk_dim.  Supported: mode VRQ_GEMM_INT8_COSINE, the
+ * dims of vrq_dim_supported (at 1024 it forwards to vrq_gemm_topk), 1 <= k <= 1024, 1 <= n < 2^32, finite
+ * queries.  VRQ_GEMM_BINARY returns VRQ_EUNSUPPORTED (it needs a bit-expansion path of its own off 1024),
+ * VRQ_GEMM_FLOAT_IP VRQ_EINVAL.  flags: 0, or a subset of VRQ_GEMM_STAGE_* under vrq_gemm_topk's ordering
+ * contract, optionally | VRQ_GEMM_NO_FALLBACK (queries the matrix path could not serve get out_count =
+ * -1); anything else VRQ_EUNSUPPORTED.
+ * vrq_gemm_topk_dim_mfma_workspace_size: bytes of workspace, 0 for an unsupported shape or mode (at 1024
+ * too: the size and plan calls answer for exactly the calls the entry point accepts).
+ * vrq_gemm_topk_dim_mfma_plan (host-only): info i64[8] as vrq_gemm_topk_plan = chunk rows, chunks, list
+ * capacity, query blocks, sample chunks, rows per sample chunk, workspace bytes, queries per block (512
+ * at d = 256, 256 at 384 .. 768, 128 at 1536 and 2048).
+ * vrq_gemm_topk_dim_mfma_prep_layout (host-only; off 1024): info i64[8] = byte offsets of Delta, alpha,
+ * beta (f64 [nq_pad] each, as vrq_gemm_topk_prep_layout), of the FINISH flags (i32 [nq]) and of the
+ * thresholds (f32 [nq_pad], u units), nq_pad, and the byte offsets of the list lengths (i32 [nq][chunks];
+ * a length above the capacity is an overflow) and of the lists (u32 [nq][chunks][capacity]).  The int8 pieces sit at offset 0 as i8 [nq_pad][dim] in
+ * natural dim order.  Delta = ||rho||_2 (1 + eps) + eps ||q/S||_2 with eps = 2^-20; hit rule of the MAIN
+ * pass: u = f32(<a, x>) * (1 / f32(norm)) >= thr.
+ * vrq_gemm_topk_dim_engine: the engine "auto" takes for a call shape, VRQ_GEMM_ENGINE_EXACT (K5d) or
+ * VRQ_GEMM_ENGINE_MFMA (K5md): K5md from a measured minimum batch per dim, K5d at nq = 1, for the modes
+ * K5md does not serve and at every dim that was not measured.  It answers "K5md or not": at dim 1024
+ * it reports VRQ_GEMM_ENGINE_EXACT although vrq_gemm_topk_dim forwards there to K5, so a caller that gets
+ * VRQ_GEMM_ENGINE_EXACT calls vrq_gemm_topk_dim with its usual flags (never adds VRQ_GEMM_SCAN_EXACT).
+ * ------------------------------------------------------------------------- */
+#define VRQ_GEMM_ENGINE_EXACT 0
+#define VRQ_GEMM_ENGINE_MFMA 1
+size_t vrq_gemm_topk_dim_mfma_workspace_size(int32_t mode, int64_t n, int32_t dim, int32_t nq, int32_t k);
+int vrq_gemm_topk_dim_mfma_plan(int32_t mode, int64_t n, int32_t dim, int32_t nq, int32_t k, int64_t* info);
+int vrq_gemm_topk_dim_mfma_prep_layout(int32_t mode, int64_t n, int32_t dim, int32_t nq, int32_t k,
+                                       int64_t* info);
+int vrq_gemm_topk_dim_mfma(int32_t mode, const uint8_t* codes, const int8_t* x8, const double* norms, int64_t n,
+                           int32_t dim, int64_t row_offset, const float* qf, int32_t nq, int32_t k, int32_t flags,
+                           int32_t* out_count, int64_t* out_rows, double* out_scores, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int vrq_gemm_topk_dim_engine(int32_t mode, int64_t n, int32_t dim, int32_t nq, int32_t k);
+
+/* ---------------------------------------------------------------------------
  * Search with more than 1024 Phase-I candidates (additive to ABI version 1; every function above keeps
  * its K <= 1024 contract and its VRQ_EUNSUPPORTED beyond it).  FAISS IndexBinaryFlat::search takes any k,
  * and K = min(k * binary_oversample, ntotal) passes 1024 at k = 103 with the default oversample of 10.

@@ -34,6 +34,8 @@ VRQ_GEMM_STAGE_MAIN = 32
 VRQ_GEMM_STAGE_FINISH = 64
 VRQ_GEMM_NO_FALLBACK = 128
 VRQ_GEMM_SCAN_EXACT = 256  # _dim entry points: the exact exhaustive scan (K5d) at dim 1024 too
+VRQ_GEMM_ENGINE_EXACT = 0  # vrq_gemm_topk_dim_engine: K5d
+VRQ_GEMM_ENGINE_MFMA = 1   # ... K5md (vrq_gemm_topk_dim_mfma)
 VRQ_RESCORE_F32 = 16  # vrq_rescore_dequant: compare_float32 rows
 VRQ_RESCORE_SIGNED_BINARY = 17  # vrq_rescore_dequant / vrq_search2: packed sign codes as +-1 rows
 VRQ_ENC_SIGNED_BINARY = 7
@@ -165,6 +167,12 @@ SIGNATURES = {
                                     _P]),
     "vrq_flat_ip_topk_dim": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I64, _P, _I32, _I32, _I32, _P, _P, _P, _P, _SZ,
                                        _P]),
+    "vrq_gemm_topk_dim_mfma_workspace_size": (_SZ, [_I32, _I64, _I32, _I32, _I32]),
+    "vrq_gemm_topk_dim_mfma_plan": (C.c_int, [_I32, _I64, _I32, _I32, _I32, _P]),
+    "vrq_gemm_topk_dim_mfma_prep_layout": (C.c_int, [_I32, _I64, _I32, _I32, _I32, _P]),
+    "vrq_gemm_topk_dim_mfma": (C.c_int, [_I32, _P, _P, _P, _I64, _I32, _I64, _P, _I32, _I32, _I32, _P, _P, _P, _P,
+                                         _SZ, _P]),
+    "vrq_gemm_topk_dim_engine": (C.c_int, [_I32, _I64, _I32, _I32, _I32]),
     "vrq_flat_ip_prepare": (C.c_int, [_P, _I64, _I32, _P, _P, _P, _P]),
     "vrq_flat_ip_topk": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I64, _P, _I32, _I32, _I32, _P, _P, _P, _P, _SZ,
                                    _P]),
@@ -250,6 +258,24 @@ def gemm_topk_dim_workspace(lib, mode: int, n: int, dim: int, nq: int, k: int, f
             return 0
         need = max(need, int(info[5]))
     return need
+
+
+def gemm_topk_dim_mfma_workspace(lib, mode: int, n: int, dim: int, nq: int, k: int) -> int:
+    """Workspace bytes of a vrq_gemm_topk_dim_mfma call (K5md; at dim 1024 the forwarded K5's); raises for a
+    shape or mode the matrix path does not serve."""
+    need = lib.vrq_gemm_topk_dim_mfma_workspace_size(mode, n, dim, nq, k)
+    if need == 0:
+        raise VrqNativeError(f"vrq_gemm_topk_dim_mfma: unsupported call mode={mode} n={n} dim={dim} nq={nq} k={k} "
+                             "(int8_cosine only; dims: vrq_dim_supported; k <= 1024)")
+    return need
+
+
+def gemm_topk_engine(lib, mode: int, n: int, dim: int, nq: int, k: int, engine):
+    """The engine a gemm_topk call runs: "auto" becomes "mfma" where vrq_gemm_topk_dim_engine picks K5md and None
+    (today's route: K5 at 1024, K5d elsewhere) where it does not; only an explicit "exact" forces the exact scan."""
+    if engine == "auto":
+        return "mfma" if lib.vrq_gemm_topk_dim_engine(mode, n, dim, nq, k) == VRQ_GEMM_ENGINE_MFMA else None
+    return engine
 
 
 def large_k(K: int, what: str) -> bool:

@@ -1,0 +1,956 @@
+// gemm_topk_dim.hip -- K5md: exhaustive int8-cosine (Phase-III) top-k of a query batch against the whole
+// corpus on the matrix cores (v_mfma_i32_32x32x32_i8) at the embedding dims other than 1024:
+// 256, 384, 512, 768, 1536, 2048.  Behind vrq_gemm_topk_dim_mfma; K5 (gemm_topk.hip) stays the d = 1024
+// pipeline and K5d (exhaustive_dim.hip) the exact f64 scan.
+//
+// The method is K5's (the header of gemm_topk.hip has the exactness argument): prep q/S = a + rho with one
+// int8 piece a; a dense sample pass keeps the running max of u = f32(<a, x>) * (1 / f32(norm)) per
+// (query, sample chunk, lane row); select takes U = the k-th largest maximum and thr = U - 2 Delta; the
+// main pass appends every row with u >= thr to a per-(query, chunk) list; finish rescores the lists by the
+// exact definition (exact_scores.h at run-time dim: the lane -> dims map and summation order of
+// phase3_cos_dim, so the scores are vrq_rescore_int8_cosine_dim's bit for bit), retries an overflowed
+// query once at the raised threshold alpha s_k + beta - Delta, and hands what is left to an exact scan.
+//
+// Delta = ||rho||_2 (1 + eps) + eps ||q/S||_2, eps = 2^-20.  Cauchy-Schwarz does not see d.  The f32 slack at
+// d = 2048: A = <a, x> is exact in i32 but |A| reaches 127 * 127 * 2048 > 2^24, so the roundings on the u
+// path are v_cvt_f32_i32 (2^-24; exact below 2^24, i.e. up to d = 1024), the norm's f64 -> f32 (2^-24),
+// v_rcp_f32 (1 ulp: 2^-23) and the product (2^-24; the main pass tests the sign of one fma instead):
+// (1 + 2^-24)^3 (1 + 2^-23) - 1 < 2^-21 relative to |u| <= ||a|| <= ||q/S|| + ||rho||.  The reference score
+// s' = s / S carries the f32 rounding of the dot: 2^-24 ||q/S||.  Sum < (2^-21 + 2^-24)(||q/S|| + ||rho||)
+// < eps (||q/S|| + ||rho||), which is what Delta adds to ||rho||.
+//
+// Matrix pass (k5md_pass_kernel<KS, DENSE>, KS = d / 32 k-steps): one workgroup per CU and query block;
+// the int8 A fragments of its queries for all of d stay in the accumulator file for the whole chunk;
+// 32-row tiles (32 d bytes + 32 f64 norms) stream HBM -> LDS by LDS-DMA in a ring of 2, in 1-KiB pieces
+// dealt round-robin to the waves and spread over the MFMA shadow; the threshold tests of tile t-1 run in
+// tile t's MFMA shadow and its hits reach a per-wave LDS stage in tile t+1, drained once per chunk.
+//   d <= 256     8 waves (two per SIMD) x 2 M-blocks of 32 queries: a B fragment feeds two MFMAs  (512 / WG)
+//   d = 384..768 8 waves x 32 queries                                                             (256 / WG)
+//   d >= 1536    4 waves (one per SIMD) x 32 queries, the 192 / 256 A registers in the AGPR half  (128 / WG)
+// LDS image of a tile: row rr at byte rr * d, its 16-byte chunk c at slot c ^ x(rr), where
+//   x(rr) = rr & 15        when d / 16 is a multiple of 16 (K5's rule),
+//   x(rr) = (rr >> 1) & 7  at d = 384 (24 chunks per row: the row stride is 8 slots mod 16, so the row's
+//                          parity picks the half and the XOR stays inside a group of 8 chunks).
+// The DMA applies x to its source address and writes LDS linearly.  A ds_read_b128 of B fragments (lane
+// (r, h) reads chunk 2s + h of row r) then finds 16 distinct slots mod 16 in each of its four 16-lane
+// groups at every dim (DESIGN section 5 "K5md" enumerates them).
+// A ragged last tile is shifted back to end at the chunk's end (rows already seen are masked), so every
+// DMA reads a whole in-bounds tile; a chunk shorter than 32 rows clamps its rows.  Every loop has a fixed
+// trip count and no workgroup waits on another.
+#include <math.h>
+
+#include "mfma_common.h"
+#include "vrq_internal.h"
+
+namespace vrq {
+namespace g5d {
+
+constexpr int GRT = 32;       // corpus rows per tile
+constexpr int STG = 1024;     // staged hit entries per wave (u32: query-in-wave << 26 | chunk row)
+constexpr int64_t kMaxChunkRows = (int64_t(1) << 26) - 32;
+constexpr int FIN_CAP = 8192, CAP_MULT = 16, kChunkMult = 4;  // K5's planning rules
+constexpr int64_t kMinSample = 32768, kMaxSample = 1 << 21;
+constexpr int KMAX5 = 1024, FB_BATCH = 1024, MAX_CHUNKS = 2048;
+constexpr int BA = 2, NR = 4;  // B fragments read BA k-steps ahead into a ring of NR
+
+__host__ __device__ constexpr int swz(int cpr, int rr) { return cpr % 16 == 0 ? (rr & 15) : ((rr >> 1) & 7); }
+
+template <int KS>
+struct Shape {
+  static constexpr int D = 32 * KS, CPR = D / 16;
+  static constexpr int W = KS > 32 ? 4 : 8;    // waves: two per SIMD while 32 queries' fragments fit beside them
+  static constexpr int MB = KS <= 8 ? 2 : 1;   // M-blocks of 32 queries per wave
+  static constexpr int QW = 32 * MB, QB = W * QW, NE = 16 * MB;
+  static constexpr int XB = CPR % 16 == 0 ? 4 : 3;  // chunk-index bits the swizzle touches
+  static constexpr int NA = 1 << (XB - 1);          // B addresses kept per lane (the rest: immediate offsets)
+  static constexpr int TB = GRT * D, PKT = TB + GRT * 8;  // tile bytes, ring slot bytes (+ norms)
+  static constexpr int PPW = (KS + W - 1) / W;      // 1-KiB row pieces per wave and tile (+ 1: the norms)
+  static constexpr int DS = (KS - 2) / (PPW + 1) > 0 ? (KS - 2) / (PPW + 1) : 1;  // k-steps between pieces
+  static constexpr int TPS = (NE + KS - 1) / KS;    // threshold tests per k-step
+  static constexpr int EOFF = KS >= 24 ? 4 : 0;
+};
+
+__device__ __forceinline__ v16i mfma_i8(const v4i& a, const v4i& b, const v16i& c) {
+  return __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ void lds_read_f64(double& d, uint32_t a) {
+  asm volatile("ds_read_b64 %0, %1" : "=v"(d) : "v"(a) : "memory");
+}
+template <int OFF>
+__device__ __forceinline__ void lds_read128_off(v4i& d, uint32_t a) {
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(a), "n"(OFF) : "memory");
+}
+// monotone u32 image of a float for ascending order; NaN -> 0 (below -inf)
+__device__ __forceinline__ uint32_t fkey(float u) {
+  const uint32_t b = __float_as_uint(u);
+  if ((b & 0x7fffffffu) > 0x7f800000u) return 0u;
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float fkey_inv(uint32_t k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+__device__ __forceinline__ double desc_key_inv(uint64_t key) {
+  const uint64_t a = ~key;
+  return __longlong_as_double((long long)((a & 0x8000000000000000ull) ? (a & 0x7fffffffffffffffull) : ~a));
+}
+// XCD-aware bijective block remap: consecutive logical blocks share one XCD's L2
+__device__ __forceinline__ int xcd_logical(int b, int nb) {
+  const int xcd = b & 7, slot = b >> 3, q8 = nb >> 3, r8 = nb & 7;
+  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot;
+}
+
+// ---------------------------------------------------------------------------------------------
+// prep: one wave per (padded) query.  qa[q] = the int8 piece a in natural dim order, d bytes;
+// delta[q] = Delta_q in u units; alpha[q] = 1 / S, beta[q] = 0 (s' = alpha s + beta).
+__global__ __launch_bounds__(256) void k5md_prep_kernel(const float* __restrict__ qf, int nq, int nq_pad, int dim,
+                                                        int8_t* __restrict__ qa, double* __restrict__ delta,
+                                                        double* __restrict__ alpha, double* __restrict__ beta) {
+  const int q = blockIdx.x * 4 + (threadIdx.x >> 6), l = lane_id();
+  if (q >= nq_pad) return;
+  int8_t* o = qa + (int64_t)q * dim;
+  if (q >= nq) {  // padding queries: zero pieces (their thresholds never accept)
+    for (int i = l; i < dim; i += WAVE) o[i] = 0;
+    if (l == 0) {
+      delta[q] = 0.0;
+      alpha[q] = 0.0;
+      beta[q] = 0.0;
+    }
+    return;
+  }
+  const float* qv = qf + (int64_t)q * dim;
+  float mx = 0.f;
+  for (int i = l; i < dim; i += WAVE) mx = fmaxf(mx, fabsf(qv[i]));
+#pragma unroll
+  for (int m = 1; m < WAVE; m <<= 1) mx = fmaxf(mx, __shfl_xor(mx, m, WAVE));
+  const double invS = mx > 0.f ? 127.0 / (double)mx : 1.0;
+  double r2 = 0.0, q2 = 0.0;
+  for (int i = l; i < dim; i += WAVE) {
+    const double x = (double)qv[i] * invS;
+    double a = rint(x);  // |a| <= 127
+    a = a > 127.0 ? 127.0 : (a < -127.0 ? -127.0 : a);
+    const double rho = x - a;  // exact, |rho| <= 1/2
+    r2 += rho * rho;
+    q2 += (double)qv[i] * (double)qv[i];
+    o[i] = (int8_t)a;
+  }
+  r2 = wave_sum_f64(r2);
+  q2 = wave_sum_f64(q2);
+  constexpr double SLACK = 1.0 / (1 << 20);  // the header's sum of roundings, < 2^-20
+  if (l == 0) {
+    delta[q] = sqrt(r2) * (1.0 + SLACK) + SLACK * sqrt(q2) * invS;
+    alpha[q] = invS;
+    beta[q] = 0.0;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The matrix pass.  DENSE = the sample pass (max of u over each lane row's rows of the chunk ->
+// dv[q][chunk * 32 + lane row]) else the thresholded pass (u >= thr[q] -> candidate lists).  Chunk c covers
+// rows [c * chunk_stride, + chunk_rows).  qbflag (retry pass): only query blocks holding a retried query.
+template <int KS, bool DENSE>
+__global__ __launch_bounds__(Shape<KS>::W * 64, 1) void k5md_pass_kernel(
+    const int8_t* __restrict__ x8, const double* __restrict__ norms, int64_t n, const int8_t* __restrict__ qa, int nq,
+    const float* __restrict__ thr, uint32_t* __restrict__ cand, int32_t* __restrict__ ccnt, int capc,
+    int64_t chunk_rows, int64_t chunk_stride, int nchunks, int nqb, float* __restrict__ dv, int64_t dv_stride,
+    const int32_t* __restrict__ qbflag) {
+  using S = Shape<KS>;
+  constexpr int D = S::D, CPR = S::CPR, W = S::W, MB = S::MB, QW = S::QW, NE = S::NE, NA = S::NA, XB = S::XB;
+  constexpr int TB = S::TB, PKT = S::PKT, PPW = S::PPW, DS = S::DS, TPS = S::TPS, EOFF = S::EOFF;
+  __shared__ __attribute__((aligned(16))) uint8_t smem[2 * PKT];
+  // per-(query, this chunk) list lengths (one row per wave), then each wave's hit stage
+  __shared__ int32_t lcnt[W * QW + (DENSE ? 0 : W * STG)];
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int l = lane_id(), r = l & 31, h = l >> 5;
+  const int L = xcd_logical(blockIdx.x, gridDim.x);
+  const int chunk = L / nqb, qb = L - chunk * nqb;
+  if (chunk >= nchunks) return;
+  if (qbflag && qbflag[qb] == 0) return;
+  const int64_t row0 = (int64_t)chunk * chunk_stride;
+  const int64_t row1 = (row0 + chunk_rows < n) ? row0 + chunk_rows : n;
+  if (row0 >= row1) return;
+  const int nrows = (int)(row1 - row0);
+  const int ntiles = (nrows + GRT - 1) / GRT;
+  const uint32_t sm0 = lds_addr(smem);
+
+  // tile t covers chunk rows [tstart(t), tstart(t) + 32): the last tile of a ragged chunk is shifted back
+  const bool tiny = nrows < GRT;
+  auto tstart = [&](int t) { return tiny ? 0 : (t * GRT < nrows - GRT ? t * GRT : nrows - GRT); };
+  auto lane_valid = [&](int t) { return tiny ? r < nrows : r >= t * GRT - tstart(t); };
+
+  // LDS-DMA: piece p = w + W i of a tile fills LDS bytes [1024 p, + 1024) of the slot; lane l's 16 bytes are
+  // slot g = 64 p + l = (tile row rr, slot-in-row cs), read from chunk cs ^ x(rr) of that row
+  uint32_t loff[PPW];
+#pragma unroll
+  for (int i = 0; i < PPW; ++i) {
+    const int g = (w + W * i) * 64 + l, rr = g / CPR, cs = g % CPR;
+    loff[i] = (uint32_t)(rr * D + ((cs ^ swz(CPR, rr)) << 4));
+  }
+  auto issue_piece = [&](int t, int slot_i, int i) {  // whole tiles; i == PPW: the tile's 32 norms
+    const int64_t tr0 = row0 + tstart(t);
+    uint8_t* slot = smem + slot_i * PKT;
+    // (pointer arguments through locals: a compound expression makes the host pass drop the launch stub)
+    if (i == PPW) {
+      const uint8_t* g = reinterpret_cast<const uint8_t*>(norms + tr0) + 4 * l;
+      uint8_t* ld = slot + TB;
+      __builtin_amdgcn_global_load_lds(g, (__attribute__((address_space(3))) void*)ld, 4, 0, 0);
+      return;
+    }
+    const int p = w + W * i;
+    if (p >= KS) return;
+    const uint8_t* g = reinterpret_cast<const uint8_t*>(x8) + tr0 * D + loff[i < PPW ? i : 0];
+    uint8_t* ld = slot + p * 1024;
+    __builtin_amdgcn_global_load_lds(g, (__attribute__((address_space(3))) void*)ld, 16, 0, 0);
+  };
+  auto issue_tiny = [&](int i) {  // the single tile of a chunk shorter than 32 rows: clamp rows
+    if (i == PPW) {
+      int64_t nr = row0 + (l >> 1);
+      nr = nr < row1 ? nr : row1 - 1;
+      const uint8_t* g = reinterpret_cast<const uint8_t*>(norms + nr) + 4 * (l & 1);
+      uint8_t* ld = smem + TB;
+      __builtin_amdgcn_global_load_lds(g, (__attribute__((address_space(3))) void*)ld, 4, 0, 0);
+      return;
+    }
+    const int p = w + W * i;
+    if (p >= KS) return;
+    const uint32_t lo = loff[i < PPW ? i : 0];
+    int64_t row = row0 + (int)(lo / D);
+    row = row < row1 ? row : row1 - 1;
+    const uint8_t* g = reinterpret_cast<const uint8_t*>(x8) + row * D + (lo % D);
+    uint8_t* ld = smem + p * 1024;
+    __builtin_amdgcn_global_load_lds(g, (__attribute__((address_space(3))) void*)ld, 16, 0, 0);
+  };
+  static_for<0, PPW + 1>([&](auto I) {
+    constexpr int i = decltype(I)::value;
+    if (tiny)
+      issue_tiny(i);
+    else
+      issue_piece(0, 0, i);
+  });
+
+  // A fragments of this wave's M-blocks of 32 queries, every k-step -> accumulator file
+  const int qbase = qb * S::QB + w * QW;
+  v4i A[MB][KS];
+#pragma unroll
+  for (int j = 0; j < MB; ++j) {
+    const int8_t* qp = qa + (int64_t)(qbase + 32 * j + r) * D + h * 16;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) A[j][s] = *reinterpret_cast<const v4i*>(qp + s * 32);
+  }
+#pragma unroll
+  for (int j = 0; j < MB; ++j)
+#pragma unroll
+    for (int s = 0; s < KS; ++s) asm volatile("" : "+a"(A[j][s]));
+  // test e of a lane: M-block e >> 4, accumulator register e & 15 -> query row of the wave
+  auto qrow = [&](int e) { return 32 * (e >> 4) + ((e & 3) + 8 * ((e >> 2) & 3) + 4 * h); };
+  float th[DENSE ? 1 : NE];
+  if constexpr (!DENSE) {
+#pragma unroll
+    for (int e = 0; e < NE; ++e) th[e] = thr[qbase + qrow(e)];
+    // landed before the tile loop (a wait for them inside it would also wait for the tile's DMA)
+#pragma unroll
+    for (int e = 0; e < NE; ++e) asm volatile("" : "+v"(th[e]));
+  }
+
+  // B fragment of k-step s for lane (r, h) = chunk 2s + h of tile row r: the swizzle touches the low XB
+  // bits of the chunk index (NA addresses per lane), the bits above are an immediate offset
+  uint32_t boff[NA];
+#pragma unroll
+  for (int j = 0; j < NA; ++j) boff[j] = (uint32_t)(r * D + (((2 * j + h) ^ swz(CPR, r)) << 4));
+
+  const uint32_t lc0 = lds_addr(lcnt + w * QW);
+  const uint32_t sg0 = lds_addr(lcnt + W * QW + (DENSE ? 0 : w * STG));  // this wave's hit stage
+  int nst = 0;                                                         // staged entries (wave-uniform)
+  if (!DENSE && l < QW) lcnt[w * QW + l] = 0;                          // visible after the first tile's barrier
+  v16i acc[2][MB] = {};                                                // [tile parity][M-block]
+  float ures[DENSE ? NE : 1];
+#pragma unroll
+  for (int e = 0; e < (DENSE ? NE : 1); ++e) ures[e] = __builtin_nanf("");
+  uint32_t hm = 0, hmd = 0;  // hit bits (bit e = test e) of the tile being tested / of the tile before it
+  float invc = 0.f, invp = 0.f;  // 1/||x|| of this lane's row of tiles t, t-1 (NaN: zero norm or a row seen before)
+  const v16i zero = {};
+  const int64_t qstride = (int64_t)nchunks * capc;
+
+  // hit of query-in-wave ql at chunk row cr -> its (query, chunk) list; a list past capc keeps counting,
+  // which the finish kernel reads as an overflow
+  auto to_list = [&](int ql, int cr) {
+    int pos;
+    lds_add_rtn32(pos, lc0 + (uint32_t)(ql * 4), 1);
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pos)::"memory");
+    if (pos < capc) cand[(int64_t)(qbase + ql) * qstride + (int64_t)chunk * capc + pos] = (uint32_t)(row0 + cr);
+  };
+  auto drain = [&]() {  // the staged entries -> lists (once per chunk, or when the stage is nearly full)
+    for (int i0 = 0; i0 < nst; i0 += 64) {
+      const int i = i0 + l;
+      int e = 0;
+      if (i < nst) lds_read32(e, sg0 + (uint32_t)(i * 4));
+      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(e)::"memory");
+      if (i < nst) to_list((int)((uint32_t)e >> 26), e & 0x3ffffff);
+    }
+    nst = 0;
+  };
+  auto flush = [&](int tt, uint32_t m) {  // hit bits of tile tt -> the stage
+    if (__ballot(m != 0) == 0) return;
+    const int lr = tstart(tt) + r;
+    if (!__ballot((m & (m - 1)) != 0)) {
+      // at most one hit per lane (the usual case): one staged entry per hit lane at its rank among them
+      const uint64_t lanes = __ballot(m != 0);
+      if (m) {
+        int pos = nst + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(lanes >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lanes, 0));
+        pos = pos < STG - 1 ? pos : STG - 1;  // (never binds: the stage drains above STG - 64)
+        lds_write32(sg0 + (uint32_t)(pos * 4), (int)(((uint32_t)qrow(__builtin_ctz(m)) << 26) | (uint32_t)lr));
+      }
+      nst += __popcll(lanes);
+      if (nst > STG - 64) drain();
+    } else {
+      for (int e = 0; e < NE; ++e)  // several hits in a lane: straight to the lists
+        if ((m >> e) & 1u) to_list(qrow(e), lr);
+    }
+  };
+  // u of test e from one tile's accumulators (NaN for rows without a score); the thresholded pass folds the
+  // threshold in (one fma: the sign of f32(A) * inv - thr, no rounding in between)
+  auto test = [&](const v16i (&a)[MB], int e, float inv) {
+    const float f = (float)a[e >> 4][e & 15];
+    if constexpr (DENSE)
+      ures[e] = fmaxf(ures[e], f * inv);
+    else
+      hm |= fmaf(f, inv, -th[e]) >= 0.f ? (1u << e) : 0u;
+  };
+
+  int sl = 0;  // t & 1
+  auto tile = [&](auto PAR, auto FIRST, int t) {
+    constexpr int p = decltype(PAR)::value;
+    constexpr bool first = decltype(FIRST)::value;  // tile 0: no previous tile to test
+    // tile t's DMA landed (this wave's part; the barrier covers the other waves'), and every wave is done
+    // reading the slot that tile t + 1 overwrites
+    wait_vm<0>();
+    barrier_all();
+    const uint32_t slot = sm0 + (uint32_t)(sl * PKT);
+    const bool dma = t + 1 < ntiles;
+    const int tn = dma ? t + 1 : t;
+    double nv = 0.0;
+    lds_read_f64(nv, slot + TB + (uint32_t)(r * 8));
+    uint32_t badr[NA];
+#pragma unroll
+    for (int j = 0; j < NA; ++j) badr[j] = slot + boff[j];
+    v4i ring[NR];
+    auto readB = [&](auto SS) {
+      constexpr int s = decltype(SS)::value;
+      lds_read128_off<(s >> (XB - 1)) * (16 << XB)>(ring[s & (NR - 1)], badr[s & (NA - 1)]);
+    };
+    static_for<0, BA>([&](auto SS) { readB(SS); });
+    VRQ_SCHED_FENCE();
+    static_for<0, KS>([&](auto SS) {
+      constexpr int s = decltype(SS)::value;
+      if constexpr (s + BA < KS) {
+        readB(std::integral_constant<int, s + BA>{});
+        // all but the BA newest LDS operations are complete: B(s), and the norm (issued before B(0))
+        asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(ring[s & (NR - 1)]), "+v"(nv) : "n"(BA) : "memory");
+      } else {
+        asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(ring[s & (NR - 1)]) : "n"(KS - 1 - s) : "memory");
+      }
+#pragma unroll
+      for (int j = 0; j < MB; ++j) acc[p][j] = mfma_i8(A[j][s], ring[s & (NR - 1)], s == 0 ? zero : acc[p][j]);
+#pragma unroll
+      for (int j = 0; j < MB; ++j) asm volatile("" : "+v"(acc[p][j]));
+      if constexpr (s == 1 && !DENSE) {
+        if (t >= 2) flush(t - 2, hmd);
+        VRQ_SCHED_FENCE();
+      }
+      // DMA of tile t + 1, spread over the MFMA shadow
+      if constexpr (s >= 2 && (s - 2) % DS == 0 && (s - 2) / DS <= PPW)
+        if (dma) issue_piece(tn, sl ^ 1, (s - 2) / DS);
+      // threshold tests / dense values of tile t-1
+      if constexpr (!first && s >= EOFF && (s - EOFF) * TPS < NE) {
+#pragma unroll
+        for (int e = (s - EOFF) * TPS; e < (s - EOFF + 1) * TPS && e < NE; ++e) {
+          test(acc[p ^ 1], e, invp);
+          // pin the test at this k-step (IR-level sinking would gather them behind the last MFMA)
+          if constexpr (DENSE)
+            asm volatile("" : "+v"(ures[e]));
+          else
+            asm volatile("" : "+v"(hm));
+        }
+      }
+      if constexpr (s == KS / 2) {  // 1/||x|| of this tile's row r (branch-free)
+        const float rc = __builtin_amdgcn_rcpf((float)nv);
+        invc = ((nv > 0.0) & lane_valid(t)) ? rc : __builtin_nanf("");
+      }
+      VRQ_SCHED_FENCE();
+    });
+    invp = invc;
+    hmd = hm;
+    hm = 0;
+    sl ^= 1;
+  };
+
+  using I0 = std::integral_constant<int, 0>;
+  using I1 = std::integral_constant<int, 1>;
+  using NOTFIRST = std::integral_constant<bool, false>;
+  tile(I0{}, std::integral_constant<bool, true>{}, 0);
+  int t = 1;
+  for (; t + 1 < ntiles; t += 2) {
+    tile(I1{}, NOTFIRST{}, t);
+    tile(I0{}, NOTFIRST{}, t + 1);
+  }
+  if (t < ntiles) tile(I1{}, NOTFIRST{}, t);
+  wait_vm<0>();
+  // tile ntiles-2 (tested during the last tile), then the last tile itself
+  if (!DENSE && ntiles >= 2) flush(ntiles - 2, hmd);
+  const int pl = (ntiles - 1) & 1;
+#pragma unroll
+  for (int e = 0; e < NE; ++e) {
+    if (pl)
+      test(acc[1], e, invp);
+    else
+      test(acc[0], e, invp);
+  }
+  if constexpr (DENSE) {  // the lane maxima of the chunk -> dv[q][chunk * 32 + r]
+#pragma unroll
+    for (int e = 0; e < NE; ++e) {
+      const int q = qbase + qrow(e);
+      if (q < nq) dv[(int64_t)q * dv_stride + (int64_t)chunk * GRT + r] = ures[e];
+    }
+  } else {
+    flush(ntiles - 1, hm);
+    drain();
+    wait_lgkm0();
+    if (l < QW && qbase + l < nq) ccnt[(int64_t)(qbase + l) * nchunks + chunk] = lcnt[w * QW + l];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// select (K5's gemm_select_kernel): per query, U = k-th largest valid value of dv (nsc sample chunks of 32
+// lane maxima; 3-pass radix select on the monotone key), thr = U - 2 Delta rounded down (-inf when the
+// sample holds fewer than k finite values); zeroes the query's list lengths.  Padding queries: thr = +inf.
+__global__ __launch_bounds__(256) void k5md_select_kernel(const float* __restrict__ dv, int64_t dv_stride,
+                                                          int64_t sstride, int nsc, int64_t n, int k,
+                                                          const double* __restrict__ delta, float* __restrict__ thr,
+                                                          int32_t* __restrict__ ccnt, int nchunks, int nq,
+                                                          int32_t* __restrict__ qbflag, int nqb) {
+  __shared__ uint32_t hist[2048];
+  __shared__ uint32_t res[3];
+  const int q = blockIdx.x, tid = threadIdx.x;
+  if (q == 0)
+    for (int i = tid; i < nqb; i += 256) qbflag[i] = 0;
+  if (q >= nq) {
+    if (tid == 0) thr[q] = __builtin_inff();
+    return;
+  }
+  for (int i = tid; i < nchunks; i += 256) ccnt[(int64_t)q * nchunks + i] = 0;
+  const float* d = dv + (int64_t)q * dv_stride;
+  uint32_t prefix = 0, pmask = 0;
+  int kk = k;
+  bool ok = true;
+  constexpr int SH[3] = {21, 10, 0}, NBITS[3] = {11, 11, 10};
+  for (int pass = 0; pass < 3 && ok; ++pass) {
+    const int sh = SH[pass];
+    const uint32_t dm = (1u << NBITS[pass]) - 1;
+    for (int i = tid; i < 2048; i += 256) hist[i] = 0;
+    __syncthreads();
+    for (int c = 0; c < nsc; ++c) {
+      const int64_t rb = (int64_t)c * sstride;
+      const int64_t len = (rb + GRT <= n) ? GRT : (n > rb ? n - rb : 0);
+      if (tid < len) {
+        const uint32_t key = fkey(d[(int64_t)c * GRT + tid]);
+        if ((key & pmask) == prefix) atomicAdd(&hist[(key >> sh) & dm], 1u);
+      }
+    }
+    __syncthreads();
+    if (tid < 64) {  // top-down search: lane L owns bins [32L, 32L + 32)
+      uint32_t loc = 0;
+      for (int i = 0; i < 32; ++i) loc += hist[tid * 32 + i];
+      uint32_t suf = loc;  // inclusive suffix sum over lanes >= tid
+      for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_down(suf, o, 64);
+        if (tid + o < 64) suf += y;
+      }
+      uint32_t above = suf - loc;
+      int found = -1;
+      uint32_t abv = 0;
+      for (int i = 31; i >= 0; --i) {
+        const uint32_t hc = hist[tid * 32 + i];
+        if (above < (uint32_t)kk && above + hc >= (uint32_t)kk) {
+          found = tid * 32 + i;
+          abv = above;
+        }
+        above += hc;
+      }
+      const uint64_t bal = __ballot(found >= 0);
+      if (tid == 0) res[0] = bal ? 1u : 0u;
+      if (found >= 0) {
+        res[1] = (uint32_t)found;
+        res[2] = abv;
+      }
+    }
+    __syncthreads();
+    if (!res[0]) {
+      ok = false;
+    } else {
+      kk -= (int)res[2];
+      prefix |= res[1] << sh;
+      pmask |= dm << sh;
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    float t = -__builtin_inff();
+    if (ok && prefix != 0u) t = __double2float_rd((double)fkey_inv(prefix) - 2.0 * delta[q]);
+    thr[q] = t;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// exact (score desc, row asc) pair sort in LDS: ascending (key, row), key = desc_key_f64(score)
+__device__ inline void sort_pairs(uint64_t* key, uint32_t* row, int n_pow2) {
+  for (int size = 2; size <= n_pow2; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      __syncthreads();
+      for (int i = threadIdx.x; i < (n_pow2 >> 1); i += blockDim.x) {
+        const int lo = ((i / stride) * stride * 2) + (i % stride), hi = lo + stride;
+        const bool up = (lo & size) == 0;
+        const uint64_t ka = key[lo], kb = key[hi];
+        const uint32_t ra = row[lo], rb = row[hi];
+        const bool gt = ka > kb || (ka == kb && ra > rb);
+        if (gt == up) {
+          key[lo] = kb;
+          key[hi] = ka;
+          row[lo] = rb;
+          row[hi] = ra;
+        }
+      }
+    }
+  }
+  __syncthreads();
+}
+
+// The reference score of one row, one wave: phase3_cos_dim's lane -> dims map and order (lane l takes dims
+// 2l, 2l+1 of every 128-dim block; exact products, f64 sum, one rounding to f32, f64 division), with the
+// query read from LDS.
+__device__ __forceinline__ double cos_row(const float* qs, const int8_t* __restrict__ xrow, double nrm, int dim) {
+  double s = 0.0;
+  for (int d = 2 * lane_id(); d < dim; d += 2 * WAVE) {
+    const char2 x = *reinterpret_cast<const char2*>(xrow + d);
+    const float2 qq = *reinterpret_cast<const float2*>(qs + d);
+    s += (double)qq.x * (double)x.x;
+    s += (double)qq.y * (double)x.y;
+  }
+  s = wave_sum_f64(s);
+  const float f = (float)s;
+  return nrm == 0.0 ? -__builtin_inf() : (double)f / nrm;
+}
+
+constexpr int FIN_NT = 512, FIN_NW = FIN_NT / WAVE;
+struct FinShared {
+  uint64_t key[KMAX5 + FB_BATCH];
+  uint32_t row[KMAX5 + FB_BATCH];
+  float q[2048];
+  int32_t pre[MAX_CHUNKS + 1];  // exclusive prefix of the (capped) list lengths
+  int32_t fill, over;
+};
+
+// Running exact top-k over candidate rows row_at(j), j < count, one wave per row: a row enters the LDS sort
+// only if it beats the current k-th by (score desc, row asc).  key/row[0..kc) hold the list in order.  All
+// threads call it; returns kc = min(k, count).
+template <class RowAt>
+__device__ int running_topk(int64_t count, RowAt row_at, const int8_t* __restrict__ x8,
+                            const double* __restrict__ norms, int dim, int k, FinShared& sh) {
+  const int tid = threadIdx.x, l = lane_id(), w = tid >> 6;
+  if (tid == 0) sh.fill = 0;
+  int kc = 0;
+  __syncthreads();
+  for (int64_t base = 0; base < count; base += FB_BATCH) {
+    const uint64_t kk = kc == k ? sh.key[k - 1] : KEY_NONE;
+    const uint32_t kr = kc == k ? sh.row[k - 1] : 0xffffffffu;
+    const int64_t end = base + FB_BATCH < count ? base + FB_BATCH : count;
+    for (int64_t j = base + w; j < end; j += FIN_NW) {
+      const uint32_t rr = row_at(j);
+      const uint64_t key_r = desc_key_f64(cos_row(sh.q, x8 + (int64_t)rr * dim, norms[rr], dim));
+      if ((kc < k || key_r < kk || (key_r == kk && rr < kr)) && l == 0) {
+        const int i = kc + atomicAdd(&sh.fill, 1);
+        sh.key[i] = key_r;
+        sh.row[i] = rr;
+      }
+    }
+    __syncthreads();
+    const int f = sh.fill;
+    if (f > 0) {
+      const int tot = kc + f, np2 = next_pow2(tot);
+      for (int i = tot + tid; i < np2; i += FIN_NT) {
+        sh.key[i] = KEY_NONE;
+        sh.row[i] = 0xffffffffu;
+      }
+      sort_pairs(sh.key, sh.row, np2);
+      kc = tot < k ? tot : k;
+    }
+    __syncthreads();
+    if (tid == 0) sh.fill = 0;
+    __syncthreads();
+  }
+  return kc;
+}
+
+__device__ __forceinline__ void write_result(int q, int k, int kc, int64_t row_offset, const FinShared& sh,
+                                             int32_t* out_count, int64_t* out_rows, double* out_scores) {
+  for (int i = threadIdx.x; i < k; i += FIN_NT) {
+    const int64_t o = (int64_t)q * k + i;
+    out_rows[o] = i < kc ? (int64_t)sh.row[i] + row_offset : -1;
+    out_scores[o] = i < kc ? desc_key_inv(sh.key[i]) : __builtin_nan("");
+  }
+  if (threadIdx.x == 0) out_count[q] = kc;
+}
+
+// finish (K5's contract): the query's lists -> exact scores -> running top-k, with fb_flag: 0 = served,
+// 2 = retry (a list overflowed with >= min(k, n) candidates recorded: the recorded k-th score s_k bounds the
+// true one from below, so thr = alpha s_k + beta - Delta keeps every row of the exact top-k), 1 = exact scan
+// (fewer than min(k, n) candidates, or an overflow in the retry pass).  RETRY serves the retried queries.
+template <bool RETRY>
+__global__ __launch_bounds__(FIN_NT) void k5md_finish_kernel(
+    const int8_t* __restrict__ x8, const double* __restrict__ norms, int64_t n, int dim, int64_t row_offset,
+    const float* __restrict__ qf, int k, const uint32_t* __restrict__ cand, const int32_t* __restrict__ ccnt,
+    int nchunks, int capc, int qpb, int32_t* __restrict__ out_count, int64_t* __restrict__ out_rows,
+    double* __restrict__ out_scores, int32_t* __restrict__ fb_flag, float* __restrict__ thr,
+    const double* __restrict__ alpha, const double* __restrict__ beta, const double* __restrict__ delta,
+    int32_t* __restrict__ qbflag) {
+  __shared__ FinShared sh;
+  const int q = blockIdx.x, tid = threadIdx.x;
+  if (RETRY && fb_flag[q] != 2) return;
+  if (tid == 0) sh.over = 0;
+  __syncthreads();
+  const int32_t* cq = ccnt + (int64_t)q * nchunks;
+  for (int c = tid; c < nchunks; c += FIN_NT) {
+    const int x = cq[c];
+    if (x > capc) sh.over = 1;
+    sh.pre[c + 1] = x < capc ? x : capc;
+  }
+  for (int i = tid; i < dim; i += FIN_NT) sh.q[i] = qf[(int64_t)q * dim + i];
+  __syncthreads();
+  if (tid < WAVE) {  // inclusive scan of pre[1 .. nchunks] by one wave: 32 entries per lane, then the lanes
+    constexpr int PER = MAX_CHUNKS / WAVE;
+    int part = 0;
+    for (int i = 0; i < PER; ++i) {
+      const int c = tid * PER + i;
+      if (c < nchunks) part += sh.pre[c + 1];
+    }
+    int incl = part;
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+      const int y = __shfl_up(incl, d, WAVE);
+      if (tid >= d) incl += y;
+    }
+    int run = incl - part;
+    for (int i = 0; i < PER; ++i) {
+      const int c = tid * PER + i;
+      if (c < nchunks) {
+        run += sh.pre[c + 1];
+        sh.pre[c + 1] = run;
+      }
+    }
+    if (tid == 0) sh.pre[0] = 0;
+  }
+  __syncthreads();
+  const int total = sh.pre[nchunks];
+  const int need = (int)((int64_t)k < n ? k : n);
+  const bool over = sh.over != 0;
+  if (total < need || (RETRY && over)) {
+    if (tid == 0) {
+      fb_flag[q] = 1;
+      thr[q] = __builtin_inff();
+    }
+    return;
+  }
+  const uint32_t* Cq = cand + (int64_t)q * nchunks * capc;
+  auto row_at = [&](int64_t j) {  // candidate j of the concatenated lists (binary search by chunk)
+    int lo = 0, hi = nchunks - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (sh.pre[mid] <= j)
+        lo = mid;
+      else
+        hi = mid - 1;
+    }
+    return Cq[(int64_t)lo * capc + (j - sh.pre[lo])];
+  };
+  const int kc = running_topk(total, row_at, x8, norms, dim, k, sh);
+  if (!RETRY && over) {
+    if (tid == 0) {
+      const double t2 = alpha[q] * desc_key_inv(sh.key[kc - 1]) + beta[q] - delta[q];
+      thr[q] = __double2float_rd(t2 - 1e-9 * fabs(t2));
+      fb_flag[q] = 2;
+      atomicOr(&qbflag[q / qpb], 1);
+    }
+    return;
+  }
+  write_result(q, k, kc, row_offset, sh, out_count, out_rows, out_scores);
+  if (tid == 0) {
+    fb_flag[q] = 0;
+    thr[q] = __builtin_inff();
+  }
+}
+
+// the exact scan of the flagged queries (heavy ties, zero-norm rows): one workgroup per flagged query scores
+// every row; skip (VRQ_GEMM_NO_FALLBACK) reports the query as unserved instead
+__global__ __launch_bounds__(FIN_NT) void k5md_fallback_kernel(
+    const int8_t* __restrict__ x8, const double* __restrict__ norms, int64_t n, int dim, int64_t row_offset,
+    const float* __restrict__ qf, int k, int32_t* __restrict__ out_count, int64_t* __restrict__ out_rows,
+    double* __restrict__ out_scores, const int32_t* __restrict__ fb_flag, bool skip) {
+  __shared__ FinShared sh;
+  const int q = blockIdx.x, tid = threadIdx.x;
+  if (fb_flag[q] != 1) return;
+  if (skip) {
+    for (int i = tid; i < k; i += FIN_NT) {
+      out_rows[(int64_t)q * k + i] = -1;
+      out_scores[(int64_t)q * k + i] = __builtin_nan("");
+    }
+    if (tid == 0) out_count[q] = -1;
+    return;
+  }
+  for (int i = tid; i < dim; i += FIN_NT) sh.q[i] = qf[(int64_t)q * dim + i];
+  __syncthreads();
+  const int kc = running_topk(n, [](int64_t j) { return (uint32_t)j; }, x8, norms, dim, k, sh);
+  write_result(q, k, kc, row_offset, sh, out_count, out_rows, out_scores);
+}
+
+// ---------------------------------------------------------------------------------------------
+struct Plan {
+  int qpb, nqb, nq_pad;  // queries per block (by dim), query blocks, padded queries
+  int64_t scr, sstride, scols;
+  int nsc;
+  int64_t chunk_rows;
+  int nchunks, capc;
+  size_t off_delta, off_alpha, off_beta, off_qbf, off_thr, off_flag, off_cnt, off_cand, off_dv, bytes;
+};
+
+__host__ inline int queries_per_block(int dim) {
+  switch (dim) {
+    case 256: return Shape<8>::QB;
+    case 384: return Shape<12>::QB;
+    case 512: return Shape<16>::QB;
+    case 768: return Shape<24>::QB;
+    case 1536: return Shape<48>::QB;
+    case 2048: return Shape<64>::QB;
+    default: return 0;
+  }
+}
+
+// K5's planning rules (gemm_plan) with the query block a function of dim
+__host__ inline int plan(int mode, int64_t n, int dim, int nq, int k, Plan* p) {
+  if (mode == VRQ_GEMM_FLOAT_IP) return VRQ_EINVAL;
+  if (mode != VRQ_GEMM_INT8_COSINE) return VRQ_EUNSUPPORTED;
+  p->qpb = queries_per_block(dim);
+  if (p->qpb == 0 || n < 1 || n >= (int64_t(1) << 32) || nq < 1 || k < 1 || k > KMAX5) return VRQ_EUNSUPPORTED;
+  p->nqb = (nq + p->qpb - 1) / p->qpb;
+  p->nq_pad = p->nqb * p->qpb;
+  const int want1 = 256 / p->nqb > 0 ? 256 / p->nqb : 1;  // one workgroup per CU and query block
+  const int want = want1 * kChunkMult;
+  int64_t S = (int64_t)((double)CAP_MULT * (double)k * (double)n / (double)FIN_CAP);
+  if (S < kMinSample) S = kMinSample;
+  if (S > kMaxSample) S = kMaxSample;
+  if (S > n) S = n;
+  int64_t nsc = want1 > (2 * (int64_t)k + GRT - 1) / GRT ? want1 : (2 * (int64_t)k + GRT - 1) / GRT;
+  const int64_t scr = ((S + nsc - 1) / nsc + GRT - 1) / GRT * GRT;
+  nsc = (S + scr - 1) / scr;
+  p->scr = scr;
+  p->nsc = (int)nsc;
+  p->sstride = n / nsc >= scr ? n / nsc : scr;  // chunks never overlap; the last may be cut at n
+  p->scols = nsc * GRT;
+  int64_t cr = (n + want - 1) / want;
+  cr = (cr + GRT - 1) / GRT * GRT;
+  if ((n + cr - 1) / cr > MAX_CHUNKS) cr = ((n + MAX_CHUNKS - 1) / MAX_CHUNKS + GRT - 1) / GRT * GRT;
+  if (cr > kMaxChunkRows) cr = kMaxChunkRows;
+  p->chunk_rows = cr;
+  p->nchunks = (int)((n + cr - 1) / cr);
+  const int64_t expect = ((int64_t)k * cr + S - 1) / S;
+  int capc = 64;
+  while (capc < CAP_MULT * expect && capc < 4096) capc <<= 1;
+  while (capc < 512 && (double)nq * p->nchunks * (2 * capc) * sizeof(uint32_t) <= (double)(1 << 30)) capc <<= 1;
+  p->capc = capc;
+  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
+  p->off_delta = al((size_t)p->nq_pad * dim);
+  p->off_alpha = p->off_delta + al((size_t)p->nq_pad * sizeof(double));
+  p->off_beta = p->off_alpha + al((size_t)p->nq_pad * sizeof(double));
+  p->off_qbf = p->off_beta + al((size_t)p->nq_pad * sizeof(double));
+  p->off_thr = p->off_qbf + al((size_t)p->nqb * sizeof(int32_t));
+  p->off_flag = p->off_thr + al((size_t)p->nq_pad * sizeof(float));
+  p->off_cnt = p->off_flag + al((size_t)nq * sizeof(int32_t));
+  p->off_cand = p->off_cnt + al((size_t)nq * p->nchunks * sizeof(int32_t));
+  p->off_dv = p->off_cand + al((size_t)nq * p->nchunks * p->capc * sizeof(uint32_t));
+  p->bytes = p->off_dv + al((size_t)nq * p->scols * sizeof(float));
+  return VRQ_OK;
+}
+
+struct Call {
+  const int8_t* x8;
+  const double* norms;
+  int64_t n;
+  const int8_t* qa;
+  int nq;
+  float* thr;
+  uint32_t* cand;
+  int32_t* cnt;
+  float* dv;
+  int32_t* qbf;
+  hipStream_t s;
+};
+
+template <int KS>
+static void launch_pass(const Plan& p, const Call& c, int pass) {  // 0 sample, 1 main, 2 retry
+  const dim3 blk(Shape<KS>::W * 64);
+  if (pass == 0)
+    hipLaunchKernelGGL((k5md_pass_kernel<KS, true>), dim3(p.nsc * p.nqb), blk, 0, c.s, c.x8, c.norms, c.n, c.qa, c.nq,
+                       (const float*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr, 0, p.scr, p.sstride, p.nsc,
+                       p.nqb, c.dv, p.scols, (const int32_t*)nullptr);
+  else
+    hipLaunchKernelGGL((k5md_pass_kernel<KS, false>), dim3(p.nchunks * p.nqb), blk, 0, c.s, c.x8, c.norms, c.n, c.qa,
+                       c.nq, (const float*)c.thr, c.cand, c.cnt, p.capc, p.chunk_rows, p.chunk_rows, p.nchunks, p.nqb,
+                       (float*)nullptr, (int64_t)0, pass == 2 ? (const int32_t*)c.qbf : (const int32_t*)nullptr);
+}
+
+static int launch_pass_dim(int dim, const Plan& p, const Call& c, int pass) {
+  switch (dim) {
+    case 256: launch_pass<8>(p, c, pass); break;
+    case 384: launch_pass<12>(p, c, pass); break;
+    case 512: launch_pass<16>(p, c, pass); break;
+    case 768: launch_pass<24>(p, c, pass); break;
+    case 1536: launch_pass<48>(p, c, pass); break;
+    case 2048: launch_pass<64>(p, c, pass); break;
+    default: return VRQ_EUNSUPPORTED;
+  }
+  VRQ_LAUNCH_CHECK();
+  return VRQ_OK;
+}
+
+static int run(const int8_t* x8, const double* norms, int64_t n, int dim, int64_t row_offset, const float* qf, int nq,
+               int k, int flags, int32_t* out_count, int64_t* out_rows, double* out_scores, void* workspace,
+               size_t workspace_bytes, hipStream_t s) {
+  Plan p;
+  const int rc = plan(VRQ_GEMM_INT8_COSINE, n, dim, nq, k, &p);
+  if (rc != VRQ_OK) return rc;
+  if (workspace_bytes < p.bytes) return VRQ_EWORKSPACE;
+  constexpr int ALL = VRQ_GEMM_STAGE_SAMPLE | VRQ_GEMM_STAGE_MAIN | VRQ_GEMM_STAGE_FINISH;
+  const int st = (flags & ALL) ? (flags & ALL) : ALL;
+  uint8_t* ws = (uint8_t*)workspace;
+  int8_t* qa = (int8_t*)ws;
+  double* delta = (double*)(ws + p.off_delta);
+  double* alpha = (double*)(ws + p.off_alpha);
+  double* beta = (double*)(ws + p.off_beta);
+  int32_t* flag = (int32_t*)(ws + p.off_flag);
+  const Call c{x8, norms, n, qa, nq, (float*)(ws + p.off_thr), (uint32_t*)(ws + p.off_cand),
+               (int32_t*)(ws + p.off_cnt), (float*)(ws + p.off_dv), (int32_t*)(ws + p.off_qbf), s};
+  if (st & VRQ_GEMM_STAGE_SAMPLE) {
+    hipLaunchKernelGGL(k5md_prep_kernel, dim3((p.nq_pad + 3) / 4), dim3(256), 0, s, qf, nq, p.nq_pad, dim, qa, delta,
+                       alpha, beta);
+    VRQ_LAUNCH_CHECK();
+    const int r0 = launch_pass_dim(dim, p, c, 0);
+    if (r0 != VRQ_OK) return r0;
+    hipLaunchKernelGGL(k5md_select_kernel, dim3(p.nq_pad), dim3(256), 0, s, (const float*)c.dv, p.scols, p.sstride,
+                       p.nsc, n, k, (const double*)delta, c.thr, c.cnt, p.nchunks, nq, c.qbf, p.nqb);
+    VRQ_LAUNCH_CHECK();
+  }
+  if (st & VRQ_GEMM_STAGE_MAIN) {
+    const int r1 = launch_pass_dim(dim, p, c, 1);
+    if (r1 != VRQ_OK) return r1;
+  }
+  if (st & VRQ_GEMM_STAGE_FINISH) {
+    // finish -> retry main pass (query blocks with a retried query) -> finish of the retried queries ->
+    // exact scan of the rest
+    hipLaunchKernelGGL(k5md_finish_kernel<false>, dim3(nq), dim3(FIN_NT), 0, s, x8, norms, n, dim, row_offset, qf, k,
+                       (const uint32_t*)c.cand, (const int32_t*)c.cnt, p.nchunks, p.capc, p.qpb, out_count, out_rows,
+                       out_scores, flag, c.thr, (const double*)alpha, (const double*)beta, (const double*)delta, c.qbf);
+    VRQ_LAUNCH_CHECK();
+    const int r2 = launch_pass_dim(dim, p, c, 2);
+    if (r2 != VRQ_OK) return r2;
+    hipLaunchKernelGGL(k5md_finish_kernel<true>, dim3(nq), dim3(FIN_NT), 0, s, x8, norms, n, dim, row_offset, qf, k,
+                       (const uint32_t*)c.cand, (const int32_t*)c.cnt, p.nchunks, p.capc, p.qpb, out_count, out_rows,
+                       out_scores, flag, c.thr, (const double*)alpha, (const double*)beta, (const double*)delta, c.qbf);
+    VRQ_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k5md_fallback_kernel, dim3(nq), dim3(FIN_NT), 0, s, x8, norms, n, dim, row_offset, qf, k,
+                       out_count, out_rows, out_scores, (const int32_t*)flag, (flags & VRQ_GEMM_NO_FALLBACK) != 0);
+    VRQ_LAUNCH_CHECK();
+  }
+  return VRQ_OK;
+}
+
+// "auto": the smallest batch from which K5md beat K5d by more than the run-to-run spread at that dim
+// (profiles/exhaustive_mfma_bench.jsonl; measured at nq = 1, 8, 64, 1024); 0 = not measured, stays on K5d
+__host__ inline int min_batch(int dim) {
+  switch (dim) {
+    case 256: case 384: case 512: case 768: return 8;  // 1.08x-1.57x at nq = 8, 0.24x-0.27x at nq = 1
+    case 1536: case 2048: return 64;                   // 0.92x / 0.75x at nq = 8, 4.7x / 4.5x at nq = 64
+    default: return 0;
+  }
+}
+
+}  // namespace g5d
+}  // namespace vrq
+
+using namespace vrq;
+
+extern "C" {
+
+size_t vrq_gemm_topk_dim_mfma_workspace_size(int32_t mode, int64_t n, int32_t dim, int32_t nq, int32_t k) {
+  if (mode != VRQ_GEMM_INT8_COSINE) return 0;  // (at 1024 too: the entry point serves no other mode)
+  if (dim == 1024) return vrq_gemm_topk_workspace_size(mode, n, dim, nq, k);
+  g5d::Plan p;
+  return g5d::plan(mode, n, dim, nq, k, &p) == VRQ_OK ? p.bytes : 0;
+}
+
+int vrq_gemm_topk_dim_mfma_plan(int32_t mode, int64_t n, int32_t dim, int32_t nq, int32_t k, int64_t* info) {
+  if (!info) return VRQ_EINVAL;
+  if (mode != VRQ_GEMM_INT8_COSINE) return mode == VRQ_GEMM_FLOAT_IP ? VRQ_EINVAL : VRQ_EUNSUPPORTED;
+  if (dim == 1024) return vrq_gemm_topk_plan(mode, n, dim, nq, k, info);
+  g5d::Plan p;
+  const int rc = g5d::plan(mode, n, dim, nq, k, &p);
+  if (rc != VRQ_OK) return rc;
+  info[0] = p.chunk_rows;
+  info[1] = p.nchunks;
+  info[2] = p.capc;
+  info[3] = p.nqb;
+  info[4] = p.nsc;
+  info[5] = p.scr;
+  info[6] = (int64_t)p.bytes;
+  info[7] = p.qpb;
+  return VRQ_OK;
+}
+
+int vrq_gemm_topk_dim_mfma_prep_layout(int32_t mode, int64_t n, int32_t dim, int32_t nq, int32_t k, int64_t* info) {
+  if (!info) return VRQ_EINVAL;
+  if (dim == 1024) return VRQ_EUNSUPPORTED;  // K5's: vrq_gemm_topk_prep_layout / vrq_gemm_topk_layout
+  g5d::Plan p;
+  const int rc = g5d::plan(mode, n, dim, nq, k, &p);
+  if (rc != VRQ_OK) return rc;
+  info[0] = (int64_t)p.off_delta;
+  info[1] = (int64_t)p.off_alpha;
+  info[2] = (int64_t)p.off_beta;
+  info[3] = (int64_t)p.off_flag;
+  info[4] = (int64_t)p.off_thr;
+  info[5] = p.nq_pad;
+  info[6] = (int64_t)p.off_cnt;
+  info[7] = (int64_t)p.off_cand;
+  return VRQ_OK;
+}
+
+int vrq_gemm_topk_dim_mfma(int32_t mode, const uint8_t* codes, const int8_t* x8, const double* norms, int64_t n,
+                           int32_t dim, int64_t row_offset, const float* qf, int32_t nq, int32_t k, int32_t flags,
+                           int32_t* out_count, int64_t* out_rows, double* out_scores, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  if (mode == VRQ_GEMM_BINARY) return VRQ_EUNSUPPORTED;  // needs its own bit-expansion path off 1024
+  if (mode != VRQ_GEMM_INT8_COSINE) return VRQ_EINVAL;
+  if (dim == 1024)
+    return vrq_gemm_topk(mode, codes, x8, norms, n, dim, row_offset, qf, nq, k, flags, out_count, out_rows, out_scores,
+                         workspace, workspace_bytes, stream);
+  if (!vrq_dim_supported(dim)) return VRQ_EUNSUPPORTED;
+  VRQ_CHECK_ARG(qf && out_count && out_rows && out_scores && workspace && x8 && norms && n > 0 && nq > 0 && k > 0);
+  constexpr int OK = VRQ_GEMM_STAGE_SAMPLE | VRQ_GEMM_STAGE_MAIN | VRQ_GEMM_STAGE_FINISH | VRQ_GEMM_NO_FALLBACK;
+  if (flags & ~OK) return VRQ_EUNSUPPORTED;
+  return g5d::run(x8, norms, n, dim, row_offset, qf, nq, k, flags, out_count, out_rows, out_scores, workspace,
+                  workspace_bytes, (hipStream_t)stream);
+}
+
+int vrq_gemm_topk_dim_engine(int32_t mode, int64_t n, int32_t dim, int32_t nq, int32_t k) {
+  g5d::Plan p;
+  if (dim == 1024 || g5d::plan(mode, n, dim, nq, k, &p) != VRQ_OK) return VRQ_GEMM_ENGINE_EXACT;
+  const int mb = g5d::min_batch(dim);
+  return mb > 0 && nq >= mb ? VRQ_GEMM_ENGINE_MFMA : VRQ_GEMM_ENGINE_EXACT;
+}
+
+}  // extern "C"

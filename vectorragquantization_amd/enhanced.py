@@ -63,7 +63,7 @@ class SearchBatch:
 
 def gemm_topk(mode: str, qf: torch.Tensor, k: int, codes: torch.Tensor | None = None,
               x8: torch.Tensor | None = None, norms: torch.Tensor | None = None, row_offset: int = 0,
-              flags: int = 0, workspace: torch.Tensor | None = None, lib=None):
+              flags: int = 0, workspace: torch.Tensor | None = None, lib=None, engine: str | None = None):
     """Exhaustive Phase-II (``mode="binary"``) or Phase-III (``mode="int8_cosine"``) top-k of a query
     batch over EVERY row on the matrix cores (``vrq_gemm_topk``, BASELINE config 5): the scores of
     ``CohereEnhancedVectorDB.py:283-293`` / ``:302-318`` ordered like the reference's stable
@@ -71,7 +71,13 @@ def gemm_topk(mode: str, qf: torch.Tensor, k: int, codes: torch.Tensor | None = 
     scores f64[nq, k]) device tensors.  At the other supported dims (256 ... 2048), or with
     VRQ_GEMM_SCAN_EXACT in ``flags``, the call goes through ``vrq_gemm_topk_dim`` to the exact
     exhaustive scan (K5d); same return contract.  ``flags``: VRQ_GEMM_STAGE_* / VRQ_GEMM_NO_FALLBACK; ``lib``:
-    another build of the library (the probe build, for sweeps), default libvrq.so."""
+    another build of the library (the probe build, for sweeps), default libvrq.so.  ``engine``: None keeps
+    that route; "exact" is K5d (``vrq_gemm_topk_dim``); "mfma" is the matrix-core pipeline at every dim (K5md,
+    ``vrq_gemm_topk_dim_mfma``: int8_cosine only, takes the stage flags); "auto" asks
+    ``vrq_gemm_topk_dim_engine``, which picks K5md from a measured minimum batch per dim and otherwise leaves
+    the call on the ``engine=None`` route (so "auto" at 1024 is K5, never the exact scan)."""
+    if engine not in (None, "exact", "mfma", "auto"):
+        raise ValueError(f"engine {engine!r}: None, 'exact', 'mfma' or 'auto'")
     m = {"binary": N.VRQ_GEMM_BINARY, "int8_cosine": N.VRQ_GEMM_INT8_COSINE}[mode]
     src = codes if m == N.VRQ_GEMM_BINARY else x8
     dev = qf.device
@@ -81,6 +87,17 @@ def gemm_topk(mode: str, qf: torch.Tensor, k: int, codes: torch.Tensor | None = 
     scores = torch.empty((nq, k), dtype=torch.float64, device=dev)
     lib = lib or N.load()
     dim = qf.shape[1]
+    engine = N.gemm_topk_engine(lib, m, n, dim, nq, k, engine)
+    if engine == "mfma":
+        need = N.gemm_topk_dim_mfma_workspace(lib, m, n, dim, nq, k)
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+        N.check(lib.vrq_gemm_topk_dim_mfma(m, N.ptr(codes), N.ptr(x8), N.ptr(norms), n, dim, row_offset, N.ptr(qf),
+                                           nq, k, flags, N.ptr(cnt), N.ptr(rows), N.ptr(scores), N.ptr(workspace),
+                                           workspace.numel(), N.stream_handle(dev)), "vrq_gemm_topk_dim_mfma")
+        return cnt, rows, scores
+    if engine == "exact" and dim == 1024:
+        flags |= N.VRQ_GEMM_SCAN_EXACT
     if dim != 1024 or flags & N.VRQ_GEMM_SCAN_EXACT:
         # the exact exhaustive scan (K5d) behind vrq_gemm_topk_dim: every supported dim, no matrix pass
         need = N.gemm_topk_dim_workspace(lib, m, n, dim, nq, k, flags)
