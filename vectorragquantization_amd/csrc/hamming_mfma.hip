@@ -49,8 +49,8 @@ constexpr int NPK = 4;                      // packed ring depth (DMA issued NPK
 constexpr int NUB = 3;                      // unpacked ring: tile t read, t+1 ready, t+2 written
 constexpr int UBT = NG * 1024;              // unpacked tile bytes (32 KiB)
 constexpr int GPW = (PKT / 1024) / MWAVES;  // LDS-DMA instructions per wave per tile (2)
-constexpr int BAHEAD = 3;                   // B fragments read this many groups ahead
-constexpr int NRING = BAHEAD < 4 ? 4 : 8;   // B fragment ring (power of two > BAHEAD)
+constexpr int BAHEAD = 2;                   // B fragments read in pairs: groups gi+2, gi+3 at the top of even gi
+constexpr int NRING = 4;                    // B fragment ring (power of two > BAHEAD + 1, the furthest read)
 #ifndef VRQ_K1M_NSR  // A/B builds: M-blocks per wave whose accumulator seeds stay in registers (capped at MB)
 #define VRQ_K1M_NSR 4
 #endif
@@ -89,10 +89,10 @@ constexpr int ENT_V_BIAS = 1025;
 // dv columns); the thresholded pass uses chunk_stride = chunk_rows and tile_stride = 64.
 // MODE: MFMA_MAIN, MFMA_SAMPLE (DENSE below) or MFMA_RERUN (mfma_hits.h).
 //
-// Schedule of the 32 k-step groups of a tile (group gi = (n-block gi>>4, k-step j = gi&15)): every
-// group reads the B fragment of group gi+BAHEAD (one ds_read_b128, immediate offset) and runs MB
-// MFMAs on the fragment of group gi.  Around them, spread so no group's vector work much exceeds
-// its MFMA shadow: the packed reads of unpack unit u (gi = 8u+1) and its unpack + LDS writes
+// Schedule of the 32 k-step groups of a tile (group gi = (n-block gi>>4, k-step j = gi&15)): the groups
+// run in pairs (2p, 2p+1); the even group reads the B fragments of groups gi+2 and gi+3 (two ds_read_b128,
+// immediate offsets) and every group runs MB MFMAs on the fragment of group gi.  Around them, spread so
+// no group's vector work much exceeds its MFMA shadow: the packed reads of unpack unit u (gi = 8u+1) and its unpack + LDS writes
 // (gi = 8u+6), the row-popcount reads (gi = 12) and writes (gi = 28); for the previous n-block the
 // max3 tree of M-block m folded into the lane's running maximum (j = 2+m), one compare + ballot after
 // the last of them, one branch to the (rare) hit extraction (j = 3+MB), which works out the M-blocks
@@ -110,12 +110,15 @@ constexpr int ENT_V_BIAS = 1025;
 // counted wait ladder.  The two kinds run in two loops over one tile body with a compile-time STEADY: the
 // steady loop's body tests neither the mode nor t nor a row against the chunk's end (its tiles and the ones
 // before them are whole), and the first n-block has no t == 0 case in either loop (pcvP starts at the
-// popcount of a row past the chunk).  Between the MFMAs of two steady tiles remain: the two waits, the
-// > 64-hits test, the barrier, the loop test, the flushed-store test, two address forms, the two
-// row-popcount reads and the first B read.  The hit extraction and the synchronous flush are marked unlikely
+// popcount of a row past the chunk).  Between the MFMAs of two steady tiles remain: the wait, the
+// > 64-hits test, the barrier, the loop test, the flushed-store test, two address forms, the
+// row-popcount read and the first two B reads.  The hit extraction and the synchronous flush are marked unlikely
 // and laid out after the loop body, so a tile's 128 MFMAs are contiguous and the no-hit path falls through.
 //
-// The counted waits.  Each group's s_waitcnt lgkmcnt and its first MFMA (M-block 0) are ONE asm statement
+// The counted waits.  One per pair of groups (17 s_waitcnt per steady tile with the tile's last, where one per
+// group made 34; DESIGN section 5 "The stream trim" has what that is worth): the even group's wait
+// retires the fragments of both groups, the odd group's first MFMA is the same statement without a wait
+// (asm_mfma_fp4).  The even group's s_waitcnt lgkmcnt and its first MFMA (M-block 0) are ONE asm statement
 // (wait_lgkm_mfma_fp4, mfma_common.h), the B fragment a plain input: a wait-only statement naming the fragment
 // as an output made the compiler pad the following MFMA with s_nop 0.  The compiler does not know that
 // statement writes M-block 0's accumulator with an MFMA, so the schedule guarantees its hazards:
@@ -133,9 +136,9 @@ constexpr int ENT_V_BIAS = 1025;
 // between the v_cmp that writes vcc and the v_cndmask of the flush's lane mask (thresholded instances), or
 // between the row test and its select (dense instance, two n-blocks).
 
-// The per-group LDS wait of the schedule above.  Group gi consumes the B fragment read at the top of
-// group gi - BAHEAD; DS operations complete in order, so the wait may leave in flight exactly the DS
-// operations issued after that read: the B reads of the groups since, and every other LDS operation
+// The per-pair LDS wait of the schedule above.  Groups gi (even) and gi + 1 consume the B fragments read at the
+// top of group gi - BAHEAD; DS operations complete in order, so the wait may leave in flight exactly the DS
+// operations issued after those reads: the two B reads of group gi, and every other LDS operation
 // of those groups on the no-hit path (a hit adds stage writes, which only makes the counted wait
 // stricter).  Per group g: pre(g) = reads issued after its B read and before its wait (packed unit,
 // row popcounts), post(g) = operations issued in its slots (unpack writes, the popcount write, the four
@@ -148,10 +151,9 @@ constexpr int k1m_post(int g, int mb, int nsr, bool dense) {
   return ((g & 7) == 6 ? 2 : 0) + (g == 28 ? 1 : 0) + (!dense && j >= 4 + mb + nsr && j < 4 + 2 * mb ? 4 : 0) +
          (!dense && g == 20 + mb ? 1 : 0) + (!dense && g == 24 + mb ? 1 : 0);
 }
-constexpr int k1m_wait(int gi, int mb, int nsr, bool dense) {
-  const int g0 = gi - BAHEAD;
-  int n = 1 + k1m_pre(gi);  // this group's B read and pre-wait reads
-  for (int g = g0 < 0 ? 0 : g0; g < gi; ++g) n += (g == g0 ? 0 : 1) + k1m_pre(g) + k1m_post(g, mb, nsr, dense);
+constexpr int k1m_wait(int gi, int mb, int nsr, bool dense) {  // gi even: the wait of the pair (gi, gi + 1)
+  int n = BAHEAD + k1m_pre(gi);  // this group's two B reads and pre-wait reads
+  for (int g = gi < BAHEAD ? 0 : gi - BAHEAD; g < gi; ++g) n += k1m_pre(g) + k1m_post(g, mb, nsr, dense);
   return n < 15 ? n : 15;
 }
 
@@ -580,20 +582,23 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
     const uint32_t ubw = ub0 + (uint32_t)(ru2 * UBT);
     const uint32_t pks = pk0 + (pko ^ (uint32_t)(2 * PKT));  // (t + 2) % NPK
     static_assert(NPK == 4 && NUB == 3, "ring walks: slot of t + 2 by XOR, unpacked slots by rotation");
-    int pcv[2];
+    v2i pcv;  // the popcounts of this lane's rows of n-blocks 0 and 1, 32 dwords apart: one DS operation
     const uint32_t pcra = pcr0 + (uint32_t)((ru0 * RT + ri) * 4);
-    lds_read32_imm<0>(pcv[0], pcra);
-    lds_read32_imm<32 * 4>(pcv[1], pcra);
+    lds_read2x32_imm<0, 32>(pcv, pcra);
     v2i pv;
     v4i pa, pb;
     VRQ_SCHED_FENCE();
     static_for<0, NG>([&](auto GI) {
       constexpr int gi = decltype(GI)::value;
       constexpr int nbk = gi >> 4, s = gi & 15, j = gi & 15;
-      if constexpr (gi + BAHEAD < NG)
-        lds_read128_imm<(gi + BAHEAD) * 1024>(ring[(gi + BAHEAD) & (NRING - 1)], blt);
-      else
-        lds_read128_imm<(gi + BAHEAD - NG) * 1024>(ring[(gi + BAHEAD) & (NRING - 1)], bln);
+      // the even group reads the next pair's two fragments (the tile's last pair: the next tile's first)
+      static_for<0, (gi & 1) ? 0 : 2>([&](auto R) {
+        constexpr int gr = gi + BAHEAD + decltype(R)::value;
+        if constexpr (gr < NG)
+          lds_read128_imm<gr * 1024>(ring[gr & (NRING - 1)], blt);
+        else
+          lds_read128_imm<(gr - NG) * 1024>(ring[gr & (NRING - 1)], bln);
+      });
       // packed reads of the unpack units (used 5 groups later) and of the row popcounts
       // (unit u's source is unit 0's with u XORed into the swizzled piece index, the second popcount piece
       // the first with its lowest index bit flipped: one kept address each)
@@ -618,6 +623,7 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
       constexpr int sm = SEED ? j - 4 - MB : 0;
       int e0 = 0, e1 = 0, e2 = 0, e3 = 0, e4 = 0, f0 = 0;
       uint32_t u0 = 0, u1 = 0, u2 = 0;
+      v2i sh = {0, 0};  // an unpack unit's two dwords shifted right by one
       int pc0 = 0, pc1 = 0;
       auto slot = [&](auto K) __attribute__((always_inline)) {
         constexpr int k = decltype(K)::value;
@@ -654,6 +660,9 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
         if constexpr (UNPACK) {  // unpack_row32 of pv.x (slots 0, 1) and pv.y (slots 2, 3)
           constexpr int half = k >> 1;
           const uint32_t wv = (uint32_t)(half ? pv.y : pv.x);
+          // the `>> 1` of both dwords as one 64-bit shift of the pair: the bit that crosses into bit 31 of the
+          // low dword lies outside the 0x44444444 mask (asm: the compiler narrows it back to two shifts)
+          if constexpr (k == 0) asm volatile("v_lshrrev_b64 %0, 1, %1" : "=v"(sh) : "v"(pv));
           if constexpr ((k & 1) == 0) {
             u0 = wv & 0x11111111u;
             u1 = wv & 0x22222222u;
@@ -664,7 +673,7 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
             r.x = (int)u0;
             r.y = (int)u1;
             r.z = (int)u2;
-            r.w = (int)((wv >> 1) & 0x44444444u);
+            r.w = (int)((uint32_t)(half ? sh.y : sh.x) & 0x44444444u);
             lds_write128_imm<(gi >> 3) * 2048 + half * 1024>(ubw + udst[0], r);  // udst[u] = udst[0] + 2048 u
           }
         }
@@ -755,11 +764,16 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
       };
       static_for<0, MB>([&](auto P) {
         constexpr int p = decltype(P)::value, m = p;
-        if constexpr (p == 0) {
-          // The group's counted wait and its first MFMA, one statement (wait_lgkm_mfma_fp4): every LDS operation
-          // issued up to the B read of group gi - BAHEAD has completed (k1m_wait) -- the fragment of this group,
-          // the packed unit read 4 groups ago, the popcounts, the seeds.  Hazards of M-block 0's accumulator,
-          // which the compiler no longer sees written by an MFMA: see "The counted waits" above the kernel.
+        if constexpr (p == 0 && (gi & 1)) {
+          // the odd group of a pair: the even group's wait retired its fragment too.  The same opaque MFMA
+          // statement without a wait, so M-block 0's accumulate chain stays one kind of statement
+          static_assert(s != 0, "an n-block starts on an even group");
+          asm_mfma_fp4(acc[nbk][m], A[m][s], ring[gi & (NRING - 1)]);
+        } else if constexpr (p == 0) {
+          // The pair's counted wait and the even group's first MFMA, one statement (wait_lgkm_mfma_fp4): every LDS
+          // operation issued up to the B reads of group gi - BAHEAD has completed (k1m_wait) -- the fragments of
+          // this group and the next, the packed unit read 3 groups ago, the popcounts, the seeds.  Hazards of
+          // M-block 0's accumulator, which the compiler no longer sees written by an MFMA: see "The counted waits" above the kernel.
           constexpr int W = k1m_wait(gi, MB, NSR, DENSE);
           if constexpr (s == 0 && m < NSR)
             wait_lgkm_mfma_fp4_seed<W>(acc[nbk][m], A[m][s], ring[gi & (NRING - 1)], seedr[m < NSR ? m : 0]);
@@ -772,12 +786,14 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
           // the group BEFORE its first consumer's, or slots away from it, so the idle state the compiler puts
           // between an asm statement's output and its next reader never lands in an MFMA gap:
           //   the row popcounts of this tile (read before group 0)       group 0          -> group 1
-          //   the packed unit read in group 8u + 1                        group 8u + 5     -> group 8u + 6
+          //   the packed unit read in group 8u + 1                        group 8u + 4     -> group 8u + 6
           //   the packed popcount pieces read in group 12                 group 16         -> group 28
           //   the staged entries read in group 20 + MB, slot 3            group 24 + MB    -> its slot 3
-          static_assert(k1m_wait(0, MB, NSR, DENSE) == 1, "group 0's wait leaves only the B read of group 3 in flight");
-          if constexpr (gi == 0) asm volatile("" : "+v"(pcv[0]), "+v"(pcv[1]));
-          if constexpr ((gi & 7) == 5) asm volatile("" : "+v"(pv));
+          // (all even groups: only those wait)
+          static_assert(k1m_wait(0, MB, NSR, DENSE) == 2, "group 0's wait leaves only the B reads of groups 2, 3 in flight");
+          static_assert(MB % 2 == 0, "the staged entries are named behind the wait of group 24 + MB: an even group");
+          if constexpr (gi == 0) asm volatile("" : "+v"(pcv));
+          if constexpr ((gi & 7) == 4) asm volatile("" : "+v"(pv));
           if constexpr (gi == 16) asm volatile("" : "+v"(pa), "+v"(pb));
           if constexpr (gi == 24 + MB && !DENSE) asm volatile("" : "+v"(fe));
         } else if constexpr (s == 0 && m < NSR) {  // register-resident seeds: the C operand
@@ -815,19 +831,20 @@ __global__ __launch_bounds__(MWAVES * 64, 1) void hamming_mfma_kernel(
     const uint32_t st_an = (uint32_t)__builtin_amdgcn_s_memtime();
 #endif
     // packed tile t+3 (unpacked next iteration) landed; this wave's LDS writes done
-    {
 #ifndef VRQ_K1M_PROBE_NOVMWAIT  // timing-only probe builds (wrong results)
-      // a steady tile: tile t + NPK was issued this iteration, one tile may stay in flight.  (vmcnt counts
-      // in issue order and the list stores sit before their iteration's DMA, so none is left behind it.)
-      if constexpr (STEADY) {
-        wait_vm<GPW>();
-      } else {
-        const int last = t + NPK < ntiles ? t + NPK : ntiles - 1;  // last tile issued so far
-        wait_tiles(last - (t + 3));
-      }
-#endif
+    // a steady tile: tile t + NPK was issued this iteration, one tile may stay in flight.  (vmcnt counts
+    // in issue order and the list stores sit before their iteration's DMA, so none is left behind it.)
+    // Its two counts are one s_waitcnt.
+    if constexpr (STEADY) {
+      asm volatile("s_waitcnt vmcnt(%2) lgkmcnt(0)" : "+v"(fpos), "+v"(fe) : "n"(GPW) : "memory");
+    } else {
+      const int last = t + NPK < ntiles ? t + NPK : ntiles - 1;  // last tile issued so far
+      wait_tiles(last - (t + 3));
+      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fpos), "+v"(fe)::"memory");
     }
+#else
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fpos), "+v"(fe)::"memory");
+#endif
 #ifdef VRQ_K1M_STAMPS
     if (t > 0) st_bsum += st_b - st_a;  // (this tile's st_b, the previous tile's st_a: retired by the wait above)
     st_a = st_an;

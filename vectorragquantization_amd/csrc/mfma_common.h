@@ -66,9 +66,10 @@ __device__ __forceinline__ void lds_read32_inplace(int& d, uint32_t a) {
 __device__ __forceinline__ void lds_write128(uint32_t a, const v4i& v) {
   asm volatile("ds_write_b128 %0, %1" ::"v"(a), "v"(v) : "memory");
 }
-template <int OFF>
-__device__ __forceinline__ void lds_read32_imm(int& d, uint32_t a) {
-  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(d) : "v"(a), "n"(OFF) : "memory");
+// two dwords, OFF0 and OFF1 dwords behind the address, in one DS operation
+template <int OFF0, int OFF1>
+__device__ __forceinline__ void lds_read2x32_imm(v2i& d, uint32_t a) {
+  asm volatile("ds_read2_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(d) : "v"(a), "n"(OFF0), "n"(OFF1) : "memory");
 }
 template <int OFF>
 __device__ __forceinline__ void lds_write128_imm(uint32_t a, const v4i& v) {
@@ -124,6 +125,11 @@ __device__ __forceinline__ void wait_lgkm_mfma_fp4(v16f& acc, const v4i& a, cons
                : "+v"(acc)
                : "a"(a), "v"(b), "n"(N)
                : "memory");
+}
+// the same MFMA with no wait in front: for a fragment that an earlier statement's wait retired, in an
+// accumulate chain whose other links are the fused statements (the caller owns the hazards of `acc` alike)
+__device__ __forceinline__ void asm_mfma_fp4(v16f& acc, const v4i& a, const v4i& b) {  // acc += A x B
+  asm volatile("v_mfma_f32_32x32x64_f8f6f4 %0, %1, %2, %0 cbsz:4 blgp:4" : "+v"(acc) : "a"(a), "v"(b) : "memory");
 }
 template <int N>
 __device__ __forceinline__ void wait_lgkm_mfma_fp4_seed(v16f& acc, const v4i& a, const v4i& b, const v16f& c) {
