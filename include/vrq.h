@@ -538,6 +538,45 @@ int vrq_gemm_topk_dim_mfma(int32_t mode, const uint8_t* codes, const int8_t* x8,
 int vrq_gemm_topk_dim_engine(int32_t mode, int64_t n, int32_t dim, int32_t nq, int32_t k);
 
 /* ---------------------------------------------------------------------------
+ * Exact float inner-product top-k on the matrix cores at every supported embedding dim (additive to ABI
+ * version 1; vrq_flat_ip_prepare / vrq_flat_ip_topk keep their "dim = 1024" contract, vrq_flat_ip_topk_dim
+ * keeps running K5d off 1024 and ignoring x8 / inv_scale / bounds, and vrq_gemm_topk_dim_mfma* keep
+ * returning VRQ_EINVAL / 0 for VRQ_GEMM_FLOAT_IP).  K5mf: K5md's matrix passes over the prepared int8
+ * image of the float rows (1 / scale in the place of the norms, as K5 does at 1024), then a finish that
+ * rescores the surviving float rows, R rows per wave in flight; one retry at a raised threshold after a
+ * list overflow, an exact scan of every row for what is left.  Exact for every finite input; outputs and
+ * order of vrq_flat_ip_topk_dim, and its score bits under the exactness condition of exact_scores.h
+ * (otherwise one of the two float32 neighbours of the exact dot).
+ * vrq_flat_ip_prepare_dim: the arguments and definitions of vrq_flat_ip_prepare (s_r = max|x_r| / 127,
+ * x8 = clamp(rint(x_r / s_r), +-127), inv_scale = 1 / s_r, rows with max|x| < 1e-30 stored as 0 with scale
+ * 1, bounds[0] = max ||s_r b_r||_2 and bounds[1] = max ||x_r - s_r b_r||_2 rounded up and max-accumulated)
+ * at every dim of vrq_dim_supported; at 1024 it forwards to vrq_flat_ip_prepare.
+ * vrq_flat_ip_topk_dim_mfma: the arguments of vrq_flat_ip_topk_dim; x8, inv_scale and bounds are required
+ * (VRQ_EINVAL when NULL).  At 1024 it forwards to vrq_flat_ip_topk.  Supported: 1 <= k <= 1024,
+ * 1 <= n < 2^32, finite inputs.  flags: 0, or a subset of VRQ_GEMM_STAGE_* under vrq_gemm_topk's ordering
+ * contract, optionally | VRQ_GEMM_NO_FALLBACK (queries the matrix path could not serve get out_count = -1);
+ * anything else (VRQ_GEMM_SCAN_EXACT included) VRQ_EUNSUPPORTED.
+ * vrq_flat_ip_topk_dim_mfma_workspace_size / _plan / _prep_layout: as their vrq_gemm_topk_dim_mfma_*
+ * namesakes without the mode argument; info has the same meaning (at 1024 the size and plan are K5's for
+ * VRQ_GEMM_FLOAT_IP, and _prep_layout returns VRQ_EUNSUPPORTED).  Delta = (||rho||_2 B0 + ||q/S||_2 B1)
+ * (1 + eps) + eps (||q/S||_2 + ||rho||_2) B0 with eps = 2^-20 and (B0, B1) = bounds; hit rule of the MAIN
+ * pass: u = f32(<a, x8_r>) * (1 / f32(inv_scale_r)) >= thr.
+ * vrq_flat_ip_dim_engine: the engine "auto" takes, VRQ_GEMM_ENGINE_EXACT (K5d; also the answer at 1024,
+ * where vrq_flat_ip_topk_dim forwards to K5) or VRQ_GEMM_ENGINE_MFMA (K5mf): K5mf from a measured minimum
+ * batch per dim, never at nq = 1, and K5d at every dim without a measured winning batch.
+ * ------------------------------------------------------------------------- */
+int vrq_flat_ip_prepare_dim(const float* xf, int64_t n, int32_t dim, int8_t* x8, double* inv_scale, double* bounds,
+                            void* stream);
+size_t vrq_flat_ip_topk_dim_mfma_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t k);
+int vrq_flat_ip_topk_dim_mfma_plan(int64_t n, int32_t dim, int32_t nq, int32_t k, int64_t* info);
+int vrq_flat_ip_topk_dim_mfma_prep_layout(int64_t n, int32_t dim, int32_t nq, int32_t k, int64_t* info);
+int vrq_flat_ip_topk_dim_mfma(const float* xf, const int8_t* x8, const double* inv_scale, const double* bounds,
+                              int64_t n, int32_t dim, int64_t row_offset, const float* qf, int32_t nq, int32_t k,
+                              int32_t flags, int32_t* out_count, int64_t* out_rows, double* out_scores,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int vrq_flat_ip_dim_engine(int64_t n, int32_t dim, int32_t nq, int32_t k);
+
+/* ---------------------------------------------------------------------------
  * Search with more than 1024 Phase-I candidates (additive to ABI version 1; every function above keeps
  * its K <= 1024 contract and its VRQ_EUNSUPPORTED beyond it).  FAISS IndexBinaryFlat::search takes any k,
  * and K = min(k * binary_oversample, ntotal) passes 1024 at k = 103 with the default oversample of 10.

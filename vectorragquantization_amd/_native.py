@@ -174,6 +174,13 @@ SIGNATURES = {
                                          _SZ, _P]),
     "vrq_gemm_topk_dim_engine": (C.c_int, [_I32, _I64, _I32, _I32, _I32]),
     "vrq_flat_ip_prepare": (C.c_int, [_P, _I64, _I32, _P, _P, _P, _P]),
+    "vrq_flat_ip_prepare_dim": (C.c_int, [_P, _I64, _I32, _P, _P, _P, _P]),
+    "vrq_flat_ip_topk_dim_mfma_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
+    "vrq_flat_ip_topk_dim_mfma_plan": (C.c_int, [_I64, _I32, _I32, _I32, _P]),
+    "vrq_flat_ip_topk_dim_mfma_prep_layout": (C.c_int, [_I64, _I32, _I32, _I32, _P]),
+    "vrq_flat_ip_topk_dim_mfma": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I64, _P, _I32, _I32, _I32, _P, _P, _P, _P,
+                                            _SZ, _P]),
+    "vrq_flat_ip_dim_engine": (C.c_int, [_I64, _I32, _I32, _I32]),
     "vrq_flat_ip_topk": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I64, _P, _I32, _I32, _I32, _P, _P, _P, _P, _SZ,
                                    _P]),
 }
@@ -275,6 +282,16 @@ def gemm_topk_engine(lib, mode: int, n: int, dim: int, nq: int, k: int, engine):
     (today's route: K5 at 1024, K5d elsewhere) where it does not; only an explicit "exact" forces the exact scan."""
     if engine == "auto":
         return "mfma" if lib.vrq_gemm_topk_dim_engine(mode, n, dim, nq, k) == VRQ_GEMM_ENGINE_MFMA else None
+    return engine
+
+
+def flat_ip_engine(lib, n: int, dim: int, nq: int, k: int, engine):
+    """The engine a flat_ip_topk call runs: "auto" becomes "mfma" where vrq_flat_ip_dim_engine picks K5mf and None
+    (today's route: K5 at 1024, K5d elsewhere) where it does not; only an explicit "exact" forces the exact scan."""
+    if engine not in (None, "exact", "mfma", "auto"):
+        raise VrqNativeError(f"flat_ip_topk: engine = {engine!r} (None, 'exact', 'mfma' or 'auto')")
+    if engine == "auto":
+        return "mfma" if lib.vrq_flat_ip_dim_engine(n, dim, nq, k) == VRQ_GEMM_ENGINE_MFMA else None
     return engine
 
 

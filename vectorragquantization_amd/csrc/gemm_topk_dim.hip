@@ -880,6 +880,497 @@ __host__ inline int min_batch(int dim) {
   }
 }
 
+// =============================================================================================
+// K5mf: exact float32 inner-product top-k (IndexFlatIP) on the matrix cores at the same six dims, behind
+// vrq_flat_ip_topk_dim_mfma.  The sample and main passes are k5md_pass_kernel over flat_ip_prepare's operands
+// (x8 = the per-row-scaled int8 image b_r of the float rows, inv_scale = 1 / s_r in the place of the norms:
+// u = f32(<a, b_r>) * (1 / f32(inv_scale_r)) ~ s_r <a, b_r>), as K5 does at 1024; select, the plan and the
+// list layout are K5md's.  New here: the corpus preparation and the query prep at a run-time dim, and a
+// finish (and exact scan) that rescores float rows, 4 d bytes each.
+//
+// Delta = (||rho|| B0 + ||q/S|| B1)(1 + eps) + eps (||q/S|| + ||rho||) B0, eps = 2^-20, (B0, B1) = the corpus
+// bounds max ||s_r b_r||, max ||x_r - s_r b_r||.  Exact part: u* - s'* = <a - q/S, s_r b_r> - <q/S, x_r - s_r b_r>,
+// so |u* - s'*| <= ||rho|| B0 + ||q/S|| B1 (Cauchy-Schwarz; d does not enter).  Roundings for d <= 2048:
+//   u path, relative to |u*| = |s_r <a, b_r>| <= ||a|| B0 <= (||q/S|| + ||rho||) B0:
+//     A = <a, b_r> is exact in i32, |A| <= 127 * 127 * 2048 < 2^25: v_cvt_f32_i32 rounds above 2^24, i.e. at
+//     d = 1536 and 2048 (2^-24); inv_scale f64 -> f32 (2^-24; its own f64 rounding, 2^-53, is far below);
+//     v_rcp_f32 (1 ulp: 2^-23); the product (2^-24; the main pass tests the sign of one fma instead):
+//     (1 + 2^-24)^3 (1 + 2^-23) - 1 < 2^-21.
+//   reference s' = f32(<q, x_r>) / S: 2^-24 |<q/S, x_r>| <= 2^-24 ||q/S|| (B0 + B1).
+//   Sum <= (2^-21 + 2^-24)(||q/S|| + ||rho||) B0 + 2^-24 ||q/S|| B1 < eps (||q/S|| + ||rho||) B0 + eps ||q/S|| B1:
+//   the first is Delta's last term, the second is inside the (1 + eps) factor on the B1 term.  eps = 2^-20
+//   holds at every d <= 2048 with a factor 1.7 to spare; no dim needs a wider one.
+//
+// Finish (k5mf_finish_kernel<KS, RETRY>): one workgroup of 8 waves per query, the query slice in registers
+// (lane l holds the 16-byte pieces l + 64 i of the query, i < NP = ceil(d / 256)).  A wave scores R candidate
+// rows per round: lanes j < R each resolve one candidate (a fixed-trip binary search of the list prefix in
+// LDS, then the list entry) for the NEXT round while this round's rows are in flight; the wave issues the
+// R * NP global_load_dwordx4 of all R rows back to back (wave-uniform row base from v_readlane, consecutive
+// lanes read consecutive pieces) and scores row i under a counted vmcnt wait while rows i + 1 .. R - 1 are
+// still landing.  Score: flat_score_dim, one summation order for the finish and for the exact scan.
+// Admission, retry and flags are K5md's; a round whose rows all fail the test against the k-th key touches
+// no LDS.  R per dim keeps the row registers (4 R NP) near 96: 8 rows up to 512, 6 at 768, 4 at 1536, 3 at
+// 2048; -DVRQ_G5F_R=n overrides it at every dim (the R = 1 A/B of DESIGN section 5 "K5mf").
+#ifndef VRQ_G5F_R
+#define VRQ_G5F_R 0
+#endif
+
+typedef float v4f __attribute__((ext_vector_type(4)));
+
+template <int KS>
+struct FShape {
+  static constexpr int D = 32 * KS, PCS = D / 4;    // 16-byte pieces of a float row
+  static constexpr int NP = (PCS + 63) / 64;        // piece rounds: lane l takes pieces l + 64 i
+  static constexpr int REM = PCS - 64 * (NP - 1);   // lanes of the last round (32 at d = 384, else 64)
+  static constexpr int R = VRQ_G5F_R > 0 ? VRQ_G5F_R : (KS <= 16 ? 8 : KS <= 24 ? 6 : KS <= 48 ? 4 : 3);
+  static constexpr int OCC = KS <= 24 ? 2 : 1;      // finish workgroups per CU the register budget allows
+  static constexpr int RPW = NP <= 1 ? 8 : NP <= 3 ? 4 : 2;  // corpus preparation: rows in flight per wave
+};
+
+template <int KS>
+struct FSlice {
+  v4f v[FShape<KS>::NP];
+};
+
+// this lane's pieces of one float row (zeros where the last round has no piece for the lane)
+template <int KS>
+__device__ __forceinline__ void fslice_load(FSlice<KS>& x, const float* __restrict__ row) {
+  using F = FShape<KS>;
+  const v4f* p = reinterpret_cast<const v4f*>(row) + lane_id();
+#pragma unroll
+  for (int i = 0; i < F::NP; ++i) {
+    if (i < F::NP - 1 || F::REM == 64) {
+      x.v[i] = p[64 * i];
+    } else {
+      x.v[i] = v4f{0.f, 0.f, 0.f, 0.f};
+      if (lane_id() < F::REM) x.v[i] = p[64 * i];
+    }
+  }
+}
+
+// The float inner product of the finish and of the exact scan: (double)(float)(sum q_i x_i), every product
+// exact in f64 (the fma rounds once, the sum), the lane's pieces in the order i = 0 .. NP - 1, then the wave
+// butterfly.  Under the exactness condition of exact_scores.h the f64 sum is exact in every order and this
+// is the one correct f32 rounding of the dot (K5d's and the oracle's bits); otherwise one of its two
+// f32 neighbours.
+template <int KS>
+__device__ __forceinline__ double flat_score_dim(const FSlice<KS>& q, const FSlice<KS>& x) {
+  double s = 0.0;
+#pragma unroll
+  for (int i = 0; i < FShape<KS>::NP; ++i) {
+    s = __builtin_fma((double)q.v[i].x, (double)x.v[i].x, s);
+    s = __builtin_fma((double)q.v[i].y, (double)x.v[i].y, s);
+    s = __builtin_fma((double)q.v[i].z, (double)x.v[i].z, s);
+    s = __builtin_fma((double)q.v[i].w, (double)x.v[i].w, s);
+  }
+  return (double)(float)wave_sum_f64(s);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Corpus preparation at dim 32 KS (flat_ip_prepare_kernel's definitions): a wave takes RPW whole rows, all
+// their loads in flight before the first max|x| reduction; the int8 image leaves as 16-byte stores (a quad
+// of lanes hands its four packed dwords to its first lane).  Rows past n are the last row again (the
+// maxima are idempotent; nothing is stored for them).
+template <int KS>
+__global__ __launch_bounds__(256) void k5mf_prepare_kernel(const float* __restrict__ xf, int64_t n,
+                                                           int8_t* __restrict__ x8, double* __restrict__ inv_scale,
+                                                           unsigned long long* __restrict__ bounds) {
+  using F = FShape<KS>;
+  constexpr int D = F::D, NP = F::NP, RPW = F::RPW;
+  __shared__ double sb[2][4];
+  const int w = threadIdx.x >> 6, l = lane_id();
+  const int64_t r0 = ((int64_t)blockIdx.x * 4 + w) * RPW;
+  FSlice<KS> x[RPW];
+#pragma unroll
+  for (int j = 0; j < RPW; ++j) {
+    const int64_t r = r0 + j < n ? r0 + j : n - 1;
+    fslice_load(x[j], xf + r * D);
+  }
+  double ex = 0.0, es = 0.0;
+#pragma unroll
+  for (int j = 0; j < RPW; ++j) {
+    const int64_t r = r0 + j < n ? r0 + j : n - 1;
+    const bool store = r0 + j < n;
+    float mxl = 0.f;
+#pragma unroll
+    for (int i = 0; i < NP; ++i)
+      mxl = fmaxf(fmaxf(mxl, fmaxf(fabsf(x[j].v[i].x), fabsf(x[j].v[i].y))),
+                  fmaxf(fabsf(x[j].v[i].z), fabsf(x[j].v[i].w)));
+    const float mx = (float)wave_allreduce64((double)mxl, [](double a, double b) { return fmax(a, b); });
+    const bool live = mx >= 1e-30f;
+    const double sc = live ? (double)mx / 127.0 : 0.0, inv = live ? 127.0 / (double)mx : 0.0;
+    double b2 = 0.0, s2 = 0.0;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      const float xe[4] = {x[j].v[i].x, x[j].v[i].y, x[j].v[i].z, x[j].v[i].w};
+      uint32_t pk = 0u;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        double b = rint((double)xe[e] * inv);
+        b = b > 127.0 ? 127.0 : (b < -127.0 ? -127.0 : b);
+        const double rs = (double)xe[e] - sc * b;
+        b2 += b * b;
+        s2 += rs * rs;
+        pk |= ((uint32_t)(int32_t)b & 0xffu) << (8 * e);
+      }
+      // quad_perm broadcasts of the quad's lanes 0..3: every lane of a quad holds its 16 bytes
+      const uint32_t a0 = dpp_u32<0x00>(pk), a1 = dpp_u32<0x55>(pk), a2 = dpp_u32<0xAA>(pk), a3 = dpp_u32<0xFF>(pk);
+      const int pc = 64 * i + l;
+      if (store && (l & 3) == 0 && pc < F::PCS)
+        *reinterpret_cast<int4*>(x8 + r * D + 4 * pc) = make_int4((int)a0, (int)a1, (int)a2, (int)a3);
+    }
+    b2 = wave_sum_f64(b2);  // exact (integers < 2^25)
+    s2 = wave_sum_f64(s2);
+    ex = fmax(ex, sc * sqrt(b2) * (1.0 + 1e-12));
+    es = fmax(es, sqrt(s2) * (1.0 + 1e-12) + 1e-300);
+    if (store && l == 0) inv_scale[r] = live ? inv : 1.0;
+  }
+  if (l == 0) {
+    sb[0][w] = ex;
+    sb[1][w] = es;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    const double* v = sb[threadIdx.x];
+    const double m = fmax(fmax(v[0], v[1]), fmax(v[2], v[3]));
+    atomicMax(bounds + threadIdx.x, (unsigned long long)__double_as_longlong(m));
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// query prep: k5md_prep_kernel's piece (natural dim order), alpha = 1 / S, beta = 0, and the float Delta of
+// the header from the corpus bounds
+__global__ __launch_bounds__(256) void k5mf_prep_kernel(const float* __restrict__ qf, int nq, int nq_pad, int dim,
+                                                        int8_t* __restrict__ qa, double* __restrict__ delta,
+                                                        double* __restrict__ alpha, double* __restrict__ beta,
+                                                        const double* __restrict__ bounds) {
+  const int q = blockIdx.x * 4 + (threadIdx.x >> 6), l = lane_id();
+  if (q >= nq_pad) return;
+  int8_t* o = qa + (int64_t)q * dim;
+  if (q >= nq) {  // padding queries: zero pieces (their thresholds never accept)
+    for (int i = l; i < dim; i += WAVE) o[i] = 0;
+    if (l == 0) {
+      delta[q] = 0.0;
+      alpha[q] = 0.0;
+      beta[q] = 0.0;
+    }
+    return;
+  }
+  const float* qv = qf + (int64_t)q * dim;
+  float mx = 0.f;
+  for (int i = l; i < dim; i += WAVE) mx = fmaxf(mx, fabsf(qv[i]));
+#pragma unroll
+  for (int m = 1; m < WAVE; m <<= 1) mx = fmaxf(mx, __shfl_xor(mx, m, WAVE));
+  const double invS = mx > 0.f ? 127.0 / (double)mx : 1.0;
+  double r2 = 0.0, q2 = 0.0;
+  for (int i = l; i < dim; i += WAVE) {
+    const double x = (double)qv[i] * invS;
+    double a = rint(x);  // |a| <= 127
+    a = a > 127.0 ? 127.0 : (a < -127.0 ? -127.0 : a);
+    const double rho = x - a;  // exact, |rho| <= 1/2
+    r2 += rho * rho;
+    q2 += (double)qv[i] * (double)qv[i];
+    o[i] = (int8_t)a;
+  }
+  r2 = wave_sum_f64(r2);
+  q2 = wave_sum_f64(q2);
+  constexpr double SLACK = 1.0 / (1 << 20);  // the header's sum of roundings, < 2^-20
+  if (l == 0) {
+    const double qn = sqrt(q2) * invS, rn = sqrt(r2), b0 = bounds[0], b1 = bounds[1];
+    delta[q] = (rn * b0 + qn * b1) * (1.0 + SLACK) + SLACK * (qn + rn) * b0;
+    alpha[q] = invS;
+    beta[q] = 0.0;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+struct FinF {
+  uint64_t key[KMAX5 + FB_BATCH];
+  uint32_t row[KMAX5 + FB_BATCH];
+  int32_t pre[MAX_CHUNKS + 1];  // exclusive prefix of the (capped) list lengths
+  int32_t fill, over;
+};
+
+// Running exact top-k over the float rows row_at(j), j < count (row_at: per lane), R rows per wave and round.
+// Batches of FB_BATCH candidates are dealt to the waves in groups of R; key/row[0..kc) hold the list in order
+// after each batch.  All threads call it; returns kc = min(k, count).  count >= 1.
+template <int KS, class RowAt>
+__device__ __forceinline__ int running_topk_f(int64_t count, RowAt row_at, const float* __restrict__ xf,
+                                              const FSlice<KS>& qs, int k, FinF& sh) {
+  constexpr int D = FShape<KS>::D, R = FShape<KS>::R;
+  const int tid = threadIdx.x, l = lane_id(), w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  if (tid == 0) sh.fill = 0;
+  int kc = 0;
+  __syncthreads();
+  // lane j < R: the row of candidate c0 + j (past the end: the last candidate again, so every address is a
+  // row of the corpus; such a row is masked at admission)
+  auto resolve = [&](int64_t c0) {
+    uint32_t rv = 0;
+    if (l < R) {
+      const int64_t c = c0 + l;
+      rv = row_at(c < count ? c : count - 1);
+    }
+    return rv;
+  };
+  for (int64_t base = 0; base < count; base += FB_BATCH) {
+    const uint64_t kk = kc == k ? sh.key[k - 1] : KEY_NONE;
+    const uint32_t kr = kc == k ? sh.row[k - 1] : 0xffffffffu;
+    const int64_t end = base + FB_BATCH < count ? base + FB_BATCH : count;
+    const int nrounds = (int)((end - base + FIN_NW * R - 1) / (FIN_NW * R));
+    int64_t c0 = base + (int64_t)w * R;
+    uint32_t rv = resolve(c0);
+    for (int t = 0; t < nrounds; ++t) {
+      FSlice<KS> x[R];
+      uint32_t rr[R];
+#pragma unroll
+      for (int j = 0; j < R; ++j) {
+        rr[j] = (uint32_t)__builtin_amdgcn_readlane((int)rv, j);
+        fslice_load(x[j], xf + (int64_t)rr[j] * D);
+      }
+      const int64_t cn = c0 + FIN_NW * R;
+      rv = resolve(cn);  // the next round's rows, resolved while this round's are in flight
+      VRQ_SCHED_FENCE();
+#pragma unroll
+      for (int j = 0; j < R; ++j) {
+        const uint64_t key_r = desc_key_f64(flat_score_dim(qs, x[j]));
+        if (c0 + j < end && (kc < k || key_r < kk || (key_r == kk && rr[j] < kr)) && l == 0) {
+          const int i = kc + atomicAdd(&sh.fill, 1);
+          sh.key[i] = key_r;
+          sh.row[i] = rr[j];
+        }
+      }
+      c0 = cn;
+    }
+    __syncthreads();
+    const int f = sh.fill;
+    if (f > 0) {
+      const int tot = kc + f, np2 = next_pow2(tot);
+      for (int i = tot + tid; i < np2; i += FIN_NT) {
+        sh.key[i] = KEY_NONE;
+        sh.row[i] = 0xffffffffu;
+      }
+      sort_pairs(sh.key, sh.row, np2);
+      kc = tot < k ? tot : k;
+    }
+    __syncthreads();
+    if (tid == 0) sh.fill = 0;
+    __syncthreads();
+  }
+  return kc;
+}
+
+__device__ __forceinline__ void write_result_f(int q, int k, int kc, int64_t row_offset, const FinF& sh,
+                                               int32_t* out_count, int64_t* out_rows, double* out_scores) {
+  for (int i = threadIdx.x; i < k; i += FIN_NT) {
+    const int64_t o = (int64_t)q * k + i;
+    out_rows[o] = i < kc ? (int64_t)sh.row[i] + row_offset : -1;
+    out_scores[o] = i < kc ? desc_key_inv(sh.key[i]) : __builtin_nan("");
+  }
+  if (threadIdx.x == 0) out_count[q] = kc;
+}
+
+// finish: k5md_finish_kernel's contract and flags over float rows
+template <int KS, bool RETRY>
+__global__ __launch_bounds__(FIN_NT, FShape<KS>::OCC) void k5mf_finish_kernel(
+    const float* __restrict__ xf, int64_t n, int64_t row_offset, const float* __restrict__ qf, int k,
+    const uint32_t* __restrict__ cand, const int32_t* __restrict__ ccnt, int nchunks, int capc, int qpb,
+    int32_t* __restrict__ out_count, int64_t* __restrict__ out_rows, double* __restrict__ out_scores,
+    int32_t* __restrict__ fb_flag, float* __restrict__ thr, const double* __restrict__ alpha,
+    const double* __restrict__ beta, const double* __restrict__ delta, int32_t* __restrict__ qbflag) {
+  __shared__ FinF sh;
+  const int q = blockIdx.x, tid = threadIdx.x;
+  if (RETRY && fb_flag[q] != 2) return;
+  FSlice<KS> qs;
+  fslice_load(qs, qf + (int64_t)q * FShape<KS>::D);
+  if (tid == 0) sh.over = 0;
+  __syncthreads();
+  const int32_t* cq = ccnt + (int64_t)q * nchunks;
+  for (int c = tid; c < nchunks; c += FIN_NT) {
+    const int x = cq[c];
+    if (x > capc) sh.over = 1;
+    sh.pre[c + 1] = x < capc ? x : capc;
+  }
+  __syncthreads();
+  if (tid < WAVE) {  // inclusive scan of pre[1 .. nchunks] by one wave: 32 entries per lane, then the lanes
+    constexpr int PER = MAX_CHUNKS / WAVE;
+    int part = 0;
+    for (int i = 0; i < PER; ++i) {
+      const int c = tid * PER + i;
+      if (c < nchunks) part += sh.pre[c + 1];
+    }
+    int incl = part;
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+      const int y = __shfl_up(incl, d, WAVE);
+      if (tid >= d) incl += y;
+    }
+    int run = incl - part;
+    for (int i = 0; i < PER; ++i) {
+      const int c = tid * PER + i;
+      if (c < nchunks) {
+        run += sh.pre[c + 1];
+        sh.pre[c + 1] = run;
+      }
+    }
+    if (tid == 0) sh.pre[0] = 0;
+  }
+  __syncthreads();
+  const int total = sh.pre[nchunks];
+  const int need = (int)((int64_t)k < n ? k : n);
+  const bool over = sh.over != 0;
+  if (total < need || (RETRY && over)) {
+    if (tid == 0) {
+      fb_flag[q] = 1;
+      thr[q] = __builtin_inff();
+    }
+    return;
+  }
+  const uint32_t* Cq = cand + (int64_t)q * nchunks * capc;
+  // candidate j of the concatenated lists: the largest chunk lo with pre[lo] <= j (fixed 11 steps)
+  auto row_at = [&](int64_t j) {
+    int lo = 0;
+#pragma unroll
+    for (int st = MAX_CHUNKS / 2; st > 0; st >>= 1) {
+      const int mid = lo + st;
+      if (mid < nchunks && sh.pre[mid] <= j) lo = mid;
+    }
+    return Cq[(int64_t)lo * capc + (j - sh.pre[lo])];
+  };
+  const int kc = running_topk_f<KS>(total, row_at, xf, qs, k, sh);
+  if (!RETRY && over) {
+    if (tid == 0) {
+      const double t2 = alpha[q] * desc_key_inv(sh.key[kc - 1]) + beta[q] - delta[q];
+      thr[q] = __double2float_rd(t2 - 1e-9 * fabs(t2));
+      fb_flag[q] = 2;
+      atomicOr(&qbflag[q / qpb], 1);
+    }
+    return;
+  }
+  write_result_f(q, k, kc, row_offset, sh, out_count, out_rows, out_scores);
+  if (tid == 0) {
+    fb_flag[q] = 0;
+    thr[q] = __builtin_inff();
+  }
+}
+
+// the exact scan of the flagged queries: every row through the same rounds and the same score function
+template <int KS>
+__global__ __launch_bounds__(FIN_NT, FShape<KS>::OCC) void k5mf_fallback_kernel(
+    const float* __restrict__ xf, int64_t n, int64_t row_offset, const float* __restrict__ qf, int k,
+    int32_t* __restrict__ out_count, int64_t* __restrict__ out_rows, double* __restrict__ out_scores,
+    const int32_t* __restrict__ fb_flag, bool skip) {
+  __shared__ FinF sh;
+  const int q = blockIdx.x, tid = threadIdx.x;
+  if (fb_flag[q] != 1) return;
+  if (skip) {
+    for (int i = tid; i < k; i += FIN_NT) {
+      out_rows[(int64_t)q * k + i] = -1;
+      out_scores[(int64_t)q * k + i] = __builtin_nan("");
+    }
+    if (tid == 0) out_count[q] = -1;
+    return;
+  }
+  FSlice<KS> qs;
+  fslice_load(qs, qf + (int64_t)q * FShape<KS>::D);
+  const int kc = running_topk_f<KS>(n, [](int64_t j) { return (uint32_t)j; }, xf, qs, k, sh);
+  write_result_f(q, k, kc, row_offset, sh, out_count, out_rows, out_scores);
+}
+
+struct FloatCall {
+  const float* xf;
+  int64_t n, row_offset;
+  const float* qf;
+  int nq, k;
+  int32_t *out_count, *flag;
+  int64_t* out_rows;
+  double* out_scores;
+  const double *alpha, *beta, *delta;
+  bool skip;
+};
+
+template <int KS>
+static void launch_float_finish(const Plan& p, const Call& c, const FloatCall& f) {
+  hipLaunchKernelGGL((k5mf_finish_kernel<KS, false>), dim3(f.nq), dim3(FIN_NT), 0, c.s, f.xf, f.n, f.row_offset, f.qf,
+                     f.k, (const uint32_t*)c.cand, (const int32_t*)c.cnt, p.nchunks, p.capc, p.qpb, f.out_count,
+                     f.out_rows, f.out_scores, f.flag, c.thr, f.alpha, f.beta, f.delta, c.qbf);
+  launch_pass<KS>(p, c, 2);
+  hipLaunchKernelGGL((k5mf_finish_kernel<KS, true>), dim3(f.nq), dim3(FIN_NT), 0, c.s, f.xf, f.n, f.row_offset, f.qf,
+                     f.k, (const uint32_t*)c.cand, (const int32_t*)c.cnt, p.nchunks, p.capc, p.qpb, f.out_count,
+                     f.out_rows, f.out_scores, f.flag, c.thr, f.alpha, f.beta, f.delta, c.qbf);
+  hipLaunchKernelGGL((k5mf_fallback_kernel<KS>), dim3(f.nq), dim3(FIN_NT), 0, c.s, f.xf, f.n, f.row_offset, f.qf, f.k,
+                     f.out_count, f.out_rows, f.out_scores, (const int32_t*)f.flag, f.skip);
+}
+
+template <int KS>
+static void launch_prepare(const float* xf, int64_t n, int8_t* x8, double* inv_scale, double* bounds, hipStream_t s) {
+  const int64_t per = 4 * FShape<KS>::RPW;
+  hipLaunchKernelGGL((k5mf_prepare_kernel<KS>), dim3((unsigned)((n + per - 1) / per)), dim3(256), 0, s, xf, n, x8,
+                     inv_scale, reinterpret_cast<unsigned long long*>(bounds));
+}
+
+// the plan of the float path: K5md's (same pieces, passes and lists)
+__host__ inline int plan_float(int64_t n, int dim, int nq, int k, Plan* p) {
+  return plan(VRQ_GEMM_INT8_COSINE, n, dim, nq, k, p);
+}
+
+static int run_float(const float* xf, const int8_t* x8, const double* inv_scale, const double* bounds, int64_t n,
+                     int dim, int64_t row_offset, const float* qf, int nq, int k, int flags, int32_t* out_count,
+                     int64_t* out_rows, double* out_scores, void* workspace, size_t workspace_bytes, hipStream_t s) {
+  Plan p;
+  const int rc = plan_float(n, dim, nq, k, &p);
+  if (rc != VRQ_OK) return rc;
+  if (workspace_bytes < p.bytes) return VRQ_EWORKSPACE;
+  constexpr int ALL = VRQ_GEMM_STAGE_SAMPLE | VRQ_GEMM_STAGE_MAIN | VRQ_GEMM_STAGE_FINISH;
+  const int st = (flags & ALL) ? (flags & ALL) : ALL;
+  uint8_t* ws = (uint8_t*)workspace;
+  int8_t* qa = (int8_t*)ws;
+  double* delta = (double*)(ws + p.off_delta);
+  double* alpha = (double*)(ws + p.off_alpha);
+  double* beta = (double*)(ws + p.off_beta);
+  const Call c{x8, inv_scale, n, qa, nq, (float*)(ws + p.off_thr), (uint32_t*)(ws + p.off_cand),
+               (int32_t*)(ws + p.off_cnt), (float*)(ws + p.off_dv), (int32_t*)(ws + p.off_qbf), s};
+  if (st & VRQ_GEMM_STAGE_SAMPLE) {
+    hipLaunchKernelGGL(k5mf_prep_kernel, dim3((p.nq_pad + 3) / 4), dim3(256), 0, s, qf, nq, p.nq_pad, dim, qa, delta,
+                       alpha, beta, bounds);
+    VRQ_LAUNCH_CHECK();
+    const int r0 = launch_pass_dim(dim, p, c, 0);
+    if (r0 != VRQ_OK) return r0;
+    hipLaunchKernelGGL(k5md_select_kernel, dim3(p.nq_pad), dim3(256), 0, s, (const float*)c.dv, p.scols, p.sstride,
+                       p.nsc, n, k, (const double*)delta, c.thr, c.cnt, p.nchunks, nq, c.qbf, p.nqb);
+    VRQ_LAUNCH_CHECK();
+  }
+  if (st & VRQ_GEMM_STAGE_MAIN) {
+    const int r1 = launch_pass_dim(dim, p, c, 1);
+    if (r1 != VRQ_OK) return r1;
+  }
+  if (st & VRQ_GEMM_STAGE_FINISH) {
+    const FloatCall f{xf, n, row_offset, qf, nq, k, out_count, (int32_t*)(ws + p.off_flag), out_rows, out_scores,
+                      alpha, beta, delta, (flags & VRQ_GEMM_NO_FALLBACK) != 0};
+    switch (dim) {
+      case 256: launch_float_finish<8>(p, c, f); break;
+      case 384: launch_float_finish<12>(p, c, f); break;
+      case 512: launch_float_finish<16>(p, c, f); break;
+      case 768: launch_float_finish<24>(p, c, f); break;
+      case 1536: launch_float_finish<48>(p, c, f); break;
+      case 2048: launch_float_finish<64>(p, c, f); break;
+      default: return VRQ_EUNSUPPORTED;
+    }
+    VRQ_LAUNCH_CHECK();
+  }
+  return VRQ_OK;
+}
+
+// "auto" of the float path, K5md's rule: per dim the smallest measured batch (nq = 1, 8, 64, 1024;
+// profiles/flat_mfma_bench.jsonl) at which K5mf's slowest call beat K5d's fastest on the same rows, never
+// nq = 1; 0 = no such batch measured, the dim stays on K5d
+__host__ inline int min_batch_float(int dim) {
+  switch (dim) {
+    case 256: case 384: case 512: case 768: return 8;  // 1.19x-2.23x at nq = 8, 0.51x-0.78x at nq = 1
+    case 1536: case 2048: return 64;                   // 0.52x / 0.41x at nq = 8, 3.3x / 2.3x at nq = 64
+    default: return 0;
+  }
+}
+
 }  // namespace g5d
 }  // namespace vrq
 
@@ -951,6 +1442,90 @@ int vrq_gemm_topk_dim_engine(int32_t mode, int64_t n, int32_t dim, int32_t nq, i
   if (dim == 1024 || g5d::plan(mode, n, dim, nq, k, &p) != VRQ_OK) return VRQ_GEMM_ENGINE_EXACT;
   const int mb = g5d::min_batch(dim);
   return mb > 0 && nq >= mb ? VRQ_GEMM_ENGINE_MFMA : VRQ_GEMM_ENGINE_EXACT;
+}
+
+int vrq_flat_ip_prepare_dim(const float* xf, int64_t n, int32_t dim, int8_t* x8, double* inv_scale, double* bounds,
+                            void* stream) {
+  if (dim == 1024) return vrq_flat_ip_prepare(xf, n, dim, x8, inv_scale, bounds, stream);
+  if (!vrq_dim_supported(dim)) return VRQ_EUNSUPPORTED;
+  VRQ_CHECK_ARG(n >= 0 && bounds);
+  if (n == 0) return VRQ_OK;
+  VRQ_CHECK_ARG(xf && x8 && inv_scale);
+  const hipStream_t s = (hipStream_t)stream;
+  switch (dim) {
+    case 256: g5d::launch_prepare<8>(xf, n, x8, inv_scale, bounds, s); break;
+    case 384: g5d::launch_prepare<12>(xf, n, x8, inv_scale, bounds, s); break;
+    case 512: g5d::launch_prepare<16>(xf, n, x8, inv_scale, bounds, s); break;
+    case 768: g5d::launch_prepare<24>(xf, n, x8, inv_scale, bounds, s); break;
+    case 1536: g5d::launch_prepare<48>(xf, n, x8, inv_scale, bounds, s); break;
+    case 2048: g5d::launch_prepare<64>(xf, n, x8, inv_scale, bounds, s); break;
+    default: return VRQ_EUNSUPPORTED;
+  }
+  VRQ_LAUNCH_CHECK();
+  return VRQ_OK;
+}
+
+size_t vrq_flat_ip_topk_dim_mfma_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t k) {
+  if (dim == 1024) return vrq_gemm_topk_workspace_size(VRQ_GEMM_FLOAT_IP, n, dim, nq, k);
+  g5d::Plan p;
+  return g5d::plan_float(n, dim, nq, k, &p) == VRQ_OK ? p.bytes : 0;
+}
+
+int vrq_flat_ip_topk_dim_mfma_plan(int64_t n, int32_t dim, int32_t nq, int32_t k, int64_t* info) {
+  if (!info) return VRQ_EINVAL;
+  if (dim == 1024) return vrq_gemm_topk_plan(VRQ_GEMM_FLOAT_IP, n, dim, nq, k, info);
+  g5d::Plan p;
+  const int rc = g5d::plan_float(n, dim, nq, k, &p);
+  if (rc != VRQ_OK) return rc;
+  info[0] = p.chunk_rows;
+  info[1] = p.nchunks;
+  info[2] = p.capc;
+  info[3] = p.nqb;
+  info[4] = p.nsc;
+  info[5] = p.scr;
+  info[6] = (int64_t)p.bytes;
+  info[7] = p.qpb;
+  return VRQ_OK;
+}
+
+int vrq_flat_ip_topk_dim_mfma_prep_layout(int64_t n, int32_t dim, int32_t nq, int32_t k, int64_t* info) {
+  if (!info) return VRQ_EINVAL;
+  if (dim == 1024) return VRQ_EUNSUPPORTED;  // K5's: vrq_gemm_topk_prep_layout / vrq_gemm_topk_layout
+  g5d::Plan p;
+  const int rc = g5d::plan_float(n, dim, nq, k, &p);
+  if (rc != VRQ_OK) return rc;
+  info[0] = (int64_t)p.off_delta;
+  info[1] = (int64_t)p.off_alpha;
+  info[2] = (int64_t)p.off_beta;
+  info[3] = (int64_t)p.off_flag;
+  info[4] = (int64_t)p.off_thr;
+  info[5] = p.nq_pad;
+  info[6] = (int64_t)p.off_cnt;
+  info[7] = (int64_t)p.off_cand;
+  return VRQ_OK;
+}
+
+int vrq_flat_ip_topk_dim_mfma(const float* xf, const int8_t* x8, const double* inv_scale, const double* bounds,
+                              int64_t n, int32_t dim, int64_t row_offset, const float* qf, int32_t nq, int32_t k,
+                              int32_t flags, int32_t* out_count, int64_t* out_rows, double* out_scores,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+  constexpr int OK = VRQ_GEMM_STAGE_SAMPLE | VRQ_GEMM_STAGE_MAIN | VRQ_GEMM_STAGE_FINISH | VRQ_GEMM_NO_FALLBACK;
+  if (flags & ~OK) return VRQ_EUNSUPPORTED;
+  if (dim == 1024)
+    return vrq_flat_ip_topk(xf, x8, inv_scale, bounds, n, dim, row_offset, qf, nq, k, flags, out_count, out_rows,
+                            out_scores, workspace, workspace_bytes, stream);
+  if (!vrq_dim_supported(dim)) return VRQ_EUNSUPPORTED;
+  VRQ_CHECK_ARG(xf && x8 && inv_scale && bounds && qf && out_count && out_rows && out_scores && workspace && n > 0 &&
+                nq > 0 && k > 0);
+  return g5d::run_float(xf, x8, inv_scale, bounds, n, dim, row_offset, qf, nq, k, flags, out_count, out_rows,
+                        out_scores, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int vrq_flat_ip_dim_engine(int64_t n, int32_t dim, int32_t nq, int32_t k) {
+  g5d::Plan p;
+  if (dim == 1024 || g5d::plan_float(n, dim, nq, k, &p) != VRQ_OK) return VRQ_GEMM_ENGINE_EXACT;
+  const int mb = g5d::min_batch_float(dim);
+  return mb > 0 && nq > 1 && nq >= mb ? VRQ_GEMM_ENGINE_MFMA : VRQ_GEMM_ENGINE_EXACT;
 }
 
 }  // extern "C"

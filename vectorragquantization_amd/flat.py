@@ -12,8 +12,12 @@ Device layout (rows = FAISS internal order): the float32 rows xf[n, 1024] (the e
 them), the matrix pass's per-row-scaled int8 copy x8[n, 1024] and 1/scale f64[n], and the corpus
 error bounds f64[2] -- all from ``vrq_flat_ip_prepare`` at add time.  A search is one
 ``vrq_flat_ip_topk`` call for the whole query batch.  At the other supported dims (256, 384, 512,
-768, 1536, 2048) the index keeps only xf and the ids, and a search is one ``vrq_flat_ip_topk_dim``
-call: the exact exhaustive scan (K5d), no prepare step.
+768, 1536, 2048) the default index (``engine=None``) keeps only xf and the ids, and a search is one
+``vrq_flat_ip_topk_dim`` call: the exact exhaustive scan (K5d), no prepare step.  An index built with
+``engine="mfma"`` or ``"auto"`` prepares and keeps x8, 1/scale and the bounds there too
+(``vrq_flat_ip_prepare_dim``, d + 8 more bytes per row) and searches through ``vrq_flat_ip_topk_dim_mfma``
+(K5mf: the matrix passes of K5md and a float finish; same rows and score bits) -- always with "mfma", and
+with "auto" for the batches ``vrq_flat_ip_dim_engine`` measured as faster there.
 """
 from __future__ import annotations
 
@@ -34,23 +38,26 @@ logger = logging.getLogger(__name__)
 
 
 def flat_ip_prepare(xf: torch.Tensor, bounds: torch.Tensor):
-    """``vrq_flat_ip_prepare``: (x8 int8[n, d], inv_scale f64[n]) of float32 rows; max-accumulates
-    the corpus bounds into ``bounds`` (f64[2], zero before the first batch)."""
+    """``vrq_flat_ip_prepare_dim``: (x8 int8[n, d], inv_scale f64[n]) of float32 rows at every supported
+    dim; max-accumulates the corpus bounds into ``bounds`` (f64[2], zero before the first batch)."""
     n, d = xf.shape
     x8 = torch.empty((n, d), dtype=torch.int8, device=xf.device)
     inv = torch.empty((n,), dtype=torch.float64, device=xf.device)
-    N.check(N.load().vrq_flat_ip_prepare(N.ptr(xf), n, d, N.ptr(x8), N.ptr(inv), N.ptr(bounds),
-                                         N.stream_handle(xf.device)), "vrq_flat_ip_prepare")
+    N.check(N.load().vrq_flat_ip_prepare_dim(N.ptr(xf), n, d, N.ptr(x8), N.ptr(inv), N.ptr(bounds),
+                                             N.stream_handle(xf.device)), "vrq_flat_ip_prepare_dim")
     return x8, inv
 
 
 def flat_ip_topk(xf: torch.Tensor, x8: torch.Tensor, inv_scale: torch.Tensor, bounds: torch.Tensor,
                  qf: torch.Tensor, k: int, row_offset: int = 0, flags: int = 0,
-                 workspace: torch.Tensor | None = None):
+                 workspace: torch.Tensor | None = None, engine: str | None = None):
     """Exact IndexFlatIP top-k of a query batch (``vrq_flat_ip_topk``).  Returns device tensors
     (count i32[nq], rows i64[nq, k] (+ row_offset, -1 padded), scores f64[nq, k] holding float32
     values), ordered (score desc, row asc).  Off dim 1024 (or with VRQ_GEMM_SCAN_EXACT) the exact
-    exhaustive scan behind ``vrq_flat_ip_topk_dim`` serves the call from ``xf`` alone."""
+    exhaustive scan behind ``vrq_flat_ip_topk_dim`` serves the call from ``xf`` alone.  ``engine``: None and
+    "exact" keep those routes; "mfma" is ``vrq_flat_ip_topk_dim_mfma`` (K5mf off 1024, needs x8 / inv_scale /
+    bounds; under VRQ_GEMM_NO_FALLBACK unserved queries come back with count -1); "auto" is "mfma" where
+    ``vrq_flat_ip_dim_engine`` picks it and the operands are there, else None."""
     dev = qf.device
     nq, n = qf.shape[0], xf.shape[0]
     cnt = torch.full((nq,), -2, dtype=torch.int32, device=dev)  # -2: never written
@@ -58,6 +65,26 @@ def flat_ip_topk(xf: torch.Tensor, x8: torch.Tensor, inv_scale: torch.Tensor, bo
     scores = torch.empty((nq, k), dtype=torch.float64, device=dev)
     lib = N.load()
     dim = qf.shape[1]
+    have = x8 is not None and inv_scale is not None and bounds is not None
+    if engine == "auto" and not have:
+        engine = None
+    engine = N.flat_ip_engine(lib, n, dim, nq, k, engine)
+    if engine == "mfma":
+        if not have:
+            raise N.VrqNativeError("flat_ip_topk(engine='mfma'): needs x8, inv_scale and bounds (flat_ip_prepare)")
+        need = lib.vrq_flat_ip_topk_dim_mfma_workspace_size(n, dim, nq, k)
+        if need == 0:
+            raise N.VrqNativeError(f"vrq_flat_ip_topk_dim_mfma: unsupported shape n={n} dim={dim} nq={nq} k={k} "
+                                   "(dims: vrq_dim_supported; k <= 1024)")
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+        N.check(lib.vrq_flat_ip_topk_dim_mfma(N.ptr(xf), N.ptr(x8), N.ptr(inv_scale), N.ptr(bounds), n, dim, row_offset,
+                                              N.ptr(qf), nq, k, flags, N.ptr(cnt), N.ptr(rows), N.ptr(scores),
+                                              N.ptr(workspace), workspace.numel(), N.stream_handle(dev)),
+                "vrq_flat_ip_topk_dim_mfma")
+        return cnt, rows, scores
+    if engine == "exact" and dim == 1024:
+        flags |= N.VRQ_GEMM_SCAN_EXACT
     if dim != 1024 or flags & N.VRQ_GEMM_SCAN_EXACT:
         # the exact exhaustive scan (K5d): reads xf only; x8 / inv_scale / bounds may be None
         need = N.gemm_topk_dim_workspace(lib, N.VRQ_GEMM_FLOAT_IP, n, dim, nq, k, flags)
@@ -122,7 +149,9 @@ class FloatIndexIDMap:
     """``faiss.IndexIDMap(faiss.IndexFlatIP(d))`` on one MI355X (HBM-resident): ``add_with_ids``,
     ``search``, ``reconstruct``, ``remove_ids``, ``ntotal`` and the ``index.faiss`` format."""
 
-    def __init__(self, d: int = 1024, device=None):
+    def __init__(self, d: int = 1024, device=None, engine: str | None = None):
+        if engine not in (None, "exact", "mfma", "auto"):
+            raise ValueError(f"FloatIndexIDMap: engine = {engine!r} (None, 'exact', 'mfma' or 'auto')")
         if not N.load().vrq_dim_supported(int(d)):
             raise ValueError(f"FloatIndexIDMap: d = {d} is not an embedding dim vrq_dim_supported accepts "
                              "(256, 384, 512, 768, 1024, 1536, 2048)")
@@ -130,8 +159,10 @@ class FloatIndexIDMap:
         self.device = _device(device)
         self._xf = _GrowBuffer((d,), torch.float32, self.device)
         self._ids = _GrowBuffer((), torch.int64, self.device)
-        # the matrix pass's operands exist at 1024 only; the other dims search xf with the exact scan
-        self._matrix = d == 1024
+        # the matrix pass's operands: always at 1024; at the other dims only for the engines that read them
+        # (engine=None searches xf with the exact scan and keeps nothing else)
+        self.engine = engine
+        self._matrix = d == 1024 or engine in ("mfma", "auto")
         if self._matrix:
             self._x8 = _GrowBuffer((d,), torch.int8, self.device)
             self._inv = _GrowBuffer((), torch.float64, self.device)
@@ -169,14 +200,19 @@ class FloatIndexIDMap:
         """Device (count, rows, scores) of the exact top-k (internal rows); ``flags`` as
         ``vrq_flat_ip_topk`` (e.g. VRQ_GEMM_NO_FALLBACK)."""
         qf = as_device_tensor(qf, torch.float32, self.device).reshape(-1, self.d)
-        need = N.gemm_topk_dim_workspace(N.load(), N.VRQ_GEMM_FLOAT_IP, self.ntotal, self.d, qf.shape[0], k, flags)
+        lib = N.load()
+        engine = self.engine if self.d != 1024 else None
+        if N.flat_ip_engine(lib, self.ntotal, self.d, qf.shape[0], k, engine) == "mfma":
+            need = lib.vrq_flat_ip_topk_dim_mfma_workspace_size(self.ntotal, self.d, qf.shape[0], k)
+        else:
+            need = N.gemm_topk_dim_workspace(lib, N.VRQ_GEMM_FLOAT_IP, self.ntotal, self.d, qf.shape[0], k, flags)
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty((max(need, 8),), dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
             if not self._matrix:
                 return flat_ip_topk(self._xf.view(), None, None, None, qf, k, flags=flags, workspace=self._ws)
             return flat_ip_topk(self._xf.view(), self._x8.view(), self._inv.view(), self.bounds, qf, k,
-                                flags=flags, workspace=self._ws)
+                                flags=flags, workspace=self._ws, engine=engine)
 
     def search(self, q, k: int):
         """FAISS ``search``: numpy (distances f32[nq, k], labels i64[nq, k]); unused slots -FLT_MAX / -1."""
@@ -221,24 +257,24 @@ class FloatIndexIDMap:
             f.write(self.to_bytes())
 
     @classmethod
-    def from_bytes(cls, b: bytes, device=None) -> "FloatIndexIDMap":
+    def from_bytes(cls, b: bytes, device=None, engine: str | None = None) -> "FloatIndexIDMap":
         d, xf, ids = ixmp_unpack(b)
-        idx = cls(d, device)
+        idx = cls(d, device, engine)
         if xf.shape[0]:
             idx.add_with_ids(xf, ids)
         return idx
 
     @classmethod
-    def read(cls, path: str, device=None) -> "FloatIndexIDMap":
+    def read(cls, path: str, device=None, engine: str | None = None) -> "FloatIndexIDMap":
         with open(path, "rb") as f:
-            return cls.from_bytes(f.read(), device)
+            return cls.from_bytes(f.read(), device, engine)
 
 
 class CohereVectorDBFloat:
     """Drop-in for the reference class (``CohereVectorDBFloat.py:13``)."""
 
     def __init__(self, folder: str, model: str = "embed-english-v3.0", embedding_dim: int = 1024, *,
-                 provider=None, device=None):
+                 provider=None, device=None, engine: str | None = None):
         if provider is None:  # the reference reads COHERE_EMBED_ENDPOINT / _KEY (:22-32)
             from .embed import CohereHTTPProvider
             provider = CohereHTTPProvider(model=model)
@@ -252,10 +288,10 @@ class CohereVectorDBFloat:
         self._setup_config(folder, model, embedding_dim)
         path = os.path.join(folder, "index.faiss")
         if os.path.exists(path):                                            # :55-64
-            self.index = FloatIndexIDMap.read(path, device)
+            self.index = FloatIndexIDMap.read(path, device, engine)
             logger.info("Existing float FAISS index loaded.")
         else:
-            self.index = FloatIndexIDMap(embedding_dim, device)
+            self.index = FloatIndexIDMap(embedding_dim, device, engine)
         self.device = self.index.device
         self.texts: Dict[int, str] = {}
         self._load_texts()
