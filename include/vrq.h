@@ -577,6 +577,41 @@ int vrq_flat_ip_topk_dim_mfma(const float* xf, const int8_t* x8, const double* i
 int vrq_flat_ip_dim_engine(int64_t n, int32_t dim, int32_t nq, int32_t k);
 
 /* ---------------------------------------------------------------------------
+ * Exhaustive binary (Phase-II) top-k on the matrix cores at every supported embedding dim (additive to ABI
+ * version 1; vrq_gemm_topk_dim keeps running K5d off 1024, and vrq_gemm_topk_dim_mfma*, vrq_gemm_topk_dim_engine
+ * keep answering VRQ_EUNSUPPORTED / 0 / VRQ_GEMM_ENGINE_EXACT for VRQ_GEMM_BINARY).  K5mb: K5's method for
+ * its binary mode -- one int8 query piece against the code bits expanded to 0/1 bytes on
+ * v_mfma_i32_32x32x32_i8, a sampled threshold, exact rescoring of the survivors by nibble tables, one retry
+ * at a raised threshold after a list overflow, an exact scan of every row for what is left -- with the
+ * k-loop length d / 32 a template axis.  Exact for every finite query; outputs and order (score desc, row
+ * asc) of vrq_gemm_topk_dim(VRQ_GEMM_BINARY, ...), and its score bits under the exactness condition of
+ * exact_scores.h.
+ * vrq_binary_topk_dim_mfma: codes u8 [n][dim / 8] (packbits, MSB first; 16-byte aligned), the other
+ * arguments as vrq_gemm_topk_dim.  At 1024 it forwards to vrq_gemm_topk(VRQ_GEMM_BINARY, ...).  Supported:
+ * the dims of vrq_dim_supported, 1 <= k <= 1024, 1 <= n < 2^32, finite queries.  flags: 0, or a subset of
+ * VRQ_GEMM_STAGE_* under vrq_gemm_topk's ordering contract, optionally | VRQ_GEMM_NO_FALLBACK (queries the
+ * matrix path could not serve get out_count = -1); anything else (VRQ_GEMM_SCAN_EXACT included)
+ * VRQ_EUNSUPPORTED.
+ * vrq_binary_topk_dim_mfma_workspace_size / _plan / _prep_layout: as their vrq_gemm_topk_dim_mfma_*
+ * namesakes without the mode argument; info has the same meaning (at 1024 the size and plan are K5's for
+ * VRQ_GEMM_BINARY, and _prep_layout returns VRQ_EUNSUPPORTED).  The int8 pieces sit at offset 0 as
+ * i8 [nq_pad][dim], inside every 32-dim k-step in K5's fragment order: byte 16 h + 4 t + b of the k-step
+ * holds the piece of packbits dim 8 b + 7 - (t + 4 h).  Delta = max(sum rho+, sum rho-)(1 + eps) +
+ * eps ||q/S||_1 with eps = 2^-20; alpha = 1 / (2S), beta = sum q / (2S); hit rule of the MAIN pass:
+ * u = <a, bits> >= ceil(thr), an integer compare.
+ * vrq_binary_topk_dim_engine: the engine "auto" takes, VRQ_GEMM_ENGINE_EXACT (K5d; also the answer at 1024,
+ * where vrq_gemm_topk_dim forwards to K5) or VRQ_GEMM_ENGINE_MFMA (K5mb): K5mb from a measured minimum
+ * batch per dim, K5d below it and at every dim without a measured winning batch.
+ * ------------------------------------------------------------------------- */
+size_t vrq_binary_topk_dim_mfma_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t k);
+int vrq_binary_topk_dim_mfma_plan(int64_t n, int32_t dim, int32_t nq, int32_t k, int64_t* info);
+int vrq_binary_topk_dim_mfma_prep_layout(int64_t n, int32_t dim, int32_t nq, int32_t k, int64_t* info);
+int vrq_binary_topk_dim_mfma(const uint8_t* codes, int64_t n, int32_t dim, int64_t row_offset, const float* qf,
+                             int32_t nq, int32_t k, int32_t flags, int32_t* out_count, int64_t* out_rows,
+                             double* out_scores, void* workspace, size_t workspace_bytes, void* stream);
+int vrq_binary_topk_dim_engine(int64_t n, int32_t dim, int32_t nq, int32_t k);
+
+/* ---------------------------------------------------------------------------
  * Search with more than 1024 Phase-I candidates (additive to ABI version 1; every function above keeps
  * its K <= 1024 contract and its VRQ_EUNSUPPORTED beyond it).  FAISS IndexBinaryFlat::search takes any k,
  * and K = min(k * binary_oversample, ntotal) passes 1024 at k = 103 with the default oversample of 10.

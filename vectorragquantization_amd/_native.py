@@ -181,6 +181,11 @@ SIGNATURES = {
     "vrq_flat_ip_topk_dim_mfma": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I64, _P, _I32, _I32, _I32, _P, _P, _P, _P,
                                             _SZ, _P]),
     "vrq_flat_ip_dim_engine": (C.c_int, [_I64, _I32, _I32, _I32]),
+    "vrq_binary_topk_dim_mfma_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
+    "vrq_binary_topk_dim_mfma_plan": (C.c_int, [_I64, _I32, _I32, _I32, _P]),
+    "vrq_binary_topk_dim_mfma_prep_layout": (C.c_int, [_I64, _I32, _I32, _I32, _P]),
+    "vrq_binary_topk_dim_mfma": (C.c_int, [_P, _I64, _I32, _I64, _P, _I32, _I32, _I32, _P, _P, _P, _P, _SZ, _P]),
+    "vrq_binary_topk_dim_engine": (C.c_int, [_I64, _I32, _I32, _I32]),
     "vrq_flat_ip_topk": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I64, _P, _I32, _I32, _I32, _P, _P, _P, _P, _SZ,
                                    _P]),
 }
@@ -282,6 +287,25 @@ def gemm_topk_engine(lib, mode: int, n: int, dim: int, nq: int, k: int, engine):
     (today's route: K5 at 1024, K5d elsewhere) where it does not; only an explicit "exact" forces the exact scan."""
     if engine == "auto":
         return "mfma" if lib.vrq_gemm_topk_dim_engine(mode, n, dim, nq, k) == VRQ_GEMM_ENGINE_MFMA else None
+    return engine
+
+
+def binary_topk_dim_mfma_workspace(lib, n: int, dim: int, nq: int, k: int) -> int:
+    """Workspace bytes of a vrq_binary_topk_dim_mfma call (K5mb; at dim 1024 the forwarded K5's); raises for a
+    shape the matrix path does not serve."""
+    need = lib.vrq_binary_topk_dim_mfma_workspace_size(n, dim, nq, k)
+    if need == 0:
+        raise VrqNativeError(f"vrq_binary_topk_dim_mfma: unsupported call n={n} dim={dim} nq={nq} k={k} "
+                             "(dims: vrq_dim_supported; k <= 1024)")
+    return need
+
+
+def binary_topk_engine(lib, n: int, dim: int, nq: int, k: int, engine):
+    """The engine a binary gemm_topk call runs: "auto" becomes "mfma" where vrq_binary_topk_dim_engine picks K5mb
+    and None (today's route: K5 at 1024, K5d elsewhere) where it does not; only an explicit "exact" forces the
+    exact scan."""
+    if engine == "auto":
+        return "mfma" if lib.vrq_binary_topk_dim_engine(n, dim, nq, k) == VRQ_GEMM_ENGINE_MFMA else None
     return engine
 
 

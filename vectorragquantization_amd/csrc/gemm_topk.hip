@@ -98,15 +98,6 @@ constexpr int64_t kMinSample = 32768;
 constexpr int64_t kMaxSample = 1 << 21;
 constexpr int QA_BYTES = 1024;       // per query: the int8 piece in fragment order
 
-// Phase-II k-permutation inside a 32-dim k-step: fragment byte j = 4t + b of lane half h holds
-// bit 8b + t + 4h of the little-endian code dword (so a dword of the fragment is (w >> (t+4h)) &
-// 0x01010101, two VALU ops), i.e. packbits dim 8b + 7 - (t + 4h) of the step.
-__host__ __device__ constexpr int ph2_pos(int dim_in_step) {
-  const int b = dim_in_step >> 3, x = 7 - (dim_in_step & 7);  // byte, bit within the byte
-  const int h = x >> 2, t = x & 3;
-  return h * 16 + 4 * t + b;
-}
-
 __device__ __forceinline__ v16i mfma_i8(const v4i& a, const v4i& b, const v16i& c) {
   return __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, c, 0, 0, 0);
 }

@@ -733,9 +733,7 @@ __host__ inline int queries_per_block(int dim) {
 }
 
 // K5's planning rules (gemm_plan) with the query block a function of dim
-__host__ inline int plan(int mode, int64_t n, int dim, int nq, int k, Plan* p) {
-  if (mode == VRQ_GEMM_FLOAT_IP) return VRQ_EINVAL;
-  if (mode != VRQ_GEMM_INT8_COSINE) return VRQ_EUNSUPPORTED;
+__host__ inline int plan_shape(int64_t n, int dim, int nq, int k, Plan* p) {
   p->qpb = queries_per_block(dim);
   if (p->qpb == 0 || n < 1 || n >= (int64_t(1) << 32) || nq < 1 || k < 1 || k > KMAX5) return VRQ_EUNSUPPORTED;
   p->nqb = (nq + p->qpb - 1) / p->qpb;
@@ -776,6 +774,13 @@ __host__ inline int plan(int mode, int64_t n, int dim, int nq, int k, Plan* p) {
   p->off_dv = p->off_cand + al((size_t)nq * p->nchunks * p->capc * sizeof(uint32_t));
   p->bytes = p->off_dv + al((size_t)nq * p->scols * sizeof(float));
   return VRQ_OK;
+}
+
+// the plan of vrq_gemm_topk_dim_mfma*: the int8-cosine mode alone
+__host__ inline int plan(int mode, int64_t n, int dim, int nq, int k, Plan* p) {
+  if (mode == VRQ_GEMM_FLOAT_IP) return VRQ_EINVAL;
+  if (mode != VRQ_GEMM_INT8_COSINE) return VRQ_EUNSUPPORTED;
+  return plan_shape(n, dim, nq, k, p);
 }
 
 struct Call {
@@ -1371,6 +1376,635 @@ __host__ inline int min_batch_float(int dim) {
   }
 }
 
+// =============================================================================================
+// K5mb: exhaustive binary (Phase-II) top-k, s = float64(q . (2 unpackbits(code) - 1)), on the matrix cores at
+// the same six dims, behind vrq_binary_topk_dim_mfma.  K5's method for its binary mode: q/S = a + rho with
+// one int8 piece a (S = max|q| / 127), u = <a, bits> against s' = (s + sum q) / (2S) = <q/S, bits>, so
+// u - s' = -<rho, bits> lies in [-sum rho+, sum rho-] and Delta = max(sum rho+, sum rho-)(1 + eps) + eps ||q/S||_1.
+// eps = 2^-20 holds up to d = 2048: u is an exact integer with |u| <= 127 * 2048 < 2^24, so the accumulators,
+// the sample maxima (stored as f32) and the hit test (an integer compare) carry no rounding at all; what is
+// left is the f64 rounding of s' = alpha s + beta and of the sums in prep, below 2^-40 ||q/S||_1.
+// Select, the plan and the list layout are K5md's.
+//
+// The piece is stored with K5's k-permutation (ph2_pos) inside every 32-dim k-step, so the B fragment dword t
+// of lane half h is (w >> (t + 4h)) & 0x01010101 of the little-endian code dword w of that k-step.
+//
+// Matrix pass (k5mb_pass_kernel<KS, DENSE>): K5md's work split per dim, A fragments of all of d in registers.
+// The data path has no packed LDS ring and no LDS-DMA.  A 32-row packed tile is one contiguous run of 4 d
+// bytes (128 KS); thread t of the workgroup loads its 16-byte piece t (and t + 64 W) straight into registers
+// with one coalesced global_load_dwordx4, two tiles ahead of the MFMAs that consume it (a thread past the
+// last piece loads the last piece again and writes nothing, so every wave issues the same number of loads and
+// the wait before a tile's expansion is a counted one: the loads of the tile after it stay in flight).
+// Piece p holds code dwords 4c .. 4c + 3 (k-steps 4c .. 4c + 3) of tile row rr, rr = p / (KS / 4),
+// c = p % (KS / 4).  During tile t's MFMAs its lane expands them into the 8 fragments (4 k-steps x both lane
+// halves) of tile t + 1 and writes each with one ds_write_b128 into the unpacked image
+// [k-step][lane half * 32 + row][16 B] of a ring of 2 (32 d bytes per slot), one fragment per k-step.  The
+// image is read back linearly (lane l reads 16 B at k-step * 1024 + 16 l), conflict-free at every dim.
+// LDS at 2048: 2 x 64 KiB of ring + 16 KiB of hit stage.
+//
+// Thresholded pass: a tile's accumulators start at -ceil(thr) of their query (the first MFMA's C operand),
+// clamped to +-2^30 for infinite or huge thresholds; a hit is acc >= 0.  Tile t-1's accumulators fold into one
+// running integer max in tile t's MFMA shadow, and tile t-1's hit bits are re-derived from the still-live
+// accumulators at the start of tile t+1 only when that max is non-negative.  Hits take K5md's per-wave LDS
+// stage and lists.  The dense pass keeps the running integer max of u per (query, sample chunk, lane row).
+//
+// Finish and exact scan: one workgroup per query builds the query's nibble table (d / 4 nibbles x 16 f64) in
+// LDS and scores one candidate row per THREAD with d / 4 lookups in nibble order (binary_score_dim, the one
+// summation order of this path; phase2_nibbles' arithmetic at a run-time dim).
+constexpr int BAB = 3;  // B fragments read BAB k-steps ahead into the ring of NR
+static_assert(BAB < NR, "B ring");
+
+template <int KS>
+struct BShape {
+  static constexpr int W = Shape<KS>::W, NT = W * 64;
+  static constexpr int RB = 4 * KS;               // code bytes per row
+  static constexpr int PPR = KS / 4;              // 16-byte pieces per row
+  static constexpr int NPC = GRT * PPR;           // pieces per tile
+  static constexpr int PL = (NPC + NT - 1) / NT;  // loads per lane and tile
+  static constexpr int NF = 8 * PL;               // fragments a lane expands per tile, one per k-step
+  static constexpr int UT = KS * 1024;            // unpacked tile: [k-step][lane][16 B]
+  static_assert(KS % 4 == 0 && NF <= KS, "a piece stays inside a row; one fragment per k-step");
+};
+
+// prep: one wave per (padded) query, run-time dim.  qa[q] = the int8 piece in ph2_pos order inside every
+// k-step; delta[q] = Delta_q; alpha = 1 / (2S), beta = sum q / (2S) (s' = alpha s + beta in u units).
+__global__ __launch_bounds__(256) void k5mb_prep_kernel(const float* __restrict__ qf, int nq, int nq_pad, int dim,
+                                                        int8_t* __restrict__ qa, double* __restrict__ delta,
+                                                        double* __restrict__ alpha, double* __restrict__ beta) {
+  const int q = blockIdx.x * 4 + (threadIdx.x >> 6), l = lane_id();
+  if (q >= nq_pad) return;
+  int8_t* o = qa + (int64_t)q * dim;
+  if (q >= nq) {  // padding queries: zero pieces (their thresholds never accept)
+    for (int i = l; i < dim; i += WAVE) o[i] = 0;
+    if (l == 0) {
+      delta[q] = 0.0;
+      alpha[q] = 0.0;
+      beta[q] = 0.0;
+    }
+    return;
+  }
+  const float* qv = qf + (int64_t)q * dim;
+  float mx = 0.f;
+  for (int i = l; i < dim; i += WAVE) mx = fmaxf(mx, fabsf(qv[i]));
+#pragma unroll
+  for (int m = 1; m < WAVE; m <<= 1) mx = fmaxf(mx, __shfl_xor(mx, m, WAVE));
+  const double invS = mx > 0.f ? 127.0 / (double)mx : 1.0;  // an all-zero query: S = 1
+  double rp = 0.0, rn = 0.0, q1 = 0.0, qs = 0.0;
+  for (int i = l; i < dim; i += WAVE) {
+    const double x = (double)qv[i] * invS;
+    double a = rint(x);  // |a| <= 127
+    a = a > 127.0 ? 127.0 : (a < -127.0 ? -127.0 : a);
+    const double rho = x - a;  // exact, |rho| <= 1/2
+    rp += rho > 0.0 ? rho : 0.0;
+    rn += rho < 0.0 ? -rho : 0.0;
+    q1 += fabs((double)qv[i]);
+    qs += (double)qv[i];
+    o[(i & ~31) + ph2_pos(i & 31)] = (int8_t)a;
+  }
+  rp = wave_sum_f64(rp);
+  rn = wave_sum_f64(rn);
+  q1 = wave_sum_f64(q1);
+  qs = wave_sum_f64(qs);
+  constexpr double SLACK = 1.0 / (1 << 20);
+  if (l == 0) {
+    delta[q] = fmax(rp, rn) * (1.0 + SLACK) + SLACK * q1 * invS;
+    alpha[q] = 0.5 * invS;
+    beta[q] = 0.5 * invS * qs;
+  }
+}
+
+// The matrix pass.  DENSE = the sample pass (max of u over each lane row's rows of the chunk ->
+// dv[q][chunk * 32 + lane row]) else the thresholded pass (u >= ceil(thr[q]) -> candidate lists); chunks,
+// query blocks and qbflag as k5md_pass_kernel.
+template <int KS, bool DENSE>
+__global__ __launch_bounds__(Shape<KS>::W * 64, 1) void k5mb_pass_kernel(
+    const uint8_t* __restrict__ codes, int64_t n, const int8_t* __restrict__ qa, int nq,
+    const float* __restrict__ thr, uint32_t* __restrict__ cand, int32_t* __restrict__ ccnt, int capc,
+    int64_t chunk_rows, int64_t chunk_stride, int nchunks, int nqb, float* __restrict__ dv, int64_t dv_stride,
+    const int32_t* __restrict__ qbflag) {
+  using S = Shape<KS>;
+  using B = BShape<KS>;
+  constexpr int D = S::D, W = S::W, MB = S::MB, QW = S::QW, NE = S::NE, TPS = S::TPS, EOFF = S::EOFF;
+  constexpr int RB = B::RB, PPR = B::PPR, NPC = B::NPC, PL = B::PL, NF = B::NF, UT = B::UT;
+  __shared__ __attribute__((aligned(16))) uint8_t smem[2 * UT];
+  // per-(query, this chunk) list lengths (one row per wave), then each wave's hit stage
+  __shared__ int32_t lcnt[W * QW + (DENSE ? 0 : W * STG)];
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int l = lane_id(), r = l & 31, h = l >> 5;
+  const int L = xcd_logical(blockIdx.x, gridDim.x);
+  const int chunk = L / nqb, qb = L - chunk * nqb;
+  if (chunk >= nchunks) return;
+  if (qbflag && qbflag[qb] == 0) return;
+  const int64_t row0 = (int64_t)chunk * chunk_stride;
+  const int64_t row1 = (row0 + chunk_rows < n) ? row0 + chunk_rows : n;
+  if (row0 >= row1) return;
+  const int nrows = (int)(row1 - row0);
+  const int ntiles = (nrows + GRT - 1) / GRT;
+  const uint32_t sm0 = lds_addr(smem);
+
+  // tile t covers chunk rows [tstart(t), tstart(t) + 32): the last tile of a ragged chunk is shifted back
+  const bool tiny = nrows < GRT;
+  auto tstart = [&](int t) { return tiny ? 0 : (t * GRT < nrows - GRT ? t * GRT : nrows - GRT); };
+  auto lane_valid = [&](int t) { return tiny ? r < nrows : r >= t * GRT - tstart(t); };
+
+  // this thread's pieces: global byte offset inside the tile (rows of a chunk shorter than 32 clamped, so every
+  // load is in bounds) and the LDS byte offset of its first fragment in the unpacked image
+  uint32_t goff[PL], uoff[PL];
+  bool pv[PL];
+#pragma unroll
+  for (int i = 0; i < PL; ++i) {
+    const int p = (int)threadIdx.x + B::NT * i, pc = p < NPC ? p : NPC - 1;
+    const int rr = pc / PPR, c = pc % PPR, rl = tiny && rr > nrows - 1 ? nrows - 1 : rr;
+    pv[i] = p < NPC;
+    goff[i] = (uint32_t)(rl * RB + 16 * c);
+    uoff[i] = (uint32_t)((4 * c * 64 + rr) * 16);
+  }
+  v4i pk[2][PL];  // the packed pieces of the tile being expanded / the tile after it
+  auto load_tile = [&](int t, v4i (&dst)[PL]) {
+    const uint8_t* base = codes + (row0 + tstart(t)) * RB;
+#pragma unroll
+    for (int i = 0; i < PL; ++i) dst[i] = *reinterpret_cast<const v4i*>(base + goff[i]);
+  };
+  // fragment j = 8 i + 2 dw + hh of a tile: code dword dw of piece i, lane half hh
+  auto expand = [&](auto J, const v4i (&src)[PL], uint32_t ub) {
+    constexpr int j = decltype(J)::value, i = j >> 3, dw = (j >> 1) & 3, hh = j & 1;
+    const uint32_t wd = (uint32_t)src[i][dw];
+    v4i f;
+    f.x = (int)((wd >> (4 * hh + 0)) & 0x01010101u);
+    f.y = (int)((wd >> (4 * hh + 1)) & 0x01010101u);
+    f.z = (int)((wd >> (4 * hh + 2)) & 0x01010101u);
+    f.w = (int)((wd >> (4 * hh + 3)) & 0x01010101u);
+    if (pv[i]) lds_write128_imm<dw * 1024 + hh * 512>(ub + uoff[i], f);
+  };
+  load_tile(0, pk[0]);
+  load_tile(ntiles > 1 ? 1 : 0, pk[1]);
+
+  // A fragments of this wave's M-blocks of 32 queries, every k-step -> accumulator file
+  const int qbase = qb * S::QB + w * QW;
+  v4i A[MB][KS];
+#pragma unroll
+  for (int j = 0; j < MB; ++j) {
+    const int8_t* qp = qa + (int64_t)(qbase + 32 * j + r) * D + h * 16;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) A[j][s] = *reinterpret_cast<const v4i*>(qp + s * 32);
+  }
+#pragma unroll
+  for (int j = 0; j < MB; ++j)
+#pragma unroll
+    for (int s = 0; s < KS; ++s) asm volatile("" : "+a"(A[j][s]));
+  // test e of a lane: M-block e >> 4, accumulator register e & 15 -> query row of the wave
+  auto qrow = [&](int e) { return 32 * (e >> 4) + ((e & 3) + 8 * ((e >> 2) & 3) + 4 * h); };
+  v16i seed[MB] = {};  // thresholded pass: -ceil(thr) of each accumulator register's query
+  if constexpr (!DENSE) {
+#pragma unroll
+    for (int e = 0; e < NE; ++e) {
+      const float c = ceilf(thr[qbase + qrow(e)]);  // +-inf / huge thresholds: always / never a hit
+      seed[e >> 4][e & 15] = c <= -1073741824.f ? 1073741824 : c >= 1073741824.f ? -1073741824 : -(int)c;
+    }
+  }
+
+  const uint32_t lc0 = lds_addr(lcnt + w * QW);
+  const uint32_t sg0 = lds_addr(lcnt + W * QW + (DENSE ? 0 : w * STG));  // this wave's hit stage
+  int nst = 0;                                                         // staged entries (wave-uniform)
+  if (!DENSE && l < QW) lcnt[w * QW + l] = 0;                          // visible after the first tile's barrier
+  v16i acc[2][MB] = {};                                                // [tile parity][M-block]
+  int imx[DENSE ? NE : 1];  // dense pass: running max of u per test (INT32_MIN: no row yet)
+#pragma unroll
+  for (int e = 0; e < (DENSE ? NE : 1); ++e) imx[e] = INT32_MIN;
+  int imax = INT32_MIN;     // thresholded pass: max of the seeded accumulators of the tile being tested
+  const int64_t qstride = (int64_t)nchunks * capc;
+
+  auto to_list = [&](int ql, int cr) {  // as k5md_pass_kernel: a list past capc keeps counting (= overflow)
+    int pos;
+    lds_add_rtn32(pos, lc0 + (uint32_t)(ql * 4), 1);
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(pos)::"memory");
+    if (pos < capc) cand[(int64_t)(qbase + ql) * qstride + (int64_t)chunk * capc + pos] = (uint32_t)(row0 + cr);
+  };
+  auto drain = [&]() {  // the staged entries -> lists (once per chunk, or when the stage is nearly full)
+    for (int i0 = 0; i0 < nst; i0 += 64) {
+      const int i = i0 + l;
+      int e = 0;
+      if (i < nst) lds_read32(e, sg0 + (uint32_t)(i * 4));
+      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(e)::"memory");
+      if (i < nst) to_list((int)((uint32_t)e >> 26), e & 0x3ffffff);
+    }
+    nst = 0;
+  };
+  // the hits of tile tt, whose seeded accumulators are a: nothing to do unless the tile's max is non-negative
+  auto flush = [&](int tt, const v16i (&a)[MB]) {
+    const bool any = __ballot(imax >= 0) != 0;
+    imax = INT32_MIN;
+    if (!any) return;
+    uint32_t m = 0;
+    static_for<0, NE>([&](auto E) {
+      constexpr int e = decltype(E)::value;
+      m |= (a[e >> 4][e & 15] >= 0 ? 1u : 0u) << e;
+    });
+    if (!lane_valid(tt)) m = 0;
+    if (__ballot(m != 0) == 0) return;
+    const int lr = tstart(tt) + r;
+    if (!__ballot((m & (m - 1)) != 0)) {
+      // at most one hit per lane (the usual case): one staged entry per hit lane at its rank among them
+      const uint64_t lanes = __ballot(m != 0);
+      if (m) {
+        int pos = nst + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(lanes >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lanes, 0));
+        pos = pos < STG - 1 ? pos : STG - 1;  // (never binds: the stage drains above STG - 64)
+        lds_write32(sg0 + (uint32_t)(pos * 4), (int)(((uint32_t)qrow(__builtin_ctz(m)) << 26) | (uint32_t)lr));
+      }
+      nst += __popcll(lanes);
+      if (nst > STG - 64) drain();
+    } else {
+      for (int e = 0; e < NE; ++e)  // several hits in a lane: straight to the lists
+        if ((m >> e) & 1u) to_list(qrow(e), lr);
+    }
+  };
+  auto test = [&](const v16i (&a)[MB], int e, bool vp) {
+    const int v = a[e >> 4][e & 15];
+    if constexpr (DENSE)
+      imx[e] = max(imx[e], vp ? v : INT32_MIN);
+    else
+      imax = max(imax, v);
+  };
+
+  // tile 0 -> slot 0 (tile t + 1 is expanded during tile t)
+  static_for<0, NF>([&](auto J) { expand(J, pk[0], sm0); });
+
+  auto tile = [&](auto PAR, auto FIRST, int t) {
+    constexpr int p = decltype(PAR)::value;
+    constexpr bool first = decltype(FIRST)::value;  // tile 0: no previous tile to test
+    // every wave's fragments of tile t are written, and every wave is done reading the slot that tile t + 1's
+    // fragments overwrite
+    wait_lgkm0();
+    barrier_all();
+    if constexpr (!DENSE)
+      if (t >= 2) flush(t - 2, acc[p]);  // (its accumulators are acc[p] until this tile's first MFMA)
+    const bool vprev = lane_valid(t - 1);
+    load_tile(t + 2 < ntiles ? t + 2 : ntiles - 1, pk[p]);  // pk[p] held tile t; pk[p ^ 1] holds tile t + 1
+    const uint32_t badr = sm0 + (uint32_t)(p * UT + l * 16), ubn = sm0 + (uint32_t)((p ^ 1) * UT);
+    v4i ring[NR];
+    auto readB = [&](auto SS) {
+      constexpr int s = decltype(SS)::value;
+      lds_read128_off<s * 1024>(ring[s & (NR - 1)], badr);
+    };
+    static_for<0, BAB>([&](auto SS) { readB(SS); });
+    VRQ_SCHED_FENCE();
+    static_for<0, KS>([&](auto SS) {
+      constexpr int s = decltype(SS)::value;
+      if constexpr (s + BAB < KS) readB(std::integral_constant<int, s + BAB>{});
+      // At most the B reads issued after B(s) stay outstanding.  A wave with a piece also has the fragment
+      // writes of the k-steps in between in flight, which a wave without one never issues: the count holds
+      // for both, and in the first it retires a read or two early (hence BAB = 3 reads ahead, not K5md's 2).
+      asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(ring[s & (NR - 1)]) : "n"(s + BAB < KS ? BAB : KS - 1 - s) : "memory");
+#pragma unroll
+      for (int j = 0; j < MB; ++j)
+        acc[p][j] = mfma_i8(A[j][s], ring[s & (NR - 1)], s == 0 ? seed[j] : acc[p][j]);
+#pragma unroll
+      for (int j = 0; j < MB; ++j) asm volatile("" : "+v"(acc[p][j]));
+      if constexpr (s < NF) expand(SS, pk[p ^ 1], ubn);
+      // tests / dense maxima of tile t-1
+      if constexpr (!first && s >= EOFF && (s - EOFF) * TPS < NE) {
+#pragma unroll
+        for (int e = (s - EOFF) * TPS; e < (s - EOFF + 1) * TPS && e < NE; ++e) {
+          test(acc[p ^ 1], e, vprev);
+          // pin the test at this k-step (IR-level sinking would gather them behind the last MFMA)
+          if constexpr (DENSE)
+            asm volatile("" : "+v"(imx[e]));
+          else
+            asm volatile("" : "+v"(imax));
+        }
+      }
+      VRQ_SCHED_FENCE();
+    });
+  };
+
+  using I0 = std::integral_constant<int, 0>;
+  using I1 = std::integral_constant<int, 1>;
+  using NOTFIRST = std::integral_constant<bool, false>;
+  tile(I0{}, std::integral_constant<bool, true>{}, 0);
+  int t = 1;
+  for (; t + 1 < ntiles; t += 2) {
+    tile(I1{}, NOTFIRST{}, t);
+    tile(I0{}, NOTFIRST{}, t + 1);
+  }
+  if (t < ntiles) tile(I1{}, NOTFIRST{}, t);
+  wait_lgkm0();
+  // tile ntiles-2 (tested during the last tile), then the last tile itself
+  const int pl = (ntiles - 1) & 1;
+  if (!DENSE && ntiles >= 2) {
+    if (pl)
+      flush(ntiles - 2, acc[0]);
+    else
+      flush(ntiles - 2, acc[1]);
+  }
+  const bool vlast = lane_valid(ntiles - 1);
+#pragma unroll
+  for (int e = 0; e < NE; ++e) {
+    if (pl)
+      test(acc[1], e, vlast);
+    else
+      test(acc[0], e, vlast);
+  }
+  if constexpr (DENSE) {  // the lane maxima of the chunk -> dv[q][chunk * 32 + r] (NaN: no row)
+#pragma unroll
+    for (int e = 0; e < NE; ++e) {
+      const int q = qbase + qrow(e);
+      if (q < nq)
+        dv[(int64_t)q * dv_stride + (int64_t)chunk * GRT + r] = imx[e] == INT32_MIN ? __builtin_nanf("") : (float)imx[e];
+    }
+  } else {
+    if (pl)
+      flush(ntiles - 1, acc[1]);
+    else
+      flush(ntiles - 1, acc[0]);
+    drain();
+    wait_lgkm0();
+    if (l < QW && qbase + l < nq) ccnt[(int64_t)(qbase + l) * nchunks + chunk] = lcnt[w * QW + l];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The binary score of one row for the query whose nibble table is tab (binary_table): tab[p * 16 + v] = the
+// f64 sum over the 4 dims of nibble p (packbits MSB first) of (bit of v ? q : -q); the row's d / 4 table
+// entries are added in nibble order.  One function for the finish and for the exact scan.
+__device__ __forceinline__ void binary_table(const float* __restrict__ q, int dim, double* tab) {
+  for (int e = threadIdx.x; e < dim * 4; e += blockDim.x) {
+    const int p = e >> 4, v = e & 15;
+    double t = 0.0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const double x = (double)q[4 * p + b];
+      t += ((v >> (3 - b)) & 1) ? x : -x;
+    }
+    tab[e] = t;
+  }
+}
+__device__ __forceinline__ double binary_score_dim(const double* tab, const uint8_t* __restrict__ code_row, int dim) {
+  const uint4* src = reinterpret_cast<const uint4*>(code_row);
+  double s = 0.0;
+  for (int i = 0; i < dim / 128; ++i) {
+    const uint4 cw = src[i];
+    const uint32_t wd[4] = {cw.x, cw.y, cw.z, cw.w};
+    const double* t = tab + i * 512;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {  // byte 16 i + 4 k + c: nibbles 2 b, 2 b + 1
+        const uint32_t byte = (wd[k] >> (8 * c)) & 0xffu;
+        s += t[(4 * k + c) * 32 + (byte >> 4)];
+        s += t[(4 * k + c) * 32 + 16 + (byte & 15)];
+      }
+  }
+  return s;
+}
+
+// Running exact top-k over the code rows row_at(j), j < count, one row per thread; K5md's admission and
+// batches.  All threads call it; returns kc = min(k, count).
+template <class RowAt>
+__device__ int running_topk_b(int64_t count, RowAt row_at, const uint8_t* __restrict__ codes, int dim,
+                              const double* tab, int k, FinF& sh) {
+  const int tid = threadIdx.x;
+  if (tid == 0) sh.fill = 0;
+  int kc = 0;
+  __syncthreads();
+  for (int64_t base = 0; base < count; base += FB_BATCH) {
+    const uint64_t kk = kc == k ? sh.key[k - 1] : KEY_NONE;
+    const uint32_t kr = kc == k ? sh.row[k - 1] : 0xffffffffu;
+    const int64_t end = base + FB_BATCH < count ? base + FB_BATCH : count;
+    for (int64_t j = base + tid; j < end; j += FIN_NT) {
+      const uint32_t rr = row_at(j);
+      const uint64_t key_r = desc_key_f64(binary_score_dim(tab, codes + (int64_t)rr * (dim / 8), dim));
+      if (kc < k || key_r < kk || (key_r == kk && rr < kr)) {
+        const int i = kc + atomicAdd(&sh.fill, 1);
+        sh.key[i] = key_r;
+        sh.row[i] = rr;
+      }
+    }
+    __syncthreads();
+    const int f = sh.fill;
+    if (f > 0) {
+      const int tot = kc + f, np2 = next_pow2(tot);
+      for (int i = tot + tid; i < np2; i += FIN_NT) {
+        sh.key[i] = KEY_NONE;
+        sh.row[i] = 0xffffffffu;
+      }
+      sort_pairs(sh.key, sh.row, np2);
+      kc = tot < k ? tot : k;
+    }
+    __syncthreads();
+    if (tid == 0) sh.fill = 0;
+    __syncthreads();
+  }
+  return kc;
+}
+
+// finish: k5md_finish_kernel's contract and flags over code rows
+template <bool RETRY>
+__global__ __launch_bounds__(FIN_NT) void k5mb_finish_kernel(
+    const uint8_t* __restrict__ codes, int64_t n, int dim, int64_t row_offset, const float* __restrict__ qf, int k,
+    const uint32_t* __restrict__ cand, const int32_t* __restrict__ ccnt, int nchunks, int capc, int qpb,
+    int32_t* __restrict__ out_count, int64_t* __restrict__ out_rows, double* __restrict__ out_scores,
+    int32_t* __restrict__ fb_flag, float* __restrict__ thr, const double* __restrict__ alpha,
+    const double* __restrict__ beta, const double* __restrict__ delta, int32_t* __restrict__ qbflag) {
+  __shared__ FinF sh;
+  __shared__ double tab[2048 * 4];
+  const int q = blockIdx.x, tid = threadIdx.x;
+  if (RETRY && fb_flag[q] != 2) return;
+  if (tid == 0) sh.over = 0;
+  __syncthreads();
+  const int32_t* cq = ccnt + (int64_t)q * nchunks;
+  for (int c = tid; c < nchunks; c += FIN_NT) {
+    const int x = cq[c];
+    if (x > capc) sh.over = 1;
+    sh.pre[c + 1] = x < capc ? x : capc;
+  }
+  binary_table(qf + (int64_t)q * dim, dim, tab);
+  __syncthreads();
+  if (tid < WAVE) {  // inclusive scan of pre[1 .. nchunks] by one wave: 32 entries per lane, then the lanes
+    constexpr int PER = MAX_CHUNKS / WAVE;
+    int part = 0;
+    for (int i = 0; i < PER; ++i) {
+      const int c = tid * PER + i;
+      if (c < nchunks) part += sh.pre[c + 1];
+    }
+    int incl = part;
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+      const int y = __shfl_up(incl, d, WAVE);
+      if (tid >= d) incl += y;
+    }
+    int run = incl - part;
+    for (int i = 0; i < PER; ++i) {
+      const int c = tid * PER + i;
+      if (c < nchunks) {
+        run += sh.pre[c + 1];
+        sh.pre[c + 1] = run;
+      }
+    }
+    if (tid == 0) sh.pre[0] = 0;
+  }
+  __syncthreads();
+  const int total = sh.pre[nchunks];
+  const int need = (int)((int64_t)k < n ? k : n);
+  const bool over = sh.over != 0;
+  if (total < need || (RETRY && over)) {
+    if (tid == 0) {
+      fb_flag[q] = 1;
+      thr[q] = __builtin_inff();
+    }
+    return;
+  }
+  const uint32_t* Cq = cand + (int64_t)q * nchunks * capc;
+  // candidate j of the concatenated lists: the largest chunk lo with pre[lo] <= j (fixed 11 steps)
+  auto row_at = [&](int64_t j) {
+    int lo = 0;
+#pragma unroll
+    for (int st = MAX_CHUNKS / 2; st > 0; st >>= 1) {
+      const int mid = lo + st;
+      if (mid < nchunks && sh.pre[mid] <= j) lo = mid;
+    }
+    return Cq[(int64_t)lo * capc + (j - sh.pre[lo])];
+  };
+  const int kc = running_topk_b(total, row_at, codes, dim, tab, k, sh);
+  if (!RETRY && over) {
+    if (tid == 0) {
+      const double t2 = alpha[q] * desc_key_inv(sh.key[kc - 1]) + beta[q] - delta[q];
+      thr[q] = __double2float_rd(t2 - 1e-9 * fabs(t2));
+      fb_flag[q] = 2;
+      atomicOr(&qbflag[q / qpb], 1);
+    }
+    return;
+  }
+  write_result_f(q, k, kc, row_offset, sh, out_count, out_rows, out_scores);
+  if (tid == 0) {
+    fb_flag[q] = 0;
+    thr[q] = __builtin_inff();
+  }
+}
+
+// the exact scan of the flagged queries: every row through the same score function
+__global__ __launch_bounds__(FIN_NT) void k5mb_fallback_kernel(
+    const uint8_t* __restrict__ codes, int64_t n, int dim, int64_t row_offset, const float* __restrict__ qf, int k,
+    int32_t* __restrict__ out_count, int64_t* __restrict__ out_rows, double* __restrict__ out_scores,
+    const int32_t* __restrict__ fb_flag, bool skip) {
+  __shared__ FinF sh;
+  __shared__ double tab[2048 * 4];
+  const int q = blockIdx.x, tid = threadIdx.x;
+  if (fb_flag[q] != 1) return;
+  if (skip) {
+    for (int i = tid; i < k; i += FIN_NT) {
+      out_rows[(int64_t)q * k + i] = -1;
+      out_scores[(int64_t)q * k + i] = __builtin_nan("");
+    }
+    if (tid == 0) out_count[q] = -1;
+    return;
+  }
+  binary_table(qf + (int64_t)q * dim, dim, tab);
+  const int kc = running_topk_b(n, [](int64_t j) { return (uint32_t)j; }, codes, dim, tab, k, sh);
+  write_result_f(q, k, kc, row_offset, sh, out_count, out_rows, out_scores);
+}
+
+struct BinaryCall {
+  const uint8_t* codes;
+  int64_t n;
+  const int8_t* qa;
+  int nq;
+  float* thr;
+  uint32_t* cand;
+  int32_t* cnt;
+  float* dv;
+  int32_t* qbf;
+  hipStream_t s;
+};
+
+template <int KS>
+static void launch_binary_pass(const Plan& p, const BinaryCall& c, int pass) {  // 0 sample, 1 main, 2 retry
+  const dim3 blk(Shape<KS>::W * 64);
+  if (pass == 0)
+    hipLaunchKernelGGL((k5mb_pass_kernel<KS, true>), dim3(p.nsc * p.nqb), blk, 0, c.s, c.codes, c.n, c.qa, c.nq,
+                       (const float*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr, 0, p.scr, p.sstride, p.nsc,
+                       p.nqb, c.dv, p.scols, (const int32_t*)nullptr);
+  else
+    hipLaunchKernelGGL((k5mb_pass_kernel<KS, false>), dim3(p.nchunks * p.nqb), blk, 0, c.s, c.codes, c.n, c.qa, c.nq,
+                       (const float*)c.thr, c.cand, c.cnt, p.capc, p.chunk_rows, p.chunk_rows, p.nchunks, p.nqb,
+                       (float*)nullptr, (int64_t)0, pass == 2 ? (const int32_t*)c.qbf : (const int32_t*)nullptr);
+}
+
+static int launch_binary_pass_dim(int dim, const Plan& p, const BinaryCall& c, int pass) {
+  switch (dim) {
+    case 256: launch_binary_pass<8>(p, c, pass); break;
+    case 384: launch_binary_pass<12>(p, c, pass); break;
+    case 512: launch_binary_pass<16>(p, c, pass); break;
+    case 768: launch_binary_pass<24>(p, c, pass); break;
+    case 1536: launch_binary_pass<48>(p, c, pass); break;
+    case 2048: launch_binary_pass<64>(p, c, pass); break;
+    default: return VRQ_EUNSUPPORTED;
+  }
+  VRQ_LAUNCH_CHECK();
+  return VRQ_OK;
+}
+
+static int run_binary(const uint8_t* codes, int64_t n, int dim, int64_t row_offset, const float* qf, int nq, int k,
+                      int flags, int32_t* out_count, int64_t* out_rows, double* out_scores, void* workspace,
+                      size_t workspace_bytes, hipStream_t s) {
+  Plan p;
+  const int rc = plan_shape(n, dim, nq, k, &p);
+  if (rc != VRQ_OK) return rc;
+  if (workspace_bytes < p.bytes) return VRQ_EWORKSPACE;
+  constexpr int ALL = VRQ_GEMM_STAGE_SAMPLE | VRQ_GEMM_STAGE_MAIN | VRQ_GEMM_STAGE_FINISH;
+  const int st = (flags & ALL) ? (flags & ALL) : ALL;
+  uint8_t* ws = (uint8_t*)workspace;
+  int8_t* qa = (int8_t*)ws;
+  double* delta = (double*)(ws + p.off_delta);
+  double* alpha = (double*)(ws + p.off_alpha);
+  double* beta = (double*)(ws + p.off_beta);
+  int32_t* flag = (int32_t*)(ws + p.off_flag);
+  const BinaryCall c{codes, n, qa, nq, (float*)(ws + p.off_thr), (uint32_t*)(ws + p.off_cand),
+                     (int32_t*)(ws + p.off_cnt), (float*)(ws + p.off_dv), (int32_t*)(ws + p.off_qbf), s};
+  if (st & VRQ_GEMM_STAGE_SAMPLE) {
+    hipLaunchKernelGGL(k5mb_prep_kernel, dim3((p.nq_pad + 3) / 4), dim3(256), 0, s, qf, nq, p.nq_pad, dim, qa, delta,
+                       alpha, beta);
+    VRQ_LAUNCH_CHECK();
+    const int r0 = launch_binary_pass_dim(dim, p, c, 0);
+    if (r0 != VRQ_OK) return r0;
+    hipLaunchKernelGGL(k5md_select_kernel, dim3(p.nq_pad), dim3(256), 0, s, (const float*)c.dv, p.scols, p.sstride,
+                       p.nsc, n, k, (const double*)delta, c.thr, c.cnt, p.nchunks, nq, c.qbf, p.nqb);
+    VRQ_LAUNCH_CHECK();
+  }
+  if (st & VRQ_GEMM_STAGE_MAIN) {
+    const int r1 = launch_binary_pass_dim(dim, p, c, 1);
+    if (r1 != VRQ_OK) return r1;
+  }
+  if (st & VRQ_GEMM_STAGE_FINISH) {
+    // finish -> retry main pass (query blocks with a retried query) -> finish of the retried queries ->
+    // exact scan of the rest
+    hipLaunchKernelGGL(k5mb_finish_kernel<false>, dim3(nq), dim3(FIN_NT), 0, s, codes, n, dim, row_offset, qf, k,
+                       (const uint32_t*)c.cand, (const int32_t*)c.cnt, p.nchunks, p.capc, p.qpb, out_count, out_rows,
+                       out_scores, flag, c.thr, (const double*)alpha, (const double*)beta, (const double*)delta, c.qbf);
+    VRQ_LAUNCH_CHECK();
+    const int r2 = launch_binary_pass_dim(dim, p, c, 2);
+    if (r2 != VRQ_OK) return r2;
+    hipLaunchKernelGGL(k5mb_finish_kernel<true>, dim3(nq), dim3(FIN_NT), 0, s, codes, n, dim, row_offset, qf, k,
+                       (const uint32_t*)c.cand, (const int32_t*)c.cnt, p.nchunks, p.capc, p.qpb, out_count, out_rows,
+                       out_scores, flag, c.thr, (const double*)alpha, (const double*)beta, (const double*)delta, c.qbf);
+    VRQ_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k5mb_fallback_kernel, dim3(nq), dim3(FIN_NT), 0, s, codes, n, dim, row_offset, qf, k, out_count,
+                       out_rows, out_scores, (const int32_t*)flag, (flags & VRQ_GEMM_NO_FALLBACK) != 0);
+    VRQ_LAUNCH_CHECK();
+  }
+  return VRQ_OK;
+}
+
+// "auto" of the binary path, K5md's rule: per dim the smallest measured batch (nq = 1, 8, 64, 1024;
+// profiles/binary_mfma_bench.jsonl) at which K5mb's slowest call beat K5d's fastest on the same codes;
+// 0 = no such batch measured, the dim stays on K5d
+__host__ inline int min_batch_binary(int dim) {
+  switch (dim) {
+    case 256: case 384: case 512: case 768: case 1536: case 2048:
+      return 8;  // 3.1x-8.7x at nq = 8, 0.51x-0.77x at nq = 1
+    default: return 0;
+  }
+}
+
 }  // namespace g5d
 }  // namespace vrq
 
@@ -1526,6 +2160,67 @@ int vrq_flat_ip_dim_engine(int64_t n, int32_t dim, int32_t nq, int32_t k) {
   if (dim == 1024 || g5d::plan_float(n, dim, nq, k, &p) != VRQ_OK) return VRQ_GEMM_ENGINE_EXACT;
   const int mb = g5d::min_batch_float(dim);
   return mb > 0 && nq > 1 && nq >= mb ? VRQ_GEMM_ENGINE_MFMA : VRQ_GEMM_ENGINE_EXACT;
+}
+
+size_t vrq_binary_topk_dim_mfma_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t k) {
+  if (dim == 1024) return vrq_gemm_topk_workspace_size(VRQ_GEMM_BINARY, n, dim, nq, k);
+  g5d::Plan p;
+  return g5d::plan_shape(n, dim, nq, k, &p) == VRQ_OK ? p.bytes : 0;
+}
+
+int vrq_binary_topk_dim_mfma_plan(int64_t n, int32_t dim, int32_t nq, int32_t k, int64_t* info) {
+  if (!info) return VRQ_EINVAL;
+  if (dim == 1024) return vrq_gemm_topk_plan(VRQ_GEMM_BINARY, n, dim, nq, k, info);
+  g5d::Plan p;
+  const int rc = g5d::plan_shape(n, dim, nq, k, &p);
+  if (rc != VRQ_OK) return rc;
+  info[0] = p.chunk_rows;
+  info[1] = p.nchunks;
+  info[2] = p.capc;
+  info[3] = p.nqb;
+  info[4] = p.nsc;
+  info[5] = p.scr;
+  info[6] = (int64_t)p.bytes;
+  info[7] = p.qpb;
+  return VRQ_OK;
+}
+
+int vrq_binary_topk_dim_mfma_prep_layout(int64_t n, int32_t dim, int32_t nq, int32_t k, int64_t* info) {
+  if (!info) return VRQ_EINVAL;
+  if (dim == 1024) return VRQ_EUNSUPPORTED;  // K5's: vrq_gemm_topk_prep_layout / vrq_gemm_topk_layout
+  g5d::Plan p;
+  const int rc = g5d::plan_shape(n, dim, nq, k, &p);
+  if (rc != VRQ_OK) return rc;
+  info[0] = (int64_t)p.off_delta;
+  info[1] = (int64_t)p.off_alpha;
+  info[2] = (int64_t)p.off_beta;
+  info[3] = (int64_t)p.off_flag;
+  info[4] = (int64_t)p.off_thr;
+  info[5] = p.nq_pad;
+  info[6] = (int64_t)p.off_cnt;
+  info[7] = (int64_t)p.off_cand;
+  return VRQ_OK;
+}
+
+int vrq_binary_topk_dim_mfma(const uint8_t* codes, int64_t n, int32_t dim, int64_t row_offset, const float* qf,
+                             int32_t nq, int32_t k, int32_t flags, int32_t* out_count, int64_t* out_rows,
+                             double* out_scores, void* workspace, size_t workspace_bytes, void* stream) {
+  constexpr int OK = VRQ_GEMM_STAGE_SAMPLE | VRQ_GEMM_STAGE_MAIN | VRQ_GEMM_STAGE_FINISH | VRQ_GEMM_NO_FALLBACK;
+  if (flags & ~OK) return VRQ_EUNSUPPORTED;
+  if (dim == 1024)
+    return vrq_gemm_topk(VRQ_GEMM_BINARY, codes, nullptr, nullptr, n, dim, row_offset, qf, nq, k, flags, out_count,
+                         out_rows, out_scores, workspace, workspace_bytes, stream);
+  if (!vrq_dim_supported(dim)) return VRQ_EUNSUPPORTED;
+  VRQ_CHECK_ARG(codes && qf && out_count && out_rows && out_scores && workspace && n > 0 && nq > 0 && k > 0);
+  return g5d::run_binary(codes, n, dim, row_offset, qf, nq, k, flags, out_count, out_rows, out_scores, workspace,
+                         workspace_bytes, (hipStream_t)stream);
+}
+
+int vrq_binary_topk_dim_engine(int64_t n, int32_t dim, int32_t nq, int32_t k) {
+  g5d::Plan p;
+  if (dim == 1024 || g5d::plan_shape(n, dim, nq, k, &p) != VRQ_OK) return VRQ_GEMM_ENGINE_EXACT;
+  const int mb = g5d::min_batch_binary(dim);
+  return mb > 0 && nq >= mb ? VRQ_GEMM_ENGINE_MFMA : VRQ_GEMM_ENGINE_EXACT;
 }
 
 }  // extern "C"

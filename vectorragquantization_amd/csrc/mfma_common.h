@@ -174,4 +174,13 @@ __device__ __forceinline__ void lds_add_rtn32(int& d, uint32_t a, int v) {
 }
 #define VRQ_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
 
+// Phase-II k-permutation inside a 32-dim k-step: fragment byte j = 4t + b of lane half h holds
+// bit 8b + t + 4h of the little-endian code dword (so a dword of the fragment is (w >> (t+4h)) &
+// 0x01010101, two VALU ops), i.e. packbits dim 8b + 7 - (t + 4h) of the step.
+__host__ __device__ constexpr int ph2_pos(int dim_in_step) {
+  const int b = dim_in_step >> 3, x = 7 - (dim_in_step & 7);  // byte, bit within the byte
+  const int h = x >> 2, t = x & 3;
+  return h * 16 + 4 * t + b;
+}
+
 }  // namespace vrq

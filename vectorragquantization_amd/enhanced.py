@@ -73,9 +73,10 @@ def gemm_topk(mode: str, qf: torch.Tensor, k: int, codes: torch.Tensor | None = 
     exhaustive scan (K5d); same return contract.  ``flags``: VRQ_GEMM_STAGE_* / VRQ_GEMM_NO_FALLBACK; ``lib``:
     another build of the library (the probe build, for sweeps), default libvrq.so.  ``engine``: None keeps
     that route; "exact" is K5d (``vrq_gemm_topk_dim``); "mfma" is the matrix-core pipeline at every dim (K5md,
-    ``vrq_gemm_topk_dim_mfma``: int8_cosine only, takes the stage flags); "auto" asks
-    ``vrq_gemm_topk_dim_engine``, which picks K5md from a measured minimum batch per dim and otherwise leaves
-    the call on the ``engine=None`` route (so "auto" at 1024 is K5, never the exact scan)."""
+    ``vrq_gemm_topk_dim_mfma``, for int8_cosine; K5mb, ``vrq_binary_topk_dim_mfma``, for binary; both take the
+    stage flags); "auto" asks ``vrq_gemm_topk_dim_engine`` / ``vrq_binary_topk_dim_engine``, which pick the
+    matrix path from a measured minimum batch per dim and otherwise leave the call on the ``engine=None``
+    route (so "auto" at 1024 is K5, never the exact scan)."""
     if engine not in (None, "exact", "mfma", "auto"):
         raise ValueError(f"engine {engine!r}: None, 'exact', 'mfma' or 'auto'")
     m = {"binary": N.VRQ_GEMM_BINARY, "int8_cosine": N.VRQ_GEMM_INT8_COSINE}[mode]
@@ -87,7 +88,18 @@ def gemm_topk(mode: str, qf: torch.Tensor, k: int, codes: torch.Tensor | None = 
     scores = torch.empty((nq, k), dtype=torch.float64, device=dev)
     lib = lib or N.load()
     dim = qf.shape[1]
-    engine = N.gemm_topk_engine(lib, m, n, dim, nq, k, engine)
+    if m == N.VRQ_GEMM_BINARY:
+        engine = N.binary_topk_engine(lib, n, dim, nq, k, engine)
+        if engine == "mfma":
+            need = N.binary_topk_dim_mfma_workspace(lib, n, dim, nq, k)
+            if workspace is None or workspace.numel() < need:
+                workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+            N.check(lib.vrq_binary_topk_dim_mfma(N.ptr(codes), n, dim, row_offset, N.ptr(qf), nq, k, flags,
+                                                 N.ptr(cnt), N.ptr(rows), N.ptr(scores), N.ptr(workspace),
+                                                 workspace.numel(), N.stream_handle(dev)), "vrq_binary_topk_dim_mfma")
+            return cnt, rows, scores
+    else:
+        engine = N.gemm_topk_engine(lib, m, n, dim, nq, k, engine)
     if engine == "mfma":
         need = N.gemm_topk_dim_mfma_workspace(lib, m, n, dim, nq, k)
         if workspace is None or workspace.numel() < need:
