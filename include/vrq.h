@@ -612,6 +612,53 @@ int vrq_binary_topk_dim_mfma(const uint8_t* codes, int64_t n, int32_t dim, int64
 int vrq_binary_topk_dim_engine(int64_t n, int32_t dim, int32_t nq, int32_t k);
 
 /* ---------------------------------------------------------------------------
+ * Filtered exhaustive top-k on the matrix cores over a list of allowed rows (additive to ABI version 1;
+ * every function above keeps its contract).  K5g: the pipelines of K5md (int8 cosine) and K5mf (float inner
+ * product) run in the virtual row space [0, m) of the list -- the plan, the chunks, the sample and the
+ * candidate lists are those of an unfiltered call on m rows -- and only the tiles' DMA source addresses, the
+ * finishes and the exact scans go through rows[]; rows that are not listed are never read.
+ * vrq_row_list: allow u64 [ceil(n / 64)] (row r = bit r & 63 of word r >> 6, the bitmap of the *_filtered
+ * calls; 8-byte aligned; bits at or past n are ignored) -> rows u32 [m], the allowed rows below n in
+ * ascending order, and *out_m = m (a device int64).  Popcount prefix sums, no atomics: the list is
+ * deterministic.  rows == NULL: count only (size the buffer from *out_m, then call again); otherwise at
+ * most rows_cap entries are written.  1 <= n < 2^32 (else VRQ_EUNSUPPORTED); workspace of
+ * vrq_row_list_workspace_size(n) bytes (0 for an unsupported n), 8-byte aligned.
+ * vrq_gemm_topk_rows: the arguments of vrq_gemm_topk_dim_mfma with (rows, m) after row_offset; n is the row
+ * count of x8 / norms.  Serves VRQ_GEMM_INT8_COSINE at every dim of vrq_dim_supported, 1024 included (K5md's
+ * KS = 32 instance; K5 has no gather).  VRQ_GEMM_BINARY returns VRQ_EUNSUPPORTED (K5mb loads packed tiles
+ * into registers and needs a gather of its own), VRQ_GEMM_FLOAT_IP VRQ_EINVAL.  codes is ignored.
+ * vrq_flat_ip_topk_rows: the arguments of vrq_flat_ip_topk_dim_mfma with (rows, m) after row_offset; xf, x8,
+ * inv_scale and bounds are required and are the whole corpus's (bounds stay valid upper bounds for a
+ * subset).
+ * Preconditions of both (not checked: the list lives on the device): rows strictly ascending, every entry
+ * < n, 0 <= m <= n.  1 <= k <= 1024, 1 <= m < 2^32 rows.  flags: 0, or a subset of VRQ_GEMM_STAGE_* under
+ * vrq_gemm_topk's ordering contract, optionally | VRQ_GEMM_NO_FALLBACK; anything else VRQ_EUNSUPPORTED.
+ * Outputs: bit-identical to vrq_gemm_topk_dim_mfma / vrq_flat_ip_topk_dim_mfma (at 1024: to the same
+ * pipelines' KS = 32 instances) on the gathered copy of the listed rows with their norms / scales, each
+ * returned row j replaced by row_offset + rows[j]; ties (score desc, row asc) in physical rows.  m < k:
+ * out_count = m.  m == 0: nothing but a fill is launched, out_count = 0 with -1 / NaN slots, and rows,
+ * workspace and the corpus pointers may be NULL.
+ * vrq_*_rows_workspace_size / _plan: of the call on a list of m rows = plan_shape(m, dim, nq, k), field for
+ * field vrq_gemm_topk_dim_mfma_plan's for n = m at the dims other than 1024 (queries per block at 1024: 128, the 4-wave shape);
+ * m == 0 answers as m == 1.
+ * ------------------------------------------------------------------------- */
+size_t vrq_row_list_workspace_size(int64_t n);
+int vrq_row_list(const uint64_t* allow, int64_t n, uint32_t* rows, int64_t rows_cap, int64_t* out_m,
+                 void* workspace, size_t workspace_bytes, void* stream);
+size_t vrq_gemm_topk_rows_workspace_size(int32_t mode, int64_t m, int32_t dim, int32_t nq, int32_t k);
+int vrq_gemm_topk_rows_plan(int32_t mode, int64_t m, int32_t dim, int32_t nq, int32_t k, int64_t* info);
+int vrq_gemm_topk_rows(int32_t mode, const uint8_t* codes, const int8_t* x8, const double* norms, int64_t n,
+                       int32_t dim, int64_t row_offset, const uint32_t* rows, int64_t m, const float* qf, int32_t nq,
+                       int32_t k, int32_t flags, int32_t* out_count, int64_t* out_rows, double* out_scores,
+                       void* workspace, size_t workspace_bytes, void* stream);
+size_t vrq_flat_ip_topk_rows_workspace_size(int64_t m, int32_t dim, int32_t nq, int32_t k);
+int vrq_flat_ip_topk_rows_plan(int64_t m, int32_t dim, int32_t nq, int32_t k, int64_t* info);
+int vrq_flat_ip_topk_rows(const float* xf, const int8_t* x8, const double* inv_scale, const double* bounds, int64_t n,
+                          int32_t dim, int64_t row_offset, const uint32_t* rows, int64_t m, const float* qf,
+                          int32_t nq, int32_t k, int32_t flags, int32_t* out_count, int64_t* out_rows,
+                          double* out_scores, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Search with more than 1024 Phase-I candidates (additive to ABI version 1; every function above keeps
  * its K <= 1024 contract and its VRQ_EUNSUPPORTED beyond it).  FAISS IndexBinaryFlat::search takes any k,
  * and K = min(k * binary_oversample, ntotal) passes 1024 at k = 103 with the default oversample of 10.

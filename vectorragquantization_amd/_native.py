@@ -188,6 +188,16 @@ SIGNATURES = {
     "vrq_binary_topk_dim_engine": (C.c_int, [_I64, _I32, _I32, _I32]),
     "vrq_flat_ip_topk": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I64, _P, _I32, _I32, _I32, _P, _P, _P, _P, _SZ,
                                    _P]),
+    "vrq_row_list_workspace_size": (_SZ, [_I64]),
+    "vrq_row_list": (C.c_int, [_P, _I64, _P, _I64, _P, _P, _SZ, _P]),
+    "vrq_gemm_topk_rows_workspace_size": (_SZ, [_I32, _I64, _I32, _I32, _I32]),
+    "vrq_gemm_topk_rows_plan": (C.c_int, [_I32, _I64, _I32, _I32, _I32, _P]),
+    "vrq_gemm_topk_rows": (C.c_int, [_I32, _P, _P, _P, _I64, _I32, _I64, _P, _I64, _P, _I32, _I32, _I32, _P, _P, _P,
+                                     _P, _SZ, _P]),
+    "vrq_flat_ip_topk_rows_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
+    "vrq_flat_ip_topk_rows_plan": (C.c_int, [_I64, _I32, _I32, _I32, _P]),
+    "vrq_flat_ip_topk_rows": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I64, _P, _I64, _P, _I32, _I32, _I32, _P, _P,
+                                        _P, _P, _SZ, _P]),
 }
 
 

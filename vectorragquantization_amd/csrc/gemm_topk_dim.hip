@@ -58,7 +58,10 @@ __host__ __device__ constexpr int swz(int cpr, int rr) { return cpr % 16 == 0 ? 
 template <int KS>
 struct Shape {
   static constexpr int D = 32 * KS, CPR = D / 16;
-  static constexpr int W = KS > 32 ? 4 : 8;    // waves: two per SIMD while 32 queries' fragments fit beside them
+  // waves: two per SIMD while 32 queries' fragments fit beside them.  KS = 32 exists for the gathered calls alone
+  // (unfiltered 1024 is K5's): its thresholded 8-wave instance needs 3 registers more than the 128 it has beside
+  // the 128 fragment registers once the list entries are live, so it takes the 4-wave shape
+  static constexpr int W = KS >= 32 ? 4 : 8;
   static constexpr int MB = KS <= 8 ? 2 : 1;   // M-blocks of 32 queries per wave
   static constexpr int QW = 32 * MB, QB = W * QW, NE = 16 * MB;
   static constexpr int XB = CPR % 16 == 0 ? 4 : 3;  // chunk-index bits the swizzle touches
@@ -79,6 +82,14 @@ __device__ __forceinline__ void lds_read_f64(double& d, uint32_t a) {
 template <int OFF>
 __device__ __forceinline__ void lds_read128_off(v4i& d, uint32_t a) {
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(a), "n"(OFF) : "memory");
+}
+// the row list of a gathered kernel instance (none: the contiguous instances)
+__device__ __forceinline__ const uint32_t* gather_rows() { return nullptr; }
+__device__ __forceinline__ const uint32_t* gather_rows(const uint32_t* rows) { return rows; }
+// a 4-byte load that the compiler does not wait for: d holds the value after the next wait_vm<0> (which names
+// it "+v"); the destination is an in/out operand, see lds_read128_inplace
+__device__ __forceinline__ void load_u32_async(uint32_t& d, const uint32_t* p) {
+  asm volatile("global_load_dword %0, %1, off" : "+v"(d) : "v"(p) : "memory");
 }
 // monotone u32 image of a float for ascending order; NaN -> 0 (below -inf)
 __device__ __forceinline__ uint32_t fkey(float u) {
@@ -147,13 +158,24 @@ __global__ __launch_bounds__(256) void k5md_prep_kernel(const float* __restrict_
 // The matrix pass.  DENSE = the sample pass (max of u over each lane row's rows of the chunk ->
 // dv[q][chunk * 32 + lane row]) else the thresholded pass (u >= thr[q] -> candidate lists).  Chunk c covers
 // rows [c * chunk_stride, + chunk_rows).  qbflag (retry pass): only query blocks holding a retried query.
-template <int KS, bool DENSE>
+//
+// G... is empty, or one `const uint32_t* rows` (K5g, the gathered pass behind the *_rows calls): the pass then
+// runs in virtual row space -- n = m = the length of the list, and chunks, tiles, the shifted last tile, the
+// clamp of a short chunk and the staged hits are all in virtual rows v -- and only the DMA source addresses go
+// through the list: the piece of tile row rr reads x8 + rows[v] * D, the norm lanes norms + rows[v].  A lane
+// loads the list entry of each of its pieces (and of its norm lane) itself, PPW + 1 four-byte loads per tile
+// from one or two cache lines, into gi[]: tile t + 2's entries are requested right after tile t + 1's piece
+// went out (during tile t), so the wait_vm<0> at the top of tile t + 1 -- which is there for tile t + 1's
+// DMA -- retires them, and the k-loop gets no wait and no cross-lane or LDS operation of its own.
+template <int KS, bool DENSE, class... G>
 __global__ __launch_bounds__(Shape<KS>::W * 64, 1) void k5md_pass_kernel(
     const int8_t* __restrict__ x8, const double* __restrict__ norms, int64_t n, const int8_t* __restrict__ qa, int nq,
     const float* __restrict__ thr, uint32_t* __restrict__ cand, int32_t* __restrict__ ccnt, int capc,
     int64_t chunk_rows, int64_t chunk_stride, int nchunks, int nqb, float* __restrict__ dv, int64_t dv_stride,
-    const int32_t* __restrict__ qbflag) {
+    const int32_t* __restrict__ qbflag, G... gather) {
   using S = Shape<KS>;
+  constexpr bool GATHER = sizeof...(G) != 0;
+  static_assert(sizeof...(G) <= 1, "one row list");
   constexpr int D = S::D, CPR = S::CPR, W = S::W, MB = S::MB, QW = S::QW, NE = S::NE, NA = S::NA, XB = S::XB;
   constexpr int TB = S::TB, PKT = S::PKT, PPW = S::PPW, DS = S::DS, TPS = S::TPS, EOFF = S::EOFF;
   __shared__ __attribute__((aligned(16))) uint8_t smem[2 * PKT];
@@ -185,7 +207,36 @@ __global__ __launch_bounds__(Shape<KS>::W * 64, 1) void k5md_pass_kernel(
     const int g = (w + W * i) * 64 + l, rr = g / CPR, cs = g % CPR;
     loff[i] = (uint32_t)(rr * D + ((cs ^ swz(CPR, rr)) << 4));
   }
+  // K5g: gi[i] = the list entry (physical row) of this lane's tile row of piece i, gi[PPW] that of norm lane
+  // l's row l >> 1, for the tile whose DMA goes out next; gvirt(t, i) = the virtual row it is read from
+  uint32_t gi[GATHER ? PPW + 1 : 1];
+  const uint32_t* const rows = gather_rows(gather...);
+  auto gvirt = [&](int t, int i) {
+    const int rr = i == PPW ? (l >> 1) : (int)(loff[i < PPW ? i : 0] / (uint32_t)D);
+    return row0 + (tiny ? (rr < nrows ? rr : nrows - 1) : tstart(t) + rr);
+  };
+  auto issue_gathered = [&](int slot_i, int i) {  // piece i of the tile gi[] stands for
+    uint8_t* slot = smem + slot_i * PKT;
+    if (i == PPW) {
+      const uint8_t* g = reinterpret_cast<const uint8_t*>(norms + gi[GATHER ? PPW : 0]) + 4 * (l & 1);
+      uint8_t* ld = slot + TB;
+      __builtin_amdgcn_global_load_lds(g, (__attribute__((address_space(3))) void*)ld, 4, 0, 0);
+      return;
+    }
+    const int p = w + W * i;
+    if (p >= KS) return;
+    const uint32_t lo = loff[i < PPW ? i : 0];
+    const uint8_t* g = reinterpret_cast<const uint8_t*>(x8) + (int64_t)gi[GATHER && i < PPW ? i : 0] * D + lo % (uint32_t)D;
+    uint8_t* ld = slot + p * 1024;
+    __builtin_amdgcn_global_load_lds(g, (__attribute__((address_space(3))) void*)ld, 16, 0, 0);
+  };
   auto issue_piece = [&](int t, int slot_i, int i) {  // whole tiles; i == PPW: the tile's 32 norms
+    if constexpr (GATHER) {
+      issue_gathered(slot_i, i);
+      // the same piece's entry two tiles on (the last tile again past the end: always a row of the list)
+      if (i == PPW || w + W * i < KS) load_u32_async(gi[i], rows + gvirt(t + 1 < ntiles ? t + 1 : ntiles - 1, i));
+      return;
+    }
     const int64_t tr0 = row0 + tstart(t);
     uint8_t* slot = smem + slot_i * PKT;
     // (pointer arguments through locals: a compound expression makes the host pass drop the launch stub)
@@ -219,9 +270,15 @@ __global__ __launch_bounds__(Shape<KS>::W * 64, 1) void k5md_pass_kernel(
     uint8_t* ld = smem + p * 1024;
     __builtin_amdgcn_global_load_lds(g, (__attribute__((address_space(3))) void*)ld, 16, 0, 0);
   };
+  if constexpr (GATHER) {  // tile 0's entries (waited for here), its pieces, then tile 1's entries behind them
+#pragma unroll
+    for (int i = 0; i <= PPW; ++i) gi[i] = (i == PPW || w + W * i < KS) ? rows[gvirt(0, i)] : 0u;
+  }
   static_for<0, PPW + 1>([&](auto I) {
     constexpr int i = decltype(I)::value;
-    if (tiny)
+    if constexpr (GATHER)
+      issue_piece(0, 0, i);
+    else if (tiny)
       issue_tiny(i);
     else
       issue_piece(0, 0, i);
@@ -323,6 +380,10 @@ __global__ __launch_bounds__(Shape<KS>::W * 64, 1) void k5md_pass_kernel(
     // tile t's DMA landed (this wave's part; the barrier covers the other waves'), and every wave is done
     // reading the slot that tile t + 1 overwrites
     wait_vm<0>();
+    if constexpr (GATHER) {  // ... and so did the list entries requested behind it
+#pragma unroll
+      for (int i = 0; i <= PPW; ++i) asm volatile("" : "+v"(gi[i]));
+    }
     barrier_all();
     const uint32_t slot = sm0 + (uint32_t)(sl * PKT);
     const bool dma = t + 1 < ntiles;
@@ -603,15 +664,19 @@ __device__ __forceinline__ void write_result(int q, int k, int kc, int64_t row_o
 // 2 = retry (a list overflowed with >= min(k, n) candidates recorded: the recorded k-th score s_k bounds the
 // true one from below, so thr = alpha s_k + beta - Delta keeps every row of the exact top-k), 1 = exact scan
 // (fewer than min(k, n) candidates, or an overflow in the retry pass).  RETRY serves the retried queries.
-template <bool RETRY>
+// G... as in k5md_pass_kernel: with a row list the lists hold virtual rows, n is the list's length, and row_at
+// hands out rows[v] -- ascending like v, so scores, ties and outputs are those of the physical rows.
+template <bool RETRY, class... G>
 __global__ __launch_bounds__(FIN_NT) void k5md_finish_kernel(
     const int8_t* __restrict__ x8, const double* __restrict__ norms, int64_t n, int dim, int64_t row_offset,
     const float* __restrict__ qf, int k, const uint32_t* __restrict__ cand, const int32_t* __restrict__ ccnt,
     int nchunks, int capc, int qpb, int32_t* __restrict__ out_count, int64_t* __restrict__ out_rows,
     double* __restrict__ out_scores, int32_t* __restrict__ fb_flag, float* __restrict__ thr,
     const double* __restrict__ alpha, const double* __restrict__ beta, const double* __restrict__ delta,
-    int32_t* __restrict__ qbflag) {
+    int32_t* __restrict__ qbflag, G... gather) {
   __shared__ FinShared sh;
+  constexpr bool GATHER = sizeof...(G) != 0;
+  const uint32_t* const rows = gather_rows(gather...);
   const int q = blockIdx.x, tid = threadIdx.x;
   if (RETRY && fb_flag[q] != 2) return;
   if (tid == 0) sh.over = 0;
@@ -668,7 +733,9 @@ __global__ __launch_bounds__(FIN_NT) void k5md_finish_kernel(
       else
         hi = mid - 1;
     }
-    return Cq[(int64_t)lo * capc + (j - sh.pre[lo])];
+    const uint32_t v = Cq[(int64_t)lo * capc + (j - sh.pre[lo])];
+    if constexpr (GATHER) return rows[v];
+    return v;
   };
   const int kc = running_topk(total, row_at, x8, norms, dim, k, sh);
   if (!RETRY && over) {
@@ -689,11 +756,13 @@ __global__ __launch_bounds__(FIN_NT) void k5md_finish_kernel(
 
 // the exact scan of the flagged queries (heavy ties, zero-norm rows): one workgroup per flagged query scores
 // every row; skip (VRQ_GEMM_NO_FALLBACK) reports the query as unserved instead
+template <class... G>
 __global__ __launch_bounds__(FIN_NT) void k5md_fallback_kernel(
     const int8_t* __restrict__ x8, const double* __restrict__ norms, int64_t n, int dim, int64_t row_offset,
     const float* __restrict__ qf, int k, int32_t* __restrict__ out_count, int64_t* __restrict__ out_rows,
-    double* __restrict__ out_scores, const int32_t* __restrict__ fb_flag, bool skip) {
+    double* __restrict__ out_scores, const int32_t* __restrict__ fb_flag, bool skip, G... gather) {
   __shared__ FinShared sh;
+  const uint32_t* const rows = gather_rows(gather...);
   const int q = blockIdx.x, tid = threadIdx.x;
   if (fb_flag[q] != 1) return;
   if (skip) {
@@ -706,7 +775,8 @@ __global__ __launch_bounds__(FIN_NT) void k5md_fallback_kernel(
   }
   for (int i = tid; i < dim; i += FIN_NT) sh.q[i] = qf[(int64_t)q * dim + i];
   __syncthreads();
-  const int kc = running_topk(n, [](int64_t j) { return (uint32_t)j; }, x8, norms, dim, k, sh);
+  const int kc = running_topk(
+      n, [=](int64_t j) { return sizeof...(G) ? rows[j] : (uint32_t)j; }, x8, norms, dim, k, sh);
   write_result(q, k, kc, row_offset, sh, out_count, out_rows, out_scores);
 }
 
@@ -720,8 +790,10 @@ struct Plan {
   size_t off_delta, off_alpha, off_beta, off_qbf, off_thr, off_flag, off_cnt, off_cand, off_dv, bytes;
 };
 
-__host__ inline int queries_per_block(int dim) {
+// (gather: the *_rows calls, which have a KS = 32 instance; unfiltered 1024 is K5's)
+__host__ inline int queries_per_block(int dim, bool gather = false) {
   switch (dim) {
+    case 1024: return gather ? Shape<32>::QB : 0;
     case 256: return Shape<8>::QB;
     case 384: return Shape<12>::QB;
     case 512: return Shape<16>::QB;
@@ -733,8 +805,8 @@ __host__ inline int queries_per_block(int dim) {
 }
 
 // K5's planning rules (gemm_plan) with the query block a function of dim
-__host__ inline int plan_shape(int64_t n, int dim, int nq, int k, Plan* p) {
-  p->qpb = queries_per_block(dim);
+__host__ inline int plan_shape(int64_t n, int dim, int nq, int k, Plan* p, bool gather = false) {
+  p->qpb = queries_per_block(dim, gather);
   if (p->qpb == 0 || n < 1 || n >= (int64_t(1) << 32) || nq < 1 || k < 1 || k > KMAX5) return VRQ_EUNSUPPORTED;
   p->nqb = (nq + p->qpb - 1) / p->qpb;
   p->nq_pad = p->nqb * p->qpb;
@@ -786,7 +858,7 @@ __host__ inline int plan(int mode, int64_t n, int dim, int nq, int k, Plan* p) {
 struct Call {
   const int8_t* x8;
   const double* norms;
-  int64_t n;
+  int64_t n;  // rows the passes cover: the corpus's, or the length of `rows`
   const int8_t* qa;
   int nq;
   float* thr;
@@ -795,12 +867,24 @@ struct Call {
   float* dv;
   int32_t* qbf;
   hipStream_t s;
+  const uint32_t* rows;  // K5g: the allowed rows, ascending (NULL: every row)
 };
 
 template <int KS>
 static void launch_pass(const Plan& p, const Call& c, int pass) {  // 0 sample, 1 main, 2 retry
   const dim3 blk(Shape<KS>::W * 64);
-  if (pass == 0)
+  if (c.rows && pass == 0)
+    hipLaunchKernelGGL((k5md_pass_kernel<KS, true, const uint32_t*>), dim3(p.nsc * p.nqb), blk, 0, c.s, c.x8, c.norms,
+                       c.n, c.qa, c.nq, (const float*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr, 0, p.scr,
+                       p.sstride, p.nsc, p.nqb, c.dv, p.scols, (const int32_t*)nullptr, c.rows);
+  else if (c.rows)
+    hipLaunchKernelGGL((k5md_pass_kernel<KS, false, const uint32_t*>), dim3(p.nchunks * p.nqb), blk, 0, c.s, c.x8,
+                       c.norms, c.n, c.qa, c.nq, (const float*)c.thr, c.cand, c.cnt, p.capc, p.chunk_rows, p.chunk_rows,
+                       p.nchunks, p.nqb, (float*)nullptr, (int64_t)0,
+                       pass == 2 ? (const int32_t*)c.qbf : (const int32_t*)nullptr, c.rows);
+  else if constexpr (KS == 32)
+    return;  // (no contiguous KS = 32 instance: launch_pass_dim refuses the call)
+  else if (pass == 0)
     hipLaunchKernelGGL((k5md_pass_kernel<KS, true>), dim3(p.nsc * p.nqb), blk, 0, c.s, c.x8, c.norms, c.n, c.qa, c.nq,
                        (const float*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr, 0, p.scr, p.sstride, p.nsc,
                        p.nqb, c.dv, p.scols, (const int32_t*)nullptr);
@@ -818,17 +902,22 @@ static int launch_pass_dim(int dim, const Plan& p, const Call& c, int pass) {
     case 768: launch_pass<24>(p, c, pass); break;
     case 1536: launch_pass<48>(p, c, pass); break;
     case 2048: launch_pass<64>(p, c, pass); break;
+    case 1024:  // the gathered calls alone (K5 has no gather)
+      if (!c.rows) return VRQ_EUNSUPPORTED;
+      launch_pass<32>(p, c, pass);
+      break;
     default: return VRQ_EUNSUPPORTED;
   }
   VRQ_LAUNCH_CHECK();
   return VRQ_OK;
 }
 
+// rows != NULL (K5g): n is the length of the list, and the call plans like an unfiltered one on n rows
 static int run(const int8_t* x8, const double* norms, int64_t n, int dim, int64_t row_offset, const float* qf, int nq,
                int k, int flags, int32_t* out_count, int64_t* out_rows, double* out_scores, void* workspace,
-               size_t workspace_bytes, hipStream_t s) {
+               size_t workspace_bytes, hipStream_t s, const uint32_t* rows = nullptr) {
   Plan p;
-  const int rc = plan(VRQ_GEMM_INT8_COSINE, n, dim, nq, k, &p);
+  const int rc = rows ? plan_shape(n, dim, nq, k, &p, true) : plan(VRQ_GEMM_INT8_COSINE, n, dim, nq, k, &p);
   if (rc != VRQ_OK) return rc;
   if (workspace_bytes < p.bytes) return VRQ_EWORKSPACE;
   constexpr int ALL = VRQ_GEMM_STAGE_SAMPLE | VRQ_GEMM_STAGE_MAIN | VRQ_GEMM_STAGE_FINISH;
@@ -840,7 +929,7 @@ static int run(const int8_t* x8, const double* norms, int64_t n, int dim, int64_
   double* beta = (double*)(ws + p.off_beta);
   int32_t* flag = (int32_t*)(ws + p.off_flag);
   const Call c{x8, norms, n, qa, nq, (float*)(ws + p.off_thr), (uint32_t*)(ws + p.off_cand),
-               (int32_t*)(ws + p.off_cnt), (float*)(ws + p.off_dv), (int32_t*)(ws + p.off_qbf), s};
+               (int32_t*)(ws + p.off_cnt), (float*)(ws + p.off_dv), (int32_t*)(ws + p.off_qbf), s, rows};
   if (st & VRQ_GEMM_STAGE_SAMPLE) {
     hipLaunchKernelGGL(k5md_prep_kernel, dim3((p.nq_pad + 3) / 4), dim3(256), 0, s, qf, nq, p.nq_pad, dim, qa, delta,
                        alpha, beta);
@@ -858,18 +947,33 @@ static int run(const int8_t* x8, const double* norms, int64_t n, int dim, int64_
   if (st & VRQ_GEMM_STAGE_FINISH) {
     // finish -> retry main pass (query blocks with a retried query) -> finish of the retried queries ->
     // exact scan of the rest
-    hipLaunchKernelGGL(k5md_finish_kernel<false>, dim3(nq), dim3(FIN_NT), 0, s, x8, norms, n, dim, row_offset, qf, k,
-                       (const uint32_t*)c.cand, (const int32_t*)c.cnt, p.nchunks, p.capc, p.qpb, out_count, out_rows,
-                       out_scores, flag, c.thr, (const double*)alpha, (const double*)beta, (const double*)delta, c.qbf);
+    const bool skip = (flags & VRQ_GEMM_NO_FALLBACK) != 0;
+    auto finish = [&](auto RETRY, auto... g) {
+      hipLaunchKernelGGL((k5md_finish_kernel<decltype(RETRY)::value, decltype(g)...>), dim3(nq), dim3(FIN_NT), 0, s, x8,
+                         norms, n, dim, row_offset, qf, k, (const uint32_t*)c.cand, (const int32_t*)c.cnt, p.nchunks,
+                         p.capc, p.qpb, out_count, out_rows, out_scores, flag, c.thr, (const double*)alpha,
+                         (const double*)beta, (const double*)delta, c.qbf, g...);
+    };
+    auto fallback = [&](auto... g) {
+      hipLaunchKernelGGL((k5md_fallback_kernel<decltype(g)...>), dim3(nq), dim3(FIN_NT), 0, s, x8, norms, n, dim,
+                         row_offset, qf, k, out_count, out_rows, out_scores, (const int32_t*)flag, skip, g...);
+    };
+    if (rows)
+      finish(std::false_type{}, rows);
+    else
+      finish(std::false_type{});
     VRQ_LAUNCH_CHECK();
     const int r2 = launch_pass_dim(dim, p, c, 2);
     if (r2 != VRQ_OK) return r2;
-    hipLaunchKernelGGL(k5md_finish_kernel<true>, dim3(nq), dim3(FIN_NT), 0, s, x8, norms, n, dim, row_offset, qf, k,
-                       (const uint32_t*)c.cand, (const int32_t*)c.cnt, p.nchunks, p.capc, p.qpb, out_count, out_rows,
-                       out_scores, flag, c.thr, (const double*)alpha, (const double*)beta, (const double*)delta, c.qbf);
+    if (rows)
+      finish(std::true_type{}, rows);
+    else
+      finish(std::true_type{});
     VRQ_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k5md_fallback_kernel, dim3(nq), dim3(FIN_NT), 0, s, x8, norms, n, dim, row_offset, qf, k,
-                       out_count, out_rows, out_scores, (const int32_t*)flag, (flags & VRQ_GEMM_NO_FALLBACK) != 0);
+    if (rows)
+      fallback(rows);
+    else
+      fallback();
     VRQ_LAUNCH_CHECK();
   }
   return VRQ_OK;
@@ -1175,14 +1279,16 @@ __device__ __forceinline__ void write_result_f(int q, int k, int kc, int64_t row
 }
 
 // finish: k5md_finish_kernel's contract and flags over float rows
-template <int KS, bool RETRY>
+template <int KS, bool RETRY, class... G>
 __global__ __launch_bounds__(FIN_NT, FShape<KS>::OCC) void k5mf_finish_kernel(
     const float* __restrict__ xf, int64_t n, int64_t row_offset, const float* __restrict__ qf, int k,
     const uint32_t* __restrict__ cand, const int32_t* __restrict__ ccnt, int nchunks, int capc, int qpb,
     int32_t* __restrict__ out_count, int64_t* __restrict__ out_rows, double* __restrict__ out_scores,
     int32_t* __restrict__ fb_flag, float* __restrict__ thr, const double* __restrict__ alpha,
-    const double* __restrict__ beta, const double* __restrict__ delta, int32_t* __restrict__ qbflag) {
+    const double* __restrict__ beta, const double* __restrict__ delta, int32_t* __restrict__ qbflag, G... gather) {
   __shared__ FinF sh;
+  constexpr bool GATHER = sizeof...(G) != 0;
+  const uint32_t* const rows = gather_rows(gather...);
   const int q = blockIdx.x, tid = threadIdx.x;
   if (RETRY && fb_flag[q] != 2) return;
   FSlice<KS> qs;
@@ -1239,7 +1345,9 @@ __global__ __launch_bounds__(FIN_NT, FShape<KS>::OCC) void k5mf_finish_kernel(
       const int mid = lo + st;
       if (mid < nchunks && sh.pre[mid] <= j) lo = mid;
     }
-    return Cq[(int64_t)lo * capc + (j - sh.pre[lo])];
+    const uint32_t v = Cq[(int64_t)lo * capc + (j - sh.pre[lo])];
+    if constexpr (GATHER) return rows[v];
+    return v;
   };
   const int kc = running_topk_f<KS>(total, row_at, xf, qs, k, sh);
   if (!RETRY && over) {
@@ -1259,12 +1367,13 @@ __global__ __launch_bounds__(FIN_NT, FShape<KS>::OCC) void k5mf_finish_kernel(
 }
 
 // the exact scan of the flagged queries: every row through the same rounds and the same score function
-template <int KS>
+template <int KS, class... G>
 __global__ __launch_bounds__(FIN_NT, FShape<KS>::OCC) void k5mf_fallback_kernel(
     const float* __restrict__ xf, int64_t n, int64_t row_offset, const float* __restrict__ qf, int k,
     int32_t* __restrict__ out_count, int64_t* __restrict__ out_rows, double* __restrict__ out_scores,
-    const int32_t* __restrict__ fb_flag, bool skip) {
+    const int32_t* __restrict__ fb_flag, bool skip, G... gather) {
   __shared__ FinF sh;
+  const uint32_t* const rows = gather_rows(gather...);
   const int q = blockIdx.x, tid = threadIdx.x;
   if (fb_flag[q] != 1) return;
   if (skip) {
@@ -1277,7 +1386,8 @@ __global__ __launch_bounds__(FIN_NT, FShape<KS>::OCC) void k5mf_fallback_kernel(
   }
   FSlice<KS> qs;
   fslice_load(qs, qf + (int64_t)q * FShape<KS>::D);
-  const int kc = running_topk_f<KS>(n, [](int64_t j) { return (uint32_t)j; }, xf, qs, k, sh);
+  const int kc = running_topk_f<KS>(
+      n, [=](int64_t j) { return sizeof...(G) ? rows[j] : (uint32_t)j; }, xf, qs, k, sh);
   write_result_f(q, k, kc, row_offset, sh, out_count, out_rows, out_scores);
 }
 
@@ -1293,17 +1403,25 @@ struct FloatCall {
   bool skip;
 };
 
+template <int KS, class... G>
+static void launch_float_finish_g(const Plan& p, const Call& c, const FloatCall& f, G... g) {
+  hipLaunchKernelGGL((k5mf_finish_kernel<KS, false, G...>), dim3(f.nq), dim3(FIN_NT), 0, c.s, f.xf, f.n, f.row_offset,
+                     f.qf, f.k, (const uint32_t*)c.cand, (const int32_t*)c.cnt, p.nchunks, p.capc, p.qpb, f.out_count,
+                     f.out_rows, f.out_scores, f.flag, c.thr, f.alpha, f.beta, f.delta, c.qbf, g...);
+  launch_pass<KS>(p, c, 2);
+  hipLaunchKernelGGL((k5mf_finish_kernel<KS, true, G...>), dim3(f.nq), dim3(FIN_NT), 0, c.s, f.xf, f.n, f.row_offset,
+                     f.qf, f.k, (const uint32_t*)c.cand, (const int32_t*)c.cnt, p.nchunks, p.capc, p.qpb, f.out_count,
+                     f.out_rows, f.out_scores, f.flag, c.thr, f.alpha, f.beta, f.delta, c.qbf, g...);
+  hipLaunchKernelGGL((k5mf_fallback_kernel<KS, G...>), dim3(f.nq), dim3(FIN_NT), 0, c.s, f.xf, f.n, f.row_offset, f.qf,
+                     f.k, f.out_count, f.out_rows, f.out_scores, (const int32_t*)f.flag, f.skip, g...);
+}
+
 template <int KS>
 static void launch_float_finish(const Plan& p, const Call& c, const FloatCall& f) {
-  hipLaunchKernelGGL((k5mf_finish_kernel<KS, false>), dim3(f.nq), dim3(FIN_NT), 0, c.s, f.xf, f.n, f.row_offset, f.qf,
-                     f.k, (const uint32_t*)c.cand, (const int32_t*)c.cnt, p.nchunks, p.capc, p.qpb, f.out_count,
-                     f.out_rows, f.out_scores, f.flag, c.thr, f.alpha, f.beta, f.delta, c.qbf);
-  launch_pass<KS>(p, c, 2);
-  hipLaunchKernelGGL((k5mf_finish_kernel<KS, true>), dim3(f.nq), dim3(FIN_NT), 0, c.s, f.xf, f.n, f.row_offset, f.qf,
-                     f.k, (const uint32_t*)c.cand, (const int32_t*)c.cnt, p.nchunks, p.capc, p.qpb, f.out_count,
-                     f.out_rows, f.out_scores, f.flag, c.thr, f.alpha, f.beta, f.delta, c.qbf);
-  hipLaunchKernelGGL((k5mf_fallback_kernel<KS>), dim3(f.nq), dim3(FIN_NT), 0, c.s, f.xf, f.n, f.row_offset, f.qf, f.k,
-                     f.out_count, f.out_rows, f.out_scores, (const int32_t*)f.flag, f.skip);
+  if (c.rows)
+    launch_float_finish_g<KS>(p, c, f, c.rows);
+  else if constexpr (KS != 32)  // (no contiguous KS = 32 instance: run_float refuses the call)
+    launch_float_finish_g<KS>(p, c, f);
 }
 
 template <int KS>
@@ -1320,9 +1438,10 @@ __host__ inline int plan_float(int64_t n, int dim, int nq, int k, Plan* p) {
 
 static int run_float(const float* xf, const int8_t* x8, const double* inv_scale, const double* bounds, int64_t n,
                      int dim, int64_t row_offset, const float* qf, int nq, int k, int flags, int32_t* out_count,
-                     int64_t* out_rows, double* out_scores, void* workspace, size_t workspace_bytes, hipStream_t s) {
+                     int64_t* out_rows, double* out_scores, void* workspace, size_t workspace_bytes, hipStream_t s,
+                     const uint32_t* rows = nullptr) {  // rows != NULL (K5g): n is the length of the list
   Plan p;
-  const int rc = plan_float(n, dim, nq, k, &p);
+  const int rc = rows ? plan_shape(n, dim, nq, k, &p, true) : plan_float(n, dim, nq, k, &p);
   if (rc != VRQ_OK) return rc;
   if (workspace_bytes < p.bytes) return VRQ_EWORKSPACE;
   constexpr int ALL = VRQ_GEMM_STAGE_SAMPLE | VRQ_GEMM_STAGE_MAIN | VRQ_GEMM_STAGE_FINISH;
@@ -1333,7 +1452,7 @@ static int run_float(const float* xf, const int8_t* x8, const double* inv_scale,
   double* alpha = (double*)(ws + p.off_alpha);
   double* beta = (double*)(ws + p.off_beta);
   const Call c{x8, inv_scale, n, qa, nq, (float*)(ws + p.off_thr), (uint32_t*)(ws + p.off_cand),
-               (int32_t*)(ws + p.off_cnt), (float*)(ws + p.off_dv), (int32_t*)(ws + p.off_qbf), s};
+               (int32_t*)(ws + p.off_cnt), (float*)(ws + p.off_dv), (int32_t*)(ws + p.off_qbf), s, rows};
   if (st & VRQ_GEMM_STAGE_SAMPLE) {
     hipLaunchKernelGGL(k5mf_prep_kernel, dim3((p.nq_pad + 3) / 4), dim3(256), 0, s, qf, nq, p.nq_pad, dim, qa, delta,
                        alpha, beta, bounds);
@@ -1358,6 +1477,10 @@ static int run_float(const float* xf, const int8_t* x8, const double* inv_scale,
       case 768: launch_float_finish<24>(p, c, f); break;
       case 1536: launch_float_finish<48>(p, c, f); break;
       case 2048: launch_float_finish<64>(p, c, f); break;
+      case 1024:  // the gathered calls alone
+        if (!rows) return VRQ_EUNSUPPORTED;
+        launch_float_finish<32>(p, c, f);
+        break;
       default: return VRQ_EUNSUPPORTED;
     }
     VRQ_LAUNCH_CHECK();
@@ -2005,6 +2128,46 @@ __host__ inline int min_batch_binary(int dim) {
   }
 }
 
+// =============================================================================================
+// K5g host side: the *_rows calls.  An empty list launches this alone.
+__global__ __launch_bounds__(256) void k5g_empty_kernel(int nq, int k, int32_t* __restrict__ out_count,
+                                                        int64_t* __restrict__ out_rows,
+                                                        double* __restrict__ out_scores) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < (int64_t)nq * k) {
+    out_rows[i] = -1;
+    out_scores[i] = __builtin_nan("");
+  }
+  if (i < nq) out_count[i] = 0;
+}
+
+static int run_empty(int nq, int k, int32_t* out_count, int64_t* out_rows, double* out_scores, hipStream_t s) {
+  const int64_t cells = (int64_t)nq * (k > 1 ? k : 1);
+  hipLaunchKernelGGL(k5g_empty_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, nq, k, out_count,
+                     out_rows, out_scores);
+  VRQ_LAUNCH_CHECK();
+  return VRQ_OK;
+}
+
+// the plan of a gathered call over a list of m rows: plan_shape(m), an empty list planned as one row
+__host__ inline int plan_rows(int64_t m, int dim, int nq, int k, Plan* p) {
+  if (m < 0) return VRQ_EINVAL;
+  return plan_shape(m > 0 ? m : 1, dim, nq, k, p, true);
+}
+
+static void plan_info(const Plan& p, int64_t* info) {
+  info[0] = p.chunk_rows;
+  info[1] = p.nchunks;
+  info[2] = p.capc;
+  info[3] = p.nqb;
+  info[4] = p.nsc;
+  info[5] = p.scr;
+  info[6] = (int64_t)p.bytes;
+  info[7] = p.qpb;
+}
+
+constexpr int ROWS_FLAGS = VRQ_GEMM_STAGE_SAMPLE | VRQ_GEMM_STAGE_MAIN | VRQ_GEMM_STAGE_FINISH | VRQ_GEMM_NO_FALLBACK;
+
 }  // namespace g5d
 }  // namespace vrq
 
@@ -2214,6 +2377,62 @@ int vrq_binary_topk_dim_mfma(const uint8_t* codes, int64_t n, int32_t dim, int64
   VRQ_CHECK_ARG(codes && qf && out_count && out_rows && out_scores && workspace && n > 0 && nq > 0 && k > 0);
   return g5d::run_binary(codes, n, dim, row_offset, qf, nq, k, flags, out_count, out_rows, out_scores, workspace,
                          workspace_bytes, (hipStream_t)stream);
+}
+
+size_t vrq_gemm_topk_rows_workspace_size(int32_t mode, int64_t m, int32_t dim, int32_t nq, int32_t k) {
+  g5d::Plan p;
+  return mode == VRQ_GEMM_INT8_COSINE && g5d::plan_rows(m, dim, nq, k, &p) == VRQ_OK ? p.bytes : 0;
+}
+
+int vrq_gemm_topk_rows_plan(int32_t mode, int64_t m, int32_t dim, int32_t nq, int32_t k, int64_t* info) {
+  if (!info) return VRQ_EINVAL;
+  if (mode != VRQ_GEMM_INT8_COSINE) return mode == VRQ_GEMM_FLOAT_IP ? VRQ_EINVAL : VRQ_EUNSUPPORTED;
+  g5d::Plan p;
+  const int rc = g5d::plan_rows(m, dim, nq, k, &p);
+  if (rc == VRQ_OK) g5d::plan_info(p, info);
+  return rc;
+}
+
+int vrq_gemm_topk_rows(int32_t mode, const uint8_t* codes, const int8_t* x8, const double* norms, int64_t n,
+                       int32_t dim, int64_t row_offset, const uint32_t* rows, int64_t m, const float* qf, int32_t nq,
+                       int32_t k, int32_t flags, int32_t* out_count, int64_t* out_rows, double* out_scores,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+  (void)codes;
+  if (mode == VRQ_GEMM_BINARY) return VRQ_EUNSUPPORTED;  // K5mb's packed tiles need a gather of their own
+  if (mode != VRQ_GEMM_INT8_COSINE) return VRQ_EINVAL;
+  if (!vrq_dim_supported(dim)) return VRQ_EUNSUPPORTED;
+  if (flags & ~g5d::ROWS_FLAGS) return VRQ_EUNSUPPORTED;
+  VRQ_CHECK_ARG(qf && out_count && out_rows && out_scores && n > 0 && nq > 0 && k > 0 && m >= 0 && m <= n);
+  if (m == 0) return g5d::run_empty(nq, k, out_count, out_rows, out_scores, (hipStream_t)stream);
+  VRQ_CHECK_ARG(rows && workspace && x8 && norms);
+  return g5d::run(x8, norms, m, dim, row_offset, qf, nq, k, flags, out_count, out_rows, out_scores, workspace,
+                  workspace_bytes, (hipStream_t)stream, rows);
+}
+
+size_t vrq_flat_ip_topk_rows_workspace_size(int64_t m, int32_t dim, int32_t nq, int32_t k) {
+  g5d::Plan p;
+  return g5d::plan_rows(m, dim, nq, k, &p) == VRQ_OK ? p.bytes : 0;
+}
+
+int vrq_flat_ip_topk_rows_plan(int64_t m, int32_t dim, int32_t nq, int32_t k, int64_t* info) {
+  if (!info) return VRQ_EINVAL;
+  g5d::Plan p;
+  const int rc = g5d::plan_rows(m, dim, nq, k, &p);
+  if (rc == VRQ_OK) g5d::plan_info(p, info);
+  return rc;
+}
+
+int vrq_flat_ip_topk_rows(const float* xf, const int8_t* x8, const double* inv_scale, const double* bounds, int64_t n,
+                          int32_t dim, int64_t row_offset, const uint32_t* rows, int64_t m, const float* qf,
+                          int32_t nq, int32_t k, int32_t flags, int32_t* out_count, int64_t* out_rows,
+                          double* out_scores, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!vrq_dim_supported(dim)) return VRQ_EUNSUPPORTED;
+  if (flags & ~g5d::ROWS_FLAGS) return VRQ_EUNSUPPORTED;
+  VRQ_CHECK_ARG(qf && out_count && out_rows && out_scores && n > 0 && nq > 0 && k > 0 && m >= 0 && m <= n);
+  if (m == 0) return g5d::run_empty(nq, k, out_count, out_rows, out_scores, (hipStream_t)stream);
+  VRQ_CHECK_ARG(rows && workspace && xf && x8 && inv_scale && bounds);
+  return g5d::run_float(xf, x8, inv_scale, bounds, m, dim, row_offset, qf, nq, k, flags, out_count, out_rows,
+                        out_scores, workspace, workspace_bytes, (hipStream_t)stream, rows);
 }
 
 int vrq_binary_topk_dim_engine(int64_t n, int32_t dim, int32_t nq, int32_t k) {

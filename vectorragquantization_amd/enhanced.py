@@ -27,6 +27,7 @@ import torch
 
 from . import _native as N
 from .docstore import DocStoreError, RocksDictReader, is_rocksdict_dir
+from . import filters
 from .filters import checked as checked_bitmap, checked_filter, class_filter, ids_bitmap
 from .index import BinaryIndexIDMap2, _GrowBuffer, as_device_tensor
 from .quant import int8_row_norms
@@ -63,7 +64,8 @@ class SearchBatch:
 
 def gemm_topk(mode: str, qf: torch.Tensor, k: int, codes: torch.Tensor | None = None,
               x8: torch.Tensor | None = None, norms: torch.Tensor | None = None, row_offset: int = 0,
-              flags: int = 0, workspace: torch.Tensor | None = None, lib=None, engine: str | None = None):
+              flags: int = 0, workspace: torch.Tensor | None = None, lib=None, engine: str | None = None,
+              rows: torch.Tensor | None = None):
     """Exhaustive Phase-II (``mode="binary"``) or Phase-III (``mode="int8_cosine"``) top-k of a query
     batch over EVERY row on the matrix cores (``vrq_gemm_topk``, BASELINE config 5): the scores of
     ``CohereEnhancedVectorDB.py:283-293`` / ``:302-318`` ordered like the reference's stable
@@ -76,18 +78,39 @@ def gemm_topk(mode: str, qf: torch.Tensor, k: int, codes: torch.Tensor | None = 
     ``vrq_gemm_topk_dim_mfma``, for int8_cosine; K5mb, ``vrq_binary_topk_dim_mfma``, for binary; both take the
     stage flags); "auto" asks ``vrq_gemm_topk_dim_engine`` / ``vrq_binary_topk_dim_engine``, which pick the
     matrix path from a measured minimum batch per dim and otherwise leave the call on the ``engine=None``
-    route (so "auto" at 1024 is K5, never the exact scan)."""
+    route (so "auto" at 1024 is K5, never the exact scan).  ``rows`` (uint32[m], ascending: ``filters.row_list`` /
+    ``filters.ids_rows``): int8_cosine over those rows alone on the gathered matrix path at every dim (K5g,
+    ``vrq_gemm_topk_rows``); the rows returned are corpus rows.  The binary mode takes no row list."""
     if engine not in (None, "exact", "mfma", "auto"):
         raise ValueError(f"engine {engine!r}: None, 'exact', 'mfma' or 'auto'")
     m = {"binary": N.VRQ_GEMM_BINARY, "int8_cosine": N.VRQ_GEMM_INT8_COSINE}[mode]
     src = codes if m == N.VRQ_GEMM_BINARY else x8
     dev = qf.device
     nq, n = qf.shape[0], src.shape[0]
+    allowed, rows = rows, None  # (rows: the output below)
+    if allowed is not None and (m == N.VRQ_GEMM_BINARY or engine == "exact"):
+        raise N.VrqNativeError("gemm_topk(rows=...): the filtered exhaustive search serves int8_cosine on the matrix "
+                               "path alone (the binary pass loads packed tiles and has no gathered variant; the "
+                               "exact scan has none either)")
     cnt = torch.full((nq,), -2, dtype=torch.int32, device=dev)  # -2: never written
     rows = torch.full((nq, k), -2, dtype=torch.int64, device=dev)
     scores = torch.empty((nq, k), dtype=torch.float64, device=dev)
     lib = lib or N.load()
     dim = qf.shape[1]
+    if allowed is not None:
+        allowed = filters.checked_rows(allowed, n, dev)
+        nr = int(allowed.shape[0])
+        need = lib.vrq_gemm_topk_rows_workspace_size(m, nr, dim, nq, k)
+        if need == 0:
+            raise N.VrqNativeError(f"vrq_gemm_topk_rows: unsupported shape m={nr} dim={dim} nq={nq} k={k} "
+                                   "(dims: vrq_dim_supported; k <= 1024)")
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+        N.check(lib.vrq_gemm_topk_rows(m, N.ptr(codes), N.ptr(x8), N.ptr(norms), n, dim, row_offset, N.ptr(allowed),
+                                       nr, N.ptr(qf), nq, k, flags, N.ptr(cnt), N.ptr(rows), N.ptr(scores),
+                                       N.ptr(workspace), workspace.numel(), N.stream_handle(dev)),
+                "vrq_gemm_topk_rows")
+        return cnt, rows, scores
     if m == N.VRQ_GEMM_BINARY:
         engine = N.binary_topk_engine(lib, n, dim, nq, k, engine)
         if engine == "mfma":

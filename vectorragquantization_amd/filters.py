@@ -54,6 +54,49 @@ def checked(allow: torch.Tensor, n: int, device) -> torch.Tensor:
     return allow.contiguous()
 
 
+def row_list(allow: torch.Tensor, n: int) -> torch.Tensor:
+    """The bitmap ``allow`` over ``n`` rows as the list the ``rows=`` searches read (``vrq_row_list``): uint32[m] on
+    the bitmap's device, the allowed rows below ``n`` in ascending order.  Two device passes (count, then emit)
+    around the one host read of m; build it once per filter and reuse it across searches."""
+    allow = checked(allow, n, allow.device)
+    lib = N.load()
+    if n < 1 or (need := lib.vrq_row_list_workspace_size(n)) == 0:
+        raise N.VrqNativeError(f"vrq_row_list: unsupported row count n={n} (1 <= n < 2^32)")
+    ws = torch.empty((need,), dtype=torch.uint8, device=allow.device)
+    m_dev = torch.empty((1,), dtype=torch.int64, device=allow.device)
+    with torch.cuda.device(allow.device):
+        stream = N.stream_handle(allow.device)
+        N.check(lib.vrq_row_list(N.ptr(allow), n, 0, 0, N.ptr(m_dev), N.ptr(ws), need, stream), "vrq_row_list")
+        m = int(m_dev.item())
+        rows = torch.empty((m,), dtype=torch.uint32, device=allow.device)
+        if m:
+            N.check(lib.vrq_row_list(N.ptr(allow), n, N.ptr(rows), m, N.ptr(m_dev), N.ptr(ws), need, stream),
+                    "vrq_row_list")
+    rows._vrq_rows_n = n  # ascending and below n by construction: checked_rows skips its device check
+    return rows
+
+
+def ids_rows(id_map: torch.Tensor, allowed_ids) -> torch.Tensor:
+    """The row list of the rows of ``id_map`` that carry one of ``allowed_ids`` (``ids_bitmap``, then ``row_list``)."""
+    return row_list(ids_bitmap(id_map, allowed_ids), int(id_map.shape[0]))
+
+
+def checked_rows(rows: torch.Tensor, n: int, device) -> torch.Tensor:
+    """``rows`` as the ``*_rows`` calls want it: a contiguous 1-D uint32 tensor on ``device``, at most ``n`` entries,
+    strictly ascending and all below ``n``; raises otherwise, since the kernels read corpus rows through it
+    unchecked.  A list made by ``row_list`` / ``ids_rows`` for the same ``n`` is taken as is; any other costs one
+    device reduction and a host read."""
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.uint32 or rows.dim() != 1 or rows.shape[0] > n:
+        raise N.VrqNativeError(f"rows must be a uint32 tensor of at most {n} row numbers (filters.row_list)")
+    if rows.device != torch.device(device):
+        raise N.VrqNativeError(f"rows is on {rows.device}, the index on {device}")
+    if getattr(rows, "_vrq_rows_n", None) != n and rows.shape[0]:
+        r = rows.to(torch.int64)
+        if not bool(((r[1:] > r[:-1]).all() & (r[-1] < n)).item()):
+            raise N.VrqNativeError(f"rows must be strictly ascending row numbers below {n}")
+    return rows.contiguous()
+
+
 def row_bitmaps(masks: torch.Tensor) -> torch.Tensor:
     """bool[S, n] (one mask per set) -> int64[S, ceil(n / 64)] on the masks' device; row s is ``row_bitmap(masks[s])``."""
     if masks.dim() != 2:

@@ -31,6 +31,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import filters
 from .docstore import DocStoreError, RocksDictReader, is_rocksdict_dir
 from .index import _GrowBuffer, _device, as_device_tensor
 
@@ -50,22 +51,44 @@ def flat_ip_prepare(xf: torch.Tensor, bounds: torch.Tensor):
 
 def flat_ip_topk(xf: torch.Tensor, x8: torch.Tensor, inv_scale: torch.Tensor, bounds: torch.Tensor,
                  qf: torch.Tensor, k: int, row_offset: int = 0, flags: int = 0,
-                 workspace: torch.Tensor | None = None, engine: str | None = None):
+                 workspace: torch.Tensor | None = None, engine: str | None = None,
+                 rows: torch.Tensor | None = None):
     """Exact IndexFlatIP top-k of a query batch (``vrq_flat_ip_topk``).  Returns device tensors
     (count i32[nq], rows i64[nq, k] (+ row_offset, -1 padded), scores f64[nq, k] holding float32
     values), ordered (score desc, row asc).  Off dim 1024 (or with VRQ_GEMM_SCAN_EXACT) the exact
     exhaustive scan behind ``vrq_flat_ip_topk_dim`` serves the call from ``xf`` alone.  ``engine``: None and
     "exact" keep those routes; "mfma" is ``vrq_flat_ip_topk_dim_mfma`` (K5mf off 1024, needs x8 / inv_scale /
     bounds; under VRQ_GEMM_NO_FALLBACK unserved queries come back with count -1); "auto" is "mfma" where
-    ``vrq_flat_ip_dim_engine`` picks it and the operands are there, else None."""
+    ``vrq_flat_ip_dim_engine`` picks it and the operands are there, else None.  ``rows`` (uint32[m], ascending:
+    ``filters.row_list`` / ``filters.ids_rows``): the search is over those rows alone, on the gathered matrix path
+    at every dim (K5g, ``vrq_flat_ip_topk_rows``; needs x8 / inv_scale / bounds of the whole corpus); the rows
+    returned are corpus rows (+ row_offset), and ``engine`` must be None, "mfma" or "auto"."""
     dev = qf.device
     nq, n = qf.shape[0], xf.shape[0]
+    allowed, rows = rows, None  # (rows: the output below)
     cnt = torch.full((nq,), -2, dtype=torch.int32, device=dev)  # -2: never written
     rows = torch.full((nq, k), -2, dtype=torch.int64, device=dev)
     scores = torch.empty((nq, k), dtype=torch.float64, device=dev)
     lib = N.load()
     dim = qf.shape[1]
     have = x8 is not None and inv_scale is not None and bounds is not None
+    if allowed is not None:
+        if engine == "exact" or not have:
+            raise N.VrqNativeError("flat_ip_topk(rows=...): the filtered search runs on the matrix path alone and "
+                                   "needs x8, inv_scale and bounds (flat_ip_prepare)")
+        allowed = filters.checked_rows(allowed, n, dev)
+        m = int(allowed.shape[0])
+        need = lib.vrq_flat_ip_topk_rows_workspace_size(m, dim, nq, k)
+        if need == 0:
+            raise N.VrqNativeError(f"vrq_flat_ip_topk_rows: unsupported shape m={m} dim={dim} nq={nq} k={k} "
+                                   "(dims: vrq_dim_supported; k <= 1024)")
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+        N.check(lib.vrq_flat_ip_topk_rows(N.ptr(xf), N.ptr(x8), N.ptr(inv_scale), N.ptr(bounds), n, dim, row_offset,
+                                          N.ptr(allowed), m, N.ptr(qf), nq, k, flags, N.ptr(cnt), N.ptr(rows),
+                                          N.ptr(scores), N.ptr(workspace), workspace.numel(), N.stream_handle(dev)),
+                "vrq_flat_ip_topk_rows")
+        return cnt, rows, scores
     if engine == "auto" and not have:
         engine = None
     engine = N.flat_ip_engine(lib, n, dim, nq, k, engine)
@@ -196,11 +219,46 @@ class FloatIndexIDMap:
         self._xf.append(xf)
         self._ids.append(ids_t)
 
-    def search_rows(self, qf, k: int, flags: int = 0):
+    def _ensure_matrix(self) -> None:
+        """The matrix operands of an index that was built without them (d != 1024, engine=None): prepared for the
+        rows added so far on the first filtered search, and kept up to date by ``add_with_ids`` from then on.
+        Unfiltered searches keep their route: ``engine`` is unchanged."""
+        if self._matrix:
+            return
+        self._x8 = _GrowBuffer((self.d,), torch.int8, self.device)
+        self._inv = _GrowBuffer((), torch.float64, self.device)
+        self.bounds = torch.zeros((2,), dtype=torch.float64, device=self.device)
+        if self.ntotal:
+            with torch.cuda.device(self.device):
+                x8, inv = flat_ip_prepare(self._xf.view(), self.bounds)
+            self._x8.append(x8)
+            self._inv.append(inv)
+        self._matrix = True
+
+    def filter_rows(self, allow=None, allowed_ids=None):
+        """The row list of a filter: ``allow`` (a row bitmap, ``filters.row_bitmap``) or ``allowed_ids`` (external
+        ids; every row of a duplicated id is allowed, unknown ids are ignored); None without either.  A list
+        is reusable across searches until rows are added or removed."""
+        if allow is not None and allowed_ids is not None:
+            raise N.VrqNativeError("allow and allowed_ids are exclusive")
+        if allowed_ids is not None:
+            return filters.ids_rows(self.id_map, allowed_ids)
+        if allow is not None:
+            return filters.row_list(filters.checked(allow, self.ntotal, self.device), self.ntotal)
+        return None
+
+    def search_rows(self, qf, k: int, flags: int = 0, allow=None, allowed_ids=None):
         """Device (count, rows, scores) of the exact top-k (internal rows); ``flags`` as
-        ``vrq_flat_ip_topk`` (e.g. VRQ_GEMM_NO_FALLBACK)."""
+        ``vrq_flat_ip_topk`` (e.g. VRQ_GEMM_NO_FALLBACK).  With ``allow`` / ``allowed_ids`` (``filter_rows``) the
+        search is over the allowed rows alone, on the gathered matrix path (K5g) at every dim."""
         qf = as_device_tensor(qf, torch.float32, self.device).reshape(-1, self.d)
         lib = N.load()
+        allowed = self.filter_rows(allow, allowed_ids)
+        if allowed is not None:
+            self._ensure_matrix()
+            with torch.cuda.device(self.device):
+                return flat_ip_topk(self._xf.view(), self._x8.view(), self._inv.view(), self.bounds, qf, k,
+                                    flags=flags, rows=allowed)
         engine = self.engine if self.d != 1024 else None
         if N.flat_ip_engine(lib, self.ntotal, self.d, qf.shape[0], k, engine) == "mfma":
             need = lib.vrq_flat_ip_topk_dim_mfma_workspace_size(self.ntotal, self.d, qf.shape[0], k)
@@ -209,20 +267,21 @@ class FloatIndexIDMap:
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty((max(need, 8),), dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
-            if not self._matrix:
+            if self._x8 is None or (self.d != 1024 and engine is None):  # (operands a filtered search left: unused)
                 return flat_ip_topk(self._xf.view(), None, None, None, qf, k, flags=flags, workspace=self._ws)
             return flat_ip_topk(self._xf.view(), self._x8.view(), self._inv.view(), self.bounds, qf, k,
                                 flags=flags, workspace=self._ws, engine=engine)
 
-    def search(self, q, k: int):
-        """FAISS ``search``: numpy (distances f32[nq, k], labels i64[nq, k]); unused slots -FLT_MAX / -1."""
+    def search(self, q, k: int, allow=None, allowed_ids=None):
+        """FAISS ``search``: numpy (distances f32[nq, k], labels i64[nq, k]); unused slots -FLT_MAX / -1.
+        ``allow`` / ``allowed_ids``: as ``search_rows`` (FAISS's ``IDSelector`` search parameter)."""
         q = np.asarray(q.cpu() if isinstance(q, torch.Tensor) else q, dtype=np.float32).reshape(-1, self.d)
         nq = q.shape[0]
         D = np.full((nq, k), -np.finfo(np.float32).max, dtype=np.float32)  # FAISS CMin neutral
         L = np.full((nq, k), -1, dtype=np.int64)
         if self.ntotal == 0 or k <= 0 or nq == 0:
             return D, L
-        cnt, rows, scores = self.search_rows(q, k)
+        cnt, rows, scores = self.search_rows(q, k, allow=allow, allowed_ids=allowed_ids)
         cnt = cnt.cpu().numpy()
         r = rows.cpu().numpy()
         s = scores.cpu().numpy()
@@ -377,15 +436,16 @@ class CohereVectorDBFloat:
         if save:
             self.save()
 
-    def search_vectors(self, qf, k: int = 10):
-        """Batched search of float32 [nq, d] queries: device (count, doc_id, score) tensors."""
+    def search_vectors(self, qf, k: int = 10, allowed_ids=None):
+        """Batched search of float32 [nq, d] queries: device (count, doc_id, score) tensors.  ``allowed_ids``: only
+        documents with one of these ids are searched (the gathered matrix path, K5g)."""
         if k < 0:
             raise ValueError("k must be non-negative")
-        cnt, rows, scores = self.index.search_rows(qf, k)
+        cnt, rows, scores = self.index.search_rows(qf, k, allowed_ids=allowed_ids)
         ids = torch.where(rows >= 0, self.index.id_map[rows.clamp_min(0)], rows)
         return cnt, ids, scores
 
-    def search(self, query: str, k: int = 10) -> List[Dict]:
+    def search(self, query: str, k: int = 10, allowed_ids=None) -> List[Dict]:
         if self.index.ntotal == 0:                                           # :146-148
             logger.warning("No docs in index, add documents first.")
             return []
@@ -393,7 +453,8 @@ class CohereVectorDBFloat:
         if not emb:
             logger.error("Query embedding generation failed.")
             return []
-        D, L = self.index.search(np.asarray(emb["float"], dtype=np.float32).reshape(1, -1), k)
+        D, L = self.index.search(np.asarray(emb["float"], dtype=np.float32).reshape(1, -1), k,
+                                 allowed_ids=allowed_ids)
         results = []
         for dist, did in zip(D[0], L[0]):                                    # :158-171
             if did == -1:
