@@ -626,7 +626,7 @@ int vrq_binary_topk_dim_engine(int64_t n, int32_t dim, int32_t nq, int32_t k);
  * vrq_gemm_topk_rows: the arguments of vrq_gemm_topk_dim_mfma with (rows, m) after row_offset; n is the row
  * count of x8 / norms.  Serves VRQ_GEMM_INT8_COSINE at every dim of vrq_dim_supported, 1024 included (K5md's
  * KS = 32 instance; K5 has no gather).  VRQ_GEMM_BINARY returns VRQ_EUNSUPPORTED (K5mb loads packed tiles
- * into registers and needs a gather of its own), VRQ_GEMM_FLOAT_IP VRQ_EINVAL.  codes is ignored.
+ * into registers and has a gather of its own: vrq_binary_topk_gather), VRQ_GEMM_FLOAT_IP VRQ_EINVAL.  codes is ignored.
  * vrq_flat_ip_topk_rows: the arguments of vrq_flat_ip_topk_dim_mfma with (rows, m) after row_offset; xf, x8,
  * inv_scale and bounds are required and are the whole corpus's (bounds stay valid upper bounds for a
  * subset).
@@ -657,6 +657,34 @@ int vrq_flat_ip_topk_rows(const float* xf, const int8_t* x8, const double* inv_s
                           int32_t dim, int64_t row_offset, const uint32_t* rows, int64_t m, const float* qf,
                           int32_t nq, int32_t k, int32_t flags, int32_t* out_count, int64_t* out_rows,
                           double* out_scores, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Filtered exhaustive binary top-k over a list of allowed rows (additive to ABI version 1).  K5gb: K5mb's
+ * pipeline in the virtual row space [0, m) of the list, as K5g runs K5md's; the list is consulted by the
+ * 16-byte piece loads of the matrix pass (each thread loads the list entry of its own pieces, one tile ahead
+ * of the piece loads), by the finish and by the exact scan; rows that are not listed are never read.  The
+ * binary mode has an entry point of its own, as it has unfiltered (vrq_binary_topk_dim_mfma):
+ * vrq_gemm_topk_rows(VRQ_GEMM_BINARY) stays VRQ_EUNSUPPORTED.
+ * vrq_binary_topk_gather: the arguments of vrq_binary_topk_dim_mfma with (rows, m) after row_offset; n is the
+ * row count of codes.  Every dim of vrq_dim_supported, 1024 included (K5mb's KS = 32 instance, which exists
+ * for this call alone: the unfiltered call at 1024 is K5).  Preconditions (not checked: the list lives on the
+ * device): rows strictly ascending, every entry < n.  1 <= k <= 1024.  flags: 0, or a subset of
+ * VRQ_GEMM_STAGE_* under vrq_gemm_topk's ordering contract, optionally | VRQ_GEMM_NO_FALLBACK; anything else
+ * VRQ_EUNSUPPORTED.  m < 0, m > n, or rows == NULL with m > 0: VRQ_EINVAL.
+ * Outputs: bit-identical to vrq_binary_topk_dim_mfma (at 1024: to this call with the identity list) on the
+ * gathered copy of the listed code rows, each returned row j replaced by row_offset + rows[j]; ties (score
+ * desc, row asc) in physical rows.  m < k: out_count = m.  m == 0: nothing but a fill is launched, out_count =
+ * 0 with -1 / NaN slots, and rows, workspace and codes may be NULL.
+ * vrq_binary_topk_gather_workspace_size / _plan: of the call on a list of m rows, field for field
+ * vrq_binary_topk_dim_mfma_plan's for n = m at the dims other than 1024 (queries per block at 1024: 128);
+ * m == 0 answers as m == 1.
+ * ------------------------------------------------------------------------- */
+size_t vrq_binary_topk_gather_workspace_size(int64_t m, int32_t dim, int32_t nq, int32_t k);
+int vrq_binary_topk_gather_plan(int64_t m, int32_t dim, int32_t nq, int32_t k, int64_t* info);
+int vrq_binary_topk_gather(const uint8_t* codes, int64_t n, int32_t dim, int64_t row_offset, const uint32_t* rows,
+                           int64_t m, const float* qf, int32_t nq, int32_t k, int32_t flags, int32_t* out_count,
+                           int64_t* out_rows, double* out_scores, void* workspace, size_t workspace_bytes,
+                           void* stream);
 
 /* ---------------------------------------------------------------------------
  * Search with more than 1024 Phase-I candidates (additive to ABI version 1; every function above keeps

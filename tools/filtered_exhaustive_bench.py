@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""The filtered exhaustive top-k over a row list (K5g: ``vrq_flat_ip_topk_rows`` / ``vrq_gemm_topk_rows``) beside
+"""The filtered exhaustive top-k over a row list (K5g: ``vrq_flat_ip_topk_rows`` / ``vrq_gemm_topk_rows``; K5gb, mode
+``binary``: ``vrq_binary_topk_gather``) beside
 the unfiltered matrix call on all rows and beside what a caller without it does -- ``index_select`` the allowed
 rows into a copy, prepare the copy, search it: HIP-event timing on the same device buffers in the same run, the
 legs alternating for ``--rounds`` rounds.
@@ -11,16 +12,18 @@ indirection alone; 0.5, 0.1, 0.01 as random rows):
   at 1024: K5): the yardstick.  Its answer is not the filtered one; it is what the scan costs without a filter;
 * ``b_rows``        the gathered call with a prebuilt list; ``b_list`` is ``filters.row_list`` alone (count, one
   host read, emit), paid once per filter;
-* ``c_gather``      ``index_select`` of the allowed rows (float rows or int8 rows and norms), ``flat_ip_prepare``
+* ``c_gather``      ``index_select`` of the allowed rows (float rows, int8 rows and norms, or code rows), ``flat_ip_prepare``
   of the copy for the float mode, and the unfiltered matrix call on it; ``c_gather_only`` is the copy (and
   prepare) alone;
 * ``d_exact``       K5d (``engine="exact"``) over all rows: what ``b_rows`` has to beat at nq = 1.
 
 Before timing, (b) is compared with (c) mapped back to corpus rows: rows equal, and score bits equal for the
-cosine mode (the float copy's own bounds may admit other candidates, never other results).  One JSON line per
+cosine and binary modes (the float copy's own bounds may admit other candidates, never other results; at 1024 the
+binary copy is searched by K5, whose scores are the same function but not the same pipeline: rows alone).  One JSON line per
 (mode, dim, nq, fraction); times in ms are the median over the rounds with the min and max beside it.
 
     python tools/filtered_exhaustive_bench.py --out profiles/filtered_exhaustive_bench.jsonl
+    python tools/filtered_exhaustive_bench.py --modes binary --out profiles/filtered_binary_bench.jsonl
 """
 import argparse
 import json
@@ -41,6 +44,8 @@ from vectorragquantization_amd.quant import int8_row_norms  # noqa: E402
 def corpus(mode, n, dim, dev):
     g = torch.Generator(device=dev)
     g.manual_seed(dim)
+    if mode == "binary":
+        return (torch.randint(0, 256, (n, dim // 8), generator=g, device=dev, dtype=torch.uint8),)
     if mode == "int8_cosine":
         x8 = torch.randint(-127, 128, (n, dim), generator=g, device=dev, dtype=torch.int8)
         return (x8, int8_row_norms(x8))
@@ -50,6 +55,8 @@ def corpus(mode, n, dim, dev):
 
 
 def search(mode, ops, qf, k, rows=None, engine="mfma"):
+    if mode == "binary":
+        return gemm_topk("binary", qf, k, codes=ops[0], rows=rows, engine=None if rows is not None else engine)
     if mode == "int8_cosine":
         return gemm_topk("int8_cosine", qf, k, x8=ops[0], norms=ops[1], rows=rows, engine=None if rows is not None else engine)
     if engine == "exact":
@@ -58,6 +65,8 @@ def search(mode, ops, qf, k, rows=None, engine="mfma"):
 
 
 def gather(mode, ops, idx):
+    if mode == "binary":
+        return (ops[0].index_select(0, idx),)
     if mode == "int8_cosine":
         return (ops[0].index_select(0, idx), ops[1].index_select(0, idx))
     xf = ops[0].index_select(0, idx)
@@ -99,7 +108,8 @@ def main():
                     cc, rc, sc = search(mode, gather(mode, ops, idx), qf, k)
                     mapped = torch.where(rc >= 0, idx[rc.clamp_min(0)], rc)
                     assert torch.equal(cb, cc) and torch.equal(rb, mapped), (mode, dim, nq, frac)
-                    assert mode != "int8_cosine" or torch.equal(sb.view(torch.int64), sc.view(torch.int64))
+                    assert mode == "float_ip" or (mode == "binary" and dim == 1024) or \
+                        torch.equal(sb.view(torch.int64), sc.view(torch.int64))
                     legs = {
                         "a_unfiltered": lambda: search(mode, ops, qf, k),
                         "b_rows": lambda: search(mode, ops, qf, k, rows=rows),

@@ -198,6 +198,10 @@ SIGNATURES = {
     "vrq_flat_ip_topk_rows_plan": (C.c_int, [_I64, _I32, _I32, _I32, _P]),
     "vrq_flat_ip_topk_rows": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I64, _P, _I64, _P, _I32, _I32, _I32, _P, _P,
                                         _P, _P, _SZ, _P]),
+    "vrq_binary_topk_gather_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
+    "vrq_binary_topk_gather_plan": (C.c_int, [_I64, _I32, _I32, _I32, _P]),
+    "vrq_binary_topk_gather": (C.c_int, [_P, _I64, _I32, _I64, _P, _I64, _P, _I32, _I32, _I32, _P, _P, _P, _P, _SZ,
+                                         _P]),
 }
 
 

@@ -1599,14 +1599,32 @@ __global__ __launch_bounds__(256) void k5mb_prep_kernel(const float* __restrict_
 // The matrix pass.  DENSE = the sample pass (max of u over each lane row's rows of the chunk ->
 // dv[q][chunk * 32 + lane row]) else the thresholded pass (u >= ceil(thr[q]) -> candidate lists); chunks,
 // query blocks and qbflag as k5md_pass_kernel.
-template <int KS, bool DENSE>
+//
+// G... is empty, or one `const uint32_t* rows` (K5gb, the gathered pass behind vrq_binary_topk_gather): the pass
+// runs in virtual row space as K5g's does (n = the length of the list; chunks, tiles, the shifted last tile, the
+// clamp of a short chunk and the staged hits are virtual rows v), and only the piece loads go through the list:
+// piece i of a thread reads 16 bytes at codes + rows[v_i] * RB + 16 c_i, v_i = the virtual row of its tile row.
+// A thread loads the list entry of each of its own pieces, PL four-byte loads per tile from the tile's one or
+// two cache lines of the list; no cross-lane distribution, no LDS.  A piece load needs its entry in a register,
+// so the entries run one tile ahead of the pieces, three ahead of the MFMAs: at the top of tile t the entries of
+// tile t + 3 are requested FIRST, then the pieces of tile t + 2 go out with the entries requested in tile t - 1.
+// In that order the entries a piece load waits for are older than everything that has to stay in flight (the
+// pieces of tile t + 1 and the newest entries), so every wait stays a counted one: per tile, with PL = 2,
+//   vmcnt(5), vmcnt(4)  entry 0 / 1 of tile t + 2 landed   (pieces of t + 1 and entries of t + 3 in flight)
+//   vmcnt(5), vmcnt(4)  piece 0 / 1 of tile t + 1 landed   (entries of t + 3 and pieces of t + 2 in flight)
+// against vmcnt(3), vmcnt(2) of the contiguous instance; with PL = 1 both are vmcnt(2) against vmcnt(1).  Past
+// the last tile the index clamps to the last tile, so every address formed is a list entry and every wave
+// issues the same number of loads.  The loads are plain C++ loads: the compiler counts the waits itself.
+template <int KS, bool DENSE, class... G>
 __global__ __launch_bounds__(Shape<KS>::W * 64, 1) void k5mb_pass_kernel(
     const uint8_t* __restrict__ codes, int64_t n, const int8_t* __restrict__ qa, int nq,
     const float* __restrict__ thr, uint32_t* __restrict__ cand, int32_t* __restrict__ ccnt, int capc,
     int64_t chunk_rows, int64_t chunk_stride, int nchunks, int nqb, float* __restrict__ dv, int64_t dv_stride,
-    const int32_t* __restrict__ qbflag) {
+    const int32_t* __restrict__ qbflag, G... gather) {
   using S = Shape<KS>;
   using B = BShape<KS>;
+  constexpr bool GATHER = sizeof...(G) != 0;
+  static_assert(sizeof...(G) <= 1, "one row list");
   constexpr int D = S::D, W = S::W, MB = S::MB, QW = S::QW, NE = S::NE, TPS = S::TPS, EOFF = S::EOFF;
   constexpr int RB = B::RB, PPR = B::PPR, NPC = B::NPC, PL = B::PL, NF = B::NF, UT = B::UT;
   __shared__ __attribute__((aligned(16))) uint8_t smem[2 * UT];
@@ -1634,6 +1652,7 @@ __global__ __launch_bounds__(Shape<KS>::W * 64, 1) void k5mb_pass_kernel(
   // load is in bounds) and the LDS byte offset of its first fragment in the unpacked image
   uint32_t goff[PL], uoff[PL];
   bool pv[PL];
+  int grl[GATHER ? PL : 1];
 #pragma unroll
   for (int i = 0; i < PL; ++i) {
     const int p = (int)threadIdx.x + B::NT * i, pc = p < NPC ? p : NPC - 1;
@@ -1641,12 +1660,30 @@ __global__ __launch_bounds__(Shape<KS>::W * 64, 1) void k5mb_pass_kernel(
     pv[i] = p < NPC;
     goff[i] = (uint32_t)(rl * RB + 16 * c);
     uoff[i] = (uint32_t)((4 * c * 64 + rr) * 16);
+    if constexpr (GATHER) {  // the list supplies the row: tile row and byte in the row apart
+      grl[i] = rl;
+      goff[i] = (uint32_t)(16 * c);
+    }
   }
   v4i pk[2][PL];  // the packed pieces of the tile being expanded / the tile after it
   auto load_tile = [&](int t, v4i (&dst)[PL]) {
     const uint8_t* base = codes + (row0 + tstart(t)) * RB;
 #pragma unroll
     for (int i = 0; i < PL; ++i) dst[i] = *reinterpret_cast<const v4i*>(base + goff[i]);
+  };
+  // K5gb: ge[t & 1][i] = the list entry (physical row) of piece i of tile t, from its request until the piece
+  // load that consumes it; tiles past the last are the last tile again
+  const uint32_t* const rows = gather_rows(gather...);
+  uint32_t ge[2][GATHER ? PL : 1];
+  auto load_entries = [&](int t, uint32_t (&dst)[GATHER ? PL : 1]) {
+    const uint32_t* base = rows + (row0 + tstart(t < ntiles ? t : ntiles - 1));
+#pragma unroll
+    for (int i = 0; i < PL; ++i) dst[GATHER ? i : 0] = base[grl[GATHER ? i : 0]];
+  };
+  auto load_gathered = [&](const uint32_t (&e)[GATHER ? PL : 1], v4i (&dst)[PL]) {
+#pragma unroll
+    for (int i = 0; i < PL; ++i)
+      dst[i] = *reinterpret_cast<const v4i*>(codes + (int64_t)e[GATHER ? i : 0] * RB + goff[i]);
   };
   // fragment j = 8 i + 2 dw + hh of a tile: code dword dw of piece i, lane half hh
   auto expand = [&](auto J, const v4i (&src)[PL], uint32_t ub) {
@@ -1659,8 +1696,17 @@ __global__ __launch_bounds__(Shape<KS>::W * 64, 1) void k5mb_pass_kernel(
     f.w = (int)((wd >> (4 * hh + 3)) & 0x01010101u);
     if (pv[i]) lds_write128_imm<dw * 1024 + hh * 512>(ub + uoff[i], f);
   };
-  load_tile(0, pk[0]);
-  load_tile(ntiles > 1 ? 1 : 0, pk[1]);
+  if constexpr (GATHER) {  // tile 0's and tile 1's entries (waited for here), their pieces, then tile 2's entries
+    load_entries(0, ge[0]);
+    load_entries(1, ge[1]);
+    load_gathered(ge[0], pk[0]);
+    load_gathered(ge[1], pk[1]);
+    VRQ_SCHED_FENCE();
+    load_entries(2, ge[0]);
+  } else {
+    load_tile(0, pk[0]);
+    load_tile(ntiles > 1 ? 1 : 0, pk[1]);
+  }
 
   // A fragments of this wave's M-blocks of 32 queries, every k-step -> accumulator file
   const int qbase = qb * S::QB + w * QW;
@@ -1762,7 +1808,14 @@ __global__ __launch_bounds__(Shape<KS>::W * 64, 1) void k5mb_pass_kernel(
     if constexpr (!DENSE)
       if (t >= 2) flush(t - 2, acc[p]);  // (its accumulators are acc[p] until this tile's first MFMA)
     const bool vprev = lane_valid(t - 1);
-    load_tile(t + 2 < ntiles ? t + 2 : ntiles - 1, pk[p]);  // pk[p] held tile t; pk[p ^ 1] holds tile t + 1
+    // pk[p] held tile t; pk[p ^ 1] holds tile t + 1
+    if constexpr (GATHER) {
+      load_entries(t + 3, ge[p ^ 1]);  // (ge[p ^ 1] held tile t + 1's, consumed in tile t - 1)
+      VRQ_SCHED_FENCE();               // the request stays in front of the pieces: see the header
+      load_gathered(ge[p], pk[p]);
+    } else {
+      load_tile(t + 2 < ntiles ? t + 2 : ntiles - 1, pk[p]);
+    }
     const uint32_t badr = sm0 + (uint32_t)(p * UT + l * 16), ubn = sm0 + (uint32_t)((p ^ 1) * UT);
     v4i ring[NR];
     auto readB = [&](auto SS) {
@@ -1920,16 +1973,18 @@ __device__ int running_topk_b(int64_t count, RowAt row_at, const uint8_t* __rest
   return kc;
 }
 
-// finish: k5md_finish_kernel's contract and flags over code rows
-template <bool RETRY>
+// finish: k5md_finish_kernel's contract and flags over code rows (G...: its row list too)
+template <bool RETRY, class... G>
 __global__ __launch_bounds__(FIN_NT) void k5mb_finish_kernel(
     const uint8_t* __restrict__ codes, int64_t n, int dim, int64_t row_offset, const float* __restrict__ qf, int k,
     const uint32_t* __restrict__ cand, const int32_t* __restrict__ ccnt, int nchunks, int capc, int qpb,
     int32_t* __restrict__ out_count, int64_t* __restrict__ out_rows, double* __restrict__ out_scores,
     int32_t* __restrict__ fb_flag, float* __restrict__ thr, const double* __restrict__ alpha,
-    const double* __restrict__ beta, const double* __restrict__ delta, int32_t* __restrict__ qbflag) {
+    const double* __restrict__ beta, const double* __restrict__ delta, int32_t* __restrict__ qbflag, G... gather) {
   __shared__ FinF sh;
   __shared__ double tab[2048 * 4];
+  constexpr bool GATHER = sizeof...(G) != 0;
+  const uint32_t* const rows = gather_rows(gather...);
   const int q = blockIdx.x, tid = threadIdx.x;
   if (RETRY && fb_flag[q] != 2) return;
   if (tid == 0) sh.over = 0;
@@ -1985,7 +2040,9 @@ __global__ __launch_bounds__(FIN_NT) void k5mb_finish_kernel(
       const int mid = lo + st;
       if (mid < nchunks && sh.pre[mid] <= j) lo = mid;
     }
-    return Cq[(int64_t)lo * capc + (j - sh.pre[lo])];
+    const uint32_t v = Cq[(int64_t)lo * capc + (j - sh.pre[lo])];
+    if constexpr (GATHER) return rows[v];
+    return v;
   };
   const int kc = running_topk_b(total, row_at, codes, dim, tab, k, sh);
   if (!RETRY && over) {
@@ -2004,13 +2061,15 @@ __global__ __launch_bounds__(FIN_NT) void k5mb_finish_kernel(
   }
 }
 
-// the exact scan of the flagged queries: every row through the same score function
+// the exact scan of the flagged queries: every row (of the list) through the same score function
+template <class... G>
 __global__ __launch_bounds__(FIN_NT) void k5mb_fallback_kernel(
     const uint8_t* __restrict__ codes, int64_t n, int dim, int64_t row_offset, const float* __restrict__ qf, int k,
     int32_t* __restrict__ out_count, int64_t* __restrict__ out_rows, double* __restrict__ out_scores,
-    const int32_t* __restrict__ fb_flag, bool skip) {
+    const int32_t* __restrict__ fb_flag, bool skip, G... gather) {
   __shared__ FinF sh;
   __shared__ double tab[2048 * 4];
+  const uint32_t* const rows = gather_rows(gather...);
   const int q = blockIdx.x, tid = threadIdx.x;
   if (fb_flag[q] != 1) return;
   if (skip) {
@@ -2022,7 +2081,8 @@ __global__ __launch_bounds__(FIN_NT) void k5mb_fallback_kernel(
     return;
   }
   binary_table(qf + (int64_t)q * dim, dim, tab);
-  const int kc = running_topk_b(n, [](int64_t j) { return (uint32_t)j; }, codes, dim, tab, k, sh);
+  const int kc = running_topk_b(
+      n, [=](int64_t j) { return sizeof...(G) ? rows[j] : (uint32_t)j; }, codes, dim, tab, k, sh);
   write_result_f(q, k, kc, row_offset, sh, out_count, out_rows, out_scores);
 }
 
@@ -2037,12 +2097,24 @@ struct BinaryCall {
   float* dv;
   int32_t* qbf;
   hipStream_t s;
+  const uint32_t* rows;  // K5gb: the allowed rows, ascending (NULL: every row)
 };
 
 template <int KS>
 static void launch_binary_pass(const Plan& p, const BinaryCall& c, int pass) {  // 0 sample, 1 main, 2 retry
   const dim3 blk(Shape<KS>::W * 64);
-  if (pass == 0)
+  if (c.rows && pass == 0)
+    hipLaunchKernelGGL((k5mb_pass_kernel<KS, true, const uint32_t*>), dim3(p.nsc * p.nqb), blk, 0, c.s, c.codes, c.n,
+                       c.qa, c.nq, (const float*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr, 0, p.scr, p.sstride,
+                       p.nsc, p.nqb, c.dv, p.scols, (const int32_t*)nullptr, c.rows);
+  else if (c.rows)
+    hipLaunchKernelGGL((k5mb_pass_kernel<KS, false, const uint32_t*>), dim3(p.nchunks * p.nqb), blk, 0, c.s, c.codes,
+                       c.n, c.qa, c.nq, (const float*)c.thr, c.cand, c.cnt, p.capc, p.chunk_rows, p.chunk_rows,
+                       p.nchunks, p.nqb, (float*)nullptr, (int64_t)0,
+                       pass == 2 ? (const int32_t*)c.qbf : (const int32_t*)nullptr, c.rows);
+  else if constexpr (KS == 32)
+    return;  // (no contiguous KS = 32 instance: launch_binary_pass_dim refuses the call)
+  else if (pass == 0)
     hipLaunchKernelGGL((k5mb_pass_kernel<KS, true>), dim3(p.nsc * p.nqb), blk, 0, c.s, c.codes, c.n, c.qa, c.nq,
                        (const float*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr, 0, p.scr, p.sstride, p.nsc,
                        p.nqb, c.dv, p.scols, (const int32_t*)nullptr);
@@ -2060,17 +2132,22 @@ static int launch_binary_pass_dim(int dim, const Plan& p, const BinaryCall& c, i
     case 768: launch_binary_pass<24>(p, c, pass); break;
     case 1536: launch_binary_pass<48>(p, c, pass); break;
     case 2048: launch_binary_pass<64>(p, c, pass); break;
+    case 1024:  // the gathered call alone (unfiltered 1024 is K5's)
+      if (!c.rows) return VRQ_EUNSUPPORTED;
+      launch_binary_pass<32>(p, c, pass);
+      break;
     default: return VRQ_EUNSUPPORTED;
   }
   VRQ_LAUNCH_CHECK();
   return VRQ_OK;
 }
 
+// rows != NULL (K5gb): n is the length of the list, and the call plans like an unfiltered one on n rows
 static int run_binary(const uint8_t* codes, int64_t n, int dim, int64_t row_offset, const float* qf, int nq, int k,
                       int flags, int32_t* out_count, int64_t* out_rows, double* out_scores, void* workspace,
-                      size_t workspace_bytes, hipStream_t s) {
+                      size_t workspace_bytes, hipStream_t s, const uint32_t* rows = nullptr) {
   Plan p;
-  const int rc = plan_shape(n, dim, nq, k, &p);
+  const int rc = plan_shape(n, dim, nq, k, &p, rows != nullptr);
   if (rc != VRQ_OK) return rc;
   if (workspace_bytes < p.bytes) return VRQ_EWORKSPACE;
   constexpr int ALL = VRQ_GEMM_STAGE_SAMPLE | VRQ_GEMM_STAGE_MAIN | VRQ_GEMM_STAGE_FINISH;
@@ -2082,7 +2159,7 @@ static int run_binary(const uint8_t* codes, int64_t n, int dim, int64_t row_offs
   double* beta = (double*)(ws + p.off_beta);
   int32_t* flag = (int32_t*)(ws + p.off_flag);
   const BinaryCall c{codes, n, qa, nq, (float*)(ws + p.off_thr), (uint32_t*)(ws + p.off_cand),
-                     (int32_t*)(ws + p.off_cnt), (float*)(ws + p.off_dv), (int32_t*)(ws + p.off_qbf), s};
+                     (int32_t*)(ws + p.off_cnt), (float*)(ws + p.off_dv), (int32_t*)(ws + p.off_qbf), s, rows};
   if (st & VRQ_GEMM_STAGE_SAMPLE) {
     hipLaunchKernelGGL(k5mb_prep_kernel, dim3((p.nq_pad + 3) / 4), dim3(256), 0, s, qf, nq, p.nq_pad, dim, qa, delta,
                        alpha, beta);
@@ -2100,18 +2177,33 @@ static int run_binary(const uint8_t* codes, int64_t n, int dim, int64_t row_offs
   if (st & VRQ_GEMM_STAGE_FINISH) {
     // finish -> retry main pass (query blocks with a retried query) -> finish of the retried queries ->
     // exact scan of the rest
-    hipLaunchKernelGGL(k5mb_finish_kernel<false>, dim3(nq), dim3(FIN_NT), 0, s, codes, n, dim, row_offset, qf, k,
-                       (const uint32_t*)c.cand, (const int32_t*)c.cnt, p.nchunks, p.capc, p.qpb, out_count, out_rows,
-                       out_scores, flag, c.thr, (const double*)alpha, (const double*)beta, (const double*)delta, c.qbf);
+    const bool skip = (flags & VRQ_GEMM_NO_FALLBACK) != 0;
+    auto finish = [&](auto RETRY, auto... g) {
+      hipLaunchKernelGGL((k5mb_finish_kernel<decltype(RETRY)::value, decltype(g)...>), dim3(nq), dim3(FIN_NT), 0, s,
+                         codes, n, dim, row_offset, qf, k, (const uint32_t*)c.cand, (const int32_t*)c.cnt, p.nchunks,
+                         p.capc, p.qpb, out_count, out_rows, out_scores, flag, c.thr, (const double*)alpha,
+                         (const double*)beta, (const double*)delta, c.qbf, g...);
+    };
+    auto fallback = [&](auto... g) {
+      hipLaunchKernelGGL((k5mb_fallback_kernel<decltype(g)...>), dim3(nq), dim3(FIN_NT), 0, s, codes, n, dim,
+                         row_offset, qf, k, out_count, out_rows, out_scores, (const int32_t*)flag, skip, g...);
+    };
+    if (rows)
+      finish(std::false_type{}, rows);
+    else
+      finish(std::false_type{});
     VRQ_LAUNCH_CHECK();
     const int r2 = launch_binary_pass_dim(dim, p, c, 2);
     if (r2 != VRQ_OK) return r2;
-    hipLaunchKernelGGL(k5mb_finish_kernel<true>, dim3(nq), dim3(FIN_NT), 0, s, codes, n, dim, row_offset, qf, k,
-                       (const uint32_t*)c.cand, (const int32_t*)c.cnt, p.nchunks, p.capc, p.qpb, out_count, out_rows,
-                       out_scores, flag, c.thr, (const double*)alpha, (const double*)beta, (const double*)delta, c.qbf);
+    if (rows)
+      finish(std::true_type{}, rows);
+    else
+      finish(std::true_type{});
     VRQ_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k5mb_fallback_kernel, dim3(nq), dim3(FIN_NT), 0, s, codes, n, dim, row_offset, qf, k, out_count,
-                       out_rows, out_scores, (const int32_t*)flag, (flags & VRQ_GEMM_NO_FALLBACK) != 0);
+    if (rows)
+      fallback(rows);
+    else
+      fallback();
     VRQ_LAUNCH_CHECK();
   }
   return VRQ_OK;
@@ -2398,7 +2490,7 @@ int vrq_gemm_topk_rows(int32_t mode, const uint8_t* codes, const int8_t* x8, con
                        int32_t k, int32_t flags, int32_t* out_count, int64_t* out_rows, double* out_scores,
                        void* workspace, size_t workspace_bytes, void* stream) {
   (void)codes;
-  if (mode == VRQ_GEMM_BINARY) return VRQ_EUNSUPPORTED;  // K5mb's packed tiles need a gather of their own
+  if (mode == VRQ_GEMM_BINARY) return VRQ_EUNSUPPORTED;  // K5mb's gather has its own entry: vrq_binary_topk_gather
   if (mode != VRQ_GEMM_INT8_COSINE) return VRQ_EINVAL;
   if (!vrq_dim_supported(dim)) return VRQ_EUNSUPPORTED;
   if (flags & ~g5d::ROWS_FLAGS) return VRQ_EUNSUPPORTED;
@@ -2433,6 +2525,32 @@ int vrq_flat_ip_topk_rows(const float* xf, const int8_t* x8, const double* inv_s
   VRQ_CHECK_ARG(rows && workspace && xf && x8 && inv_scale && bounds);
   return g5d::run_float(xf, x8, inv_scale, bounds, m, dim, row_offset, qf, nq, k, flags, out_count, out_rows,
                         out_scores, workspace, workspace_bytes, (hipStream_t)stream, rows);
+}
+
+size_t vrq_binary_topk_gather_workspace_size(int64_t m, int32_t dim, int32_t nq, int32_t k) {
+  g5d::Plan p;
+  return g5d::plan_rows(m, dim, nq, k, &p) == VRQ_OK ? p.bytes : 0;
+}
+
+int vrq_binary_topk_gather_plan(int64_t m, int32_t dim, int32_t nq, int32_t k, int64_t* info) {
+  if (!info) return VRQ_EINVAL;
+  g5d::Plan p;
+  const int rc = g5d::plan_rows(m, dim, nq, k, &p);
+  if (rc == VRQ_OK) g5d::plan_info(p, info);
+  return rc;
+}
+
+int vrq_binary_topk_gather(const uint8_t* codes, int64_t n, int32_t dim, int64_t row_offset, const uint32_t* rows,
+                           int64_t m, const float* qf, int32_t nq, int32_t k, int32_t flags, int32_t* out_count,
+                           int64_t* out_rows, double* out_scores, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+  if (!vrq_dim_supported(dim)) return VRQ_EUNSUPPORTED;
+  if (flags & ~g5d::ROWS_FLAGS) return VRQ_EUNSUPPORTED;
+  VRQ_CHECK_ARG(qf && out_count && out_rows && out_scores && n > 0 && nq > 0 && k > 0 && m >= 0 && m <= n);
+  if (m == 0) return g5d::run_empty(nq, k, out_count, out_rows, out_scores, (hipStream_t)stream);
+  VRQ_CHECK_ARG(rows && workspace && codes);
+  return g5d::run_binary(codes, m, dim, row_offset, qf, nq, k, flags, out_count, out_rows, out_scores, workspace,
+                         workspace_bytes, (hipStream_t)stream, rows);
 }
 
 int vrq_binary_topk_dim_engine(int64_t n, int32_t dim, int32_t nq, int32_t k) {

@@ -79,8 +79,9 @@ def gemm_topk(mode: str, qf: torch.Tensor, k: int, codes: torch.Tensor | None = 
     stage flags); "auto" asks ``vrq_gemm_topk_dim_engine`` / ``vrq_binary_topk_dim_engine``, which pick the
     matrix path from a measured minimum batch per dim and otherwise leave the call on the ``engine=None``
     route (so "auto" at 1024 is K5, never the exact scan).  ``rows`` (uint32[m], ascending: ``filters.row_list`` /
-    ``filters.ids_rows``): int8_cosine over those rows alone on the gathered matrix path at every dim (K5g,
-    ``vrq_gemm_topk_rows``); the rows returned are corpus rows.  The binary mode takes no row list."""
+    ``filters.ids_rows``): the search over those rows alone on the gathered matrix path at every dim, 1024 included
+    (int8_cosine: K5g, ``vrq_gemm_topk_rows``; binary: K5gb, ``vrq_binary_topk_gather``), whatever ``engine`` is
+    but "exact", which raises: the exact scan takes no row list.  The rows returned are corpus rows."""
     if engine not in (None, "exact", "mfma", "auto"):
         raise ValueError(f"engine {engine!r}: None, 'exact', 'mfma' or 'auto'")
     m = {"binary": N.VRQ_GEMM_BINARY, "int8_cosine": N.VRQ_GEMM_INT8_COSINE}[mode]
@@ -88,10 +89,9 @@ def gemm_topk(mode: str, qf: torch.Tensor, k: int, codes: torch.Tensor | None = 
     dev = qf.device
     nq, n = qf.shape[0], src.shape[0]
     allowed, rows = rows, None  # (rows: the output below)
-    if allowed is not None and (m == N.VRQ_GEMM_BINARY or engine == "exact"):
-        raise N.VrqNativeError("gemm_topk(rows=...): the filtered exhaustive search serves int8_cosine on the matrix "
-                               "path alone (the binary pass loads packed tiles and has no gathered variant; the "
-                               "exact scan has none either)")
+    if allowed is not None and engine == "exact":
+        raise N.VrqNativeError("gemm_topk(rows=...): the filtered exhaustive search runs on the matrix path alone "
+                               "(the exact scan has no gathered variant)")
     cnt = torch.full((nq,), -2, dtype=torch.int32, device=dev)  # -2: never written
     rows = torch.full((nq, k), -2, dtype=torch.int64, device=dev)
     scores = torch.empty((nq, k), dtype=torch.float64, device=dev)
@@ -100,12 +100,19 @@ def gemm_topk(mode: str, qf: torch.Tensor, k: int, codes: torch.Tensor | None = 
     if allowed is not None:
         allowed = filters.checked_rows(allowed, n, dev)
         nr = int(allowed.shape[0])
-        need = lib.vrq_gemm_topk_rows_workspace_size(m, nr, dim, nq, k)
+        binary = m == N.VRQ_GEMM_BINARY
+        need = lib.vrq_binary_topk_gather_workspace_size(nr, dim, nq, k) if binary else \
+            lib.vrq_gemm_topk_rows_workspace_size(m, nr, dim, nq, k)
         if need == 0:
-            raise N.VrqNativeError(f"vrq_gemm_topk_rows: unsupported shape m={nr} dim={dim} nq={nq} k={k} "
-                                   "(dims: vrq_dim_supported; k <= 1024)")
+            raise N.VrqNativeError(f"{'vrq_binary_topk_gather' if binary else 'vrq_gemm_topk_rows'}: unsupported shape "
+                                   f"m={nr} dim={dim} nq={nq} k={k} (dims: vrq_dim_supported; k <= 1024)")
         if workspace is None or workspace.numel() < need:
             workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+        if binary:
+            N.check(lib.vrq_binary_topk_gather(N.ptr(codes), n, dim, row_offset, N.ptr(allowed), nr, N.ptr(qf), nq, k,
+                                               flags, N.ptr(cnt), N.ptr(rows), N.ptr(scores), N.ptr(workspace),
+                                               workspace.numel(), N.stream_handle(dev)), "vrq_binary_topk_gather")
+            return cnt, rows, scores
         N.check(lib.vrq_gemm_topk_rows(m, N.ptr(codes), N.ptr(x8), N.ptr(norms), n, dim, row_offset, N.ptr(allowed),
                                        nr, N.ptr(qf), nq, k, flags, N.ptr(cnt), N.ptr(rows), N.ptr(scores),
                                        N.ptr(workspace), workspace.numel(), N.stream_handle(dev)),
