@@ -904,6 +904,53 @@ int vrq_search2_perquery(int32_t mode, const uint8_t* codes, const void* q, cons
                          int64_t set_words, const int32_t* query_set);
 
 /* ---------------------------------------------------------------------------
+ * Filtered search over a row list, reading only the allowed rows (K1g; additive to ABI version 1).  The bitmap
+ * calls above stream every row whatever the bitmap says; these run the counting scan, on either engine, in the
+ * row space of an ascending list of allowed rows (vrq_row_list builds one from a bitmap) and read the listed
+ * rows alone, so their cost follows the list's length m, not the corpus.
+ * vrq_scan_gather / vrq_hamming_topk_gather / vrq_search3_gather / vrq_search2_gather: the arguments of the
+ *   *_batch call, `engine` included, with `allow` replaced by
+ *   rows  device u32 [m], 4-byte aligned: the allowed rows, strictly ascending, every entry < n (preconditions,
+ *         as for the vrq_*_rows calls: not checked on the device).  Not read when m == 0.
+ *   m     0 <= m <= n.
+ *   Every output is, bit for bit, what the *_batch call of the same engine returns for the bitmap that has
+ *   exactly the listed rows set; equivalently, what the *_large call returns on the gathered copy codes[rows]
+ *   with its rows mapped back through the list.  out_rows are row_offset + physical row, and rescore_row[r] is
+ *   indexed by the physical row r.  m < K gives lists of length m.  m == 0 launches no chunk of the scan and
+ *   answers exactly as the bitmap call does with an all-zero bitmap: counts 0, rows -1, the padding values.
+ *   Returns VRQ_EINVAL for m < 0, m > n, an engine outside VRQ_LARGE_ENGINE_*, or a null or misaligned `rows`
+ *   with m > 0.  Shapes, flags, stage masks, K > VRQ_K_LARGE_MAX and the other return codes are those of the
+ *   *_batch calls on an m-row corpus; every argument and the workspace size are checked before anything is
+ *   launched.  VRQ_LARGE_ENGINE_AUTO reads the *_batch calls' table at m rows.
+ * vrq_*_gather_workspace_size(m, ...): vrq_*_batch_workspace_size at m rows (m = 0 answers as m = 1).
+ * vrq_scan_gather_plan(m, dim, nq, K, engine, info): vrq_scan_batch_plan at m rows -- the chunks, the ragged
+ *   last tile, the chunk prefixes and K1hm's flush interval all count list positions; info[0] is the engine
+ *   that runs.
+ * ------------------------------------------------------------------------- */
+int vrq_scan_gather_plan(int64_t m, int32_t dim, int32_t nq, int32_t K, int32_t engine, int64_t* info);
+size_t vrq_scan_gather_workspace_size(int64_t m, int32_t dim, int32_t nq, int32_t K);
+int vrq_scan_gather(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq, int32_t K,
+                    int32_t stages, const uint32_t* rows, int64_t m, void* workspace, size_t workspace_bytes,
+                    void* stream, int32_t engine);
+size_t vrq_hamming_topk_gather_workspace_size(int64_t m, int32_t code_bytes, int32_t nq, int32_t k);
+int vrq_hamming_topk_gather(const uint8_t* codes, int64_t n, int32_t code_bytes, int64_t row_offset,
+                            const uint8_t* queries, int32_t nq, int32_t k, const uint32_t* rows, int64_t m,
+                            int32_t* out_dist, int64_t* out_rows, void* workspace, size_t workspace_bytes,
+                            void* stream, int32_t engine);
+size_t vrq_search3_gather_workspace_size(int64_t m, int32_t dim, int32_t nq, int32_t K);
+int vrq_search3_gather(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
+                       int64_t n, int32_t dim, int64_t row_offset, const float* qf, const uint8_t* qb, int32_t nq,
+                       int32_t k, int32_t K, int32_t K3, int32_t flags, const uint32_t* rows, int64_t m,
+                       int32_t* out_count, int64_t* out_rows, int32_t* out_dist, double* out_binary,
+                       double* out_cosine, void* workspace, size_t workspace_bytes, void* stream, int32_t engine);
+size_t vrq_search2_gather_workspace_size(int64_t m, int32_t dim, int32_t nq, int32_t K);
+int vrq_search2_gather(int32_t mode, const uint8_t* codes, const void* q, const double* minmax, double limit,
+                       const int64_t* rescore_row, int64_t n, int32_t dim, int64_t row_offset, const float* qf,
+                       const uint8_t* qb, int32_t nq, int32_t k, int32_t K, int32_t flags, const uint32_t* rows,
+                       int64_t m, int32_t* out_count, int64_t* out_rows, int32_t* out_dist, double* out_score,
+                       void* workspace, size_t workspace_bytes, void* stream, int32_t engine);
+
+/* ---------------------------------------------------------------------------
  * Row-sharded search with more than 1024 Phase-I candidates (additive to ABI version 1; vrq_shard_search3,
  * vrq_shard_search2, vrq_merge_shards and vrq_merge_shards2 keep their K <= 1024 contract).
  * vrq_shard_search3_large / vrq_shard_search2_large: the arguments and outputs of vrq_shard_search3 /

@@ -11,9 +11,13 @@ as random bits and as one contiguous range of rows), on preallocated buffers:
 * ``b_filtered``    ``vrq_search3_filtered``, and its stages through ``vrq_scan_filtered``: ``count``,
   ``threshold``, ``emit``;
 * ``c_gather``      today's route: ``torch.index_select`` of the allowed codes, int8 rows and norms into a
-  compact corpus (timed), then ``vrq_search3_large`` on it; ``c_gather_only`` is the copy alone.
+  compact corpus (timed), then ``vrq_search3_large`` on it; ``c_gather_only`` is the copy alone;
+* ``g_rows``        ``vrq_search3_gather`` (K1g) on ``--engine``: the scan over the row list, which reads the allowed
+  rows only; ``g_scan`` is its scan alone (``vrq_scan_gather``).  The list is built outside the timed window and
+  its build time (``filters.row_list``, one wall-clock measurement) is reported once as ``g_list_build_ms``.
+  With ``--engine mfma`` the bitmap call of the same engine is timed too (``b_batch``: ``vrq_search3_batch``).
 
-Before timing, (b) is compared with (c) mapped back to the original rows, bit for bit.  One JSON line per
+Before timing, (b) is compared with (c) mapped back to the original rows, and (g) with (b), bit for bit.  One JSON line per
 (dim, nq, filter); times in ms are the median over the rounds with the min and max beside it; ``b_over_a`` and
 ``b_over_c`` are ratios of the medians.  Random codes and int8 rows; queries are corpus rows with d/16 .. d/4
 flipped bits.
@@ -24,6 +28,7 @@ import argparse
 import json
 import os
 import sys
+import time
 
 import torch
 
@@ -60,8 +65,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--window-ms", type=float, default=search2_bench.MIN_WINDOW_MS)
+    ap.add_argument("--engine", default="valu", choices=("valu", "mfma"), help="engine of the gathered leg")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     a = ap.parse_args()
+    engine = {"valu": N.VRQ_LARGE_ENGINE_VALU, "mfma": N.VRQ_LARGE_ENGINE_MFMA}[a.engine]
     search2_bench.MIN_WINDOW_MS = a.window_ms
     dev = torch.device("cuda", 0)
     lib = N.load()
@@ -106,6 +113,17 @@ def main():
                     gneed = lib.vrq_search3_large_workspace_size(m, d, nq, K)
                     gws = torch.empty((gneed,), dtype=torch.uint8, device=dev)
                     scan = (P(codes), n, d, P(qb), nq, K)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    lst = filters.row_list(allow, n)
+                    torch.cuda.synchronize()
+                    build_ms = (time.perf_counter() - t0) * 1e3
+                    assert int(lst.shape[0]) == m
+                    # (a workspace of the gathered call's own: it is sized by the list)
+                    rneed = max(lib.vrq_search3_gather_workspace_size(m, d, nq, K), 8)
+                    rws = torch.empty((rneed,), dtype=torch.uint8, device=dev)
+                    bneed = lib.vrq_search3_batch_workspace_size(n, d, nq, K)
+                    bws = torch.empty((bneed,), dtype=torch.uint8, device=dev)
 
                     def gather():
                         torch.index_select(codes, 0, keep, out=gcodes[:m])
@@ -127,7 +145,18 @@ def main():
                             lib.vrq_scan_filtered(*scan, bit, P(allow), *tail), "stage")
                     legs["c_gather"] = compact
                     legs["c_gather_only"] = gather
+                    legs["g_rows"] = lambda: N.check(lib.vrq_search3_gather(*three, P(lst), m, *outs, P(rws), rneed, st,
+                                                                            engine), "g")
+                    legs["g_scan"] = lambda: N.check(lib.vrq_scan_gather(*scan, 0, P(lst), m, P(rws), rneed, st,
+                                                                         engine), "g_scan")
+                    if engine == N.VRQ_LARGE_ENGINE_MFMA:
+                        legs["b_batch"] = lambda: N.check(lib.vrq_search3_batch(*three, P(allow), *outs, P(bws), bneed,
+                                                                                st, engine), "b_batch")
                     got = results(legs["b_filtered"])
+                    rowsout = results(legs["g_rows"])
+                    assert all(torch.equal(x.view(torch.int64) if x.dtype == torch.float64 else x,
+                                           y.view(torch.int64) if y.dtype == torch.float64 else y)
+                               for x, y in zip(rowsout, got)), "the gathered call differs from the bitmap call"
                     want = results(compact)
                     want[1] = torch.where(want[1] >= 0, keep[want[1].clamp_min(0)], want[1])
                     same = all(torch.equal(x.view(torch.int64) if x.dtype == torch.float64 else x,
@@ -142,18 +171,22 @@ def main():
                         for name, call in legs.items():
                             times[name].append(window(call, reps[name]))
                     rec = {"dim": d, "n": n, "nq": nq, "K": K, "selectivity": sel, "filter": kind, "allowed": m,
-                           "rounds": a.rounds, "filtered_equals_gathered": same}
+                           "rounds": a.rounds, "filtered_equals_gathered": same, "engine": a.engine,
+                           "g_list_build_ms": round(build_ms, 4)}
                     for name in legs:
                         rec[name] = summary(times[name])
                     rec["b_finish_ms"] = round(rec["b_filtered"]["ms"] - rec["b_scan"]["ms"], 4)
                     rec["b_over_a"] = round(rec["b_filtered"]["ms"] / rec["a_large"]["ms"], 3)
                     rec["b_over_c"] = round(rec["b_filtered"]["ms"] / rec["c_gather"]["ms"], 3)
+                    like = rec["b_batch" if "b_batch" in rec else "b_filtered"]["ms"]
+                    rec["g_over_b"] = round(rec["g_rows"]["ms"] / like, 3)
+                    rec["g_over_c"] = round(rec["g_rows"]["ms"] / rec["c_gather"]["ms"], 3)
                     line = json.dumps(rec)
                     print(line, flush=True)
                     if out:
                         out.write(line + "\n")
                         out.flush()
-                    del legs, gws
+                    del legs, gws, rws, bws
             del ws
         del codes, x8, norms, gcodes, gx8, gnorms
         torch.cuda.empty_cache()

@@ -154,6 +154,19 @@ SIGNATURES = {
                                        _P, _P, _P, _P, _P, _P, _SZ, _P, _I32, _I32, _I64, _P]),
     "vrq_search2_perquery": (C.c_int, [_I32, _P, _P, _P, _D, _P, _I64, _I32, _I64, _P, _P, _I32, _I32, _I32, _I32,
                                        _P, _P, _P, _P, _P, _P, _SZ, _P, _I32, _I32, _I64, _P]),
+    # the *_batch prototypes with (const uint64* allow) replaced by (const uint32* rows, int64 m)
+    "vrq_scan_gather_plan": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _P]),
+    "vrq_scan_gather_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
+    "vrq_scan_gather": (C.c_int, [_P, _I64, _I32, _P, _I32, _I32, _I32, _P, _I64, _P, _SZ, _P, _I32]),
+    "vrq_hamming_topk_gather_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
+    "vrq_hamming_topk_gather": (C.c_int, [_P, _I64, _I32, _I64, _P, _I32, _I32, _P, _I64, _P, _P, _P, _SZ, _P,
+                                          _I32]),
+    "vrq_search3_gather_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
+    "vrq_search3_gather": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _P,
+                                     _I64, _P, _P, _P, _P, _P, _P, _SZ, _P, _I32]),
+    "vrq_search2_gather_workspace_size": (_SZ, [_I64, _I32, _I32, _I32]),
+    "vrq_search2_gather": (C.c_int, [_I32, _P, _P, _P, _D, _P, _I64, _I32, _I64, _P, _P, _I32, _I32, _I32, _I32,
+                                     _P, _I64, _P, _P, _P, _P, _P, _SZ, _P, _I32]),
     "vrq_gemm_topk_workspace_size": (_SZ, [_I32, _I64, _I32, _I32, _I32]),
     "vrq_gemm_topk_pieces": (C.c_int, []),
     "vrq_gemm_topk_plan": (C.c_int, [_I32, _I64, _I32, _I32, _I32, _P]),
@@ -393,13 +406,23 @@ class SearchCall:
 
     With ``query_set`` (one set id per query; ``allow`` then holds a bitmap per set, ``filters.row_bitmaps``)
     the route is ``<base>_perquery``: a batch call with the filter's shape after the engine.  It has no earlier
-    route to preserve, so ``engine=None`` means "auto" there; its workspace is the batch call's."""
+    route to preserve, so ``engine=None`` means "auto" there; its workspace is the batch call's.
+
+    With ``rows`` (an ascending uint32 row list, ``filters.row_list``; exclusive with ``allow`` / ``query_set``)
+    the route is ``<base>_gather``: the batch call over the list, which reads the listed rows only.
+    ``engine=None`` means "auto" there too; its workspace is its own, sized by the list's length."""
 
     def __init__(self, base: str, K: int, flags: int = 0, allow=None, engine=None, what: str = None,
-                 plain: str = None, query_set=None):
+                 plain: str = None, query_set=None, rows=None):
         what = what or base
         self.perquery = query_set is not None
-        if self.perquery:
+        self.gather = rows is not None
+        if self.gather:
+            if allow is not None or query_set is not None:
+                raise VrqNativeError(f"{what}: rows is exclusive with allow / query_set")
+            self.m = int(rows.shape[0])
+            engine = "auto" if engine is None else engine
+        elif self.perquery:
             if allow is None:
                 raise VrqNativeError(f"{what}: query_set without allow (a bitmap per set, filters.row_bitmaps)")
             engine = "auto" if engine is None else engine
@@ -407,7 +430,9 @@ class SearchCall:
             raise VrqNativeError(f"{what}: a {allow.ndim}-D allow needs query_set (one set id per query)")
         self.engine = batch_engine(engine, K, flags, what)
         self.sized_by = None  # the call whose *_workspace_size serves this one (default: its own)
-        if self.perquery:
+        if self.gather:
+            self.name = base + "_gather"
+        elif self.perquery:
             self.name = base + "_perquery"
             self.sized_by = base + "_batch"
         elif self.engine is not None:
@@ -421,6 +446,8 @@ class SearchCall:
 
     def workspace_bytes(self, lib, n: int, width: int, nq: int, K: int) -> int:
         """``<name>_workspace_size`` (``width``: dim, or code bytes for vrq_hamming_topk*); 0 for an empty shape."""
+        if self.gather:  # sized by the list (an empty one is sized as one row)
+            n = max(self.m, 1)
         return getattr(lib, (self.sized_by or self.name) + "_workspace_size")(n, width, nq, K) if n and nq and K else 0
 
     def workspace(self, lib, n: int, width: int, nq: int, K: int, device, have=None):
@@ -431,12 +458,14 @@ class SearchCall:
             return have
         return torch.empty((max(8, need),), dtype=torch.uint8, device=device)
 
-    def __call__(self, lib, head: tuple, tail: tuple, allow, ws, device, label: str = None, query_set=None) -> None:
+    def __call__(self, lib, head: tuple, tail: tuple, allow, ws, device, label: str = None, query_set=None,
+                 rows=None) -> None:
         """``name(*head, [allow,] *tail, ws, bytes, stream[, engine[, nsets, set_words, query_set]])``: the
         bitmap's pointer goes between the inputs and the outputs of a *_filtered / *_batch / *_perquery call, the
-        engine ends a *_batch call, the filter's shape (from the 2-D ``allow``) a *_perquery call.  Raises unless
-        VRQ_OK."""
-        args = head + ((ptr(allow),) if self.bitmap else ()) + tail + (ptr(ws), ws.numel(), stream_handle(device))
+        engine ends a *_batch call, the filter's shape (from the 2-D ``allow``) a *_perquery call.  A *_gather call
+        has ``rows`` (``filters.checked_rows``) and its length where the bitmap goes.  Raises unless VRQ_OK."""
+        mid = (ptr(rows) if self.m else 0, self.m) if self.gather else (ptr(allow),) if self.bitmap else ()
+        args = head + mid + tail + (ptr(ws), ws.numel(), stream_handle(device))
         end = () if self.engine is None else (self.engine,)
         if self.perquery:
             end += (int(allow.shape[0]), set_words_of(allow), ptr(query_set)) if allow is not None else (1, 0, 0)

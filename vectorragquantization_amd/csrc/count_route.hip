@@ -107,6 +107,16 @@ int count_route_launch(const CountPlan& p, const uint8_t* codes, int64_t n, int 
     a.tc = (int32_t*)(ws + p.off_tc) + (int64_t)b0 * 2;
     a.lists = (uint64_t*)(ws + p.off_lists) + (int64_t)b0 * K;
     int rc;
+    if (filter.empty_list) {  // K1g over an empty list: what an all-zero bitmap leaves, without a scan
+      if (stages & kLargeStageCount &&
+          hipMemsetAsync(a.hist, 0, (size_t)a.nq * p.nchunks * bins * sizeof(uint32_t), s) != hipSuccess)
+        return VRQ_EHIP;
+      if (stages & kLargeStageThreshold) {
+        rc = large_threshold_launch(a.hist, a.nq, p.nchunks, bins, want, K, true, a.tc, a.prefix, a.lists, s);
+        if (rc != VRQ_OK) return rc;
+      }
+      continue;
+    }
     if (stages & kLargeStageCount) {
       rc = mfma ? large_mfma_count_launch(cb, a, s) : large_count_launch(cb, a, s);
       if (rc != VRQ_OK) return rc;

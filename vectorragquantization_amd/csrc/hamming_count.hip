@@ -76,6 +76,20 @@ struct TileRing {
                                        (__attribute__((address_space(3))) void*)(buf + gi * 1024), 16, 0, 0);
     }
   }
+  // FILTER_ROWS (K1g): the same pieces of the listed rows: pa[gi] is the list entry of piece gi's tile row
+  // (RowSlab::piece_entries; clamped there)
+  __device__ __forceinline__ void issue_rows(int slot, const uint32_t (&pa)[C]) const {
+    uint8_t* buf = base + slot * TILE;
+#pragma unroll
+    for (int gi = 0; gi < C; ++gi) {
+      const int p = gi * 64 + l;
+      const int r = p / C, cs = p % C;
+      const int rr = SHIFT < 0 ? 0 : (r >> SHIFT) % C;
+      const int c = (cs + C - rr) % C;
+      __builtin_amdgcn_global_load_lds(codes + (int64_t)pa[gi] * CB + c * 16,
+                                       (__attribute__((address_space(3))) void*)(buf + gi * 1024), 16, 0, 0);
+    }
+  }
   // the lane's row of slot `slot` -> registers, retired before return
   __device__ __forceinline__ void read(int slot, v4u (&rv)[C]) const {
     const uint32_t boff = (uint32_t)(slot * TILE);
@@ -141,10 +155,12 @@ template <int CB, int FILTER>
 __global__ __launch_bounds__(64 * large_waves(CB)) void hamming_count_kernel(
     const uint8_t* __restrict__ codes, int64_t n, const uint8_t* __restrict__ queries, int nq, int64_t chunk_rows,
     int nchunks, int nqg, uint32_t* __restrict__ hist_out, const uint64_t* __restrict__ allow, int nsets,
-    int64_t set_words, const int32_t* __restrict__ query_set) {
+    int64_t set_words, const int32_t* __restrict__ query_set, const uint32_t* __restrict__ rows) {
   using Ring = TileRing<CB>;
+  using Slab = RowSlab<4>;
   constexpr int C = Ring::C, NW = large_waves(CB), QG = large_qg(CB), BINS = CB * 8 + 1;
-  __shared__ __attribute__((aligned(16))) uint8_t ring[NW * 2 * Ring::TILE];
+  constexpr bool GATHER = FILTER == FILTER_ROWS;  // n is the list's length, the chunk's rows are list positions
+  __shared__ __attribute__((aligned(16))) uint8_t ring[NW * 2 * Ring::TILE + (GATHER ? NW * Slab::BYTES : 0)];
   __shared__ uint32_t hist[QG * BINS];
 
   const int L = xcd_linear_block();
@@ -184,13 +200,29 @@ __global__ __launch_bounds__(64 * large_waves(CB)) void hamming_count_kernel(
   const int ntiles = (nrows + 63) >> 6;
   const int ntw = w < ntiles ? (ntiles - w + NW - 1) / NW : 0;
   Ring tr(ring + w * 2 * Ring::TILE, codes, row0, row1);
-  if (ntw > 0) tr.issue(w, 0);
-  if (ntw > 1) tr.issue(w + NW, 1);
+  const Slab rs{ring + NW * 2 * Ring::TILE + w * Slab::BYTES, rows, row0, row1, w, NW, l};
+  if constexpr (GATHER) {
+    if (ntw > 0) rs.fill(tr, ntw);
+  } else {
+    if (ntw > 0) tr.issue(w, 0);
+    if (ntw > 1) tr.issue(w + NW, 1);
+  }
   for (int i = 0; i < ntw; ++i) {
-    if (i + 1 < ntw) wait_vmcnt<C>(); else wait_vmcnt<0>();
+    if (i + 1 < ntw) wait_vmcnt<C + GATHER>(); else wait_vmcnt<0>();
     v4u rv[C];
+    uint32_t pa[GATHER ? C : 1];
+    if constexpr (GATHER)
+      if (i + 2 < ntw) rs.piece_entries(i + 2, pa);  // (retired by the wait of read())
     tr.read(i & 1, rv);
-    if (i + 2 < ntw) tr.issue(w + (i + 2) * NW, i & 1);  // (the slot's reads are retired)
+    if constexpr (GATHER) {
+      if (i + 2 < ntw) {
+        Slab::pin(pa);
+        tr.issue_rows(i & 1, pa);
+      }
+      rs.request(i + 4);
+    } else {
+      if (i + 2 < ntw) tr.issue(w + (i + 2) * NW, i & 1);  // (the slot's reads are retired)
+    }
     bool live = (w + i * NW) * 64 + l < nrows;
     if constexpr (FILTER == FILTER_SETS) {
       const int idx = __builtin_amdgcn_readfirstlane((int)(row0 >> 6) + w + i * NW);
@@ -353,10 +385,13 @@ __global__ __launch_bounds__(64) void hamming_emit_kernel(const uint8_t* __restr
                                                           uint64_t* __restrict__ lists,
                                                           const uint64_t* __restrict__ allow, int nsets,
                                                           int64_t set_words,
-                                                          const int32_t* __restrict__ query_set) {
+                                                          const int32_t* __restrict__ query_set,
+                                                          const uint32_t* __restrict__ rows) {
   using Ring = TileRing<CB>;
+  using Slab = RowSlab<4>;
   constexpr int C = Ring::C, QE = LARGE_QE;
-  __shared__ __attribute__((aligned(16))) uint8_t ring[2 * Ring::TILE];
+  constexpr bool GATHER = FILTER == FILTER_ROWS;
+  __shared__ __attribute__((aligned(16))) uint8_t ring[2 * Ring::TILE + (GATHER ? Slab::BYTES : 0)];
 
   const int L = xcd_linear_block();
   const int chunk = L / nqg;
@@ -405,13 +440,32 @@ __global__ __launch_bounds__(64) void hamming_emit_kernel(const uint8_t* __restr
 
   const int ntiles = (nrows + 63) >> 6;
   Ring tr(ring, codes, row0, row1);
-  tr.issue(0, 0);
-  if (ntiles > 1) tr.issue(1, 1);
+  const Slab rs{ring + 2 * Ring::TILE, rows, row0, row1, 0, 1, l};
+  if constexpr (GATHER) {
+    rs.fill(tr, ntiles);
+  } else {
+    tr.issue(0, 0);
+    if (ntiles > 1) tr.issue(1, 1);
+  }
   for (int i = 0; i < ntiles; ++i) {
-    if (i + 1 < ntiles) wait_vmcnt<C>(); else wait_vmcnt<0>();
+    if (i + 1 < ntiles) wait_vmcnt<C + GATHER>(); else wait_vmcnt<0>();
     v4u rv[C];
+    uint32_t pa[GATHER ? C : 1], krow = 0;  // krow: the list entry of the lane's own row, the key's row field
+    if constexpr (GATHER) {
+      rs.entry(krow, i, l);
+      if (i + 2 < ntiles) rs.piece_entries(i + 2, pa);
+    }
     tr.read(i & 1, rv);
-    if (i + 2 < ntiles) tr.issue(i + 2, i & 1);
+    if constexpr (GATHER) {
+      asm volatile("" : "+v"(krow));
+      if (i + 2 < ntiles) {
+        Slab::pin(pa);
+        tr.issue_rows(i & 1, pa);
+      }
+      rs.request(i + 4);
+    } else {
+      if (i + 2 < ntiles) tr.issue(i + 2, i & 1);
+    }
     const int local = i * 64 + l;
     const bool inrows = local < nrows;
     bool live = inrows;
@@ -445,7 +499,8 @@ __global__ __launch_bounds__(64) void hamming_emit_kernel(const uint8_t* __restr
         const bool lt = live && d < T[j], eq = live && d == T[j];
         const uint64_t mlt = __ballot(lt), meq = __ballot(eq);
         if (mlt | meq) {
-          const uint64_t key = ((uint64_t)(uint32_t)d << KEY_ROW_BITS) | (uint64_t)(row0 + local);
+          const uint64_t key =
+              ((uint64_t)(uint32_t)d << KEY_ROW_BITS) | (GATHER ? (uint64_t)krow : (uint64_t)(row0 + local));
           uint64_t* o = lists + (int64_t)(q0 + j) * K;
           if (lt) {
             const int pos = ltpos[j] + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mlt >> 32),
@@ -483,7 +538,7 @@ int large_count_launch(int cb, const CountPassArgs& a, hipStream_t s) {
     return filter_kind(a.filter, [&](auto F) -> int {
       hipLaunchKernelGGL((hamming_count_kernel<CB, decltype(F)::value>), grid, block, 0, s, a.codes, a.n, a.q, a.nq,
                          a.chunk_rows, a.nchunks, nqg, a.hist, a.filter.allow, a.filter.nsets, a.filter.set_words,
-                         a.filter.query_set);
+                         a.filter.query_set, a.filter.rows);
       VRQ_LAUNCH_CHECK();
       return VRQ_OK;
     });
@@ -498,7 +553,7 @@ int large_emit_launch(int cb, const CountPassArgs& a, hipStream_t s) {
     return filter_kind(a.filter, [&](auto F) -> int {
       hipLaunchKernelGGL((hamming_emit_kernel<CB, decltype(F)::value>), grid, block, 0, s, a.codes, a.n, a.q, a.nq,
                          a.K, a.chunk_rows, a.nchunks, nqg, a.tc, a.prefix, a.lists, a.filter.allow, a.filter.nsets,
-                         a.filter.set_words, a.filter.query_set);
+                         a.filter.set_words, a.filter.query_set, a.filter.rows);
       VRQ_LAUNCH_CHECK();
       return VRQ_OK;
     });

@@ -132,6 +132,19 @@ struct Engine {
                                        (__attribute__((address_space(3))) void*)(buf + gi * 1024), 16, 0, 0);
     }
   }
+  // FILTER_ROWS (K1g): the same pieces of the listed rows: pa[gi] is the list entry of piece gi's tile row
+  // (RowSlab::piece_entries; clamped there)
+  __device__ __forceinline__ void issue_rows(int slot, const uint32_t (&pa)[C]) const {
+    uint8_t* buf = ring + slot * TILE;
+#pragma unroll
+    for (int gi = 0; gi < C; ++gi) {
+      const int p = gi * 64 + l;
+      const int r = p / C, cs = p % C;
+      const int c = (cs + C - Cd::rot(r)) % C;
+      __builtin_amdgcn_global_load_lds(codes + (int64_t)pa[gi] * CB + c * 16,
+                                       (__attribute__((address_space(3))) void*)(buf + gi * 1024), 16, 0, 0);
+    }
+  }
   // both n-blocks of the tile in `slot` -> registers, retired before return
   __device__ __forceinline__ void read(int slot, v4i (&rb)[2][NPH]) const {
     const uint32_t boff = (uint32_t)(slot * TILE);
@@ -179,13 +192,16 @@ template <int KS, int MB, int FILTER>
 __global__ __launch_bounds__(64 * CountCode<KS>::NW) void hamming_count_mfma_kernel(
     const uint8_t* __restrict__ codes, int64_t n, const uint8_t* __restrict__ queries, int nq, int64_t chunk_rows,
     int nchunks, int nqb, uint32_t* __restrict__ hist_out, const uint64_t* __restrict__ allow, int nsets,
-    int64_t set_words, const int32_t* __restrict__ query_set) {
+    int64_t set_words, const int32_t* __restrict__ query_set, const uint32_t* __restrict__ rows) {
   using Cd = CountCode<KS>;
   using Eng = Engine<KS, MB>;
+  using Slab = RowSlab<4>;
   constexpr int C = Cd::C, NPH = Cd::NPH, NW = Cd::NW, BINS = Cd::BINS, QREAL = Cd::QREAL, NG = Cd::NG;
   constexpr int WORDS = MB * NG * BINS;
-  static_assert(Cd::template count_lds<MB>() <= 160 * 1024, "LDS budget");
-  __shared__ __attribute__((aligned(16))) uint8_t ring[NW * 2 * Cd::TILE];
+  constexpr bool GATHER = FILTER == FILTER_ROWS;  // n is the list's length, the chunk's rows are list positions
+  static_assert(Cd::template count_lds<MB>() + NW * (MB * 128 + (GATHER ? Slab::BYTES : 0)) <= 160 * 1024,
+                "LDS budget");
+  __shared__ __attribute__((aligned(16))) uint8_t ring[NW * 2 * Cd::TILE + (GATHER ? NW * Slab::BYTES : 0)];
   __shared__ uint32_t hist[WORDS];
 
   const int L = linear_block();
@@ -241,14 +257,30 @@ __global__ __launch_bounds__(64 * CountCode<KS>::NW) void hamming_count_mfma_ker
     const int nts = ntiles - t0 < SEGT ? ntiles - t0 : SEGT;
     // this wave's tiles of the segment: t0 + w, t0 + w + NW, ...
     const int ntw = w < nts ? (nts - w + NW - 1) / NW : 0;
-    if (ntw > 0) e.issue(t0 + w, 0);
-    if (ntw > 1) e.issue(t0 + w + NW, 1);
+    const Slab rs{ring + NW * 2 * Cd::TILE + w * Slab::BYTES, rows, row0, row1, t0 + w, NW, l};
+    if constexpr (GATHER) {
+      if (ntw > 0) rs.fill(e, ntw);  // (the segment before this one ended on vmcnt(0): every slot is free)
+    } else {
+      if (ntw > 0) e.issue(t0 + w, 0);
+      if (ntw > 1) e.issue(t0 + w + NW, 1);
+    }
     for (int i = 0; i < ntw; ++i) {
-      if (i + 1 < ntw) wait_vm<C>(); else wait_vm<0>();
+      if (i + 1 < ntw) wait_vm<C + GATHER>(); else wait_vm<0>();
       const int tile = t0 + w + i * NW;
       v4i rb[2][NPH];
+      uint32_t pa[GATHER ? C : 1];
+      if constexpr (GATHER)
+        if (i + 2 < ntw) rs.piece_entries(i + 2, pa);  // (retired by the wait of read())
       e.read(i & 1, rb);
-      if (i + 2 < ntw) e.issue(tile + 2 * NW, i & 1);  // (the slot's reads are retired)
+      if constexpr (GATHER) {
+        if (i + 2 < ntw) {
+          Slab::pin(pa);
+          e.issue_rows(i & 1, pa);
+        }
+        rs.request(i + 4);
+      } else {
+        if (i + 2 < ntw) e.issue(tile + 2 * NW, i & 1);  // (the slot's reads are retired)
+      }
       uint64_t word = ~0ull;
       if constexpr (FILTER == FILTER_ONE) {
         word = tile_allow_word(allow, row0, tile);
@@ -344,11 +376,14 @@ __global__ __launch_bounds__(64) void hamming_emit_mfma_kernel(
     const uint8_t* __restrict__ codes, int64_t n, const uint8_t* __restrict__ queries, int nq, int K,
     int64_t chunk_rows, int nchunks, int nqb, const int32_t* __restrict__ tc, const int32_t* __restrict__ prefix,
     uint64_t* __restrict__ lists, const uint64_t* __restrict__ allow, int nsets, int64_t set_words,
-    const int32_t* __restrict__ query_set) {
+    const int32_t* __restrict__ query_set, const uint32_t* __restrict__ rows) {
   using Cd = CountCode<KS>;
   using Eng = Engine<KS, MB>;
+  // eight slots: the hit path of tile i reads the tile's own run for the keys' row fields after request(i + 4)
+  using Slab = RowSlab<8>;
   constexpr int C = Cd::C, NPH = Cd::NPH, QPW = 32 * MB;
-  __shared__ __attribute__((aligned(16))) uint8_t ring[2 * Cd::TILE];
+  constexpr bool GATHER = FILTER == FILTER_ROWS;
+  __shared__ __attribute__((aligned(16))) uint8_t ring[2 * Cd::TILE + (GATHER ? Slab::BYTES : 0)];
   __shared__ int32_t Tq[QPW], ltpos[QPW], eqpos[QPW], tq[QPW];
 
   const int L = linear_block();
@@ -399,13 +434,29 @@ __global__ __launch_bounds__(64) void hamming_emit_mfma_kernel(
   if constexpr (FILTER == FILTER_SETS) sets.init(query_set, q0 + l, l < QPW && q0 + l < nq, nsets, set_words);
 
   const int ntiles = (nrows + 63) >> 6;
-  e.issue(0, 0);
-  if (ntiles > 1) e.issue(1, 1);
+  const Slab rs{ring + 2 * Cd::TILE, rows, row0, row1, 0, 1, l};
+  if constexpr (GATHER) {
+    rs.fill(e, ntiles);
+  } else {
+    e.issue(0, 0);
+    if (ntiles > 1) e.issue(1, 1);
+  }
   for (int i = 0; i < ntiles; ++i) {
-    if (i + 1 < ntiles) wait_vm<C>(); else wait_vm<0>();
+    if (i + 1 < ntiles) wait_vm<C + GATHER>(); else wait_vm<0>();
     v4i rb[2][NPH];
+    uint32_t pa[GATHER ? C : 1];
+    if constexpr (GATHER)
+      if (i + 2 < ntiles) rs.piece_entries(i + 2, pa);
     e.read(i & 1, rb);
-    if (i + 2 < ntiles) e.issue(i + 2, i & 1);
+    if constexpr (GATHER) {
+      if (i + 2 < ntiles) {
+        Slab::pin(pa);
+        e.issue_rows(i & 1, pa);
+      }
+      rs.request(i + 4);
+    } else {
+      if (i + 2 < ntiles) e.issue(i + 2, i & 1);
+    }
     uint64_t word = ~0ull;
     if constexpr (FILTER == FILTER_ONE) {
       word = tile_allow_word(allow, row0, i);
@@ -464,12 +515,14 @@ __global__ __launch_bounds__(64) void hamming_emit_mfma_kernel(
           lds_read32(T, T0 + (uint32_t)(ql * 4));
           lds_read32(lp, lt0 + (uint32_t)(ql * 4));
           lds_read32(ep, eq0 + (uint32_t)(ql * 4));
-          asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(T), "+v"(lp), "+v"(ep)::"memory");
+          uint32_t krow = 0;  // GATHER: the list entry of the lane's row, the key's row field
+          if constexpr (GATHER) rs.entry(krow, i, nb * 32 + (lo & 31));
+          asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(T), "+v"(lp), "+v"(ep), "+v"(krow)::"memory");
           if (hit) {
             const int pos = lt ? lp + __popc(hlt & below) : ep + __popc(heq & below);
             if ((uint32_t)pos < (uint32_t)K)
-              lists[(int64_t)(q0 + ql) * K + pos] =
-                  ((uint64_t)(uint32_t)(v + T + 1) << KEY_ROW_BITS) | (uint64_t)(row0 + local);
+              lists[(int64_t)(q0 + ql) * K + pos] = ((uint64_t)(uint32_t)(v + T + 1) << KEY_ROW_BITS) |
+                                                    (GATHER ? (uint64_t)krow : (uint64_t)(row0 + local));
           }
           if ((lo & 31) == 0) {  // one lane per half moves its query's positions on
             lds_add32(lt0 + (uint32_t)(ql * 4), __popc(hlt));
@@ -501,7 +554,7 @@ int count_launch(const CountPassArgs& a, hipStream_t s) {
   return filter_kind(a.filter, [&](auto F) -> int {
     hipLaunchKernelGGL((hamming_count_mfma_kernel<KS, MB, decltype(F)::value>), grid, block, 0, s, a.codes, a.n, a.q,
                        a.nq, a.chunk_rows, a.nchunks, nqb, a.hist, a.filter.allow, a.filter.nsets, a.filter.set_words,
-                       a.filter.query_set);
+                       a.filter.query_set, a.filter.rows);
     VRQ_LAUNCH_CHECK();
     return VRQ_OK;
   });
@@ -514,7 +567,7 @@ int emit_launch(const CountPassArgs& a, hipStream_t s) {
   return filter_kind(a.filter, [&](auto F) -> int {
     hipLaunchKernelGGL((hamming_emit_mfma_kernel<KS, MB, decltype(F)::value>), grid, block, 0, s, a.codes, a.n, a.q,
                        a.nq, a.K, a.chunk_rows, a.nchunks, nqb, a.tc, a.prefix, a.lists, a.filter.allow,
-                       a.filter.nsets, a.filter.set_words, a.filter.query_set);
+                       a.filter.nsets, a.filter.set_words, a.filter.query_set, a.filter.rows);
     VRQ_LAUNCH_CHECK();
     return VRQ_OK;
   });

@@ -2188,6 +2188,82 @@ int vrq_search2_perquery(int32_t mode, const uint8_t* codes, const void* q, cons
                             perquery_call(allow, nsets, set_words, query_set, engine));
 }
 
+// ---- the gather calls (K1g): the batch calls over an ascending row list in place of the bitmap.  The scan, its
+// plan and its workspace are those of an m-row corpus (the list's positions); the list turns a position into
+// the row that is read and into the row field of a key, so the finish sees physical rows as ever.  m == 0
+// launches no chunk: the threshold stage pads the K-lists and the finish answers as for an all-zero bitmap. ----
+static CountCall gather_call(const uint32_t* rows, int64_t m, int engine) {
+  RowFilter f;
+  f.rows = rows;
+  f.empty_list = m == 0;
+  return {engine, true, false, false, f};
+}
+// the scan's row count: an empty list plans as one row and launches no chunk (count_route_launch)
+static int64_t gather_rows(int64_t m, int64_t n) { return m == 0 && n > 0 ? 1 : m; }
+// the list's checks, in front of everything else the call checks
+#define VRQ_CHECK_ROWS(rows, m, n, engine)                                                \
+  VRQ_CHECK_ARG(engine_ok(engine) && (n) >= 0 && (m) >= 0 && (m) <= (n));                 \
+  VRQ_CHECK_ARG((m) == 0 || ((rows) && ((uintptr_t)(rows) & 3) == 0))
+
+size_t vrq_search3_gather_workspace_size(int64_t m, int32_t dim, int32_t nq, int32_t K) {
+  return vrq_search3_batch_workspace_size(m < 1 ? 1 : m, dim, nq, K);
+}
+
+size_t vrq_search2_gather_workspace_size(int64_t m, int32_t dim, int32_t nq, int32_t K) {
+  return vrq_search3_gather_workspace_size(m, dim, nq, K);
+}
+
+size_t vrq_scan_gather_workspace_size(int64_t m, int32_t dim, int32_t nq, int32_t K) {
+  return vrq_search3_gather_workspace_size(m, dim, nq, K);
+}
+
+size_t vrq_hamming_topk_gather_workspace_size(int64_t m, int32_t code_bytes, int32_t nq, int32_t k) {
+  return vrq_hamming_topk_batch_workspace_size(m < 1 ? 1 : m, code_bytes, nq, k);
+}
+
+int vrq_scan_gather_plan(int64_t m, int32_t dim, int32_t nq, int32_t K, int32_t engine, int64_t* info) {
+  return vrq_scan_batch_plan(m, dim, nq, K, engine, info);  // (every code size has a gathered instance of both engines)
+}
+
+int vrq_scan_gather(const uint8_t* codes, int64_t n, int32_t dim, const uint8_t* qb, int32_t nq, int32_t K,
+                    int32_t stages, const uint32_t* rows, int64_t m, void* workspace, size_t workspace_bytes,
+                    void* stream, int32_t engine) {
+  VRQ_CHECK_ROWS(rows, m, n, engine);
+  return scan_large_impl(codes, gather_rows(m, n), dim, qb, nq, K, stages, workspace, workspace_bytes, stream,
+                         gather_call(rows, m, engine));
+}
+
+int vrq_hamming_topk_gather(const uint8_t* codes, int64_t n, int32_t code_bytes, int64_t row_offset,
+                            const uint8_t* queries, int32_t nq, int32_t k, const uint32_t* rows, int64_t m,
+                            int32_t* out_dist, int64_t* out_rows, void* workspace, size_t workspace_bytes,
+                            void* stream, int32_t engine) {
+  VRQ_CHECK_ROWS(rows, m, n, engine);
+  return hamming_topk_large_impl(codes, gather_rows(m, n), code_bytes, row_offset, queries, nq, k, out_dist, out_rows,
+                                 workspace, workspace_bytes, stream, gather_call(rows, m, engine));
+}
+
+int vrq_search3_gather(const uint8_t* codes, const int8_t* x8, const double* norms, const int64_t* rescore_row,
+                       int64_t n, int32_t dim, int64_t row_offset, const float* qf, const uint8_t* qb, int32_t nq,
+                       int32_t k, int32_t K, int32_t K3, int32_t flags, const uint32_t* rows, int64_t m,
+                       int32_t* out_count, int64_t* out_rows, int32_t* out_dist, double* out_binary,
+                       double* out_cosine, void* workspace, size_t workspace_bytes, void* stream, int32_t engine) {
+  VRQ_CHECK_ROWS(rows, m, n, engine);
+  return search3_large_impl(codes, x8, norms, rescore_row, gather_rows(m, n), dim, row_offset, qf, qb, nq, k, K, K3,
+                            flags, out_count, out_rows, out_dist, out_binary, out_cosine, workspace, workspace_bytes,
+                            stream, gather_call(rows, m, engine));
+}
+
+int vrq_search2_gather(int32_t mode, const uint8_t* codes, const void* q, const double* minmax, double limit,
+                       const int64_t* rescore_row, int64_t n, int32_t dim, int64_t row_offset, const float* qf,
+                       const uint8_t* qb, int32_t nq, int32_t k, int32_t K, int32_t flags, const uint32_t* rows,
+                       int64_t m, int32_t* out_count, int64_t* out_rows, int32_t* out_dist, double* out_score,
+                       void* workspace, size_t workspace_bytes, void* stream, int32_t engine) {
+  VRQ_CHECK_ROWS(rows, m, n, engine);
+  return search2_large_impl(mode, codes, q, minmax, limit, rescore_row, gather_rows(m, n), dim, row_offset, qf, qb,
+                            nq, k, K, flags, out_count, out_rows, out_dist, out_score, workspace, workspace_bytes,
+                            stream, gather_call(rows, m, engine));
+}
+
 // ---- the per-shard calls for K up to VRQ_K_LARGE_MAX: K1h, the sort, the scores of every candidate ----
 size_t vrq_shard_search3_large_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t K) {
   return vrq_search3_large_workspace_size(n, dim, nq, K);

@@ -176,16 +176,23 @@ int count_code_bytes(int cb, F&& f) {
 // [ceil(n / 64)], bit r & 63 of word r >> 6: row r takes part (nsets and set_words are not read).  Otherwise
 // `allow` holds nsets such bitmaps, bitmap s at allow + s * set_words (set_words >= ceil(n / 64)), and query q
 // is filtered by bitmap query_set[q] (device i32 [nq]): -1 allows every row, any other value outside
-// [0, nsets) allows none.
+// [0, nsets) allows none.  rows != null (K1g; allow must be null): the scan's n is the length m of the ascending
+// list `rows` u32 [m] (device), its row space is the list's positions, and it reads rows[0..m) of `codes` alone;
+// the keys it emits carry rows[v].  empty_list: the list has no entry (m == 0; the scan's n is 1 and rows is not
+// read): no chunk is launched, the threshold stage runs on cleared histograms and pads every K-list.
 struct RowFilter {
   const uint64_t* allow = nullptr;
   int nsets = 0;
   int64_t set_words = 0;
   const int32_t* query_set = nullptr;
+  const uint32_t* rows = nullptr;
+  bool empty_list = false;
 };
-// filter -> f(std::integral_constant<int, FILTER_*>) (row_filter.h: 0 off, 1 one bitmap, 2 per-query sets)
+// filter -> f(std::integral_constant<int, FILTER_*>) (row_filter.h: 0 off, 1 one bitmap, 2 per-query sets,
+// 3 a row list)
 template <class F>
 int filter_kind(const RowFilter& r, F&& f) {
+  if (r.rows) return f(std::integral_constant<int, 3>{});
   if (!r.allow) return f(std::integral_constant<int, 0>{});
   if (!r.query_set) return f(std::integral_constant<int, 1>{});
   return f(std::integral_constant<int, 2>{});

@@ -157,11 +157,32 @@ def checked_filter(allow, query_set, n: int, nq: int, device):
     return (checked(allow, n, device) if allow is not None else None), None
 
 
-def class_filter(id_map: torch.Tensor, allowed_ids, allowed_ids_per_query, nq: int):
+FILTER_ROUTES = (None, "bitmap", "gather")
+
+
+def split_route(flt, filter_route):
+    """What ``class_filter`` returned first, as the ``(allow, rows)`` pair of a wrapper's arguments."""
+    return (None, flt) if filter_route == "gather" else (flt, None)
+
+
+def class_filter(id_map: torch.Tensor, allowed_ids, allowed_ids_per_query, nq: int, filter_route=None):
     """The ``(allow, query_set)`` of a class's ``search_vectors``: ``allowed_ids`` (one collection for the whole
     batch) -> a 1-D bitmap and None; ``allowed_ids_per_query`` (a sequence of ``nq`` entries, each None or a
     collection of ids) -> ``ids_bitmaps``; neither -> ``(None, None)``.  Raises for both at once, and for a
-    sequence whose length is not the batch's."""
+    sequence whose length is not the batch's.  ``filter_route``: None and "bitmap" are the above; with "gather"
+    the first element is the uint32 row list of ``allowed_ids`` (``ids_rows``) for the ``rows=`` argument in
+    place of the bitmap (``split_route`` tells them apart); per-query lists are not built, so "gather" with
+    ``allowed_ids_per_query`` raises."""
+    if filter_route not in FILTER_ROUTES:
+        raise N.VrqNativeError(f"filter_route {filter_route!r} (None, 'bitmap' or 'gather')")
+    if filter_route == "gather":
+        if allowed_ids_per_query is not None:
+            raise N.VrqNativeError("filter_route='gather' takes allowed_ids, not allowed_ids_per_query")
+        if allowed_ids is None:
+            return None, None
+        if id_map.shape[0] == 0:  # (vrq_row_list takes no empty corpus)
+            return torch.empty((0,), dtype=torch.uint32, device=id_map.device), None
+        return ids_rows(id_map, allowed_ids), None
     if allowed_ids_per_query is None:
         return (ids_bitmap(id_map, allowed_ids) if allowed_ids is not None else None), None
     if allowed_ids is not None:

@@ -51,7 +51,7 @@ import torch
 from . import _native as N
 from . import quant as Q
 from .docstore import DocStoreError, RocksDictReader, is_rocksdict_dir
-from .filters import class_filter, ids_bitmap
+from .filters import class_filter, ids_bitmap, split_route
 from .index import BinaryIndexIDMap2, _GrowBuffer, as_device_tensor, torch_to_np
 
 logger = logging.getLogger(__name__)
@@ -304,7 +304,7 @@ class _QuantizedVectorDB:
 
     # -- search ------------------------------------------------------------------------
     def search_vectors(self, query, k: int = 10, binary_oversample: int = 10, compare_float32: bool = False,
-                       allowed_ids=None, engine=None, allowed_ids_per_query=None):
+                       allowed_ids=None, engine=None, allowed_ids_per_query=None, filter_route=None):
         """Batched search of query embeddings (f32[nq, d]; i16[nq, d] for VectorDBInt16) on the device.
         Returns (doc_id i64[nq, kk], row i64[nq, kk], hamming i32[nq, kk], score f64[nq, kk]) with
         kk = min(k, K); rows past the candidates are -1.  ``allowed_ids`` (None: all): only these documents
@@ -312,24 +312,28 @@ class _QuantizedVectorDB:
         ``engine`` ("auto", "mfma", "valu"; default None): Phase I through ``vrq_hamming_topk_batch``.
         ``allowed_ids_per_query`` (exclusive with ``allowed_ids``): a sequence of nq entries, each None
         (unfiltered) or a collection of ids, one filter per query through the ``*_perquery`` call, where
-        ``engine=None`` means "auto"; an empty collection, or one of unknown ids, finds nothing."""
+        ``engine=None`` means "auto"; an empty collection, or one of unknown ids, finds nothing.
+        ``filter_route`` (None | "bitmap" | "gather"): how ``allowed_ids`` reaches Phase I -- None and "bitmap" are
+        the bitmap calls, "gather" builds the row list and takes the ``*_gather`` call, which reads the allowed rows
+        only; same result."""
         n = self.index.ntotal
         if k < 0 or binary_oversample < 0:
             raise ValueError("k and binary_oversample must be non-negative")
         qv = as_device_tensor(query, self.VEC_DTYPE, self.device).reshape(-1, self.embedding_dim)
         qb = self._codes(qv)["codes"]
-        allow, qset = class_filter(self.index.id_map, allowed_ids, allowed_ids_per_query, qv.shape[0])
+        allow, qset = class_filter(self.index.id_map, allowed_ids, allowed_ids_per_query, qv.shape[0], filter_route)
+        allow, lst = split_route(allow, filter_route)
         with torch.cuda.device(self.device):
             if self.HAMMING_ONLY:
                 rows, ham, sc = Q.vectordb_search("bin16", self.index.codes, None, None, qb, k, binary_oversample,
-                                                  allow=allow, engine=engine, query_set=qset)
+                                                  allow=allow, engine=engine, query_set=qset, rows=lst)
             else:
                 mode = "f32" if compare_float32 else self.MODE
                 src = self._f.view() if compare_float32 else self._q.view()
                 rr = self.index.rescore_rows()
                 rows, ham, sc = Q.vectordb_search(mode, self.index.codes, src, qv, qb, k, binary_oversample,
                                                   self._mm.view() if self.LOCAL and not compare_float32 else None,
-                                                  self.limit, rr, allow, engine, qset)
+                                                  self.limit, rr, allow, engine, qset, lst)
                 if compare_float32:
                     self._check_float_rows(rows)
         ids = torch.where(rows >= 0, self.index.id_map[rows.clamp_min(0)], rows) if n else rows
@@ -346,11 +350,13 @@ class _QuantizedVectorDB:
                 raise KeyError(str(e))
 
     def search(self, query: str, k: int = 10, binary_oversample: int = 10, compare_float32: bool = False,
-               allowed_ids=None, engine=None) -> List[Dict]:
+               allowed_ids=None, engine=None, filter_route=None) -> List[Dict]:
         if self.index.ntotal == 0:
             logger.error("No documents indexed. Please add documents before searching.")
             return []
         kw = {} if engine is None else {"engine": engine}
+        if filter_route is not None:
+            kw["filter_route"] = filter_route
         if allowed_ids is not None:
             kw["allowed_ids"] = allowed_ids = [int(i) for i in allowed_ids]
             if not any(i in self.texts for i in allowed_ids):   # an empty set, or none of them indexed
