@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from oracle import oracle_np as O
-from tests.test_gpu_exhaustive_dims import DIMS, _assert_exact, _grid_queries, _rows, dev  # noqa: F401
+from tests.test_gpu_exhaustive_dims import DIMS, G, _assert_exact, _grid_queries, _rows, dev  # noqa: F401
 from vectorragquantization_amd import _native as N
 
 gpu = pytest.mark.gpu
@@ -166,6 +166,36 @@ def test_identical_rows_overflow_retry_fallback(dev, dim):
     assert np.all(cnt == k) and np.array_equal(rows, np.tile(np.arange(k), (nq, 1)))
     assert np.array_equal(sc, np.repeat(O.flat_ip_scores(row, qf), k, axis=1))
     assert np.all(_run(ops, qf, k, dev, flags=N.VRQ_GEMM_NO_FALLBACK)[0] == -1)
+
+
+@gpu
+def test_retry_serves_an_overflowed_list(dev):
+    """The construction of tests/test_gpu_gemm_dims_mfma.py over float rows: a whole main chunk that no sample
+    chunk touches holds grid rows graded towards query 0, the best last.  With the plan's numbers and the oracle's
+    scores (n = 557 056, chunks of 544 rows, capacity 512): the graded rows score 14.3 .. 27.0, the k-th best
+    sampled row 13.3, and a row at or above that is a hit whatever Delta is (u >= s' - Delta, thr <= U - 2 Delta,
+    U <= the k-th best sampled s' + Delta), so all 544 are hits: the list keeps the first 512 and overflows, and
+    the true top-k, chunk rows 530 .. 543, is among those it dropped.  The retry at the raised threshold (139 rows
+    pass it) must serve the query without the exact scan."""
+    dim, nq, k = 256, 3, 10
+    n = next(c for c in range(1 << 15, 1 << 22, 1 << 15) if _plan(c, dim, nq, k)[0] > _plan(c, dim, nq, k)[2])
+    cr, nchunks, capc, _, nsc, scr = _plan(n, dim, nq, k)[:6]
+    sstride = n // nsc
+    m = next(c for c in range(nchunks // 2, nchunks - 1)
+             if all(not (s * sstride < (c + 1) * cr and c * cr < s * sstride + scr) for s in range(n // sstride + 1)))
+    rng = np.random.default_rng(7000)
+    X, qf = _rows(rng, "float_ip", n, dim), _grid_queries(rng, nq, dim)
+    g = np.linspace(0.8, 1.5, cr)[:, None]
+    X[m * cr:(m + 1) * cr] = np.round((qf[0] * g / 14 + 0.004 * rng.standard_normal((cr, dim))) / G) * G
+    ops = _prepare(X, dev)
+    ws = torch.empty((_plan(n, dim, nq, k)[6],), dtype=torch.uint8, device=dev)
+    _run(ops, qf, k, dev, flags=N.VRQ_GEMM_STAGE_SAMPLE | N.VRQ_GEMM_STAGE_MAIN, workspace=ws)
+    lay = (C.c_int64 * 8)()
+    assert N.load().vrq_flat_ip_topk_dim_mfma_prep_layout(n, dim, nq, k, lay) == N.VRQ_OK
+    assert int(ws[lay[6] + 4 * m:lay[6] + 4 * m + 4].cpu().numpy().view(np.int32)[0]) > capc   # (query 0, chunk m)
+    out = _run(ops, qf, k, dev, flags=N.VRQ_GEMM_NO_FALLBACK, workspace=ws)
+    assert np.all(out[0] == k) and np.any(out[1][0] >= m * cr + capc)       # rows the list had dropped
+    _assert_exact("float_ip", X, qf, k, out)
 
 
 class _FloatProvider:

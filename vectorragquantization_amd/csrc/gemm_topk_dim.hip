@@ -600,22 +600,34 @@ __device__ __forceinline__ double cos_row(const float* qs, const int8_t* __restr
   return nrm == 0.0 ? -__builtin_inf() : (double)f / nrm;
 }
 
+// =============================================================================================
+// Finish and exact scan: one stage for the three scores.  A score family F -- Int8Cos, FloatIP<KS>, Binary --
+// is the kernels' first argument; it holds the corpus pointers and is everything a score has of its own:
+//   F::OCC                 workgroups per CU asked of the compiler (the launch bound)
+//   F::Lds                 the LDS of its per-workgroup query state, a base of FinShared (empty: FloatIP's
+//                          query is in registers)
+//   f.query(qf, q, sh)     makes query q ready and returns the state score_batch takes; what it writes to LDS is
+//                          published by the caller's next barrier
+//   f.score_batch(qs, base, end, count, row_at, admit)
+//                          scores the candidates row_at(j), base <= j < end <= count, and hands each to
+//                          admit(mine, key, row), mine = this thread speaks for the row: how candidates are dealt
+//                          to threads or waves and the order of the loads
+// and, on the host, its prep-kernel launch, its pass-kernel launch and family<KS>(), the device family at a dim.
 constexpr int FIN_NT = 512, FIN_NW = FIN_NT / WAVE;
-struct FinShared {
+template <class QS>
+struct FinShared : QS {
   uint64_t key[KMAX5 + FB_BATCH];
   uint32_t row[KMAX5 + FB_BATCH];
-  float q[2048];
   int32_t pre[MAX_CHUNKS + 1];  // exclusive prefix of the (capped) list lengths
   int32_t fill, over;
 };
 
-// Running exact top-k over candidate rows row_at(j), j < count, one wave per row: a row enters the LDS sort
-// only if it beats the current k-th by (score desc, row asc).  key/row[0..kc) hold the list in order.  All
-// threads call it; returns kc = min(k, count).
-template <class RowAt>
-__device__ int running_topk(int64_t count, RowAt row_at, const int8_t* __restrict__ x8,
-                            const double* __restrict__ norms, int dim, int k, FinShared& sh) {
-  const int tid = threadIdx.x, l = lane_id(), w = tid >> 6;
+// Running exact top-k over candidate rows row_at(j), j < count, in batches of FB_BATCH: a row enters the LDS
+// sort only if it beats the current k-th by (score desc, row asc).  key/row[0..kc) hold the list in order after
+// each batch.  All threads call it; returns kc = min(k, count).  count >= 1.
+template <class F, class Q, class RowAt, class Sh>
+__device__ __forceinline__ int running_topk(const F& f, const Q& qs, int64_t count, RowAt row_at, int k, Sh& sh) {
+  const int tid = threadIdx.x;
   if (tid == 0) sh.fill = 0;
   int kc = 0;
   __syncthreads();
@@ -623,19 +635,17 @@ __device__ int running_topk(int64_t count, RowAt row_at, const int8_t* __restric
     const uint64_t kk = kc == k ? sh.key[k - 1] : KEY_NONE;
     const uint32_t kr = kc == k ? sh.row[k - 1] : 0xffffffffu;
     const int64_t end = base + FB_BATCH < count ? base + FB_BATCH : count;
-    for (int64_t j = base + w; j < end; j += FIN_NW) {
-      const uint32_t rr = row_at(j);
-      const uint64_t key_r = desc_key_f64(cos_row(sh.q, x8 + (int64_t)rr * dim, norms[rr], dim));
-      if ((kc < k || key_r < kk || (key_r == kk && rr < kr)) && l == 0) {
+    f.score_batch(qs, base, end, count, row_at, [&](bool mine, uint64_t key_r, uint32_t rr) {
+      if (mine && (kc < k || key_r < kk || (key_r == kk && rr < kr))) {
         const int i = kc + atomicAdd(&sh.fill, 1);
         sh.key[i] = key_r;
         sh.row[i] = rr;
       }
-    }
+    });
     __syncthreads();
-    const int f = sh.fill;
-    if (f > 0) {
-      const int tot = kc + f, np2 = next_pow2(tot);
+    const int fl = sh.fill;
+    if (fl > 0) {
+      const int tot = kc + fl, np2 = next_pow2(tot);
       for (int i = tot + tid; i < np2; i += FIN_NT) {
         sh.key[i] = KEY_NONE;
         sh.row[i] = 0xffffffffu;
@@ -650,7 +660,8 @@ __device__ int running_topk(int64_t count, RowAt row_at, const int8_t* __restric
   return kc;
 }
 
-__device__ __forceinline__ void write_result(int q, int k, int kc, int64_t row_offset, const FinShared& sh,
+template <class Sh>
+__device__ __forceinline__ void write_result(int q, int k, int kc, int64_t row_offset, const Sh& sh,
                                              int32_t* out_count, int64_t* out_rows, double* out_scores) {
   for (int i = threadIdx.x; i < k; i += FIN_NT) {
     const int64_t o = (int64_t)q * k + i;
@@ -666,15 +677,14 @@ __device__ __forceinline__ void write_result(int q, int k, int kc, int64_t row_o
 // (fewer than min(k, n) candidates, or an overflow in the retry pass).  RETRY serves the retried queries.
 // G... as in k5md_pass_kernel: with a row list the lists hold virtual rows, n is the list's length, and row_at
 // hands out rows[v] -- ascending like v, so scores, ties and outputs are those of the physical rows.
-template <bool RETRY, class... G>
-__global__ __launch_bounds__(FIN_NT) void k5md_finish_kernel(
-    const int8_t* __restrict__ x8, const double* __restrict__ norms, int64_t n, int dim, int64_t row_offset,
-    const float* __restrict__ qf, int k, const uint32_t* __restrict__ cand, const int32_t* __restrict__ ccnt,
-    int nchunks, int capc, int qpb, int32_t* __restrict__ out_count, int64_t* __restrict__ out_rows,
-    double* __restrict__ out_scores, int32_t* __restrict__ fb_flag, float* __restrict__ thr,
-    const double* __restrict__ alpha, const double* __restrict__ beta, const double* __restrict__ delta,
-    int32_t* __restrict__ qbflag, G... gather) {
-  __shared__ FinShared sh;
+template <class F, bool RETRY, class... G>
+__global__ __launch_bounds__(FIN_NT, F::OCC) void k5m_finish_kernel(
+    const F f, int64_t n, int64_t row_offset, const float* __restrict__ qf, int k,
+    const uint32_t* __restrict__ cand, const int32_t* __restrict__ ccnt, int nchunks, int capc, int qpb,
+    int32_t* __restrict__ out_count, int64_t* __restrict__ out_rows, double* __restrict__ out_scores,
+    int32_t* __restrict__ fb_flag, float* __restrict__ thr, const double* __restrict__ alpha,
+    const double* __restrict__ beta, const double* __restrict__ delta, int32_t* __restrict__ qbflag, G... gather) {
+  __shared__ FinShared<typename F::Lds> sh;
   constexpr bool GATHER = sizeof...(G) != 0;
   const uint32_t* const rows = gather_rows(gather...);
   const int q = blockIdx.x, tid = threadIdx.x;
@@ -687,7 +697,7 @@ __global__ __launch_bounds__(FIN_NT) void k5md_finish_kernel(
     if (x > capc) sh.over = 1;
     sh.pre[c + 1] = x < capc ? x : capc;
   }
-  for (int i = tid; i < dim; i += FIN_NT) sh.q[i] = qf[(int64_t)q * dim + i];
+  const auto qs = f.query(qf, q, sh);
   __syncthreads();
   if (tid < WAVE) {  // inclusive scan of pre[1 .. nchunks] by one wave: 32 entries per lane, then the lanes
     constexpr int PER = MAX_CHUNKS / WAVE;
@@ -724,20 +734,19 @@ __global__ __launch_bounds__(FIN_NT) void k5md_finish_kernel(
     return;
   }
   const uint32_t* Cq = cand + (int64_t)q * nchunks * capc;
-  auto row_at = [&](int64_t j) {  // candidate j of the concatenated lists (binary search by chunk)
-    int lo = 0, hi = nchunks - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (sh.pre[mid] <= j)
-        lo = mid;
-      else
-        hi = mid - 1;
+  // candidate j of the concatenated lists: the largest chunk lo with pre[lo] <= j (fixed 11 steps)
+  auto row_at = [&](int64_t j) {
+    int lo = 0;
+#pragma unroll
+    for (int st = MAX_CHUNKS / 2; st > 0; st >>= 1) {
+      const int mid = lo + st;
+      if (mid < nchunks && sh.pre[mid] <= j) lo = mid;
     }
     const uint32_t v = Cq[(int64_t)lo * capc + (j - sh.pre[lo])];
     if constexpr (GATHER) return rows[v];
     return v;
   };
-  const int kc = running_topk(total, row_at, x8, norms, dim, k, sh);
+  const int kc = running_topk(f, qs, total, row_at, k, sh);
   if (!RETRY && over) {
     if (tid == 0) {
       const double t2 = alpha[q] * desc_key_inv(sh.key[kc - 1]) + beta[q] - delta[q];
@@ -755,13 +764,14 @@ __global__ __launch_bounds__(FIN_NT) void k5md_finish_kernel(
 }
 
 // the exact scan of the flagged queries (heavy ties, zero-norm rows): one workgroup per flagged query scores
-// every row; skip (VRQ_GEMM_NO_FALLBACK) reports the query as unserved instead
-template <class... G>
-__global__ __launch_bounds__(FIN_NT) void k5md_fallback_kernel(
-    const int8_t* __restrict__ x8, const double* __restrict__ norms, int64_t n, int dim, int64_t row_offset,
-    const float* __restrict__ qf, int k, int32_t* __restrict__ out_count, int64_t* __restrict__ out_rows,
-    double* __restrict__ out_scores, const int32_t* __restrict__ fb_flag, bool skip, G... gather) {
-  __shared__ FinShared sh;
+// every row (of the list) through the family's own rounds and score function; skip (VRQ_GEMM_NO_FALLBACK)
+// reports the query as unserved instead.  running_topk's first barrier publishes the query state.
+template <class F, class... G>
+__global__ __launch_bounds__(FIN_NT, F::OCC) void k5m_fallback_kernel(
+    const F f, int64_t n, int64_t row_offset, const float* __restrict__ qf, int k, int32_t* __restrict__ out_count,
+    int64_t* __restrict__ out_rows, double* __restrict__ out_scores, const int32_t* __restrict__ fb_flag, bool skip,
+    G... gather) {
+  __shared__ FinShared<typename F::Lds> sh;
   const uint32_t* const rows = gather_rows(gather...);
   const int q = blockIdx.x, tid = threadIdx.x;
   if (fb_flag[q] != 1) return;
@@ -773,12 +783,48 @@ __global__ __launch_bounds__(FIN_NT) void k5md_fallback_kernel(
     if (tid == 0) out_count[q] = -1;
     return;
   }
-  for (int i = tid; i < dim; i += FIN_NT) sh.q[i] = qf[(int64_t)q * dim + i];
-  __syncthreads();
+  const auto qs = f.query(qf, q, sh);
   const int kc = running_topk(
-      n, [=](int64_t j) { return sizeof...(G) ? rows[j] : (uint32_t)j; }, x8, norms, dim, k, sh);
+      f, qs, n, [=](int64_t j) { return sizeof...(G) ? rows[j] : (uint32_t)j; }, k, sh);
   write_result(q, k, kc, row_offset, sh, out_count, out_rows, out_scores);
 }
+
+// K5md's score: int8 rows by cos_row, the float query in LDS, one row per wave and round.
+struct Int8Cos {
+  const int8_t* x8;
+  const double* norms;
+  int dim;
+  static constexpr int OCC = 1;
+  struct Lds {
+    float q[2048];
+  };
+  template <class Sh>
+  __device__ __forceinline__ const float* query(const float* __restrict__ qf, int q, Sh& sh) const {
+    for (int i = threadIdx.x; i < dim; i += FIN_NT) sh.q[i] = qf[(int64_t)q * dim + i];
+    return sh.q;
+  }
+  template <class RowAt, class Admit>
+  __device__ __forceinline__ void score_batch(const float* qs, int64_t base, int64_t end, int64_t, RowAt row_at,
+                                              Admit admit) const {
+    const int l = lane_id(), w = threadIdx.x >> 6;
+    for (int64_t j = base + w; j < end; j += FIN_NW) {
+      const uint32_t rr = row_at(j);
+      admit(l == 0, desc_key_f64(cos_row(qs, x8 + (int64_t)rr * dim, norms[rr], dim)), rr);
+    }
+  }
+  template <class... A>
+  void prep(dim3 grid, hipStream_t s, A... a) const {
+    hipLaunchKernelGGL(k5md_prep_kernel, grid, dim3(256), 0, s, a...);
+  }
+  template <int KS, bool DENSE, class... A>
+  void pass(dim3 grid, dim3 blk, hipStream_t s, A... a) const {
+    hipLaunchKernelGGL((k5md_pass_kernel<KS, DENSE>), grid, blk, 0, s, x8, norms, a...);
+  }
+  template <int KS>
+  Int8Cos family() const {
+    return *this;
+  }
+};
 
 // ---------------------------------------------------------------------------------------------
 struct Plan {
@@ -790,18 +836,25 @@ struct Plan {
   size_t off_delta, off_alpha, off_beta, off_qbf, off_thr, off_flag, off_cnt, off_cand, off_dv, bytes;
 };
 
-// (gather: the *_rows calls, which have a KS = 32 instance; unfiltered 1024 is K5's)
-__host__ inline int queries_per_block(int dim, bool gather = false) {
+// dim -> KS = dim / 32, the one place: fn(std::integral_constant<int, KS>) -> int at a served dim, else
+// VRQ_EUNSUPPORTED.  KS = 32 exists for the gathered calls only (the *_rows calls; unfiltered 1024 is K5's).
+template <class Fn>
+static int with_ks(int dim, bool gather, Fn fn) {
   switch (dim) {
-    case 1024: return gather ? Shape<32>::QB : 0;
-    case 256: return Shape<8>::QB;
-    case 384: return Shape<12>::QB;
-    case 512: return Shape<16>::QB;
-    case 768: return Shape<24>::QB;
-    case 1536: return Shape<48>::QB;
-    case 2048: return Shape<64>::QB;
-    default: return 0;
+    case 256: return fn(std::integral_constant<int, 8>{});
+    case 384: return fn(std::integral_constant<int, 12>{});
+    case 512: return fn(std::integral_constant<int, 16>{});
+    case 768: return fn(std::integral_constant<int, 24>{});
+    case 1024: return gather ? fn(std::integral_constant<int, 32>{}) : VRQ_EUNSUPPORTED;
+    case 1536: return fn(std::integral_constant<int, 48>{});
+    case 2048: return fn(std::integral_constant<int, 64>{});
+    default: return VRQ_EUNSUPPORTED;
   }
+}
+
+__host__ inline int queries_per_block(int dim, bool gather = false) {  // 0: no pass at this dim
+  const int qb = with_ks(dim, gather, [](auto KS) { return Shape<decltype(KS)::value>::QB; });
+  return qb > 0 ? qb : 0;
 }
 
 // K5's planning rules (gemm_plan) with the query block a function of dim
@@ -855,130 +908,6 @@ __host__ inline int plan(int mode, int64_t n, int dim, int nq, int k, Plan* p) {
   return plan_shape(n, dim, nq, k, p);
 }
 
-struct Call {
-  const int8_t* x8;
-  const double* norms;
-  int64_t n;  // rows the passes cover: the corpus's, or the length of `rows`
-  const int8_t* qa;
-  int nq;
-  float* thr;
-  uint32_t* cand;
-  int32_t* cnt;
-  float* dv;
-  int32_t* qbf;
-  hipStream_t s;
-  const uint32_t* rows;  // K5g: the allowed rows, ascending (NULL: every row)
-};
-
-template <int KS>
-static void launch_pass(const Plan& p, const Call& c, int pass) {  // 0 sample, 1 main, 2 retry
-  const dim3 blk(Shape<KS>::W * 64);
-  if (c.rows && pass == 0)
-    hipLaunchKernelGGL((k5md_pass_kernel<KS, true, const uint32_t*>), dim3(p.nsc * p.nqb), blk, 0, c.s, c.x8, c.norms,
-                       c.n, c.qa, c.nq, (const float*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr, 0, p.scr,
-                       p.sstride, p.nsc, p.nqb, c.dv, p.scols, (const int32_t*)nullptr, c.rows);
-  else if (c.rows)
-    hipLaunchKernelGGL((k5md_pass_kernel<KS, false, const uint32_t*>), dim3(p.nchunks * p.nqb), blk, 0, c.s, c.x8,
-                       c.norms, c.n, c.qa, c.nq, (const float*)c.thr, c.cand, c.cnt, p.capc, p.chunk_rows, p.chunk_rows,
-                       p.nchunks, p.nqb, (float*)nullptr, (int64_t)0,
-                       pass == 2 ? (const int32_t*)c.qbf : (const int32_t*)nullptr, c.rows);
-  else if constexpr (KS == 32)
-    return;  // (no contiguous KS = 32 instance: launch_pass_dim refuses the call)
-  else if (pass == 0)
-    hipLaunchKernelGGL((k5md_pass_kernel<KS, true>), dim3(p.nsc * p.nqb), blk, 0, c.s, c.x8, c.norms, c.n, c.qa, c.nq,
-                       (const float*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr, 0, p.scr, p.sstride, p.nsc,
-                       p.nqb, c.dv, p.scols, (const int32_t*)nullptr);
-  else
-    hipLaunchKernelGGL((k5md_pass_kernel<KS, false>), dim3(p.nchunks * p.nqb), blk, 0, c.s, c.x8, c.norms, c.n, c.qa,
-                       c.nq, (const float*)c.thr, c.cand, c.cnt, p.capc, p.chunk_rows, p.chunk_rows, p.nchunks, p.nqb,
-                       (float*)nullptr, (int64_t)0, pass == 2 ? (const int32_t*)c.qbf : (const int32_t*)nullptr);
-}
-
-static int launch_pass_dim(int dim, const Plan& p, const Call& c, int pass) {
-  switch (dim) {
-    case 256: launch_pass<8>(p, c, pass); break;
-    case 384: launch_pass<12>(p, c, pass); break;
-    case 512: launch_pass<16>(p, c, pass); break;
-    case 768: launch_pass<24>(p, c, pass); break;
-    case 1536: launch_pass<48>(p, c, pass); break;
-    case 2048: launch_pass<64>(p, c, pass); break;
-    case 1024:  // the gathered calls alone (K5 has no gather)
-      if (!c.rows) return VRQ_EUNSUPPORTED;
-      launch_pass<32>(p, c, pass);
-      break;
-    default: return VRQ_EUNSUPPORTED;
-  }
-  VRQ_LAUNCH_CHECK();
-  return VRQ_OK;
-}
-
-// rows != NULL (K5g): n is the length of the list, and the call plans like an unfiltered one on n rows
-static int run(const int8_t* x8, const double* norms, int64_t n, int dim, int64_t row_offset, const float* qf, int nq,
-               int k, int flags, int32_t* out_count, int64_t* out_rows, double* out_scores, void* workspace,
-               size_t workspace_bytes, hipStream_t s, const uint32_t* rows = nullptr) {
-  Plan p;
-  const int rc = rows ? plan_shape(n, dim, nq, k, &p, true) : plan(VRQ_GEMM_INT8_COSINE, n, dim, nq, k, &p);
-  if (rc != VRQ_OK) return rc;
-  if (workspace_bytes < p.bytes) return VRQ_EWORKSPACE;
-  constexpr int ALL = VRQ_GEMM_STAGE_SAMPLE | VRQ_GEMM_STAGE_MAIN | VRQ_GEMM_STAGE_FINISH;
-  const int st = (flags & ALL) ? (flags & ALL) : ALL;
-  uint8_t* ws = (uint8_t*)workspace;
-  int8_t* qa = (int8_t*)ws;
-  double* delta = (double*)(ws + p.off_delta);
-  double* alpha = (double*)(ws + p.off_alpha);
-  double* beta = (double*)(ws + p.off_beta);
-  int32_t* flag = (int32_t*)(ws + p.off_flag);
-  const Call c{x8, norms, n, qa, nq, (float*)(ws + p.off_thr), (uint32_t*)(ws + p.off_cand),
-               (int32_t*)(ws + p.off_cnt), (float*)(ws + p.off_dv), (int32_t*)(ws + p.off_qbf), s, rows};
-  if (st & VRQ_GEMM_STAGE_SAMPLE) {
-    hipLaunchKernelGGL(k5md_prep_kernel, dim3((p.nq_pad + 3) / 4), dim3(256), 0, s, qf, nq, p.nq_pad, dim, qa, delta,
-                       alpha, beta);
-    VRQ_LAUNCH_CHECK();
-    const int r0 = launch_pass_dim(dim, p, c, 0);
-    if (r0 != VRQ_OK) return r0;
-    hipLaunchKernelGGL(k5md_select_kernel, dim3(p.nq_pad), dim3(256), 0, s, (const float*)c.dv, p.scols, p.sstride,
-                       p.nsc, n, k, (const double*)delta, c.thr, c.cnt, p.nchunks, nq, c.qbf, p.nqb);
-    VRQ_LAUNCH_CHECK();
-  }
-  if (st & VRQ_GEMM_STAGE_MAIN) {
-    const int r1 = launch_pass_dim(dim, p, c, 1);
-    if (r1 != VRQ_OK) return r1;
-  }
-  if (st & VRQ_GEMM_STAGE_FINISH) {
-    // finish -> retry main pass (query blocks with a retried query) -> finish of the retried queries ->
-    // exact scan of the rest
-    const bool skip = (flags & VRQ_GEMM_NO_FALLBACK) != 0;
-    auto finish = [&](auto RETRY, auto... g) {
-      hipLaunchKernelGGL((k5md_finish_kernel<decltype(RETRY)::value, decltype(g)...>), dim3(nq), dim3(FIN_NT), 0, s, x8,
-                         norms, n, dim, row_offset, qf, k, (const uint32_t*)c.cand, (const int32_t*)c.cnt, p.nchunks,
-                         p.capc, p.qpb, out_count, out_rows, out_scores, flag, c.thr, (const double*)alpha,
-                         (const double*)beta, (const double*)delta, c.qbf, g...);
-    };
-    auto fallback = [&](auto... g) {
-      hipLaunchKernelGGL((k5md_fallback_kernel<decltype(g)...>), dim3(nq), dim3(FIN_NT), 0, s, x8, norms, n, dim,
-                         row_offset, qf, k, out_count, out_rows, out_scores, (const int32_t*)flag, skip, g...);
-    };
-    if (rows)
-      finish(std::false_type{}, rows);
-    else
-      finish(std::false_type{});
-    VRQ_LAUNCH_CHECK();
-    const int r2 = launch_pass_dim(dim, p, c, 2);
-    if (r2 != VRQ_OK) return r2;
-    if (rows)
-      finish(std::true_type{}, rows);
-    else
-      finish(std::true_type{});
-    VRQ_LAUNCH_CHECK();
-    if (rows)
-      fallback(rows);
-    else
-      fallback();
-    VRQ_LAUNCH_CHECK();
-  }
-  return VRQ_OK;
-}
-
 // "auto": the smallest batch from which K5md beat K5d by more than the run-to-run spread at that dim
 // (profiles/exhaustive_mfma_bench.jsonl; measured at nq = 1, 8, 64, 1024); 0 = not measured, stays on K5d
 __host__ inline int min_batch(int dim) {
@@ -1010,14 +939,14 @@ __host__ inline int min_batch(int dim) {
 //   the first is Delta's last term, the second is inside the (1 + eps) factor on the B1 term.  eps = 2^-20
 //   holds at every d <= 2048 with a factor 1.7 to spare; no dim needs a wider one.
 //
-// Finish (k5mf_finish_kernel<KS, RETRY>): one workgroup of 8 waves per query, the query slice in registers
+// Finish (the shared stage with FloatIP<KS>): one workgroup of 8 waves per query, the query slice in registers
 // (lane l holds the 16-byte pieces l + 64 i of the query, i < NP = ceil(d / 256)).  A wave scores R candidate
 // rows per round: lanes j < R each resolve one candidate (a fixed-trip binary search of the list prefix in
 // LDS, then the list entry) for the NEXT round while this round's rows are in flight; the wave issues the
 // R * NP global_load_dwordx4 of all R rows back to back (wave-uniform row base from v_readlane, consecutive
 // lanes read consecutive pieces) and scores row i under a counted vmcnt wait while rows i + 1 .. R - 1 are
 // still landing.  Score: flat_score_dim, one summation order for the finish and for the exact scan.
-// Admission, retry and flags are K5md's; a round whose rows all fail the test against the k-th key touches
+// Admission, retry and flags are the shared stage's; a round whose rows all fail the test against the k-th key touches
 // no LDS.  R per dim keeps the row registers (4 R NP) near 96: 8 rows up to 512, 6 at 768, 4 at 1536, 3 at
 // 2048; -DVRQ_G5F_R=n overrides it at every dim (the R = 1 A/B of DESIGN section 5 "K5mf").
 #ifndef VRQ_G5F_R
@@ -1193,38 +1122,34 @@ __global__ __launch_bounds__(256) void k5mf_prep_kernel(const float* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------
-struct FinF {
-  uint64_t key[KMAX5 + FB_BATCH];
-  uint32_t row[KMAX5 + FB_BATCH];
-  int32_t pre[MAX_CHUNKS + 1];  // exclusive prefix of the (capped) list lengths
-  int32_t fill, over;
-};
-
-// Running exact top-k over the float rows row_at(j), j < count (row_at: per lane), R rows per wave and round.
-// Batches of FB_BATCH candidates are dealt to the waves in groups of R; key/row[0..kc) hold the list in order
-// after each batch.  All threads call it; returns kc = min(k, count).  count >= 1.
-template <int KS, class RowAt>
-__device__ __forceinline__ int running_topk_f(int64_t count, RowAt row_at, const float* __restrict__ xf,
-                                              const FSlice<KS>& qs, int k, FinF& sh) {
-  constexpr int D = FShape<KS>::D, R = FShape<KS>::R;
-  const int tid = threadIdx.x, l = lane_id(), w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  if (tid == 0) sh.fill = 0;
-  int kc = 0;
-  __syncthreads();
-  // lane j < R: the row of candidate c0 + j (past the end: the last candidate again, so every address is a
-  // row of the corpus; such a row is masked at admission)
-  auto resolve = [&](int64_t c0) {
-    uint32_t rv = 0;
-    if (l < R) {
-      const int64_t c = c0 + l;
-      rv = row_at(c < count ? c : count - 1);
-    }
-    return rv;
-  };
-  for (int64_t base = 0; base < count; base += FB_BATCH) {
-    const uint64_t kk = kc == k ? sh.key[k - 1] : KEY_NONE;
-    const uint32_t kr = kc == k ? sh.row[k - 1] : 0xffffffffu;
-    const int64_t end = base + FB_BATCH < count ? base + FB_BATCH : count;
+// K5mf's score: float rows by flat_score_dim, the query slice in registers, R rows per wave and round.
+template <int KS>
+struct FloatIP {
+  const float* xf;
+  static constexpr int OCC = FShape<KS>::OCC;
+  struct Lds {};
+  template <class Sh>
+  __device__ __forceinline__ FSlice<KS> query(const float* __restrict__ qf, int q, Sh&) const {
+    FSlice<KS> qs;
+    fslice_load(qs, qf + (int64_t)q * FShape<KS>::D);
+    return qs;
+  }
+  // The candidates of a batch are dealt to the waves in groups of R (row_at: per lane).
+  template <class RowAt, class Admit>
+  __device__ __forceinline__ void score_batch(const FSlice<KS>& qs, int64_t base, int64_t end, int64_t count,
+                                              RowAt row_at, Admit admit) const {
+    constexpr int D = FShape<KS>::D, R = FShape<KS>::R;
+    const int l = lane_id(), w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // lane j < R: the row of candidate c0 + j (past the end: the last candidate again, so every address is a
+    // row of the corpus; such a row is masked at admission)
+    auto resolve = [&](int64_t c0) {
+      uint32_t rv = 0;
+      if (l < R) {
+        const int64_t c = c0 + l;
+        rv = row_at(c < count ? c : count - 1);
+      }
+      return rv;
+    };
     const int nrounds = (int)((end - base + FIN_NW * R - 1) / (FIN_NW * R));
     int64_t c0 = base + (int64_t)w * R;
     uint32_t rv = resolve(c0);
@@ -1240,252 +1165,36 @@ __device__ __forceinline__ int running_topk_f(int64_t count, RowAt row_at, const
       rv = resolve(cn);  // the next round's rows, resolved while this round's are in flight
       VRQ_SCHED_FENCE();
 #pragma unroll
-      for (int j = 0; j < R; ++j) {
-        const uint64_t key_r = desc_key_f64(flat_score_dim(qs, x[j]));
-        if (c0 + j < end && (kc < k || key_r < kk || (key_r == kk && rr[j] < kr)) && l == 0) {
-          const int i = kc + atomicAdd(&sh.fill, 1);
-          sh.key[i] = key_r;
-          sh.row[i] = rr[j];
-        }
-      }
+      for (int j = 0; j < R; ++j) admit(c0 + j < end && l == 0, desc_key_f64(flat_score_dim(qs, x[j])), rr[j]);
       c0 = cn;
     }
-    __syncthreads();
-    const int f = sh.fill;
-    if (f > 0) {
-      const int tot = kc + f, np2 = next_pow2(tot);
-      for (int i = tot + tid; i < np2; i += FIN_NT) {
-        sh.key[i] = KEY_NONE;
-        sh.row[i] = 0xffffffffu;
-      }
-      sort_pairs(sh.key, sh.row, np2);
-      kc = tot < k ? tot : k;
-    }
-    __syncthreads();
-    if (tid == 0) sh.fill = 0;
-    __syncthreads();
   }
-  return kc;
-}
-
-__device__ __forceinline__ void write_result_f(int q, int k, int kc, int64_t row_offset, const FinF& sh,
-                                               int32_t* out_count, int64_t* out_rows, double* out_scores) {
-  for (int i = threadIdx.x; i < k; i += FIN_NT) {
-    const int64_t o = (int64_t)q * k + i;
-    out_rows[o] = i < kc ? (int64_t)sh.row[i] + row_offset : -1;
-    out_scores[o] = i < kc ? desc_key_inv(sh.key[i]) : __builtin_nan("");
-  }
-  if (threadIdx.x == 0) out_count[q] = kc;
-}
-
-// finish: k5md_finish_kernel's contract and flags over float rows
-template <int KS, bool RETRY, class... G>
-__global__ __launch_bounds__(FIN_NT, FShape<KS>::OCC) void k5mf_finish_kernel(
-    const float* __restrict__ xf, int64_t n, int64_t row_offset, const float* __restrict__ qf, int k,
-    const uint32_t* __restrict__ cand, const int32_t* __restrict__ ccnt, int nchunks, int capc, int qpb,
-    int32_t* __restrict__ out_count, int64_t* __restrict__ out_rows, double* __restrict__ out_scores,
-    int32_t* __restrict__ fb_flag, float* __restrict__ thr, const double* __restrict__ alpha,
-    const double* __restrict__ beta, const double* __restrict__ delta, int32_t* __restrict__ qbflag, G... gather) {
-  __shared__ FinF sh;
-  constexpr bool GATHER = sizeof...(G) != 0;
-  const uint32_t* const rows = gather_rows(gather...);
-  const int q = blockIdx.x, tid = threadIdx.x;
-  if (RETRY && fb_flag[q] != 2) return;
-  FSlice<KS> qs;
-  fslice_load(qs, qf + (int64_t)q * FShape<KS>::D);
-  if (tid == 0) sh.over = 0;
-  __syncthreads();
-  const int32_t* cq = ccnt + (int64_t)q * nchunks;
-  for (int c = tid; c < nchunks; c += FIN_NT) {
-    const int x = cq[c];
-    if (x > capc) sh.over = 1;
-    sh.pre[c + 1] = x < capc ? x : capc;
-  }
-  __syncthreads();
-  if (tid < WAVE) {  // inclusive scan of pre[1 .. nchunks] by one wave: 32 entries per lane, then the lanes
-    constexpr int PER = MAX_CHUNKS / WAVE;
-    int part = 0;
-    for (int i = 0; i < PER; ++i) {
-      const int c = tid * PER + i;
-      if (c < nchunks) part += sh.pre[c + 1];
-    }
-    int incl = part;
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-      const int y = __shfl_up(incl, d, WAVE);
-      if (tid >= d) incl += y;
-    }
-    int run = incl - part;
-    for (int i = 0; i < PER; ++i) {
-      const int c = tid * PER + i;
-      if (c < nchunks) {
-        run += sh.pre[c + 1];
-        sh.pre[c + 1] = run;
-      }
-    }
-    if (tid == 0) sh.pre[0] = 0;
-  }
-  __syncthreads();
-  const int total = sh.pre[nchunks];
-  const int need = (int)((int64_t)k < n ? k : n);
-  const bool over = sh.over != 0;
-  if (total < need || (RETRY && over)) {
-    if (tid == 0) {
-      fb_flag[q] = 1;
-      thr[q] = __builtin_inff();
-    }
-    return;
-  }
-  const uint32_t* Cq = cand + (int64_t)q * nchunks * capc;
-  // candidate j of the concatenated lists: the largest chunk lo with pre[lo] <= j (fixed 11 steps)
-  auto row_at = [&](int64_t j) {
-    int lo = 0;
-#pragma unroll
-    for (int st = MAX_CHUNKS / 2; st > 0; st >>= 1) {
-      const int mid = lo + st;
-      if (mid < nchunks && sh.pre[mid] <= j) lo = mid;
-    }
-    const uint32_t v = Cq[(int64_t)lo * capc + (j - sh.pre[lo])];
-    if constexpr (GATHER) return rows[v];
-    return v;
-  };
-  const int kc = running_topk_f<KS>(total, row_at, xf, qs, k, sh);
-  if (!RETRY && over) {
-    if (tid == 0) {
-      const double t2 = alpha[q] * desc_key_inv(sh.key[kc - 1]) + beta[q] - delta[q];
-      thr[q] = __double2float_rd(t2 - 1e-9 * fabs(t2));
-      fb_flag[q] = 2;
-      atomicOr(&qbflag[q / qpb], 1);
-    }
-    return;
-  }
-  write_result_f(q, k, kc, row_offset, sh, out_count, out_rows, out_scores);
-  if (tid == 0) {
-    fb_flag[q] = 0;
-    thr[q] = __builtin_inff();
-  }
-}
-
-// the exact scan of the flagged queries: every row through the same rounds and the same score function
-template <int KS, class... G>
-__global__ __launch_bounds__(FIN_NT, FShape<KS>::OCC) void k5mf_fallback_kernel(
-    const float* __restrict__ xf, int64_t n, int64_t row_offset, const float* __restrict__ qf, int k,
-    int32_t* __restrict__ out_count, int64_t* __restrict__ out_rows, double* __restrict__ out_scores,
-    const int32_t* __restrict__ fb_flag, bool skip, G... gather) {
-  __shared__ FinF sh;
-  const uint32_t* const rows = gather_rows(gather...);
-  const int q = blockIdx.x, tid = threadIdx.x;
-  if (fb_flag[q] != 1) return;
-  if (skip) {
-    for (int i = tid; i < k; i += FIN_NT) {
-      out_rows[(int64_t)q * k + i] = -1;
-      out_scores[(int64_t)q * k + i] = __builtin_nan("");
-    }
-    if (tid == 0) out_count[q] = -1;
-    return;
-  }
-  FSlice<KS> qs;
-  fslice_load(qs, qf + (int64_t)q * FShape<KS>::D);
-  const int kc = running_topk_f<KS>(
-      n, [=](int64_t j) { return sizeof...(G) ? rows[j] : (uint32_t)j; }, xf, qs, k, sh);
-  write_result_f(q, k, kc, row_offset, sh, out_count, out_rows, out_scores);
-}
-
-struct FloatCall {
-  const float* xf;
-  int64_t n, row_offset;
-  const float* qf;
-  int nq, k;
-  int32_t *out_count, *flag;
-  int64_t* out_rows;
-  double* out_scores;
-  const double *alpha, *beta, *delta;
-  bool skip;
 };
 
-template <int KS, class... G>
-static void launch_float_finish_g(const Plan& p, const Call& c, const FloatCall& f, G... g) {
-  hipLaunchKernelGGL((k5mf_finish_kernel<KS, false, G...>), dim3(f.nq), dim3(FIN_NT), 0, c.s, f.xf, f.n, f.row_offset,
-                     f.qf, f.k, (const uint32_t*)c.cand, (const int32_t*)c.cnt, p.nchunks, p.capc, p.qpb, f.out_count,
-                     f.out_rows, f.out_scores, f.flag, c.thr, f.alpha, f.beta, f.delta, c.qbf, g...);
-  launch_pass<KS>(p, c, 2);
-  hipLaunchKernelGGL((k5mf_finish_kernel<KS, true, G...>), dim3(f.nq), dim3(FIN_NT), 0, c.s, f.xf, f.n, f.row_offset,
-                     f.qf, f.k, (const uint32_t*)c.cand, (const int32_t*)c.cnt, p.nchunks, p.capc, p.qpb, f.out_count,
-                     f.out_rows, f.out_scores, f.flag, c.thr, f.alpha, f.beta, f.delta, c.qbf, g...);
-  hipLaunchKernelGGL((k5mf_fallback_kernel<KS, G...>), dim3(f.nq), dim3(FIN_NT), 0, c.s, f.xf, f.n, f.row_offset, f.qf,
-                     f.k, f.out_count, f.out_rows, f.out_scores, (const int32_t*)f.flag, f.skip, g...);
-}
-
-template <int KS>
-static void launch_float_finish(const Plan& p, const Call& c, const FloatCall& f) {
-  if (c.rows)
-    launch_float_finish_g<KS>(p, c, f, c.rows);
-  else if constexpr (KS != 32)  // (no contiguous KS = 32 instance: run_float refuses the call)
-    launch_float_finish_g<KS>(p, c, f);
-}
+// the operands of a K5mf call: the float rows for the finish, flat_ip_prepare's image of them for the passes
+struct FloatOperands {
+  const float* xf;
+  const int8_t* x8;
+  const double *inv_scale, *bounds;
+  template <class... A>
+  void prep(dim3 grid, hipStream_t s, A... a) const {
+    hipLaunchKernelGGL(k5mf_prep_kernel, grid, dim3(256), 0, s, a..., bounds);
+  }
+  template <int KS, bool DENSE, class... A>
+  void pass(dim3 grid, dim3 blk, hipStream_t s, A... a) const {
+    hipLaunchKernelGGL((k5md_pass_kernel<KS, DENSE>), grid, blk, 0, s, x8, inv_scale, a...);
+  }
+  template <int KS>
+  FloatIP<KS> family() const {
+    return {xf};
+  }
+};
 
 template <int KS>
 static void launch_prepare(const float* xf, int64_t n, int8_t* x8, double* inv_scale, double* bounds, hipStream_t s) {
   const int64_t per = 4 * FShape<KS>::RPW;
   hipLaunchKernelGGL((k5mf_prepare_kernel<KS>), dim3((unsigned)((n + per - 1) / per)), dim3(256), 0, s, xf, n, x8,
                      inv_scale, reinterpret_cast<unsigned long long*>(bounds));
-}
-
-// the plan of the float path: K5md's (same pieces, passes and lists)
-__host__ inline int plan_float(int64_t n, int dim, int nq, int k, Plan* p) {
-  return plan(VRQ_GEMM_INT8_COSINE, n, dim, nq, k, p);
-}
-
-static int run_float(const float* xf, const int8_t* x8, const double* inv_scale, const double* bounds, int64_t n,
-                     int dim, int64_t row_offset, const float* qf, int nq, int k, int flags, int32_t* out_count,
-                     int64_t* out_rows, double* out_scores, void* workspace, size_t workspace_bytes, hipStream_t s,
-                     const uint32_t* rows = nullptr) {  // rows != NULL (K5g): n is the length of the list
-  Plan p;
-  const int rc = rows ? plan_shape(n, dim, nq, k, &p, true) : plan_float(n, dim, nq, k, &p);
-  if (rc != VRQ_OK) return rc;
-  if (workspace_bytes < p.bytes) return VRQ_EWORKSPACE;
-  constexpr int ALL = VRQ_GEMM_STAGE_SAMPLE | VRQ_GEMM_STAGE_MAIN | VRQ_GEMM_STAGE_FINISH;
-  const int st = (flags & ALL) ? (flags & ALL) : ALL;
-  uint8_t* ws = (uint8_t*)workspace;
-  int8_t* qa = (int8_t*)ws;
-  double* delta = (double*)(ws + p.off_delta);
-  double* alpha = (double*)(ws + p.off_alpha);
-  double* beta = (double*)(ws + p.off_beta);
-  const Call c{x8, inv_scale, n, qa, nq, (float*)(ws + p.off_thr), (uint32_t*)(ws + p.off_cand),
-               (int32_t*)(ws + p.off_cnt), (float*)(ws + p.off_dv), (int32_t*)(ws + p.off_qbf), s, rows};
-  if (st & VRQ_GEMM_STAGE_SAMPLE) {
-    hipLaunchKernelGGL(k5mf_prep_kernel, dim3((p.nq_pad + 3) / 4), dim3(256), 0, s, qf, nq, p.nq_pad, dim, qa, delta,
-                       alpha, beta, bounds);
-    VRQ_LAUNCH_CHECK();
-    const int r0 = launch_pass_dim(dim, p, c, 0);
-    if (r0 != VRQ_OK) return r0;
-    hipLaunchKernelGGL(k5md_select_kernel, dim3(p.nq_pad), dim3(256), 0, s, (const float*)c.dv, p.scols, p.sstride,
-                       p.nsc, n, k, (const double*)delta, c.thr, c.cnt, p.nchunks, nq, c.qbf, p.nqb);
-    VRQ_LAUNCH_CHECK();
-  }
-  if (st & VRQ_GEMM_STAGE_MAIN) {
-    const int r1 = launch_pass_dim(dim, p, c, 1);
-    if (r1 != VRQ_OK) return r1;
-  }
-  if (st & VRQ_GEMM_STAGE_FINISH) {
-    const FloatCall f{xf, n, row_offset, qf, nq, k, out_count, (int32_t*)(ws + p.off_flag), out_rows, out_scores,
-                      alpha, beta, delta, (flags & VRQ_GEMM_NO_FALLBACK) != 0};
-    switch (dim) {
-      case 256: launch_float_finish<8>(p, c, f); break;
-      case 384: launch_float_finish<12>(p, c, f); break;
-      case 512: launch_float_finish<16>(p, c, f); break;
-      case 768: launch_float_finish<24>(p, c, f); break;
-      case 1536: launch_float_finish<48>(p, c, f); break;
-      case 2048: launch_float_finish<64>(p, c, f); break;
-      case 1024:  // the gathered calls alone
-        if (!rows) return VRQ_EUNSUPPORTED;
-        launch_float_finish<32>(p, c, f);
-        break;
-      default: return VRQ_EUNSUPPORTED;
-    }
-    VRQ_LAUNCH_CHECK();
-  }
-  return VRQ_OK;
 }
 
 // "auto" of the float path, K5md's rule: per dim the smallest measured batch (nq = 1, 8, 64, 1024;
@@ -1933,162 +1642,47 @@ __device__ __forceinline__ double binary_score_dim(const double* tab, const uint
   return s;
 }
 
-// Running exact top-k over the code rows row_at(j), j < count, one row per thread; K5md's admission and
-// batches.  All threads call it; returns kc = min(k, count).
-template <class RowAt>
-__device__ int running_topk_b(int64_t count, RowAt row_at, const uint8_t* __restrict__ codes, int dim,
-                              const double* tab, int k, FinF& sh) {
-  const int tid = threadIdx.x;
-  if (tid == 0) sh.fill = 0;
-  int kc = 0;
-  __syncthreads();
-  for (int64_t base = 0; base < count; base += FB_BATCH) {
-    const uint64_t kk = kc == k ? sh.key[k - 1] : KEY_NONE;
-    const uint32_t kr = kc == k ? sh.row[k - 1] : 0xffffffffu;
-    const int64_t end = base + FB_BATCH < count ? base + FB_BATCH : count;
-    for (int64_t j = base + tid; j < end; j += FIN_NT) {
-      const uint32_t rr = row_at(j);
-      const uint64_t key_r = desc_key_f64(binary_score_dim(tab, codes + (int64_t)rr * (dim / 8), dim));
-      if (kc < k || key_r < kk || (key_r == kk && rr < kr)) {
-        const int i = kc + atomicAdd(&sh.fill, 1);
-        sh.key[i] = key_r;
-        sh.row[i] = rr;
-      }
-    }
-    __syncthreads();
-    const int f = sh.fill;
-    if (f > 0) {
-      const int tot = kc + f, np2 = next_pow2(tot);
-      for (int i = tot + tid; i < np2; i += FIN_NT) {
-        sh.key[i] = KEY_NONE;
-        sh.row[i] = 0xffffffffu;
-      }
-      sort_pairs(sh.key, sh.row, np2);
-      kc = tot < k ? tot : k;
-    }
-    __syncthreads();
-    if (tid == 0) sh.fill = 0;
-    __syncthreads();
-  }
-  return kc;
-}
-
-// finish: k5md_finish_kernel's contract and flags over code rows (G...: its row list too)
-template <bool RETRY, class... G>
-__global__ __launch_bounds__(FIN_NT) void k5mb_finish_kernel(
-    const uint8_t* __restrict__ codes, int64_t n, int dim, int64_t row_offset, const float* __restrict__ qf, int k,
-    const uint32_t* __restrict__ cand, const int32_t* __restrict__ ccnt, int nchunks, int capc, int qpb,
-    int32_t* __restrict__ out_count, int64_t* __restrict__ out_rows, double* __restrict__ out_scores,
-    int32_t* __restrict__ fb_flag, float* __restrict__ thr, const double* __restrict__ alpha,
-    const double* __restrict__ beta, const double* __restrict__ delta, int32_t* __restrict__ qbflag, G... gather) {
-  __shared__ FinF sh;
-  __shared__ double tab[2048 * 4];
-  constexpr bool GATHER = sizeof...(G) != 0;
-  const uint32_t* const rows = gather_rows(gather...);
-  const int q = blockIdx.x, tid = threadIdx.x;
-  if (RETRY && fb_flag[q] != 2) return;
-  if (tid == 0) sh.over = 0;
-  __syncthreads();
-  const int32_t* cq = ccnt + (int64_t)q * nchunks;
-  for (int c = tid; c < nchunks; c += FIN_NT) {
-    const int x = cq[c];
-    if (x > capc) sh.over = 1;
-    sh.pre[c + 1] = x < capc ? x : capc;
-  }
-  binary_table(qf + (int64_t)q * dim, dim, tab);
-  __syncthreads();
-  if (tid < WAVE) {  // inclusive scan of pre[1 .. nchunks] by one wave: 32 entries per lane, then the lanes
-    constexpr int PER = MAX_CHUNKS / WAVE;
-    int part = 0;
-    for (int i = 0; i < PER; ++i) {
-      const int c = tid * PER + i;
-      if (c < nchunks) part += sh.pre[c + 1];
-    }
-    int incl = part;
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-      const int y = __shfl_up(incl, d, WAVE);
-      if (tid >= d) incl += y;
-    }
-    int run = incl - part;
-    for (int i = 0; i < PER; ++i) {
-      const int c = tid * PER + i;
-      if (c < nchunks) {
-        run += sh.pre[c + 1];
-        sh.pre[c + 1] = run;
-      }
-    }
-    if (tid == 0) sh.pre[0] = 0;
-  }
-  __syncthreads();
-  const int total = sh.pre[nchunks];
-  const int need = (int)((int64_t)k < n ? k : n);
-  const bool over = sh.over != 0;
-  if (total < need || (RETRY && over)) {
-    if (tid == 0) {
-      fb_flag[q] = 1;
-      thr[q] = __builtin_inff();
-    }
-    return;
-  }
-  const uint32_t* Cq = cand + (int64_t)q * nchunks * capc;
-  // candidate j of the concatenated lists: the largest chunk lo with pre[lo] <= j (fixed 11 steps)
-  auto row_at = [&](int64_t j) {
-    int lo = 0;
-#pragma unroll
-    for (int st = MAX_CHUNKS / 2; st > 0; st >>= 1) {
-      const int mid = lo + st;
-      if (mid < nchunks && sh.pre[mid] <= j) lo = mid;
-    }
-    const uint32_t v = Cq[(int64_t)lo * capc + (j - sh.pre[lo])];
-    if constexpr (GATHER) return rows[v];
-    return v;
-  };
-  const int kc = running_topk_b(total, row_at, codes, dim, tab, k, sh);
-  if (!RETRY && over) {
-    if (tid == 0) {
-      const double t2 = alpha[q] * desc_key_inv(sh.key[kc - 1]) + beta[q] - delta[q];
-      thr[q] = __double2float_rd(t2 - 1e-9 * fabs(t2));
-      fb_flag[q] = 2;
-      atomicOr(&qbflag[q / qpb], 1);
-    }
-    return;
-  }
-  write_result_f(q, k, kc, row_offset, sh, out_count, out_rows, out_scores);
-  if (tid == 0) {
-    fb_flag[q] = 0;
-    thr[q] = __builtin_inff();
-  }
-}
-
-// the exact scan of the flagged queries: every row (of the list) through the same score function
-template <class... G>
-__global__ __launch_bounds__(FIN_NT) void k5mb_fallback_kernel(
-    const uint8_t* __restrict__ codes, int64_t n, int dim, int64_t row_offset, const float* __restrict__ qf, int k,
-    int32_t* __restrict__ out_count, int64_t* __restrict__ out_rows, double* __restrict__ out_scores,
-    const int32_t* __restrict__ fb_flag, bool skip, G... gather) {
-  __shared__ FinF sh;
-  __shared__ double tab[2048 * 4];
-  const uint32_t* const rows = gather_rows(gather...);
-  const int q = blockIdx.x, tid = threadIdx.x;
-  if (fb_flag[q] != 1) return;
-  if (skip) {
-    for (int i = tid; i < k; i += FIN_NT) {
-      out_rows[(int64_t)q * k + i] = -1;
-      out_scores[(int64_t)q * k + i] = __builtin_nan("");
-    }
-    if (tid == 0) out_count[q] = -1;
-    return;
-  }
-  binary_table(qf + (int64_t)q * dim, dim, tab);
-  const int kc = running_topk_b(
-      n, [=](int64_t j) { return sizeof...(G) ? rows[j] : (uint32_t)j; }, codes, dim, tab, k, sh);
-  write_result_f(q, k, kc, row_offset, sh, out_count, out_rows, out_scores);
-}
-
-struct BinaryCall {
+// K5mb's score: code rows by binary_score_dim, the query's nibble table in LDS, one row per thread.
+struct Binary {
   const uint8_t* codes;
-  int64_t n;
+  int dim;
+  static constexpr int OCC = 1;
+  struct Lds {
+    double tab[2048 * 4];
+  };
+  template <class Sh>
+  __device__ __forceinline__ const double* query(const float* __restrict__ qf, int q, Sh& sh) const {
+    binary_table(qf + (int64_t)q * dim, dim, sh.tab);
+    return sh.tab;
+  }
+  template <class RowAt, class Admit>
+  __device__ __forceinline__ void score_batch(const double* tab, int64_t base, int64_t end, int64_t, RowAt row_at,
+                                              Admit admit) const {
+    for (int64_t j = base + threadIdx.x; j < end; j += FIN_NT) {
+      const uint32_t rr = row_at(j);
+      admit(true, desc_key_f64(binary_score_dim(tab, codes + (int64_t)rr * (dim / 8), dim)), rr);
+    }
+  }
+  template <class... A>
+  void prep(dim3 grid, hipStream_t s, A... a) const {
+    hipLaunchKernelGGL(k5mb_prep_kernel, grid, dim3(256), 0, s, a...);
+  }
+  template <int KS, bool DENSE, class... A>
+  void pass(dim3 grid, dim3 blk, hipStream_t s, A... a) const {
+    hipLaunchKernelGGL((k5mb_pass_kernel<KS, DENSE>), grid, blk, 0, s, codes, a...);
+  }
+  template <int KS>
+  Binary family() const {
+    return *this;
+  }
+};
+
+// =============================================================================================
+// The host driver of the three paths.  F = Int8Cos, FloatOperands or Binary supplies the prep-kernel launch,
+// the pass-kernel launch and the finish family; the plan, the workspace, the stage flags and the sequence of
+// launches are the same for all.
+struct Call {
+  int64_t n;  // rows the passes cover: the corpus's, or the length of `rows`
   const int8_t* qa;
   int nq;
   float* thr;
@@ -2097,55 +1691,44 @@ struct BinaryCall {
   float* dv;
   int32_t* qbf;
   hipStream_t s;
-  const uint32_t* rows;  // K5gb: the allowed rows, ascending (NULL: every row)
+  const uint32_t* rows;  // K5g / K5gb: the allowed rows, ascending (NULL: every row)
 };
 
-template <int KS>
-static void launch_binary_pass(const Plan& p, const BinaryCall& c, int pass) {  // 0 sample, 1 main, 2 retry
-  const dim3 blk(Shape<KS>::W * 64);
-  if (c.rows && pass == 0)
-    hipLaunchKernelGGL((k5mb_pass_kernel<KS, true, const uint32_t*>), dim3(p.nsc * p.nqb), blk, 0, c.s, c.codes, c.n,
-                       c.qa, c.nq, (const float*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr, 0, p.scr, p.sstride,
-                       p.nsc, p.nqb, c.dv, p.scols, (const int32_t*)nullptr, c.rows);
-  else if (c.rows)
-    hipLaunchKernelGGL((k5mb_pass_kernel<KS, false, const uint32_t*>), dim3(p.nchunks * p.nqb), blk, 0, c.s, c.codes,
-                       c.n, c.qa, c.nq, (const float*)c.thr, c.cand, c.cnt, p.capc, p.chunk_rows, p.chunk_rows,
-                       p.nchunks, p.nqb, (float*)nullptr, (int64_t)0,
-                       pass == 2 ? (const int32_t*)c.qbf : (const int32_t*)nullptr, c.rows);
-  else if constexpr (KS == 32)
-    return;  // (no contiguous KS = 32 instance: launch_binary_pass_dim refuses the call)
-  else if (pass == 0)
-    hipLaunchKernelGGL((k5mb_pass_kernel<KS, true>), dim3(p.nsc * p.nqb), blk, 0, c.s, c.codes, c.n, c.qa, c.nq,
-                       (const float*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr, 0, p.scr, p.sstride, p.nsc,
-                       p.nqb, c.dv, p.scols, (const int32_t*)nullptr);
-  else
-    hipLaunchKernelGGL((k5mb_pass_kernel<KS, false>), dim3(p.nchunks * p.nqb), blk, 0, c.s, c.codes, c.n, c.qa, c.nq,
-                       (const float*)c.thr, c.cand, c.cnt, p.capc, p.chunk_rows, p.chunk_rows, p.nchunks, p.nqb,
-                       (float*)nullptr, (int64_t)0, pass == 2 ? (const int32_t*)c.qbf : (const int32_t*)nullptr);
+template <int KS, class F>
+static void launch_pass(const F& f, const Plan& p, const Call& c, int pass) {  // 0 sample, 1 main, 2 retry
+  auto go = [&](auto... g) {
+    const dim3 blk(Shape<KS>::W * 64);
+    if (pass == 0)
+      f.template pass<KS, true>(dim3(p.nsc * p.nqb), blk, c.s, c.n, c.qa, c.nq, (const float*)nullptr,
+                                (uint32_t*)nullptr, (int32_t*)nullptr, 0, p.scr, p.sstride, p.nsc, p.nqb, c.dv,
+                                p.scols, (const int32_t*)nullptr, g...);
+    else
+      f.template pass<KS, false>(dim3(p.nchunks * p.nqb), blk, c.s, c.n, c.qa, c.nq, (const float*)c.thr, c.cand,
+                                 c.cnt, p.capc, p.chunk_rows, p.chunk_rows, p.nchunks, p.nqb, (float*)nullptr,
+                                 (int64_t)0, pass == 2 ? (const int32_t*)c.qbf : (const int32_t*)nullptr, g...);
+  };
+  if (c.rows)
+    go(c.rows);
+  else if constexpr (KS != 32)  // (no contiguous KS = 32 instance: with_ks refuses the call)
+    go();
 }
 
-static int launch_binary_pass_dim(int dim, const Plan& p, const BinaryCall& c, int pass) {
-  switch (dim) {
-    case 256: launch_binary_pass<8>(p, c, pass); break;
-    case 384: launch_binary_pass<12>(p, c, pass); break;
-    case 512: launch_binary_pass<16>(p, c, pass); break;
-    case 768: launch_binary_pass<24>(p, c, pass); break;
-    case 1536: launch_binary_pass<48>(p, c, pass); break;
-    case 2048: launch_binary_pass<64>(p, c, pass); break;
-    case 1024:  // the gathered call alone (unfiltered 1024 is K5's)
-      if (!c.rows) return VRQ_EUNSUPPORTED;
-      launch_binary_pass<32>(p, c, pass);
-      break;
-    default: return VRQ_EUNSUPPORTED;
-  }
+template <class F>
+static int launch_pass_dim(const F& f, int dim, const Plan& p, const Call& c, int pass) {
+  const int rc = with_ks(dim, c.rows != nullptr, [&](auto KS) {
+    launch_pass<decltype(KS)::value>(f, p, c, pass);
+    return VRQ_OK;
+  });
+  if (rc != VRQ_OK) return rc;
   VRQ_LAUNCH_CHECK();
   return VRQ_OK;
 }
 
-// rows != NULL (K5gb): n is the length of the list, and the call plans like an unfiltered one on n rows
-static int run_binary(const uint8_t* codes, int64_t n, int dim, int64_t row_offset, const float* qf, int nq, int k,
-                      int flags, int32_t* out_count, int64_t* out_rows, double* out_scores, void* workspace,
-                      size_t workspace_bytes, hipStream_t s, const uint32_t* rows = nullptr) {
+// rows != NULL (K5g, K5gb): n is the length of the list, and the call plans like an unfiltered one on n rows
+template <class F>
+static int run(const F& f, int64_t n, int dim, int64_t row_offset, const float* qf, int nq, int k, int flags,
+               int32_t* out_count, int64_t* out_rows, double* out_scores, void* workspace, size_t workspace_bytes,
+               hipStream_t s, const uint32_t* rows = nullptr) {
   Plan p;
   const int rc = plan_shape(n, dim, nq, k, &p, rows != nullptr);
   if (rc != VRQ_OK) return rc;
@@ -2158,53 +1741,50 @@ static int run_binary(const uint8_t* codes, int64_t n, int dim, int64_t row_offs
   double* alpha = (double*)(ws + p.off_alpha);
   double* beta = (double*)(ws + p.off_beta);
   int32_t* flag = (int32_t*)(ws + p.off_flag);
-  const BinaryCall c{codes, n, qa, nq, (float*)(ws + p.off_thr), (uint32_t*)(ws + p.off_cand),
-                     (int32_t*)(ws + p.off_cnt), (float*)(ws + p.off_dv), (int32_t*)(ws + p.off_qbf), s, rows};
+  const Call c{n, qa, nq, (float*)(ws + p.off_thr), (uint32_t*)(ws + p.off_cand), (int32_t*)(ws + p.off_cnt),
+               (float*)(ws + p.off_dv), (int32_t*)(ws + p.off_qbf), s, rows};
   if (st & VRQ_GEMM_STAGE_SAMPLE) {
-    hipLaunchKernelGGL(k5mb_prep_kernel, dim3((p.nq_pad + 3) / 4), dim3(256), 0, s, qf, nq, p.nq_pad, dim, qa, delta,
-                       alpha, beta);
+    f.prep(dim3((p.nq_pad + 3) / 4), s, qf, nq, p.nq_pad, dim, qa, delta, alpha, beta);
     VRQ_LAUNCH_CHECK();
-    const int r0 = launch_binary_pass_dim(dim, p, c, 0);
+    const int r0 = launch_pass_dim(f, dim, p, c, 0);
     if (r0 != VRQ_OK) return r0;
     hipLaunchKernelGGL(k5md_select_kernel, dim3(p.nq_pad), dim3(256), 0, s, (const float*)c.dv, p.scols, p.sstride,
                        p.nsc, n, k, (const double*)delta, c.thr, c.cnt, p.nchunks, nq, c.qbf, p.nqb);
     VRQ_LAUNCH_CHECK();
   }
   if (st & VRQ_GEMM_STAGE_MAIN) {
-    const int r1 = launch_binary_pass_dim(dim, p, c, 1);
+    const int r1 = launch_pass_dim(f, dim, p, c, 1);
     if (r1 != VRQ_OK) return r1;
   }
   if (st & VRQ_GEMM_STAGE_FINISH) {
     // finish -> retry main pass (query blocks with a retried query) -> finish of the retried queries ->
     // exact scan of the rest
     const bool skip = (flags & VRQ_GEMM_NO_FALLBACK) != 0;
-    auto finish = [&](auto RETRY, auto... g) {
-      hipLaunchKernelGGL((k5mb_finish_kernel<decltype(RETRY)::value, decltype(g)...>), dim3(nq), dim3(FIN_NT), 0, s,
-                         codes, n, dim, row_offset, qf, k, (const uint32_t*)c.cand, (const int32_t*)c.cnt, p.nchunks,
-                         p.capc, p.qpb, out_count, out_rows, out_scores, flag, c.thr, (const double*)alpha,
-                         (const double*)beta, (const double*)delta, c.qbf, g...);
-    };
-    auto fallback = [&](auto... g) {
-      hipLaunchKernelGGL((k5mb_fallback_kernel<decltype(g)...>), dim3(nq), dim3(FIN_NT), 0, s, codes, n, dim,
-                         row_offset, qf, k, out_count, out_rows, out_scores, (const int32_t*)flag, skip, g...);
-    };
-    if (rows)
-      finish(std::false_type{}, rows);
-    else
-      finish(std::false_type{});
-    VRQ_LAUNCH_CHECK();
-    const int r2 = launch_binary_pass_dim(dim, p, c, 2);
-    if (r2 != VRQ_OK) return r2;
-    if (rows)
-      finish(std::true_type{}, rows);
-    else
-      finish(std::true_type{});
-    VRQ_LAUNCH_CHECK();
-    if (rows)
-      fallback(rows);
-    else
-      fallback();
-    VRQ_LAUNCH_CHECK();
+    return with_ks(dim, rows != nullptr, [&](auto KS) {
+      const auto fam = f.template family<decltype(KS)::value>();
+      using Fam = std::remove_const_t<decltype(fam)>;
+      auto stage = [&](auto... g) {
+        auto finish = [&](auto RETRY) {
+          hipLaunchKernelGGL((k5m_finish_kernel<Fam, decltype(RETRY)::value, decltype(g)...>), dim3(nq), dim3(FIN_NT),
+                             0, s, fam, n, row_offset, qf, k, (const uint32_t*)c.cand, (const int32_t*)c.cnt,
+                             p.nchunks, p.capc, p.qpb, out_count, out_rows, out_scores, flag, c.thr,
+                             (const double*)alpha, (const double*)beta, (const double*)delta, c.qbf, g...);
+        };
+        finish(std::false_type{});
+        VRQ_LAUNCH_CHECK();
+        const int r2 = launch_pass_dim(f, dim, p, c, 2);
+        if (r2 != VRQ_OK) return r2;
+        finish(std::true_type{});
+        VRQ_LAUNCH_CHECK();
+        hipLaunchKernelGGL((k5m_fallback_kernel<Fam, decltype(g)...>), dim3(nq), dim3(FIN_NT), 0, s, fam, n,
+                           row_offset, qf, k, out_count, out_rows, out_scores, (const int32_t*)flag, skip, g...);
+        VRQ_LAUNCH_CHECK();
+        return (int)VRQ_OK;
+      };
+      if (rows) return stage(rows);
+      if constexpr (decltype(KS)::value != 32) return stage();
+      return (int)VRQ_EUNSUPPORTED;
+    });
   }
   return VRQ_OK;
 }
@@ -2247,7 +1827,9 @@ __host__ inline int plan_rows(int64_t m, int dim, int nq, int k, Plan* p) {
   return plan_shape(m > 0 ? m : 1, dim, nq, k, p, true);
 }
 
-static void plan_info(const Plan& p, int64_t* info) {
+// the bodies of the *_plan and *_prep_layout entries: rc = the plan's return code, passed through
+static int plan_info(int rc, const Plan& p, int64_t* info) {
+  if (rc != VRQ_OK) return rc;
   info[0] = p.chunk_rows;
   info[1] = p.nchunks;
   info[2] = p.capc;
@@ -2256,6 +1838,20 @@ static void plan_info(const Plan& p, int64_t* info) {
   info[5] = p.scr;
   info[6] = (int64_t)p.bytes;
   info[7] = p.qpb;
+  return VRQ_OK;
+}
+
+static int prep_layout_info(int rc, const Plan& p, int64_t* info) {
+  if (rc != VRQ_OK) return rc;
+  info[0] = (int64_t)p.off_delta;
+  info[1] = (int64_t)p.off_alpha;
+  info[2] = (int64_t)p.off_beta;
+  info[3] = (int64_t)p.off_flag;
+  info[4] = (int64_t)p.off_thr;
+  info[5] = p.nq_pad;
+  info[6] = (int64_t)p.off_cnt;
+  info[7] = (int64_t)p.off_cand;
+  return VRQ_OK;
 }
 
 constexpr int ROWS_FLAGS = VRQ_GEMM_STAGE_SAMPLE | VRQ_GEMM_STAGE_MAIN | VRQ_GEMM_STAGE_FINISH | VRQ_GEMM_NO_FALLBACK;
@@ -2279,34 +1875,14 @@ int vrq_gemm_topk_dim_mfma_plan(int32_t mode, int64_t n, int32_t dim, int32_t nq
   if (mode != VRQ_GEMM_INT8_COSINE) return mode == VRQ_GEMM_FLOAT_IP ? VRQ_EINVAL : VRQ_EUNSUPPORTED;
   if (dim == 1024) return vrq_gemm_topk_plan(mode, n, dim, nq, k, info);
   g5d::Plan p;
-  const int rc = g5d::plan(mode, n, dim, nq, k, &p);
-  if (rc != VRQ_OK) return rc;
-  info[0] = p.chunk_rows;
-  info[1] = p.nchunks;
-  info[2] = p.capc;
-  info[3] = p.nqb;
-  info[4] = p.nsc;
-  info[5] = p.scr;
-  info[6] = (int64_t)p.bytes;
-  info[7] = p.qpb;
-  return VRQ_OK;
+  return g5d::plan_info(g5d::plan(mode, n, dim, nq, k, &p), p, info);
 }
 
 int vrq_gemm_topk_dim_mfma_prep_layout(int32_t mode, int64_t n, int32_t dim, int32_t nq, int32_t k, int64_t* info) {
   if (!info) return VRQ_EINVAL;
   if (dim == 1024) return VRQ_EUNSUPPORTED;  // K5's: vrq_gemm_topk_prep_layout / vrq_gemm_topk_layout
   g5d::Plan p;
-  const int rc = g5d::plan(mode, n, dim, nq, k, &p);
-  if (rc != VRQ_OK) return rc;
-  info[0] = (int64_t)p.off_delta;
-  info[1] = (int64_t)p.off_alpha;
-  info[2] = (int64_t)p.off_beta;
-  info[3] = (int64_t)p.off_flag;
-  info[4] = (int64_t)p.off_thr;
-  info[5] = p.nq_pad;
-  info[6] = (int64_t)p.off_cnt;
-  info[7] = (int64_t)p.off_cand;
-  return VRQ_OK;
+  return g5d::prep_layout_info(g5d::plan(mode, n, dim, nq, k, &p), p, info);
 }
 
 int vrq_gemm_topk_dim_mfma(int32_t mode, const uint8_t* codes, const int8_t* x8, const double* norms, int64_t n,
@@ -2322,8 +1898,8 @@ int vrq_gemm_topk_dim_mfma(int32_t mode, const uint8_t* codes, const int8_t* x8,
   VRQ_CHECK_ARG(qf && out_count && out_rows && out_scores && workspace && x8 && norms && n > 0 && nq > 0 && k > 0);
   constexpr int OK = VRQ_GEMM_STAGE_SAMPLE | VRQ_GEMM_STAGE_MAIN | VRQ_GEMM_STAGE_FINISH | VRQ_GEMM_NO_FALLBACK;
   if (flags & ~OK) return VRQ_EUNSUPPORTED;
-  return g5d::run(x8, norms, n, dim, row_offset, qf, nq, k, flags, out_count, out_rows, out_scores, workspace,
-                  workspace_bytes, (hipStream_t)stream);
+  return g5d::run(g5d::Int8Cos{x8, norms, dim}, n, dim, row_offset, qf, nq, k, flags, out_count, out_rows, out_scores,
+                  workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int vrq_gemm_topk_dim_engine(int32_t mode, int64_t n, int32_t dim, int32_t nq, int32_t k) {
@@ -2341,15 +1917,12 @@ int vrq_flat_ip_prepare_dim(const float* xf, int64_t n, int32_t dim, int8_t* x8,
   if (n == 0) return VRQ_OK;
   VRQ_CHECK_ARG(xf && x8 && inv_scale);
   const hipStream_t s = (hipStream_t)stream;
-  switch (dim) {
-    case 256: g5d::launch_prepare<8>(xf, n, x8, inv_scale, bounds, s); break;
-    case 384: g5d::launch_prepare<12>(xf, n, x8, inv_scale, bounds, s); break;
-    case 512: g5d::launch_prepare<16>(xf, n, x8, inv_scale, bounds, s); break;
-    case 768: g5d::launch_prepare<24>(xf, n, x8, inv_scale, bounds, s); break;
-    case 1536: g5d::launch_prepare<48>(xf, n, x8, inv_scale, bounds, s); break;
-    case 2048: g5d::launch_prepare<64>(xf, n, x8, inv_scale, bounds, s); break;
-    default: return VRQ_EUNSUPPORTED;
-  }
+  const int rc = g5d::with_ks(dim, false, [&](auto KS) {
+    if constexpr (decltype(KS)::value != 32)  // (1024 is vrq_flat_ip_prepare's, above)
+      g5d::launch_prepare<decltype(KS)::value>(xf, n, x8, inv_scale, bounds, s);
+    return VRQ_OK;
+  });
+  if (rc != VRQ_OK) return rc;
   VRQ_LAUNCH_CHECK();
   return VRQ_OK;
 }
@@ -2357,41 +1930,21 @@ int vrq_flat_ip_prepare_dim(const float* xf, int64_t n, int32_t dim, int8_t* x8,
 size_t vrq_flat_ip_topk_dim_mfma_workspace_size(int64_t n, int32_t dim, int32_t nq, int32_t k) {
   if (dim == 1024) return vrq_gemm_topk_workspace_size(VRQ_GEMM_FLOAT_IP, n, dim, nq, k);
   g5d::Plan p;
-  return g5d::plan_float(n, dim, nq, k, &p) == VRQ_OK ? p.bytes : 0;
+  return g5d::plan_shape(n, dim, nq, k, &p) == VRQ_OK ? p.bytes : 0;
 }
 
 int vrq_flat_ip_topk_dim_mfma_plan(int64_t n, int32_t dim, int32_t nq, int32_t k, int64_t* info) {
   if (!info) return VRQ_EINVAL;
   if (dim == 1024) return vrq_gemm_topk_plan(VRQ_GEMM_FLOAT_IP, n, dim, nq, k, info);
   g5d::Plan p;
-  const int rc = g5d::plan_float(n, dim, nq, k, &p);
-  if (rc != VRQ_OK) return rc;
-  info[0] = p.chunk_rows;
-  info[1] = p.nchunks;
-  info[2] = p.capc;
-  info[3] = p.nqb;
-  info[4] = p.nsc;
-  info[5] = p.scr;
-  info[6] = (int64_t)p.bytes;
-  info[7] = p.qpb;
-  return VRQ_OK;
+  return g5d::plan_info(g5d::plan_shape(n, dim, nq, k, &p), p, info);
 }
 
 int vrq_flat_ip_topk_dim_mfma_prep_layout(int64_t n, int32_t dim, int32_t nq, int32_t k, int64_t* info) {
   if (!info) return VRQ_EINVAL;
   if (dim == 1024) return VRQ_EUNSUPPORTED;  // K5's: vrq_gemm_topk_prep_layout / vrq_gemm_topk_layout
   g5d::Plan p;
-  const int rc = g5d::plan_float(n, dim, nq, k, &p);
-  if (rc != VRQ_OK) return rc;
-  info[0] = (int64_t)p.off_delta;
-  info[1] = (int64_t)p.off_alpha;
-  info[2] = (int64_t)p.off_beta;
-  info[3] = (int64_t)p.off_flag;
-  info[4] = (int64_t)p.off_thr;
-  info[5] = p.nq_pad;
-  info[6] = (int64_t)p.off_cnt;
-  info[7] = (int64_t)p.off_cand;
-  return VRQ_OK;
+  return g5d::prep_layout_info(g5d::plan_shape(n, dim, nq, k, &p), p, info);
 }
 
 int vrq_flat_ip_topk_dim_mfma(const float* xf, const int8_t* x8, const double* inv_scale, const double* bounds,
@@ -2406,13 +1959,13 @@ int vrq_flat_ip_topk_dim_mfma(const float* xf, const int8_t* x8, const double* i
   if (!vrq_dim_supported(dim)) return VRQ_EUNSUPPORTED;
   VRQ_CHECK_ARG(xf && x8 && inv_scale && bounds && qf && out_count && out_rows && out_scores && workspace && n > 0 &&
                 nq > 0 && k > 0);
-  return g5d::run_float(xf, x8, inv_scale, bounds, n, dim, row_offset, qf, nq, k, flags, out_count, out_rows,
-                        out_scores, workspace, workspace_bytes, (hipStream_t)stream);
+  return g5d::run(g5d::FloatOperands{xf, x8, inv_scale, bounds}, n, dim, row_offset, qf, nq, k, flags, out_count,
+                  out_rows, out_scores, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int vrq_flat_ip_dim_engine(int64_t n, int32_t dim, int32_t nq, int32_t k) {
   g5d::Plan p;
-  if (dim == 1024 || g5d::plan_float(n, dim, nq, k, &p) != VRQ_OK) return VRQ_GEMM_ENGINE_EXACT;
+  if (dim == 1024 || g5d::plan_shape(n, dim, nq, k, &p) != VRQ_OK) return VRQ_GEMM_ENGINE_EXACT;
   const int mb = g5d::min_batch_float(dim);
   return mb > 0 && nq > 1 && nq >= mb ? VRQ_GEMM_ENGINE_MFMA : VRQ_GEMM_ENGINE_EXACT;
 }
@@ -2427,34 +1980,14 @@ int vrq_binary_topk_dim_mfma_plan(int64_t n, int32_t dim, int32_t nq, int32_t k,
   if (!info) return VRQ_EINVAL;
   if (dim == 1024) return vrq_gemm_topk_plan(VRQ_GEMM_BINARY, n, dim, nq, k, info);
   g5d::Plan p;
-  const int rc = g5d::plan_shape(n, dim, nq, k, &p);
-  if (rc != VRQ_OK) return rc;
-  info[0] = p.chunk_rows;
-  info[1] = p.nchunks;
-  info[2] = p.capc;
-  info[3] = p.nqb;
-  info[4] = p.nsc;
-  info[5] = p.scr;
-  info[6] = (int64_t)p.bytes;
-  info[7] = p.qpb;
-  return VRQ_OK;
+  return g5d::plan_info(g5d::plan_shape(n, dim, nq, k, &p), p, info);
 }
 
 int vrq_binary_topk_dim_mfma_prep_layout(int64_t n, int32_t dim, int32_t nq, int32_t k, int64_t* info) {
   if (!info) return VRQ_EINVAL;
   if (dim == 1024) return VRQ_EUNSUPPORTED;  // K5's: vrq_gemm_topk_prep_layout / vrq_gemm_topk_layout
   g5d::Plan p;
-  const int rc = g5d::plan_shape(n, dim, nq, k, &p);
-  if (rc != VRQ_OK) return rc;
-  info[0] = (int64_t)p.off_delta;
-  info[1] = (int64_t)p.off_alpha;
-  info[2] = (int64_t)p.off_beta;
-  info[3] = (int64_t)p.off_flag;
-  info[4] = (int64_t)p.off_thr;
-  info[5] = p.nq_pad;
-  info[6] = (int64_t)p.off_cnt;
-  info[7] = (int64_t)p.off_cand;
-  return VRQ_OK;
+  return g5d::prep_layout_info(g5d::plan_shape(n, dim, nq, k, &p), p, info);
 }
 
 int vrq_binary_topk_dim_mfma(const uint8_t* codes, int64_t n, int32_t dim, int64_t row_offset, const float* qf,
@@ -2467,8 +2000,8 @@ int vrq_binary_topk_dim_mfma(const uint8_t* codes, int64_t n, int32_t dim, int64
                          out_rows, out_scores, workspace, workspace_bytes, stream);
   if (!vrq_dim_supported(dim)) return VRQ_EUNSUPPORTED;
   VRQ_CHECK_ARG(codes && qf && out_count && out_rows && out_scores && workspace && n > 0 && nq > 0 && k > 0);
-  return g5d::run_binary(codes, n, dim, row_offset, qf, nq, k, flags, out_count, out_rows, out_scores, workspace,
-                         workspace_bytes, (hipStream_t)stream);
+  return g5d::run(g5d::Binary{codes, dim}, n, dim, row_offset, qf, nq, k, flags, out_count, out_rows, out_scores,
+                  workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 size_t vrq_gemm_topk_rows_workspace_size(int32_t mode, int64_t m, int32_t dim, int32_t nq, int32_t k) {
@@ -2480,9 +2013,7 @@ int vrq_gemm_topk_rows_plan(int32_t mode, int64_t m, int32_t dim, int32_t nq, in
   if (!info) return VRQ_EINVAL;
   if (mode != VRQ_GEMM_INT8_COSINE) return mode == VRQ_GEMM_FLOAT_IP ? VRQ_EINVAL : VRQ_EUNSUPPORTED;
   g5d::Plan p;
-  const int rc = g5d::plan_rows(m, dim, nq, k, &p);
-  if (rc == VRQ_OK) g5d::plan_info(p, info);
-  return rc;
+  return g5d::plan_info(g5d::plan_rows(m, dim, nq, k, &p), p, info);
 }
 
 int vrq_gemm_topk_rows(int32_t mode, const uint8_t* codes, const int8_t* x8, const double* norms, int64_t n,
@@ -2497,8 +2028,8 @@ int vrq_gemm_topk_rows(int32_t mode, const uint8_t* codes, const int8_t* x8, con
   VRQ_CHECK_ARG(qf && out_count && out_rows && out_scores && n > 0 && nq > 0 && k > 0 && m >= 0 && m <= n);
   if (m == 0) return g5d::run_empty(nq, k, out_count, out_rows, out_scores, (hipStream_t)stream);
   VRQ_CHECK_ARG(rows && workspace && x8 && norms);
-  return g5d::run(x8, norms, m, dim, row_offset, qf, nq, k, flags, out_count, out_rows, out_scores, workspace,
-                  workspace_bytes, (hipStream_t)stream, rows);
+  return g5d::run(g5d::Int8Cos{x8, norms, dim}, m, dim, row_offset, qf, nq, k, flags, out_count, out_rows, out_scores,
+                  workspace, workspace_bytes, (hipStream_t)stream, rows);
 }
 
 size_t vrq_flat_ip_topk_rows_workspace_size(int64_t m, int32_t dim, int32_t nq, int32_t k) {
@@ -2509,9 +2040,7 @@ size_t vrq_flat_ip_topk_rows_workspace_size(int64_t m, int32_t dim, int32_t nq, 
 int vrq_flat_ip_topk_rows_plan(int64_t m, int32_t dim, int32_t nq, int32_t k, int64_t* info) {
   if (!info) return VRQ_EINVAL;
   g5d::Plan p;
-  const int rc = g5d::plan_rows(m, dim, nq, k, &p);
-  if (rc == VRQ_OK) g5d::plan_info(p, info);
-  return rc;
+  return g5d::plan_info(g5d::plan_rows(m, dim, nq, k, &p), p, info);
 }
 
 int vrq_flat_ip_topk_rows(const float* xf, const int8_t* x8, const double* inv_scale, const double* bounds, int64_t n,
@@ -2523,8 +2052,8 @@ int vrq_flat_ip_topk_rows(const float* xf, const int8_t* x8, const double* inv_s
   VRQ_CHECK_ARG(qf && out_count && out_rows && out_scores && n > 0 && nq > 0 && k > 0 && m >= 0 && m <= n);
   if (m == 0) return g5d::run_empty(nq, k, out_count, out_rows, out_scores, (hipStream_t)stream);
   VRQ_CHECK_ARG(rows && workspace && xf && x8 && inv_scale && bounds);
-  return g5d::run_float(xf, x8, inv_scale, bounds, m, dim, row_offset, qf, nq, k, flags, out_count, out_rows,
-                        out_scores, workspace, workspace_bytes, (hipStream_t)stream, rows);
+  return g5d::run(g5d::FloatOperands{xf, x8, inv_scale, bounds}, m, dim, row_offset, qf, nq, k, flags, out_count,
+                  out_rows, out_scores, workspace, workspace_bytes, (hipStream_t)stream, rows);
 }
 
 size_t vrq_binary_topk_gather_workspace_size(int64_t m, int32_t dim, int32_t nq, int32_t k) {
@@ -2535,9 +2064,7 @@ size_t vrq_binary_topk_gather_workspace_size(int64_t m, int32_t dim, int32_t nq,
 int vrq_binary_topk_gather_plan(int64_t m, int32_t dim, int32_t nq, int32_t k, int64_t* info) {
   if (!info) return VRQ_EINVAL;
   g5d::Plan p;
-  const int rc = g5d::plan_rows(m, dim, nq, k, &p);
-  if (rc == VRQ_OK) g5d::plan_info(p, info);
-  return rc;
+  return g5d::plan_info(g5d::plan_rows(m, dim, nq, k, &p), p, info);
 }
 
 int vrq_binary_topk_gather(const uint8_t* codes, int64_t n, int32_t dim, int64_t row_offset, const uint32_t* rows,
@@ -2549,8 +2076,8 @@ int vrq_binary_topk_gather(const uint8_t* codes, int64_t n, int32_t dim, int64_t
   VRQ_CHECK_ARG(qf && out_count && out_rows && out_scores && n > 0 && nq > 0 && k > 0 && m >= 0 && m <= n);
   if (m == 0) return g5d::run_empty(nq, k, out_count, out_rows, out_scores, (hipStream_t)stream);
   VRQ_CHECK_ARG(rows && workspace && codes);
-  return g5d::run_binary(codes, m, dim, row_offset, qf, nq, k, flags, out_count, out_rows, out_scores, workspace,
-                         workspace_bytes, (hipStream_t)stream, rows);
+  return g5d::run(g5d::Binary{codes, dim}, m, dim, row_offset, qf, nq, k, flags, out_count, out_rows, out_scores,
+                  workspace, workspace_bytes, (hipStream_t)stream, rows);
 }
 
 int vrq_binary_topk_dim_engine(int64_t n, int32_t dim, int32_t nq, int32_t k) {
